@@ -39,6 +39,8 @@ One JSON line on rank 0.  Extra objects:
                  by per-rank checksums; its own ms_per_step / roofline / per-rank device times
   c_abi_multi    (N=1) the same configs[4] shape through the C ABI's single-process multi-device group
                  (wf_hip_multi_*: one host thread per device, dlopen()ed RCCL) over every device this process sees
+  dump_outputs   (--dump-outputs DIR) the .npy files written from the last timed step and the streams they hold
+Kept near 16 KB: the per-shape objects go in without their explanations (terse).
 """
 from __future__ import annotations
 
@@ -85,6 +87,10 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs / pcie_inclusive legs (profiling runs)")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="CPU work budget (core-seconds) of the baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (m_decibels, the bars of a bars configuration, "
+                         "m_last_silent) as float32 DIR/<name>.npy; the smoothing state is zeroed in front of the warm-up steps so "
+                         "that the same arguments give the same outputs (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -217,6 +223,51 @@ def copy_ceiling(torch, mib=1024, reps=20):
     gbps = 2.0 * n * 4 * reps / (e0.elapsed_time(e1) * 1e-3) / 1e9
     del src, dst
     return {"achieved": gbps, "unit": "GB/s", "frac_of_peak": gbps / HBM_PEAK_GBPS, "what": f"torch copy_ of {mib} MiB, bytes read + written, {reps} repetitions by events"}
+
+
+PROSE = ("timed_by", "traffic_source", "achieved_events", "frac_wall", "sample", "kind", "class")
+
+
+def terse(o):
+    """other_configs / configs4 / c_abi_multi as they go into the line: the figures at 6 significant digits, without the explanations
+    and the derived figures the headline's objects carry once.  The line has to be read back whole, and in full it had grown
+    past 20 KB (22 KB); this keeps it near 16 KB."""
+    if isinstance(o, dict):
+        return {k: terse(v) for k, v in o.items() if k not in PROSE}
+    if isinstance(o, list):
+        return [terse(v) for v in o]
+    if isinstance(o, float):
+        return float(f"{o:.6g}")
+    return o
+
+
+DUMP_BYTES = 32 << 20     # --dump-outputs: bytes written in all (every rank together); beyond it a sample of the streams
+DUMP_SEED = 0x44554D50    # the sample: the same streams in every run with the same --streams / --gpus
+
+
+def dump_outputs(batch, out_dir, flags, rank=0, world=1):
+    """--dump-outputs: what the last timed step left for a caller of the path -- m_decibels (not with bars-only ticks), the bar
+    heights of a bars configuration and m_last_silent (0 / 1) -- as float32 DIR/<name>.npy, [streams, ...] in stream order
+    (<name>_rank<r>.npy when there are several ranks).  Every stream when the whole batch fits DUMP_BYTES, else a fixed sample
+    of streams drawn with DUMP_SEED.  Returns what was written, for the result line."""
+    import numpy as np
+    import waveform_amd as wf
+    reads = {}
+    if not flags & wf.TICK_NO_DECIBELS:
+        reads["decibels"] = batch.decibels
+    if batch.cfg.bars:
+        reads["bars"] = batch.bars
+    reads["last_silent"] = batch.last_silent
+    per_stream = 4 * (batch.output_channels * batch.bins * ("decibels" in reads) + batch.display_channels * batch.num_bars * ("bars" in reads) + 1)
+    n = min(batch.streams, max(1, DUMP_BYTES // (world * per_stream)))
+    pick = np.arange(batch.streams) if n == batch.streams else np.sort(np.random.default_rng(DUMP_SEED).choice(batch.streams, n, replace=False))
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, read in reads.items():
+        np.save(out / f"{name}{suffix}.npy", read()[pick].astype(np.float32))
+    return {"dir": str(out), "files": [f"{name}{suffix}.npy" for name in reads], "streams": int(n), "of_streams": batch.streams,
+            "sample": None if n == batch.streams else f"numpy default_rng({DUMP_SEED:#x}).choice({batch.streams}, {n}, replace=False), sorted"}
 
 
 WARM_MS, TIMED_MS = 40.0, 30.0  # other shapes: device time of the untimed lead-in (clocks settle in 15-20 ms) and of the timed region
@@ -554,6 +605,11 @@ def main():
             dist.all_reduce(w, op=dist.ReduceOp.MAX)
             lead_in_ticks = int(w.item())
         run(lead_in_ticks - 16)
+    if args.dump_outputs:
+        # the lead-in runs for a time, not a number of ticks, and the EMA carries every tick into the next: from a zeroed smoothing
+        # state the outputs depend on the arguments alone (the W + K ticks below over the same resident audio)
+        import numpy as np
+        batch.set_tsmooth(np.zeros((args.streams, batch.capture_channels, batch.bins), np.float32))
     # warm-up: W untimed steps
     if args.warmup > 0:
         run(args.warmup)
@@ -564,6 +620,7 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    dumped = dump_outputs(batch, args.dump_outputs, flags, rank, world) if args.dump_outputs else None
     per_rank_ms, ranks_seen = [elapsed * 1e3 / args.steps], 1
     # The scaling curve's N = 1 point, taken in THIS run: rank 0 alone over the same K steps while the other ranks wait at a
     # barrier (their GPUs idle) -- the driver computes efficiency itself from its own N = 1 run; this is the same ratio from one
@@ -632,6 +689,8 @@ def main():
             "roofline": roofline(batch, "cfg3_n4096" if (args.streams, args.fft, flags) == (STREAMS_PER_GPU, FFT_SIZE, 0) else None, kernel_ms, flags,
                                  wall_ms=ms_per_step, cold_ms=cold_ms),
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         n1 = solo_rate if solo_rate else value
         out["config"]["scaling_point"] = {"n": world, "spectra_per_s": value, "per_gpu_spectra_per_s": value / world, "n1_spectra_per_s": n1,
                                           "efficiency_vs_n1": value / (world * n1),
@@ -687,7 +746,7 @@ def main():
         except Exception as e:
             print(f"bench.py: pcie_inclusive failed: {e}", file=sys.stderr)
         try:
-            out["other_configs"] = other_configs(wf, local_rank, 0 if args.no_cpu_baseline else host_cores())
+            out["other_configs"] = terse(other_configs(wf, local_rank, 0 if args.no_cpu_baseline else host_cores()))
         except Exception as e:
             print(f"bench.py: other_configs failed: {e}", file=sys.stderr)
     if world == 1 and not args.no_other_configs and not args.bars_allgather:
@@ -698,9 +757,9 @@ def main():
             print(f"bench.py: configs4 failed: {e}", file=sys.stderr)
     if rank == 0:
         if cfg4 is not None:
-            out["configs4"] = cfg4
+            out["configs4"] = terse(cfg4)
         if world == 1 and not args.no_other_configs and not args.bars_allgather:
-            out["c_abi_multi"] = c_abi_multi()
+            out["c_abi_multi"] = terse(c_abi_multi())
         # One compact object with every figure that matters, twice: inside `roofline` (a standard key: the driver keeps those whole)
         # and as the LAST key of the line (the driver keeps the last 8 KB of stdout) -- the long per-shape objects in between may
         # be cut, the figures are not.

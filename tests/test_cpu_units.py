@@ -20,14 +20,19 @@ ROOT = Path(__file__).resolve().parent.parent
 
 # ---- wf_synth.h -----------------------------------------------------------------------------------
 def test_synth_numpy_matches_c():
+    """tools/synth.py against include/wf_synth.h: the C function's values stored in tests/golden/synth_noise.npz, and live through
+    the harness library (oracle/_ref/libwfref.so) wherever it has been built"""
     from oracle import wfref
-    if not wfref.available():
-        pytest.skip("libwfref.so not built")
-    L = wfref.lib()
-    for stream, ch, i0 in ((0, 0, 0), (7, 1, 12345), (65535, 1, 2**33 + 5)):
+    z = np.load(ROOT / "tests" / "golden" / "synth_noise.npz")
+    assert int(z["seed"]) == synth.DEFAULT_SEED
+    L = wfref.lib() if wfref.available() else None
+    for k, (stream, ch, i0) in enumerate(((0, 0, 0), (7, 1, 12345), (65535, 1, 2**33 + 5))):
+        assert tuple(int(v) for v in z["cases"][k]) == (stream, ch, i0)
         a = synth.noise(synth.DEFAULT_SEED, stream, ch, i0, 257)
-        b = np.array([L.wfref_noise(synth.DEFAULT_SEED, stream, ch, i0 + i) for i in range(257)], np.float32)
-        assert np.array_equal(a, b)
+        assert np.array_equal(a, z[f"noise_{k}"])
+        if L is not None:
+            b = np.array([L.wfref_noise(synth.DEFAULT_SEED, stream, ch, i0 + i) for i in range(257)], np.float32)
+            assert np.array_equal(a, b)
     x = synth.noise(1, 2, 0, 0, 1 << 16)
     assert x.min() >= -1.0 and x.max() < 1.0 and abs(float(x.mean())) < 0.01
     assert abs(float(x.var()) - 1 / 3) < 0.01
@@ -717,6 +722,47 @@ def test_bench_line_puts_the_baseline_shapes_first():
     """the driver keeps the head of the standard keys and the last 8 KB of stdout: BASELINE shapes first, the reference-range extras last"""
     keys = _bench_shape_keys()
     assert keys[:4] == ["cfg3_n4096", "cfg4_n16384_bars", "cfg5shape_8192streams_barsonly", "cfg2_batch"] and keys[-2:] == ["n65536", "n800_mixed_radix"], keys
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs over a stand-in for the batch: float32 files of at most 64 MB in all, the same streams in every run
+    (a seeded sample when the whole batch is larger), rows taken whole and in stream order; a bars-only tick leaves no decibels"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    import waveform_amd as wf
+
+    class Batch:
+        def __init__(self, streams, bars):
+            self.streams, self.output_channels, self.bins, self.display_channels, self.num_bars = streams, 2, 2048, 2, 26
+            self.cfg = scenarios.make_config(dict(fft_size=4096, stereo=1, bars=int(bars)))
+
+        def decibels(self):
+            return np.arange(self.streams * 2 * 2048, dtype=np.float32).reshape(self.streams, 2, 2048)
+
+        def bars(self):
+            return np.arange(self.streams * 2 * 26, dtype=np.float32).reshape(self.streams, 2, 26)
+
+        def last_silent(self):
+            return np.arange(self.streams) % 3 == 0
+
+    got = []
+    for run in ("a", "b"):
+        info = bench.dump_outputs(Batch(4096, False), tmp_path / run, 0)
+        files = {f.name: np.load(f) for f in sorted((tmp_path / run).iterdir())}
+        assert sorted(files) == sorted(info["files"]) == ["decibels.npy", "last_silent.npy"]
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 64 << 20
+        assert all(a.dtype == np.float32 for a in files.values())
+        got.append(files)
+    db, silent = got[0]["decibels.npy"], got[0]["last_silent.npy"]
+    assert 0 < info["streams"] < 4096 and db.shape == (info["streams"], 2, 2048) and silent.shape == (info["streams"],)
+    picked = db[:, 0, 0].astype(np.int64) // (2 * 2048)
+    assert np.all(np.diff(picked) > 0) and np.array_equal(db, Batch(4096, False).decibels()[picked])
+    assert np.array_equal(silent, (picked % 3 == 0).astype(np.float32))
+    assert all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+    # a small batch goes whole; bars-only ticks (no m_decibels store) dump the bars instead
+    info = bench.dump_outputs(Batch(64, True), tmp_path / "bars", wf.TICK_NO_DECIBELS)
+    assert info["files"] == ["bars.npy", "last_silent.npy"] and info["streams"] == 64 and info["sample"] is None
+    assert np.array_equal(np.load(tmp_path / "bars" / "bars.npy"), Batch(64, True).bars())
 
 
 def test_node_check_names_every_reason():

@@ -631,10 +631,12 @@ def test_canary_guards_behind_every_device_block(monkeypatch):
         b.push_synth(scenarios.SEED, 0, 800)
         b.tick()
         b.sync()
-        hip = C.CDLL("libamdhip64.so")
-        hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        # the HIP runtime the library is linked against, looked up through the library's own handle: a process that imported torch
+        # after loading the library holds torch's copy of the runtime too, and that is what the bare name libamdhip64.so finds
+        memset, device_synchronize = wf.lib()["hipMemset"], wf.lib()["hipDeviceSynchronize"]
+        memset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
         end_of_rows = b.decibels_device_ptr() + 3 * b.output_channels * b.bins * 4
-        assert hip.hipMemset(C.c_void_p(end_of_rows + 8), 0, 4) == 0 and hip.hipDeviceSynchronize() == 0
+        assert memset(C.c_void_p(end_of_rows + 8), 0, 4) == 0 and device_synchronize() == 0
         with pytest.raises(wf.WfHipError) as e:
             b.sync()
         assert "WF_HIP_CANARY" in str(e.value) and "past its end" in str(e.value), str(e.value)

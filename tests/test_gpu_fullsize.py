@@ -325,6 +325,37 @@ def test_bench_multi_rank_path_with_the_collective():
     assert line["roofline"]["summary"] == line["summary"]
 
 
+def test_bench_line_reads_back_whole_and_dumps_the_same_outputs_twice(tmp_path):
+    """bench.py as the driver runs it (--gpus 1 --steps K --warmup W, every leg): one JSON line that stays under 20 KB (at 22 KB
+    it was no longer read back whole) and that timed exactly K steps; --dump-outputs: what the last timed step computed, float32,
+    at most 64 MB, and the same bits from a second run with the same headline arguments (the legs after the timed path left out)"""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    dumps = []
+    for i, extra in enumerate(([], ["--no-cpu-baseline", "--no-other-configs"])):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(d)] + extra,
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        text = r.stdout.strip().splitlines()[-1]
+        line = json.loads(text)
+        if not extra:
+            assert len(text.encode()) < 20_000, f"bench.py's line is {len(text.encode())} bytes"
+            assert "other_configs" in line and "configs4" in line and list(line)[-1] == "summary"
+        assert line["steps"] == 20 and line["value"] > 0
+        assert line["dump_outputs"]["files"] == ["decibels.npy", "last_silent.npy"]
+        files = sorted(d.iterdir())
+        assert [f.name for f in files] == ["decibels.npy", "last_silent.npy"] and sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.name: np.load(f) for f in files})
+    db = dumps[0]["decibels.npy"]
+    assert db.dtype == np.float32 and db.shape == (line["dump_outputs"]["streams"], 2, 2048) and np.isfinite(db).all() and db.max() > db.min()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), f"{k} differs between two runs with the same arguments"
+
+
 def test_roctx_ranges_are_opt_in_and_change_nothing():
     """WF_HIP_ROCTX=1: wf_hip_tick pushes / pops a roctx range around itself, resolved at run time from the profiler's marker library
     ("Tracing"); the rows are the same bits, and without a marker library on the box the tick simply runs"""

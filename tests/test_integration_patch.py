@@ -32,8 +32,8 @@ def _child(code, batched=None, timeout=900):
 def test_patch_applies_cleanly_to_the_reference_tree(tmp_path):
     """patch(1) takes integration/waveform-hip.patch against the reference's two files without fuzz or rejects, and the result
     has WAVSourceHIP first in callbacks::create and the binding in PLUGIN_SOURCES"""
-    if not (REF / "src" / "source.cpp").exists():
-        pytest.skip("the reference tree is not on this box (the prebuilt oracle/_ref/libwfref_plugin.so travels instead)")
+    if not os.access(REF / "src" / "source.cpp", os.R_OK):
+        pytest.skip("the reference tree is not on this box or not readable (the prebuilt oracle/_ref/libwfref_plugin.so travels instead)")
     (tmp_path / "src").mkdir()
     shutil.copy(REF / "src" / "source.cpp", tmp_path / "src" / "source.cpp")
     shutil.copy(REF / "CMakeLists.txt", tmp_path / "CMakeLists.txt")

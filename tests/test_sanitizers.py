@@ -12,6 +12,7 @@ repository runs under AddressSanitizer + UndefinedBehaviorSanitizer and ThreadSa
 
 Every run is a child process with the sanitizer's runtime preloaded; a report fails the test (non-zero exit / text on stderr)."""
 import os
+import platform
 import subprocess
 import sys
 from pathlib import Path
@@ -28,12 +29,27 @@ def _runtime(name):
     return p
 
 
+def _fixed_layout():
+    """GCC's ThreadSanitizer runtime knows the address-space layout of kernels that randomise mmap over fewer bits than some use
+    today; there every child dies with "FATAL: ThreadSanitizer: unexpected memory mapping" before the test's code runs.  Its
+    children therefore run with address-space randomisation off for that one process (setarch -R, a personality flag), wherever
+    the system lets a process set it."""
+    cmd = ["setarch", platform.machine(), "-R"]
+    try:
+        return cmd if subprocess.run(cmd + ["true"], capture_output=True).returncode == 0 else []
+    except OSError:
+        return []
+
+
 def _child(args, preload, env_extra=None, timeout=600):
-    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1",
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", TSAN_OPTIONS=f"halt_on_error=1:second_deadlock_stack=1:suppressions={ROOT / 'tests' / 'tsan.supp'}",
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     env.update(env_extra or {})
-    r = subprocess.run([sys.executable] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
+    # the runtime is preloaded into the python child alone (env), not into setarch
+    prefix = _fixed_layout() if "tsan" in Path(preload).name else []
+    r = subprocess.run(prefix + ["env", f"LD_PRELOAD={preload}", sys.executable] + [str(a) for a in args], capture_output=True, text=True,
+                       timeout=timeout, env=env, cwd=ROOT)
     report = [l for l in r.stderr.splitlines() if "Sanitizer" in l or "runtime error" in l]
     assert r.returncode == 0 and not report, (r.stdout[-1500:], r.stderr[-4000:])
     return r.stdout
