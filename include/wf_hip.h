@@ -149,6 +149,47 @@ int wf_hip_push_synth(wf_hip *h, uint32_t first, uint32_t count, uint64_t seed, 
  * not read. */
 int wf_hip_push_audio_muted(wf_hip *h, uint32_t first, uint32_t count, const float *samples, uint32_t frames);
 
+/* ---- audio ingest in any libobs sample format ------------------------------------------
+ * capture_audio takes channels m_channel_base .. m_channel_base + m_capture_channels out of a packet of up to
+ * MAX_AUDIO_CHANNELS (8) channels (src/source.cpp:1827-1828, :1872-1886; a mono capture picks its channel with the P_CHANNEL
+ * setting, :333, :1089-1103).  wf_hip_push_pcm does the same with the packet in its own sample format: the bus carries the
+ * packet's bytes (s16: half of float32, u8: a quarter) and the device converts, picks the captured channels and appends them
+ * to the rings -- and, where the RMS producer follows the audio, their squared per-frame peak (:1842-1871) -- in one pass.
+ * Values are libobs' enum audio_format. */
+typedef enum wf_hip_pcm_format {
+    WF_HIP_PCM_U8 = 1, WF_HIP_PCM_S16, WF_HIP_PCM_S32, WF_HIP_PCM_F32,                        /* interleaved: [frames][channels] */
+    WF_HIP_PCM_U8_PLANAR, WF_HIP_PCM_S16_PLANAR, WF_HIP_PCM_S32_PLANAR, WF_HIP_PCM_F32_PLANAR /* planar: [channels][frames] */
+} wf_hip_pcm_format;
+/* The conversion to the float32 the rings hold is exact (bit for bit what these expressions give in float):
+ *   u8:  (x - 128) * 2^-7      s16: x * 2^-15      s32: (float)x * 2^-31, (float)x rounded to nearest even
+ *   f32: the bits pass unchanged
+ * -- the full-scale mapping audio converters use. */
+typedef enum wf_hip_pcm_memory {
+    WF_HIP_PCM_HOST = 0,   /* any host memory; the call returns once the packet has been copied (wf_hip_push_audio) */
+    WF_HIP_PCM_PINNED = 1, /* wf_hip_host_alloc memory; does not wait, `slot` as wf_hip_push_audio_async / wf_hip_ingest_done */
+    WF_HIP_PCM_DEVICE = 2  /* device memory of the handle's device, read in place (wf_hip_push_audio_device) */
+} wf_hip_pcm_memory;
+typedef struct wf_hip_pcm {
+    const void *data;                  /* the blocks of streams first .. first+count-1, one after the other: stream i's block
+                                          starts at i * channels * frames * bytes_per_sample */
+    uint32_t format;                   /* wf_hip_pcm_format */
+    uint32_t channels;                 /* channels in the packet, 1..8 */
+    uint32_t channel_base;             /* first captured channel (m_channel_base): channel_base + capture_channels <= channels;
+                                          a two-channel capture needs 0 (the asserts of src/source.cpp:1827-1828) */
+    uint32_t frames;                   /* frames per stream; with frames_per_stream: the block size (max_frames) */
+    const uint32_t *frames_per_stream; /* NULL, or [count] frame counts <= frames: a ragged push by the rules of
+                                          wf_hip_push_audio_ragged_async (WF_HIP_PCM_PINNED only; not while the RMS producer
+                                          follows the audio; at most 65535 streams) */
+    uint32_t memory;                   /* wf_hip_pcm_memory */
+    uint32_t slot;                     /* WF_HIP_PCM_PINNED: 0 / 1, released by wf_hip_ingest_done(slot) */
+} wf_hip_pcm;
+/* Appends the captured channels of `pcm` to streams [first, first+count), as wf_hip_push_audio* does with planar float32: a
+ * packet longer than the ring keeps its newest ring_frames frames, every handle kind (spectrum, level meter, waveform) takes
+ * it.  Host packets cross the bus in their own width; a planar one with more channels than captured sends only the
+ * captured planes.  WF_HIP_ERR_INVALID before anything is enqueued for a bad format, channel count, channel pick, memory
+ * kind, slot, a NULL pointer, or device data not aligned to its sample size. */
+int wf_hip_push_pcm(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm);
+
 /* ---- the tick ------------------------------------------------------------------------- */
 typedef struct wf_hip_tick_params {
     float seconds;          /* tick_spectrum(seconds): only TVEXPONENTIAL smoothing uses it */
@@ -413,6 +454,9 @@ wf_hip *wf_hip_multi_shard(wf_hip_multi *m, uint32_t i, int *device, uint32_t *f
  * the number of devices) */
 int wf_hip_multi_push_audio(wf_hip_multi *m, uint32_t first, uint32_t count, const float *samples, uint32_t frames);
 int wf_hip_multi_push_synth(wf_hip_multi *m, uint32_t first, uint32_t count, uint64_t seed, uint32_t stream_id0, uint64_t index0, uint32_t frames);
+/* wf_hip_push_pcm with global stream indices: the packet is split at the shard boundaries (stream i's block at
+ * i * channels * frames * bytes_per_sample).  WF_HIP_PCM_HOST packets without frames_per_stream only. */
+int wf_hip_multi_push_pcm(wf_hip_multi *m, uint32_t first, uint32_t count, const wf_hip_pcm *pcm);
 int wf_hip_multi_set_hidden(wf_hip_multi *m, uint32_t first, uint32_t count, const uint8_t *mask);
 int wf_hip_multi_reset(wf_hip_multi *m, uint32_t first, uint32_t count);
 /* WAVSource*::tick_spectrum for every stream of every shard (wf_hip_tick on each device, issued concurrently by the

@@ -63,6 +63,50 @@ OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST
  TABLE_INTERP_SHAPE) = range(8)
 
 
+# wf_hip_pcm_format / wf_hip_pcm_memory: libobs' enum audio_format, by numpy dtype (the planar format is the interleaved one + 4)
+PCM_FORMAT = {np.dtype(np.uint8): 1, np.dtype(np.int16): 2, np.dtype(np.int32): 3, np.dtype(np.float32): 4}
+PCM_HOST, PCM_PINNED, PCM_DEVICE = 0, 1, 2
+
+
+class Pcm(C.Structure):
+    """struct wf_hip_pcm (include/wf_hip.h): one packet in any libobs sample format"""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_uint32), ("channels", C.c_uint32), ("channel_base", C.c_uint32),
+                ("frames", C.c_uint32), ("frames_per_stream", C.POINTER(C.c_uint32)), ("memory", C.c_uint32), ("slot", C.c_uint32)]
+
+
+def _pcm(samples, interleaved: bool, channel_base: int, frames, slot):
+    """(wf_hip_pcm, count, keep-alive) for a numpy array, a PinnedBuffer or a torch tensor on the device.  Shape
+    [count, frames, channels] interleaved, [count, channels, frames] planar; `frames`: None, or the per-stream frame counts of
+    a ragged push (the shape's frame axis is then max_frames)."""
+    keep = []
+    if isinstance(samples, PinnedBuffer):
+        if slot is None:
+            raise ValueError("a pinned buffer needs a slot (0 / 1)")
+        ptr, memory, shape, dtype = samples.ptr, PCM_PINNED, samples.array.shape, samples.array.dtype
+    elif hasattr(samples, "data_ptr") and getattr(samples, "is_cuda", False):
+        if not samples.is_contiguous():
+            raise ValueError("a device tensor must be contiguous")
+        ptr, memory, shape = samples.data_ptr(), PCM_DEVICE, tuple(samples.shape)
+        dtype = np.dtype(str(samples.dtype).replace("torch.", ""))
+    else:
+        arr = np.ascontiguousarray(samples)
+        keep.append(arr)
+        ptr, memory, shape, dtype = arr.ctypes.data, PCM_HOST, arr.shape, arr.dtype
+    if dtype not in PCM_FORMAT or len(shape) != 3:
+        raise ValueError(f"expected a [count, frames, channels] / [count, channels, frames] array of uint8, int16, int32 or float32, "
+                         f"got {dtype} {shape}")
+    count = shape[0]
+    block_frames, channels = (shape[1], shape[2]) if interleaved else (shape[2], shape[1])
+    pcm = Pcm(data=ptr, format=PCM_FORMAT[dtype] + (0 if interleaved else 4), channels=channels, channel_base=channel_base,
+              frames=block_frames, memory=memory, slot=0 if slot is None else slot)
+    if frames is not None:
+        f = np.ascontiguousarray(frames, dtype=np.uint32)
+        assert f.shape == (count,), f.shape
+        keep.append(f)
+        pcm.frames_per_stream = f.ctypes.data_as(C.POINTER(C.c_uint32))
+    return pcm, count, keep
+
+
 class Readback(C.Structure):
     """wf_hip_readback: the page-locked destinations of one wf_hip_read_async (NULL leaves an output out)"""
     _fields_ = [("rows", C.c_void_p), ("last_silent", C.c_void_p), ("bars", C.c_void_p), ("premirror", C.c_void_p), ("vertices", C.c_void_p),
@@ -109,6 +153,9 @@ def lib():
     L.wf_hip_host_alloc.argtypes = [C.c_size_t]
     L.wf_hip_host_free.argtypes = [vp]
     L.wf_hip_push_synth.argtypes = [vp, u32, u32, u64, u32, u64, u32]
+    L.wf_hip_push_audio_ragged_async.argtypes = [vp, u32, u32, vp, C.POINTER(u32), u32, u32]
+    L.wf_hip_push_pcm.argtypes = [vp, u32, u32, C.POINTER(Pcm)]
+    L.wf_hip_multi_push_pcm.argtypes = [vp, u32, u32, C.POINTER(Pcm)]
     L.wf_hip_push_audio_muted.argtypes = [vp, u32, u32, fp, u32]
     L.wf_hip_enable_input_rms.argtypes = [vp, C.c_int]
     L.wf_hip_tick.argtypes = [vp, C.POINTER(TickParams)]
@@ -275,6 +322,22 @@ class SpectrumBatch:
 
     def push_audio_device(self, dev_ptr: int, count: int, frames: int, first: int = 0):
         self._ck(self.L.wf_hip_push_audio_device(self.h, first, count, C.c_void_p(dev_ptr), frames))
+
+    def push_pcm(self, samples, *, interleaved: bool, channel_base: int = 0, frames=None, slot: int | None = None, first: int = 0):
+        """wf_hip_push_pcm: a packet in its own sample format, converted and channel-picked on the device.  The format comes
+        from the dtype (uint8, int16, int32, float32); shape [count, frames, channels] interleaved, [count, channels, frames]
+        planar.  A numpy array is copied before the call returns; a PinnedBuffer goes through the pipelined form (`slot`,
+        ingest_done); a torch tensor on the handle's device is read in place.  frames: per-stream frame counts (ragged,
+        PinnedBuffer only)."""
+        pcm, count, keep = _pcm(samples, interleaved, channel_base, frames, slot)
+        self._ck(self.L.wf_hip_push_pcm(self.h, first, count, C.byref(pcm)))
+        del keep
+
+    def push_audio_ragged_async(self, pinned: "PinnedBuffer", frames, max_frames: int, slot: int, first: int = 0):
+        """wf_hip_push_audio_ragged_async: pinned [count, capture_channels, max_frames] float32, frames[count] per stream"""
+        f = np.ascontiguousarray(frames, dtype=np.uint32)
+        self._ck(self.L.wf_hip_push_audio_ragged_async(self.h, first, len(f), C.c_void_p(pinned.ptr), f.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                        max_frames, slot))
 
     def push_synth(self, seed: int, index0: int, frames: int, first: int = 0, count: int | None = None, stream_id0: int = 0):
         count = self.streams - first if count is None else count
@@ -449,15 +512,17 @@ class SpectrumBatch:
 
 
 class PinnedBuffer:
-    """page-locked host memory (wf_hip_host_alloc) viewed as a float32 numpy array"""
+    """page-locked host memory (wf_hip_host_alloc) viewed as a numpy array (float32 unless `dtype` says otherwise)"""
 
-    def __init__(self, shape):
+    def __init__(self, shape, dtype=np.float32):
         self.L = lib()
+        dt = np.dtype(dtype)
         n = int(np.prod(shape))
-        self.ptr = self.L.wf_hip_host_alloc(n * 4)
+        self.ptr = self.L.wf_hip_host_alloc(max(n * dt.itemsize, 1))
         if not self.ptr:
             raise MemoryError("wf_hip_host_alloc failed")
-        self.array = np.ctypeslib.as_array(C.cast(self.ptr, C.POINTER(C.c_float)), shape=(n,)).reshape(shape)
+        raw = np.ctypeslib.as_array(C.cast(self.ptr, C.POINTER(C.c_uint8)), shape=(n * dt.itemsize,))
+        self.array = raw.view(dt).reshape(shape)
 
     def close(self):
         if getattr(self, "ptr", None):
@@ -527,6 +592,14 @@ class MultiBatch:
         s = np.ascontiguousarray(samples, dtype=np.float32)
         assert s.ndim == 3 and s.shape[1] == self.capture_channels, s.shape
         self._ck(self.L.wf_hip_multi_push_audio(self.m, first, s.shape[0], s.ctypes.data_as(C.POINTER(C.c_float)), s.shape[2]))
+
+    def push_pcm(self, samples, *, interleaved: bool, channel_base: int = 0, frames=None, slot: int | None = None, first: int = 0):
+        """wf_hip_multi_push_pcm: SpectrumBatch.push_pcm with global stream indices (host numpy arrays only)"""
+        if frames is not None or slot is not None or not isinstance(samples, np.ndarray):
+            raise ValueError("a group takes host numpy packets without per-stream frame counts")
+        pcm, count, keep = _pcm(samples, interleaved, channel_base, None, None)
+        self._ck(self.L.wf_hip_multi_push_pcm(self.m, first, count, C.byref(pcm)))
+        del keep
 
     def push_synth(self, seed: int, index0: int, frames: int, first: int = 0, count: int | None = None, stream_id0: int = 0):
         count = self.streams - first if count is None else count

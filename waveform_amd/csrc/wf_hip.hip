@@ -17,6 +17,7 @@
 #include "wf_hip_internal.hpp"
 #include "wf_geometry.hpp"
 #include "wf_ring.hpp"
+#include "wf_pcm.hpp"
 #include "wf_meter.hpp"
 #include "wf_rms.hpp"
 #include "wf_wave.hpp"
@@ -397,6 +398,140 @@ int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, c
     return WF_HIP_OK;
 }
 
+// ---- wf_hip_push_pcm ----------------------------------------------------------------------------------------------------
+uint32_t pcm_sample_bytes(uint32_t format)
+{
+    const uint32_t base = (format - 1u) & 3u; // u8, s16, s32, f32
+    return base == 0 ? 1u : base == 1 ? 2u : 4u;
+}
+
+using PcmLaunch = void (*)(dim3, hipStream_t, const wf::PcmPushArgs &);
+template<uint32_t Fmt, bool Interleaved, bool Ragged>
+void launch_pcm(dim3 grid, hipStream_t stream, const wf::PcmPushArgs &a)
+{
+    hipLaunchKernelGGL((wf::ring_push_pcm_kernel<Fmt, Interleaved, Ragged>), grid, dim3(wf::PCM_THREADS), 0, stream, a);
+}
+template<bool Interleaved, bool Ragged>
+PcmLaunch pcm_launcher_of(uint32_t base)
+{
+    switch(base) {
+    case WF_HIP_PCM_U8: return launch_pcm<WF_HIP_PCM_U8, Interleaved, Ragged>;
+    case WF_HIP_PCM_S16: return launch_pcm<WF_HIP_PCM_S16, Interleaved, Ragged>;
+    case WF_HIP_PCM_S32: return launch_pcm<WF_HIP_PCM_S32, Interleaved, Ragged>;
+    default: return launch_pcm<WF_HIP_PCM_F32, Interleaved, Ragged>;
+    }
+}
+PcmLaunch pcm_launcher(uint32_t format, bool ragged)
+{
+    const bool inter = format <= WF_HIP_PCM_F32;
+    const uint32_t base = inter ? format : format - 4u;
+    return inter ? (ragged ? pcm_launcher_of<true, true>(base) : pcm_launcher_of<true, false>(base))
+                 : (ragged ? pcm_launcher_of<false, true>(base) : pcm_launcher_of<false, false>(base));
+}
+
+// the descriptor's rules (include/wf_hip.h); nothing is enqueued before they hold
+int pcm_check(wf_hip *h, uint32_t count, const wf_hip_pcm *pcm)
+{
+    if(pcm == nullptr || pcm->data == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "pcm or pcm->data is NULL");
+    if(pcm->format < WF_HIP_PCM_U8 || pcm->format > WF_HIP_PCM_F32_PLANAR)
+        return fail(h, WF_HIP_ERR_INVALID, "format %u is not a wf_hip_pcm_format", pcm->format);
+    if(pcm->channels < 1 || pcm->channels > 8)
+        return fail(h, WF_HIP_ERR_INVALID, "%u channels: a packet has 1..8", pcm->channels);
+    if(pcm->channels < h->cap_ch || pcm->channel_base > pcm->channels - h->cap_ch || (h->cap_ch > 1 && pcm->channel_base != 0))
+        return fail(h, WF_HIP_ERR_INVALID, "cannot capture %u channel(s) from channel %u of a %u-channel packet", h->cap_ch, pcm->channel_base,
+                    pcm->channels);
+    if(pcm->memory > WF_HIP_PCM_DEVICE || (pcm->memory == WF_HIP_PCM_PINNED && pcm->slot > 1))
+        return fail(h, WF_HIP_ERR_INVALID, "memory %u / slot %u: expected host, pinned with slot 0 / 1, or device", pcm->memory, pcm->slot);
+    if(pcm->memory == WF_HIP_PCM_DEVICE && (uintptr_t)pcm->data % pcm_sample_bytes(pcm->format))
+        return fail(h, WF_HIP_ERR_INVALID, "device data is not aligned to its sample size");
+    if(pcm->frames_per_stream) {
+        if(pcm->memory != WF_HIP_PCM_PINNED || pcm->frames == 0)
+            return fail(h, WF_HIP_ERR_INVALID, "a ragged push needs WF_HIP_PCM_PINNED memory and frames (max_frames) > 0");
+        if(rms_follows_audio(h))
+            return fail(h, WF_HIP_ERR_INVALID, "ragged pushes are not available while the device RMS producer follows the audio (wf_hip_enable_input_rms)");
+        if(count > 65535u)
+            return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
+    } else if(rms_follows_audio(h) && pcm->frames > h->rms_cap)
+        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", pcm->frames, h->rms_cap);
+    return WF_HIP_OK;
+}
+
+int ensure_copy_stream(wf_hip *h)
+{
+    if(h->copy_stream != nullptr)
+        return WF_HIP_OK;
+    WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    for(int i = 0; i < 2; ++i) {
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_consumed[i], hipEventDisableTiming));
+    }
+    return WF_HIP_OK;
+}
+
+// the H2D copy of a host packet into `dst`: interleaved (or every plane captured) in one piece; planar with more channels than
+// captured: only the captured planes, one 2-D copy over the streams.  Returns the staged layout's channel count and base.
+hipError_t pcm_copy(wf_hip *h, void *dst, const wf_hip_pcm *pcm, uint32_t count, hipStream_t stream, uint32_t *channels, uint32_t *base)
+{
+    const size_t plane = (size_t)pcm->frames * pcm_sample_bytes(pcm->format);
+    const size_t block = plane * pcm->channels;
+    if(pcm->format <= WF_HIP_PCM_F32 || pcm->channels == h->cap_ch) {
+        *channels = pcm->channels;
+        *base = pcm->channel_base;
+        return hipMemcpyAsync(dst, pcm->data, block * count, hipMemcpyHostToDevice, stream);
+    }
+    *channels = h->cap_ch;
+    *base = 0;
+    return hipMemcpy2DAsync(dst, plane * h->cap_ch, static_cast<const unsigned char *>(pcm->data) + plane * pcm->channel_base, block,
+                            plane * h->cap_ch, count, hipMemcpyHostToDevice, stream);
+}
+
+// the append: ring_push_pcm_kernel over the (staged) packet, then what push_common runs behind ring_push_kernel
+int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm, const void *d_src, uint32_t channels, uint32_t base,
+               const uint32_t *d_frames)
+{
+    const bool ragged = d_frames != nullptr;
+    const uint32_t bps = pcm_sample_bytes(pcm->format), frames = pcm->frames;
+    wf::PcmPushArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.cap_ch = h->cap_ch;
+    a.block_bytes = (size_t)channels * frames * bps;
+    a.channels = channels;
+    a.base = base;
+    a.frames = frames;
+    a.frames_per_stream = d_frames;
+    a.rms_ring = rms_follows_audio(h) ? h->d_rms_ring : nullptr;
+    a.rms_cap = h->rms_cap;
+    const PcmLaunch launch = pcm_launcher(pcm->format, ragged);
+    if(ragged) {
+        a.first = first;
+        a.src = static_cast<const unsigned char *>(d_src);
+        launch(dim3(1, count), h->stream, a);
+        WF_HIP_TRY(h, hipGetLastError());
+        return WF_HIP_OK;
+    }
+    const uint32_t tile = pcm->format <= WF_HIP_PCM_F32 ? wf::PCM_TILE / (channels * bps) : wf::PCM_TILE / bps;
+    const uint32_t tiles = (uint32_t)std::min<size_t>(((size_t)frames + tile - 1) / tile, 64);
+    for(uint32_t off = 0; off < count; off += PUSH_SLICE) {
+        const uint32_t cnt = std::min(PUSH_SLICE, count - off);
+        a.first = first + off;
+        a.src = static_cast<const unsigned char *>(d_src) + (size_t)off * a.block_bytes;
+        launch(dim3(tiles, cnt), h->stream, a);
+        if(a.rms_ring)
+            rms_after_push(h, first + off, cnt, frames);
+    }
+    hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
+                       h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
+    WF_HIP_TRY(h, hipGetLastError());
+    if(frames % 4u)
+        h->all_aligned = false;
+    return WF_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -729,6 +864,82 @@ int wf_hip_push_synth(wf_hip *h, uint32_t first, uint32_t count, uint64_t seed, 
                        h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
     WF_HIP_TRY(h, hipGetLastError());
     if(frames % 4u)
+        h->all_aligned = false;
+    return WF_HIP_OK;
+}
+
+int wf_hip_push_pcm(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm)
+{
+    if(h == nullptr)
+        return WF_HIP_ERR_INVALID;
+    WF_TRY_RC(pcm_check(h, count, pcm));
+    WF_TRY_RC(check_range(h, first, count));
+    const bool ragged = pcm->frames_per_stream != nullptr;
+    if(pcm->frames == 0)
+        return WF_HIP_OK;
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t bps = pcm_sample_bytes(pcm->format);
+    if(pcm->memory == WF_HIP_PCM_DEVICE)
+        return pcm_append(h, first, count, pcm, pcm->data, pcm->channels, pcm->channel_base, nullptr);
+    // the bytes that cross the bus: whole frames of an interleaved packet, the captured planes of a planar one
+    const uint32_t staged_ch = pcm->format <= WF_HIP_PCM_F32 ? pcm->channels : h->cap_ch;
+    const size_t floats = ((size_t)count * staged_ch * pcm->frames * bps + 3) / 4; // (the staging blocks are the float paths')
+    uint32_t channels = 0, base = 0;
+    if(pcm->memory == WF_HIP_PCM_HOST) {
+        WF_TRY_RC(ensure_stage(h, floats)); // (ordered after the previous push's append on the same stream)
+        WF_HIP_TRY(h, pcm_copy(h, h->d_stage, pcm, count, h->stream, &channels, &base));
+        WF_TRY_RC(pcm_append(h, first, count, pcm, h->d_stage, channels, base, nullptr));
+        WF_HIP_TRY(h, hipStreamSynchronize(h->stream)); // `data` is borrowed for the call only
+        return WF_HIP_OK;
+    }
+    // WF_HIP_PCM_PINNED: wf_hip_push_audio_async's pipeline (copy stream, the slot's staging block and events)
+    const uint32_t slot = pcm->slot;
+    WF_TRY_RC(ensure_copy_stream(h));
+    if(ragged && h->slot_used[slot])
+        WF_HIP_TRY(h, hipEventSynchronize(h->ev_consumed[slot])); // the slot's frame counts are free again
+    if(h->stage_async_floats[slot] < floats) {
+        if(h->slot_used[slot])
+            WF_HIP_TRY(h, hipEventSynchronize(h->ev_consumed[slot])); // the old block may still feed an append
+        dev_release(h, h->d_stage_async[slot]);
+        h->d_stage_async[slot] = nullptr;
+        const size_t want = grown(h->stage_async_floats[slot], floats);
+        h->stage_async_floats[slot] = 0;
+        float *p = nullptr;
+        WF_TRY_RC(dev_alloc(h, &p, want));
+        h->d_stage_async[slot] = p;
+        h->stage_async_floats[slot] = want;
+    }
+    bool aligned = true;
+    if(ragged) {
+        if(h->frames_async_cap[slot] < count) {
+            dev_release(h, h->d_frames_async[slot]);
+            h->d_frames_async[slot] = nullptr;
+            if(h->h_frames_async[slot])
+                (void)hipHostFree(h->h_frames_async[slot]);
+            h->h_frames_async[slot] = nullptr;
+            h->frames_async_cap[slot] = 0;
+            const size_t want = std::max<size_t>(count, 64);
+            WF_TRY_RC(dev_alloc(h, &h->d_frames_async[slot], want));
+            WF_HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_frames_async[slot]), want * sizeof(uint32_t), hipHostMallocDefault));
+            h->frames_async_cap[slot] = want;
+        }
+        for(uint32_t i = 0; i < count; ++i) {
+            h->h_frames_async[slot][i] = pcm->frames_per_stream[i];
+            aligned = aligned && (pcm->frames_per_stream[i] % 4u) == 0;
+        }
+    }
+    if(h->slot_used[slot])
+        WF_HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_consumed[slot], 0));
+    WF_HIP_TRY(h, pcm_copy(h, h->d_stage_async[slot], pcm, count, h->copy_stream, &channels, &base));
+    if(ragged)
+        WF_HIP_TRY(h, hipMemcpyAsync(h->d_frames_async[slot], h->h_frames_async[slot], (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                     h->copy_stream));
+    WF_HIP_TRY(h, hipEventRecord(h->ev_copied[slot], h->copy_stream));
+    WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
+    WF_TRY_RC(pcm_append(h, first, count, pcm, h->d_stage_async[slot], channels, base, ragged ? h->d_frames_async[slot] : nullptr));
+    WF_HIP_TRY(h, hipEventRecord(h->ev_consumed[slot], h->stream));
+    h->slot_used[slot] = true;
+    if(!aligned)
         h->all_aligned = false;
     return WF_HIP_OK;
 }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "wf_hip.h"
+#include "wf_hip_multi_shards.hpp"
 
 namespace {
 
@@ -445,6 +446,23 @@ void destroy_impl(wf_hip_multi *m)
 }
 
 } // namespace
+
+int wf::multi::for_each_shard(wf_hip_multi *m, uint32_t first, uint32_t count,
+                              const std::function<int(wf_hip *, uint32_t, uint32_t, uint32_t)> &fn)
+{
+    int rc = check_range(m, first, count);
+    if(rc)
+        return rc;
+    return run_all(m, [&](uint32_t i) {
+        Shard &s = *m->shard[i];
+        uint32_t lf, lc, off;
+        if(!overlap(s, first, count, &lf, &lc, &off))
+            return (int)WF_HIP_OK;
+        return fn(s.h, lf, lc, off);
+    });
+}
+
+int wf::multi::fail(wf_hip_multi *m, int code, const char *msg) { return mfail(m, code, "%s", msg); }
 
 extern "C" {
 
