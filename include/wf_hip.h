@@ -29,6 +29,9 @@
  *   wf_hip_enable_input_rms
  *                        capture_audio's RMS part + sync_rms_buffer + update_input_rms
  *                        (src/source.cpp:1842-1871, :810-835; src/source_generic.cpp:392-403)
+ *   wf_hip_enable_loudness
+ *                        not in the reference: BS.1770-4 / EBU R128 loudness and true peak of every stream, measured as
+ *                        the pushes arrive (WF_HIP_OUT_LOUDNESS)
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -266,6 +269,51 @@ int wf_hip_enable_input_rms(wf_hip *h, int feed);
  * wf_hip_push_audio*_async: wf_hip_ingest_done(slot) says when `sq` may be written again. */
 int wf_hip_push_rms_ragged_async(wf_hip *h, uint32_t first, uint32_t count, const float *pinned_sq, const uint32_t *frames,
                                  uint32_t max_frames, uint32_t slot);
+/* ---- loudness (ITU-R BS.1770-4 / EBU R128, EBU Tech 3341 / 3342) --------------------------------------------------------
+ * An opt-in producer that follows the audio rings: once enabled, every frame any push appends to a stream (wf_hip_push_audio*,
+ * wf_hip_push_synth, wf_hip_push_pcm, and the wf_hip_multi_push_* calls through their shards) is measured exactly once, in
+ * push order, by one kernel launch per push.  Definitions (per stream):
+ *   channels     the captured channels (1 or 2), each with weight 1.0 (a mono handle reads 3.01 LU below the same signal
+ *                captured as dual-mono stereo)
+ *   K-weighting  the BS.1770-4 shelf, then the RLB high-pass: bilinear transforms (pre-warped) of the analogue prototypes
+ *                behind Tables 1 and 2, derived on the host for the batch's rate (equal to the tables at 48 kHz); float64
+ *   loudness     L = -0.691 + 10 log10(sum over channels of the mean square)
+ *   sub-blocks   100 ms = sample_rate / 10 frames, counted from enable / reset; momentary = the last 4 complete sub-blocks,
+ *                short-term = the last 30.  At every completed sub-block, once 4 exist, the 400 ms block enters the integrated
+ *                set; once 30 exist, the 3 s block enters the range set (a 100 ms hop for both)
+ *   gating sets  two histograms per stream of 800 bins of 0.1 LU from -70 LUFS: bin b holds blocks with
+ *                -70 + 0.1 b <= L < -70 + 0.1 (b + 1) (blocks above +10 LUFS go to the last bin), each bin a count and a float64
+ *                energy sum.  Only blocks with L > -70 LUFS (the absolute gate) enter.  A bin passes a relative gate when its
+ *                centre (-70 + 0.1 (b + 0.5)) lies above the gate.
+ *   integrated   the mean energy of the bins above the relative gate (-10 LU below the mean of the set)
+ *   range        EBU Tech 3342: over the bins above -20 LU below the mean of the range set, the nearest-rank P95 minus P10,
+ *                each taken as its bin's centre
+ *   true peak    BS.1770-4 Annex 2 style: 4x oversampling by a 48-tap linear-phase polyphase FIR (4 phases of 12 taps, a
+ *                Kaiser-windowed sinc, beta 7, cut-off at the input's Nyquist frequency, each phase scaled to unit DC gain),
+ *                the largest |value| of the oversampled signal and of the samples themselves, since enable / reset.  The
+ *                last 11 samples of every channel are kept, so a packet boundary changes nothing.
+ * Determinism: no float atomics, fixed-order reductions; the same frames in the same packets give bit-identical readings. */
+typedef struct wf_hip_loudness {
+    float momentary;   /* LUFS, the last 400 ms */
+    float short_term;  /* LUFS, the last 3 s */
+    float integrated;  /* LUFS, gated (-70 LUFS absolute, -10 LU relative) */
+    float range;       /* LU, EBU Tech 3342 (-70 LUFS absolute, -20 LU relative, P95 - P10) */
+    float true_peak;   /* dBTP, the largest since enable / reset */
+    uint32_t reserved; /* 0 */
+    uint64_t frames;   /* frames measured since enable / reset */
+} wf_hip_loudness;
+/* A value with nothing to report is -INFINITY (a window not yet filled since enable / reset, an empty gated set, digital
+ * silence, a silent true peak); `range` is then 0. */
+/* (re)starts the measurement of streams [first, first+count) from the next push on: filter state, sub-blocks, histograms,
+ * true peak and frames start afresh.  The first call turns the producer on and allocates the state of every stream of the
+ * batch (the others start measuring too).  One entry point for enable and reset keeps the release ABI within its 75 exports.
+ * WF_HIP_ERR_INVALID when cfg.sample_rate % 10 != 0 (the 100 ms step must be whole frames).  Spectrum, meter and waveform
+ * batches alike.  wf_hip_reset leaves the loudness state alone (a settings change does not restart an integration).  While
+ * the producer is on, a push of more frames than the ring holds (wf_hip_ring_frames) is refused with WF_HIP_ERR_INVALID
+ * before anything is enqueued.  A multi-device group: call it on each shard (wf_hip_multi_shard) with local indices;
+ * WF_HIP_OUT_LOUDNESS is read through wf_hip_multi_read. */
+int wf_hip_enable_loudness(wf_hip *h, uint32_t first, uint32_t count);
+
 /* waits for everything the handle has issued.  With WF_HIP_CANARY=1 in the environment of wf_hip_create every device block of the
  * handle ends in guard bytes, which this call then reads back: a kernel that wrote past a buffer makes it return
  * WF_HIP_ERR_RUNTIME with the block named in wf_hip_last_error (a debugging aid: one small copy per block and sync) */
@@ -298,9 +346,11 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_TSMOOTH,        /* float [capture_channels][fft_size/2]       m_tsmooth_buf (spectrum batches) */
     WF_HIP_OUT_METER,          /* float [capture_channels]                   meter batches: m_meter_val (dBFS) */
     WF_HIP_OUT_INPUT_RMS,      /* float                                      m_input_rms as of the last tick (wf_hip_enable_input_rms) */
-    WF_HIP_OUT_WAVEFORM_TS     /* uint64                                     waveform batches: m_waveform_ts (src/source.hpp:135, the timestamp of
+    WF_HIP_OUT_WAVEFORM_TS,    /* uint64                                     waveform batches: m_waveform_ts (src/source.hpp:135, the timestamp of
                                   the next point the sweep will draw, ns) -- what a source needs to continue the sweep on the host
                                   (src/source_generic.cpp:318-353) when it leaves a batch */
+    WF_HIP_OUT_LOUDNESS        /* wf_hip_loudness                            the loudness producer's readings (wf_hip_enable_loudness) as of the
+                                  pushes issued so far; 0 bytes while the producer is off */
 } wf_hip_output;
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);

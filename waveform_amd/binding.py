@@ -58,7 +58,8 @@ TICK_NO_DECIBELS = 1
 
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
-OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS = range(10)
+OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
+    OUT_LOUDNESS = range(11)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -105,6 +106,18 @@ def _pcm(samples, interleaved: bool, channel_base: int, frames, slot):
         keep.append(f)
         pcm.frames_per_stream = f.ctypes.data_as(C.POINTER(C.c_uint32))
     return pcm, count, keep
+
+
+class Loudness(C.Structure):
+    """struct wf_hip_loudness (include/wf_hip.h): one stream's loudness readings."""
+    _fields_ = [("momentary", C.c_float), ("short_term", C.c_float), ("integrated", C.c_float), ("range", C.c_float),
+                ("true_peak", C.c_float), ("reserved", C.c_uint32), ("frames", C.c_uint64)]
+
+
+LOUDNESS_DTYPE = np.dtype({"names": [n for n, _ in Loudness._fields_],
+                           "formats": [np.float32] * 5 + [np.uint32, np.uint64],
+                           "offsets": [getattr(Loudness, n).offset for n, _ in Loudness._fields_],
+                           "itemsize": C.sizeof(Loudness)})
 
 
 class Readback(C.Structure):
@@ -158,6 +171,7 @@ def lib():
     L.wf_hip_multi_push_pcm.argtypes = [vp, u32, u32, C.POINTER(Pcm)]
     L.wf_hip_push_audio_muted.argtypes = [vp, u32, u32, fp, u32]
     L.wf_hip_enable_input_rms.argtypes = [vp, C.c_int]
+    L.wf_hip_enable_loudness.argtypes = [vp, u32, u32]
     L.wf_hip_tick.argtypes = [vp, C.POINTER(TickParams)]
     L.wf_hip_set_hidden.argtypes = [vp, u32, u32, C.POINTER(C.c_uint8)]
     L.wf_hip_set_input_rms.argtypes = [vp, u32, u32, fp]
@@ -303,6 +317,21 @@ class SpectrumBatch:
     def input_rms(self, first: int = 0, count: int | None = None) -> np.ndarray:
         count = self.streams - first if count is None else count
         return self._read(OUT_INPUT_RMS, first, count, (), np.float32)
+
+    def enable_loudness(self):
+        """BS.1770-4 / EBU R128 loudness and true peak of every stream, measured from the next push on"""
+        self._ck(self.L.wf_hip_enable_loudness(self.h, 0, self.streams))
+
+    def reset_loudness(self, first: int = 0, count: int | None = None):
+        """restarts the measurement of streams [first, first+count) (the producer must be on)"""
+        count = self.streams - first if count is None else count
+        if int(self.L.wf_hip_output_bytes(self.h, OUT_LOUDNESS)) == 0:
+            raise WfHipError(-1, "the loudness producer is not enabled (enable_loudness)")
+        self._ck(self.L.wf_hip_enable_loudness(self.h, first, count))
+
+    def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array with the fields of wf_hip_loudness (LOUDNESS_DTYPE)"""
+        return self._read(OUT_LOUDNESS, first, count, (), LOUDNESS_DTYPE)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -630,6 +659,28 @@ class MultiBatch:
         count = self.streams - first if count is None else count
         out = np.empty((count, self.display_channels, self.num_bars), np.float32)
         self._ck(self.L.wf_hip_multi_read(self.m, OUT_BARS, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def _loudness_on_shards(self, first: int, count: int):
+        """wf_hip_enable_loudness on every shard the global range overlaps, with local indices"""
+        for h, _, s0, n in self.shards:
+            lo, hi = max(first, s0), min(first + count, s0 + n)
+            if lo < hi and self.L.wf_hip_enable_loudness(h, lo - s0, hi - lo) != 0:
+                raise WfHipError(-1, self.L.wf_hip_last_error(h).decode())
+
+    def enable_loudness(self):
+        self._loudness_on_shards(0, self.streams)
+
+    def reset_loudness(self, first: int = 0, count: int | None = None):
+        count = self.streams - first if count is None else count
+        if int(self.L.wf_hip_output_bytes(self.shards[0][0], OUT_LOUDNESS)) == 0:
+            raise WfHipError(-1, "the loudness producer is not enabled (enable_loudness)")
+        self._loudness_on_shards(first, count)
+
+    def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = self.streams - first if count is None else count
+        out = np.empty(count, LOUDNESS_DTYPE)
+        self._ck(self.L.wf_hip_multi_read(self.m, OUT_LOUDNESS, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:

@@ -20,6 +20,7 @@
 #include "wf_pcm.hpp"
 #include "wf_meter.hpp"
 #include "wf_rms.hpp"
+#include "wf_loudness.hpp"
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
@@ -368,6 +369,39 @@ void rms_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames)
                        h->d_rms_bsum, h->d_wpos, h->rms_cap, first, frames);
 }
 
+// the loudness producer (wf_hip_enable_loudness) follows every push: one launch behind the write positions' advance over
+// the frames the push appended, ring[wpos - n, wpos) (d_frames: a ragged push's per-stream counts, capped at `frames`)
+inline bool loudness_on(const wf_hip *h) { return h->d_loud != nullptr; }
+
+// ring trimming would drop frames from the measurement: while the producer is on, nothing longer than the ring is taken
+int loudness_check(wf_hip *h, uint32_t frames)
+{
+    if(loudness_on(h) && frames > h->ring_cap)
+        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the ring capacity %u while the loudness producer is on", frames, h->ring_cap);
+    return WF_HIP_OK;
+}
+
+void loudness_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, const uint32_t *d_frames)
+{
+    if(!loudness_on(h) || frames == 0)
+        return;
+    wf::LoudPushArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.frames_per_stream = d_frames;
+    a.state = h->d_loud;
+    a.hist = h->d_loud_hist;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.first = first;
+    a.frames = frames;
+    a.k = h->loud_k;
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::loudness_push_kernel<2>, dim3(count), dim3(128), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::loudness_push_kernel<1>, dim3(count), dim3(64), 0, h->stream, a);
+}
+
 // d_src feeds the audio rings (nullptr: zeros); d_rms_src feeds the squared-peak ring when the producer is enabled
 // (capture_audio takes the RMS from the packet even when it is muted, src/source.cpp:1842-1871 vs :1879-1880)
 int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, const float *d_rms_src, uint32_t frames)
@@ -377,6 +411,7 @@ int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, c
     // a packet longer than the ring keeps its newest ring_cap frames, as CircularBuffer + capture_audio's trimming would
     if(rms_follows_audio(h) && frames > h->rms_cap)
         return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", frames, h->rms_cap);
+    WF_TRY_RC(loudness_check(h, frames));
     // the kernels index (stream, channel) rows by blockIdx.y (at most 65535): larger batches go in slices
     for(uint32_t off = 0; off < count; off += PUSH_SLICE) {
         const uint32_t cnt = std::min(PUSH_SLICE, count - off);
@@ -392,6 +427,7 @@ int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, c
     }
     hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
                        h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
+    loudness_after_push(h, first, count, frames, nullptr);
     WF_HIP_TRY(h, hipGetLastError());
     if(frames % 4u)
         h->all_aligned = false;
@@ -452,8 +488,12 @@ int pcm_check(wf_hip *h, uint32_t count, const wf_hip_pcm *pcm)
             return fail(h, WF_HIP_ERR_INVALID, "ragged pushes are not available while the device RMS producer follows the audio (wf_hip_enable_input_rms)");
         if(count > 65535u)
             return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
+        for(uint32_t i = 0; i < count; ++i)
+            WF_TRY_RC(loudness_check(h, std::min(pcm->frames_per_stream[i], pcm->frames)));
     } else if(rms_follows_audio(h) && pcm->frames > h->rms_cap)
         return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", pcm->frames, h->rms_cap);
+    else
+        WF_TRY_RC(loudness_check(h, pcm->frames));
     return WF_HIP_OK;
 }
 
@@ -511,6 +551,7 @@ int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm,
         a.first = first;
         a.src = static_cast<const unsigned char *>(d_src);
         launch(dim3(1, count), h->stream, a);
+        loudness_after_push(h, first, count, frames, d_frames);
         WF_HIP_TRY(h, hipGetLastError());
         return WF_HIP_OK;
     }
@@ -526,6 +567,7 @@ int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm,
     }
     hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
                        h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
+    loudness_after_push(h, first, count, frames, nullptr);
     WF_HIP_TRY(h, hipGetLastError());
     if(frames % 4u)
         h->all_aligned = false;
@@ -742,6 +784,8 @@ int wf_hip_push_audio_ragged_async(wf_hip *h, uint32_t first, uint32_t count, co
         return fail(h, WF_HIP_ERR_INVALID, "ragged pushes are not available while the device RMS producer follows the audio (wf_hip_enable_input_rms)");
     if(count > 65535u)
         return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
+    for(uint32_t i = 0; i < count; ++i)
+        WF_TRY_RC(loudness_check(h, std::min(frames[i], max_frames)));
     WF_HIP_TRY(h, hipSetDevice(h->device));
     if(h->copy_stream == nullptr) {
         WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
@@ -792,6 +836,7 @@ int wf_hip_push_audio_ragged_async(wf_hip *h, uint32_t first, uint32_t count, co
     hipLaunchKernelGGL(wf::ring_push_ragged_kernel, dim3(1, count), dim3(256), 0, h->stream, h->d_ring, h->d_wpos,
                        h->d_flags + (size_t)h->flag_cur * h->n_streams, h->ring_cap, h->ring_stride, h->cap_ch, first, h->d_stage_async[slot],
                        h->d_frames_async[slot], max_frames);
+    loudness_after_push(h, first, count, max_frames, h->d_frames_async[slot]);
     WF_HIP_TRY(h, hipGetLastError());
     WF_HIP_TRY(h, hipEventRecord(h->ev_consumed[slot], h->stream));
     h->slot_used[slot] = true;
@@ -848,6 +893,7 @@ int wf_hip_push_synth(wf_hip *h, uint32_t first, uint32_t count, uint64_t seed, 
         return WF_HIP_OK;
     if(rms_follows_audio(h) && frames > h->rms_cap)
         return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", frames, h->rms_cap);
+    WF_TRY_RC(loudness_check(h, frames));
     WF_HIP_TRY(h, hipSetDevice(h->device));
     const uint32_t gx = std::min<uint32_t>((frames + 255) / 256, 256);
     for(uint32_t off = 0; off < count; off += PUSH_SLICE) {
@@ -862,6 +908,7 @@ int wf_hip_push_synth(wf_hip *h, uint32_t first, uint32_t count, uint64_t seed, 
     }
     hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
                        h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
+    loudness_after_push(h, first, count, frames, nullptr);
     WF_HIP_TRY(h, hipGetLastError());
     if(frames % 4u)
         h->all_aligned = false;
@@ -1299,6 +1346,43 @@ static int enable_rms_producer(wf_hip *h, bool feed)
 
 int wf_hip_enable_input_rms(wf_hip *h, int feed) { return enable_rms_producer(h, feed != 0); }
 
+static int clear_loudness(wf_hip *h, uint32_t first, uint32_t count)
+{
+    WF_HIP_TRY(h, hipMemsetAsync(h->d_loud + first, 0, (size_t)count * sizeof(wf::LoudState), h->stream));
+    WF_HIP_TRY(h, hipMemsetAsync(h->d_loud_hist + (size_t)first * 2, 0, (size_t)count * 2 * sizeof(wf::LoudHist), h->stream));
+    return WF_HIP_OK;
+}
+
+int wf_hip_enable_loudness(wf_hip *h, uint32_t first, uint32_t count)
+{
+    WF_TRY_RC(check_range(h, first, count));
+    if(h->d_loud) { // on already: restart the range
+        WF_HIP_TRY(h, hipSetDevice(h->device));
+        WF_TRY_RC(clear_loudness(h, first, count));
+        h->main_dirty = true;
+        return WF_HIP_OK;
+    }
+    if(h->cfg.sample_rate % 10 != 0 || h->cfg.sample_rate == 0)
+        return fail(h, WF_HIP_ERR_INVALID, "sample_rate %u: the loudness producer's 100 ms step must be whole frames", h->cfg.sample_rate);
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    WF_TRY_RC(join_lanes(h));
+    wf::LoudState *st = nullptr;
+    wf::LoudHist *hist = nullptr;
+    wf_hip_loudness *out = nullptr;
+    int rc = dev_alloc(h, &st, h->n_streams);
+    if(rc == WF_HIP_OK) rc = dev_alloc(h, &hist, (size_t)h->n_streams * 2);
+    if(rc == WF_HIP_OK) rc = dev_alloc(h, &out, h->n_streams);
+    if(rc)
+        return rc;
+    h->loud_k = wf::host::loudness_coefs(h->cfg.sample_rate);
+    h->d_loud = st;
+    h->d_loud_hist = hist;
+    h->d_loud_out = out; // from here on every push feeds the producer
+    WF_TRY_RC(clear_loudness(h, 0, h->n_streams));
+    h->main_dirty = true;
+    return WF_HIP_OK;
+}
+
 int wf_hip_push_rms_ragged_async(wf_hip *h, uint32_t first, uint32_t count, const float *pinned_sq, const uint32_t *frames, uint32_t max_frames,
                                  uint32_t slot)
 {
@@ -1699,6 +1783,10 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         static_assert(sizeof(unsigned long long) == sizeof(uint64_t));
         *per_stream = sizeof(uint64_t);
         return h->d_wts;
+    case WF_HIP_OUT_LOUDNESS:
+        if(h->d_loud_out == nullptr) { *why = "the loudness producer is not enabled (wf_hip_enable_loudness)"; return nullptr; }
+        *per_stream = sizeof(wf_hip_loudness);
+        return h->d_loud_out;
     }
     *why = "unknown output";
     return nullptr;
@@ -1725,6 +1813,12 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
         return fail(h, WF_HIP_ERR_INVALID, "%s", why);
     if(out == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL");
+    if(what == WF_HIP_OUT_LOUDNESS) { // the readings are made from the state when asked for, behind the pushes issued so far
+        WF_HIP_TRY(h, hipSetDevice(h->device));
+        hipLaunchKernelGGL(wf::loudness_read_kernel, dim3(count), dim3(64), 0, h->stream, h->d_loud, h->d_loud_hist, h->d_loud_out, first,
+                           h->loud_k.sub_frames);
+        WF_HIP_TRY(h, hipGetLastError());
+    }
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
         rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));

@@ -11,8 +11,11 @@
 #include <vector>
 
 #include "wf_hip.h"
+
+namespace wf { struct LoudState; struct LoudHist; }
 #include "wf_dev_guard.hpp"
 #include "wf_host_tables.hpp"
+#include "wf_loudness_tables.hpp"
 #include "wf_tick_phases.hpp" // TickArgs, BarsOnlyState (plain structs: no kernel is instantiated by including it)
 
 struct wf_hip {
@@ -141,6 +144,11 @@ struct wf_hip {
     hipEvent_t ev_sq_consumed[2] = {nullptr, nullptr};
     bool sq_slot_used[2] = {false, false};
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
+    // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), nullptr while it is off
+    struct wf::LoudState *d_loud = nullptr;       // [n_streams]
+    struct wf::LoudHist *d_loud_hist = nullptr;   // [n_streams][2]: integrated, range
+    wf_hip_loudness *d_loud_out = nullptr;        // [n_streams] what the last wf_hip_read(WF_HIP_OUT_LOUDNESS) computed
+    wf::LoudCoefs loud_k{};
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;
