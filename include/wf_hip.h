@@ -32,6 +32,8 @@
  *   wf_hip_enable_loudness
  *                        not in the reference: BS.1770-4 / EBU R128 loudness and true peak of every stream, measured as
  *                        the pushes arrive (WF_HIP_OUT_LOUDNESS)
+ *   WF_HIP_OUT_PEAKS     not in the reference: the strongest spectral peaks of every m_decibels row, found on the device
+ *                        when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -349,9 +351,35 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_WAVEFORM_TS,    /* uint64                                     waveform batches: m_waveform_ts (src/source.hpp:135, the timestamp of
                                   the next point the sweep will draw, ns) -- what a source needs to continue the sweep on the host
                                   (src/source_generic.cpp:318-353) when it leaves a batch */
-    WF_HIP_OUT_LOUDNESS        /* wf_hip_loudness                            the loudness producer's readings (wf_hip_enable_loudness) as of the
+    WF_HIP_OUT_LOUDNESS,       /* wf_hip_loudness                            the loudness producer's readings (wf_hip_enable_loudness) as of the
                                   pushes issued so far; 0 bytes while the producer is off */
+    WF_HIP_OUT_PEAKS           /* wf_hip_peaks [output_channels]             the strongest peaks of each m_decibels row as of the newest tick
+                                  (spectrum batches; definition below) */
 } wf_hip_output;
+/* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
+ * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
+ *   candidate      bin k with 1 <= k <= M-2, d[k] > d[k-1], d[k] >= d[k+1] and d[k] > cfg.floor_db
+ *   order          d[k] descending, equal values lower k first; the first WF_HIP_MAX_PEAKS are kept.  Selection and order use
+ *                  the row's values only, so a host that holds the row reproduces them exactly.
+ *   interpolation  the parabola through a = d[k-1], b = d[k], c = d[k+1]: p = 0.5 (a - c) / (a - 2b + c) (the denominator is
+ *                  strictly negative, so -0.5 < p <= 0.5), hz = (k + p) sample_rate / fft_size, db = b - 0.25 (a - c) p;
+ *                  computed in float64 from the float32 row and rounded to float32 once.
+ * The peaks describe the rows the batch displays, after slope, smoothing, volume normalisation and roll-off, and the search
+ * covers the whole row, not only the cutoff range.  A stream whose row holds no candidate -- hidden, freshly created or
+ * reset (rows at DB_MIN), silent with rows at or below the floor -- has count 0.  After WF_HIP_TICK_NO_DECIBELS ticks the
+ * peaks are as stale as the rows.  The peaks are computed when read, by one kernel behind the ticks issued so far, into a
+ * block the first read allocates: a handle whose peaks are never read pays nothing.  Meter and waveform batches: wf_hip_read
+ * returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads them through wf_hip_multi_read. */
+#define WF_HIP_MAX_PEAKS 8
+typedef struct wf_hip_peak {
+    float hz;
+    float db;
+} wf_hip_peak;
+typedef struct wf_hip_peaks {
+    uint32_t count;                     /* valid entries, 0..WF_HIP_MAX_PEAKS */
+    uint32_t reserved;                  /* 0 */
+    wf_hip_peak peak[WF_HIP_MAX_PEAKS]; /* strongest first; unused entries: hz 0, db -INFINITY */
+} wf_hip_peaks;                         /* 72 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

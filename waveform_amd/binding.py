@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS = range(11)
+    OUT_LOUDNESS, OUT_PEAKS = range(12)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -118,6 +118,12 @@ LOUDNESS_DTYPE = np.dtype({"names": [n for n, _ in Loudness._fields_],
                            "formats": [np.float32] * 5 + [np.uint32, np.uint64],
                            "offsets": [getattr(Loudness, n).offset for n, _ in Loudness._fields_],
                            "itemsize": C.sizeof(Loudness)})
+
+
+# struct wf_hip_peaks (include/wf_hip.h): the strongest peaks of one m_decibels row
+MAX_PEAKS = 8
+PEAKS_DTYPE = np.dtype([("count", np.uint32), ("reserved", np.uint32),
+                        ("peak", np.dtype([("hz", np.float32), ("db", np.float32)]), (MAX_PEAKS,))])
 
 
 class Readback(C.Structure):
@@ -332,6 +338,11 @@ class SpectrumBatch:
     def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array with the fields of wf_hip_loudness (LOUDNESS_DTYPE)"""
         return self._read(OUT_LOUDNESS, first, count, (), LOUDNESS_DTYPE)
+
+    def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count, output_channels] structured array of wf_hip_peaks (PEAKS_DTYPE): the strongest peaks of each m_decibels row
+        as of the newest tick, found on the device when read"""
+        return self._read(OUT_PEAKS, first, count, (self.output_channels,), PEAKS_DTYPE)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -681,6 +692,12 @@ class MultiBatch:
         count = self.streams - first if count is None else count
         out = np.empty(count, LOUDNESS_DTYPE)
         self._ck(self.L.wf_hip_multi_read(self.m, OUT_LOUDNESS, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = self.streams - first if count is None else count
+        out = np.empty((count, self.output_channels), PEAKS_DTYPE)
+        self._ck(self.L.wf_hip_multi_read(self.m, OUT_PEAKS, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:

@@ -21,6 +21,7 @@
 #include "wf_meter.hpp"
 #include "wf_rms.hpp"
 #include "wf_loudness.hpp"
+#include "wf_peaks.hpp"
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
@@ -1787,9 +1788,32 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         if(h->d_loud_out == nullptr) { *why = "the loudness producer is not enabled (wf_hip_enable_loudness)"; return nullptr; }
         *per_stream = sizeof(wf_hip_loudness);
         return h->d_loud_out;
+    case WF_HIP_OUT_PEAKS: // (computed from the rows when read, into a block the first read allocates: read_peaks)
+        if(h->meter || h->wave) { *why = "meter / waveform batch: spectral peaks belong to spectrum batches"; return nullptr; }
+        *per_stream = (size_t)h->out_ch * sizeof(wf_hip_peaks);
+        return h->d_decibels;
     }
     *why = "unknown output";
     return nullptr;
+}
+
+// WF_HIP_OUT_PEAKS of streams [first, first+count): one wavefront per m_decibels row, on `stream` behind the ticks issued
+static int read_peaks(wf_hip *h, uint32_t first, uint32_t count, void *out)
+{
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    if(h->d_peaks == nullptr)
+        WF_TRY_RC(dev_alloc(h, &h->d_peaks, (size_t)h->n_streams * h->out_ch));
+    wf::PeaksArgs a{};
+    a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
+    a.out = h->d_peaks + (size_t)first * h->out_ch;
+    a.n_rows = count * h->out_ch;
+    a.M = h->M;
+    a.floor_db = (float)h->cfg.floor_db;
+    a.hz_per_bin = (double)h->cfg.sample_rate / (double)h->N;
+    hipLaunchKernelGGL(wf::peaks_read_kernel, dim3((a.n_rows + wf::WF_PEAKS_WAVES - 1) / wf::WF_PEAKS_WAVES), dim3(64 * wf::WF_PEAKS_WAVES), 0,
+                       h->stream, a);
+    WF_HIP_TRY(h, hipGetLastError());
+    return read_back(h, a.out, out, (size_t)a.n_rows * sizeof(wf_hip_peaks));
 }
 
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
@@ -1819,6 +1843,8 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
                            h->loud_k.sub_frames);
         WF_HIP_TRY(h, hipGetLastError());
     }
+    if(what == WF_HIP_OUT_PEAKS)
+        return read_peaks(h, first, count, out);
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
         rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));
