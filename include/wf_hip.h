@@ -34,6 +34,8 @@
  *                        the pushes arrive (WF_HIP_OUT_LOUDNESS)
  *   WF_HIP_OUT_PEAKS     not in the reference: the strongest spectral peaks of every m_decibels row, found on the device
  *                        when read
+ *   WF_HIP_OUT_SIGNAL    not in the reference: level, DC, clipping and stereo phase correlation of every stream's newest
+ *                        window of audio, measured on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -353,8 +355,11 @@ typedef enum wf_hip_output {
                                   (src/source_generic.cpp:318-353) when it leaves a batch */
     WF_HIP_OUT_LOUDNESS,       /* wf_hip_loudness                            the loudness producer's readings (wf_hip_enable_loudness) as of the
                                   pushes issued so far; 0 bytes while the producer is off */
-    WF_HIP_OUT_PEAKS           /* wf_hip_peaks [output_channels]             the strongest peaks of each m_decibels row as of the newest tick
+    WF_HIP_OUT_PEAKS,          /* wf_hip_peaks [output_channels]             the strongest peaks of each m_decibels row as of the newest tick
                                   (spectrum batches; definition below) */
+    WF_HIP_OUT_SIGNAL          /* wf_hip_signal                              level, DC, clipping and stereo phase of the newest
+                                  wf_hip_fft_size() frames in the rings as of the pushes issued so far (spectrum and meter
+                                  batches; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -380,6 +385,45 @@ typedef struct wf_hip_peaks {
     uint32_t reserved;                  /* 0 */
     wf_hip_peak peak[WF_HIP_MAX_PEAKS]; /* strongest first; unused entries: hz 0, db -INFINITY */
 } wf_hip_peaks;                         /* 72 bytes */
+/* ---- signal statistics (WF_HIP_OUT_SIGNAL) --------------------------------------------------------------------------------
+ * Per stream, over a window of W = wf_hip_fft_size() frames: the newest W frames of each captured channel's ring, positions
+ * (wpos - W .. wpos - 1) mod the ring's capacity of the stream's write position.  Every push issued before the read counts,
+ * whatever its path (blocking, async / pinned, ragged, device, synth, muted, wf_hip_push_pcm); the A/V-sync delay is not
+ * applied.  W is one analysis window on spectrum batches and the meter buffer on meter batches.  After create and
+ * wf_hip_reset the rings hold zeros, and a window not yet filled by pushes counts those zeros: a host that keeps a
+ * zero-prefixed history of what it pushed reproduces the read.
+ *   sums           taken in float64 over the float32 samples, l and r being captured channels 0 and 1:
+ *                  S1 = sum x, S2 = sum x^2, Slr = sum l r, Smid = sum ((l + r) / 2)^2, Sside = sum ((l - r) / 2)^2
+ *                  (l + r and l - r of two float32 values are exact in float64, so l = -r gives Smid exactly 0).  The
+ *                  reduction order is fixed and uses no atomics: the same ring contents read bit-identically.  Each field
+ *                  is computed in float64 from the sums and rounded to float32 once.
+ *   rms_db         10 log10(S2 / W) (dBFS: a full-scale sine reads -3.01)
+ *   peak_db        20 log10(max |x|)
+ *   dc             S1 / W
+ *   clipped        samples with |x| >= WF_HIP_FULL_SCALE (32767 / 32768: s16's positive extreme counts, u8's 127/128 does not)
+ *   correlation    Slr / sqrt(S2l S2r) clamped to [-1, 1]; 0 when S2l or S2r is 0
+ *   balance_db     10 log10(S2r / S2l), positive when the right channel is louder; 0 when both are 0, +-INFINITY when one is
+ *   mid_db         10 log10(Smid / W)
+ *   side_db        10 log10(Sside / W)
+ * Every dB field is -INFINITY when its sum or maximum is 0.  With one captured channel ch[1] reads {-INFINITY, -INFINITY,
+ * 0, 0}, correlation and balance_db 0, mid_db and side_db -INFINITY.  Computed when read, by one kernel on the handle's
+ * stream behind the pushes issued so far, into a block the first read allocates: a handle that never reads it allocates and
+ * launches nothing new.  Waveform batches: wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A
+ * multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_FULL_SCALE 0.999969482421875f /* 32767 / 32768, exact in float32 */
+typedef struct wf_hip_channel_signal {
+    float rms_db;     /* 10 log10(S2 / W), dBFS */
+    float peak_db;    /* 20 log10(max |x|) */
+    float dc;         /* S1 / W */
+    uint32_t clipped; /* samples with |x| >= WF_HIP_FULL_SCALE */
+} wf_hip_channel_signal;                       /* 16 bytes */
+typedef struct wf_hip_signal {
+    wf_hip_channel_signal ch[2]; /* captured channels 0 and 1 */
+    float correlation;           /* Slr / sqrt(S2l S2r), clamped to [-1, 1] */
+    float balance_db;            /* 10 log10(S2r / S2l): positive means right is louder */
+    float mid_db;                /* 10 log10(Smid / W), mid  = (l + r) / 2 */
+    float side_db;               /* 10 log10(Sside / W), side = (l - r) / 2 */
+} wf_hip_signal;                               /* 48 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS = range(12)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL = range(13)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -124,6 +124,13 @@ LOUDNESS_DTYPE = np.dtype({"names": [n for n, _ in Loudness._fields_],
 MAX_PEAKS = 8
 PEAKS_DTYPE = np.dtype([("count", np.uint32), ("reserved", np.uint32),
                         ("peak", np.dtype([("hz", np.float32), ("db", np.float32)]), (MAX_PEAKS,))])
+
+
+# struct wf_hip_signal (include/wf_hip.h): level, DC, clipping and stereo phase of one stream's newest fft_size frames
+FULL_SCALE = np.float32(0.999969482421875)  # WF_HIP_FULL_SCALE, 32767 / 32768: |x| at or above it counts as clipped
+CHANNEL_SIGNAL_DTYPE = np.dtype([("rms_db", np.float32), ("peak_db", np.float32), ("dc", np.float32), ("clipped", np.uint32)])
+SIGNAL_DTYPE = np.dtype([("ch", CHANNEL_SIGNAL_DTYPE, (2,)), ("correlation", np.float32), ("balance_db", np.float32),
+                         ("mid_db", np.float32), ("side_db", np.float32)])
 
 
 class Readback(C.Structure):
@@ -343,6 +350,11 @@ class SpectrumBatch:
         """[count, output_channels] structured array of wf_hip_peaks (PEAKS_DTYPE): the strongest peaks of each m_decibels row
         as of the newest tick, found on the device when read"""
         return self._read(OUT_PEAKS, first, count, (self.output_channels,), PEAKS_DTYPE)
+
+    def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_signal (SIGNAL_DTYPE): level, DC, clipping and stereo phase of each stream's
+        newest fft_size frames as of the pushes issued so far, measured on the device when read"""
+        return self._read(OUT_SIGNAL, first, count, (), SIGNAL_DTYPE)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -698,6 +710,12 @@ class MultiBatch:
         count = self.streams - first if count is None else count
         out = np.empty((count, self.output_channels), PEAKS_DTYPE)
         self._ck(self.L.wf_hip_multi_read(self.m, OUT_PEAKS, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = self.streams - first if count is None else count
+        out = np.empty(count, SIGNAL_DTYPE)
+        self._ck(self.L.wf_hip_multi_read(self.m, OUT_SIGNAL, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:

@@ -22,6 +22,7 @@
 #include "wf_rms.hpp"
 #include "wf_loudness.hpp"
 #include "wf_peaks.hpp"
+#include "wf_signal.hpp"
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
@@ -1792,6 +1793,10 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         if(h->meter || h->wave) { *why = "meter / waveform batch: spectral peaks belong to spectrum batches"; return nullptr; }
         *per_stream = (size_t)h->out_ch * sizeof(wf_hip_peaks);
         return h->d_decibels;
+    case WF_HIP_OUT_SIGNAL: // (computed from the rings when read, into a block the first read allocates: read_signal)
+        if(h->wave) { *why = "waveform batch: signal statistics belong to spectrum and meter batches (a window of fft_size frames)"; return nullptr; }
+        *per_stream = sizeof(wf_hip_signal);
+        return h->d_ring;
     }
     *why = "unknown output";
     return nullptr;
@@ -1814,6 +1819,29 @@ static int read_peaks(wf_hip *h, uint32_t first, uint32_t count, void *out)
                        h->stream, a);
     WF_HIP_TRY(h, hipGetLastError());
     return read_back(h, a.out, out, (size_t)a.n_rows * sizeof(wf_hip_peaks));
+}
+
+// WF_HIP_OUT_SIGNAL of streams [first, first+count): one workgroup per stream over its newest fft_size frames, on `stream`
+// behind the pushes issued
+static int read_signal(wf_hip *h, uint32_t first, uint32_t count, void *out)
+{
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    if(h->d_signal == nullptr)
+        WF_TRY_RC(dev_alloc(h, &h->d_signal, (size_t)h->n_streams));
+    wf::SignalArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = h->d_signal + first;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.W = h->N; // (<= ring_cap: wf_hip_create sizes the ring from it)
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::signal_read_kernel<2>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::signal_read_kernel<1>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
+    WF_HIP_TRY(h, hipGetLastError());
+    return read_back(h, a.out, out, (size_t)count * sizeof(wf_hip_signal));
 }
 
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
@@ -1845,6 +1873,8 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
     }
     if(what == WF_HIP_OUT_PEAKS)
         return read_peaks(h, first, count, out);
+    if(what == WF_HIP_OUT_SIGNAL)
+        return read_signal(h, first, count, out);
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
         rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));
