@@ -107,7 +107,20 @@ const char *wf_hip_last_error(const wf_hip *h);
  *              the ring keeps its newest ring_frames samples. */
 int wf_hip_create(const wf_config *cfg, int device, uint32_t max_streams, uint32_t ring_frames, wf_hip **out);
 void wf_hip_destroy(wf_hip *h);
-/* re-initialise streams [first, first+count): smoothing state 0, decibels DB_MIN, rings = N zeros */
+/* re-initialise streams [first, first+count) as update() does; afterwards they read, and tick, as the same streams of a
+ * freshly created handle given the settings listed as left in force below (the loudness state among them).  Re-initialised:
+ *   spectrum batches  m_tsmooth_buf = 0, rings = N zeros with the write position at N, m_decibels = DB_MIN, m_last_silent and
+ *                     the hidden state (wf_hip_set_hidden) cleared, bars and premirror at the bottom border, vertices and
+ *                     vertex counts 0 (no geometry until the next tick)
+ *   meter batches     empty rings, m_meter_buf = m_meter_val = DB_MIN, m_last_silent and the hidden state cleared
+ *   waveform batches  rings = width zeros, rows DB_MIN, m_waveform_ts = 0, the hidden state cleared
+ *   all               the device RMS producer's state (wf_hip_enable_input_rms): m_input_rms = 0, nothing measured yet;
+ *                     the next wf_hip_bars_mirror_ready hands over the handle's own bars (the reset state of these streams)
+ *                     instead of a set the ticks before the reset wrote
+ * Left in force, as settings rather than state: the per-stream delay (wf_hip_set_stream_delay), the values given by
+ * wf_hip_set_input_rms, the audio timestamps (wf_hip_set_stream_audio_ts), the loudness state (wf_hip_enable_loudness
+ * restarts it), the mirror buffers (wf_hip_set_bars_mirrors) and which of their two sets the ticks write.  A readback issued
+ * before the call (wf_hip_read_async) still returns the state before it. */
 int wf_hip_reset(wf_hip *h, uint32_t first, uint32_t count);
 
 /* ---- geometry of the batch ---------------------------------------------------------- */

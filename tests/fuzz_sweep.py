@@ -1,4 +1,4 @@
-"""extended fuzz sweep (development aid): python tests/fuzz_sweep.py LO HI [pow2,any,huge,meter,wave,dropin-pow2,dropin-any,dropin-meter,dropin-wave,batched-pow2,batched-any,batched-huge,batched-meter,batched-wave]
+"""extended fuzz sweep (development aid): python tests/fuzz_sweep.py LO HI [pow2,any,huge,meter,wave,dropin-pow2,dropin-any,dropin-meter,dropin-wave,dropin-update,batched-pow2,batched-any,batched-huge,batched-meter,batched-wave,batched-update]
 runs the same case functions as tests/test_gpu_fuzz.py over seeds [LO, HI) and lists failures and skips"""
 import os
 import sys
@@ -16,11 +16,11 @@ run = {"pow2": lambda s: f.run_spectrum_case(s, "pow2"), "any": lambda s: f.run_
        "wave": f.test_hip_waveform_matches_oracle_on_random_case}
 
 
-for _fam in ("pow2", "any", "huge"):
+for _fam in ("pow2", "any", "huge", "update"):
     run["batched-" + _fam] = (lambda fam: (lambda s: f.run_dropin_batched_case(s, fam)))(_fam)
 run["batched-meter"] = f.run_dropin_batched_meter_case
 run["batched-wave"] = f.run_dropin_batched_wave_case
-for _fam in ("pow2", "any", "huge", "meter", "wave"):
+for _fam in ("pow2", "any", "huge", "meter", "wave", "update"):
     run["dropin-" + _fam] = (lambda fam: (lambda s: f.run_dropin_case(s, fam)))(_fam)
 
 bad = skipped = 0

@@ -285,6 +285,13 @@ def make_config(overrides: dict):
     return wf.Config.defaults(**overrides)
 
 
+def config_with(cfg, changes: dict):
+    """a copy of the wf_config struct `cfg` with `changes` applied"""
+    d = {name: getattr(cfg, name) for name, _ in cfg._fields_}
+    d.update(changes)
+    return make_config(d)
+
+
 class _Feeder:
     """turns ('noise', n) etc. into sample blocks; the stream index in the hash is always 0"""
 
@@ -355,6 +362,8 @@ def play(backend, scenario: dict):
             backend.set_hidden(True)
         elif op == "show":
             backend.set_hidden(False)
+        elif op == "update":
+            backend.update(step[1])  # WAVSource::update() mid-stream with these wf_config fields changed (an empty dict: the same settings)
         else:
             raise ValueError(op)
     return records
@@ -376,7 +385,8 @@ class RefBackend:
         # before the first packet is not a capture timeout of the harness's making
         wfref.lib().wfref_set_clock_ns(1_000_000_000)
         self.sr = int(cfg.sample_rate)
-        self.src = wfref.RefSource(ref_settings(cfg, **(extra_settings or {})), isa=isa, sample_rate=self.sr, channels=int(cfg.capture_channels))
+        self.extra_settings = dict(extra_settings or {})
+        self.src = wfref.RefSource(ref_settings(cfg, **self.extra_settings), isa=isa, sample_rate=self.sr, channels=int(cfg.capture_channels))
         assert self.src.capture_channels == cfg.capture_channels
         self.capture_channels = int(cfg.capture_channels)
         self.disp = 2 if cfg.stereo else 1
@@ -417,6 +427,14 @@ class RefBackend:
 
     def set_hidden(self, hidden):
         self.src.show(not hidden)
+
+    def update(self, changes):
+        """the settings in force with `changes` (wf_config fields) applied, handed to update() at the current clock; the harness
+        merges them into the source's settings (the audio sync offset stays)"""
+        from helpers import ref_settings
+        self.cfg = config_with(self.cfg, changes)
+        self.src.L.wfref_set_clock_ns(self.now)
+        self.src.update(ref_settings(self.cfg, **self.extra_settings))
 
     def observe(self):
         if self.cfg.meter:
@@ -519,6 +537,9 @@ class OracleBackend:
         self.hidden = hidden
         self._state()
 
+    def update(self, changes):
+        raise NotImplementedError(f"{type(self).__name__}: no mid-stream update() (RefBackend plays it)")
+
     def observe(self):
         if self.cfg.meter:
             return dict(db=self.src.levels()[None], bars=self.src.bars()[None], silent=self.src.last_silent)
@@ -594,6 +615,9 @@ class HipBackend:
     def set_hidden(self, hidden):
         self.hidden = hidden
         self._state()
+
+    def update(self, changes):
+        raise NotImplementedError(f"{type(self).__name__}: no mid-stream update() (RefBackend plays it)")
 
     def observe(self):
         if self.cfg.meter:

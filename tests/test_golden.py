@@ -125,14 +125,17 @@ def test_reference_plugin_with_hip_tick(name):
     _check_renders(wfref, cfg, drawn, on_host)
 
 
-def _check_renders(wfref, cfg, drawn, on_host):
+def _check_renders(wfref, cfg, drawn, on_host, joins=0):
     """WAVSourceHIP::render (host/wav_source_hip.cpp): every render() of a spectrum display must have been drawn from the device's
     bar tops / curve points and vertices -- none handed to the reference's own render_bars / render_curve, i.e. no
     apply_interp_filter*, apply_filter* or vertex loop on the host (the bars and vertex buffers the scenario compares are then
-    the device's)"""
+    the device's).  joins: renders of a batched source in the first frame after it (re)joined a group -- update() -- where no
+    device display exists yet: the device's rows of that frame belong to whoever held the slot before, so render() draws what
+    update() left (rows of DB_MIN) with the reference's loops; exactly one such render per join"""
     if cfg.meter or cfg.waveform or not (cfg.bars or cfg.curve) or scenarios.no_vertex_buffer(cfg):
         return
-    assert wfref.hip_host_renders() == on_host, "render() ran the reference's interpolation and vertex loops on the host"
+    assert wfref.hip_host_renders() == on_host + joins, \
+        f"render() ran the reference's interpolation and vertex loops on the host {wfref.hip_host_renders() - on_host} times ({joins} joins)"
     assert wfref.hip_device_renders() > drawn, "no render() was served from the device's display"
 
 
@@ -599,6 +602,93 @@ def test_sixty_four_sources_share_one_batch():
         print(f"plugin mode, 64 sources x FFT 4096 stereo, {disp}, tick + render per source and frame: display from the device "
               f"{2e6 / v_dev:.1f} us, device rows + the reference's render on the host {2e6 / v_host:.1f} us, reference AVX2 {2e6 / v_ref:.1f} us")
         assert v_dev > v_ref
+
+
+class _Member:
+    """one batched WAVSourceHIP source and its generic twin, fed the same packets and update() calls; `want` is what the hip
+    source must show at its next tick: the twin's previous frame -- or, right after it was created or updated (it has then
+    joined a slot whose device rows belong to the frame before), the state creation / update() left"""
+
+    def __init__(self, cfg, stream):
+        self.hip = scenarios.RefBackend(cfg, isa="hip")
+        self.twin = scenarios.RefBackend(cfg, isa="generic")
+        assert self.hip.src.using_hip
+        self.stream = stream
+        self.want = self.twin.observe()
+
+    def update(self, changes):
+        self.hip.update(changes)
+        self.twin.update(changes)
+        self.want = self.twin.observe()
+
+    def frame(self, f, hop):
+        a = scenarios.synth.block(scenarios.SEED, self.stream, 1, 2, f * hop, hop)[0][: self.hip.capture_channels]
+        for be in (self.hip, self.twin):
+            be.push(a, muted=False)
+            be.tick(1.0 / 60.0)
+        got, want = self.hip.observe(), self.want
+        self.want = self.twin.observe()
+        return got, want
+
+    def close(self):
+        self.hip.src.close()
+        self.twin.src.close()
+
+
+SLOT_REUSE = {
+    "mirrored_bars": (dict(fft_size=2048, stereo=1, slope=1.0, bars=1, interp_mode=1, mirror_freq_axis=1, vertices=1), dict(fft_size=4096)),
+    "stepped_bars": (dict(fft_size=2048, stereo=1, slope=1.0, bars=1, interp_mode=1, channel_spacing=6, vertices=3), dict(fft_size=1024)),
+    "meter": (dict(meter=1, meter_ms=20), dict(meter_ms=30)),
+    "waveform": (dict(waveform=1, stereo=1, width=400), dict(width=320)),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SLOT_REUSE))
+def test_batched_sources_update_leave_and_reuse_slots(name, monkeypatch):
+    """Eight sources of one configuration in one batched group (spectrum with a device display, level meter, waveform), each
+    with a generic twin.  Source 2 re-runs update() with the same settings: it leaves its slot and rejoins the same one through
+    wf_hip_reset.  Source 6 is destroyed and a new source takes its slot.  Source 4 changes a setting that leaves the group.
+    Over 20 frames every source's rows, bars and vertex buffers equal its twin's one frame late."""
+    from test_gpu_fuzz import _compare, _undo_db
+    from helpers import assert_levels_close
+    wfref = _hip_env(batched=True)
+    monkeypatch.setenv("WF_HIP_BATCH_CAPACITY", "8")
+    base, leave = SLOT_REUSE[name]
+    cfg = scenarios.make_config(base)
+    hop, frames = 800, 20
+    before = wfref.hip_fallback_ticks()
+    drawn, on_host = wfref.hip_device_renders(), wfref.hip_host_renders()
+    members = [_Member(cfg, 10 + i) for i in range(8)]
+    joins = 8
+    try:
+        for f in range(frames):
+            if f == 5:
+                members[2].update({})                 # the same settings: back into slot 2 through wf_hip_reset
+                joins += 1
+            if f == 8:
+                members[6].close()                    # slot 6 freed ...
+                members[6] = _Member(cfg, 100)        # ... and taken by a new source
+                joins += 1
+            if f == 11:
+                members[4].update(leave)              # another configuration: another group
+                joins += 1
+            for i, m in enumerate(members):
+                got, want = m.frame(f, hop)
+                what = f"{name}: source {i} frame {f}"
+                assert got["silent"] == want["silent"], what + f": m_last_silent {got['silent']} != {want['silent']}"
+                ct = m.twin.cfg
+                if ct.meter:
+                    assert_levels_close(got["db"], want["db"], want["db"], what + " levels")
+                elif ct.waveform:
+                    assert_db_close(got["db"], want["db"], what + " rows", lin_eps=None)
+                else:
+                    _compare([got], [want], _undo_db(ct), what, cfg_stepped=ct.vertices == 3, cfg=ct)
+        assert all(m.hip.src.using_hip for m in members) and wfref.hip_fallback_ticks() == before, "fell back to the CPU class"
+        _check_renders(wfref, cfg, drawn, on_host, joins=joins)
+    finally:
+        for m in members:
+            m.close()
 
 
 @pytest.mark.gpu

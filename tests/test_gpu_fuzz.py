@@ -141,6 +141,70 @@ def draw(seed: int, family: str = "pow2", fft_size: int | None = None):
     return cfg, steps, sync_ms
 
 
+def draw_update(seed: int):
+    """the script draw(seed) makes (pow2 for even seeds, any for odd ones; draw itself untouched, so every earlier seed keeps its
+    script) with 1-3 mid-stream update() calls inserted behind ticks: the same settings, or a changed window, smoothing /
+    gravity, slope or fft size.  Returns the base family as well."""
+    base = "pow2" if seed % 2 == 0 else "any"
+    cfg, steps, sync_ms = draw(seed, base)
+    r = np.random.default_rng(990000 + seed)
+    ticks = [i for i, st in enumerate(steps) if st[0] == "tick"][:-1]
+    at = sorted(int(i) for i in r.choice(ticks, size=min(int(r.integers(1, 4)), len(ticks)), replace=False))
+    for i in reversed(at):
+        kind = int(r.integers(0, 5))
+        if kind == 0:
+            d = {}
+        elif kind == 1:
+            d = dict(window=int(r.integers(0, 6)))
+        elif kind == 2:
+            d = dict(tsmoothing=int(r.integers(0, 3)), gravity=float(np.float32(r.uniform(0.05, 0.95))))
+        elif kind == 3:
+            d = dict(slope=float(np.float32(r.choice([0.0, 0.5, 1.0, 2.5]))))
+        else:
+            d = dict(fft_size=int(r.choice([1024, 2048, 4096, 8192])) if base == "pow2" else 16 * int(r.integers(8, 4096 // 16 + 1)))
+        steps.insert(i + 1, ("update", d))
+    return base, cfg, steps, sync_ms
+
+
+def _configs_in_force(cfg_dict, steps):
+    """the wf_config overrides in force at every tick of a script with update steps"""
+    cur, out = dict(cfg_dict), []
+    for st in steps:
+        if st[0] == "update":
+            cur = {**cur, **st[1]}
+        elif st[0] == "tick":
+            out.append(dict(cur))
+    return out
+
+
+class _ObservedAtUpdate:
+    """the generic twin of a batched source: records as play() takes them, except that the record of the frame an update()
+    follows becomes the state the update() left -- what the batched source shows at the next tick instead of that frame (the
+    m_hip_joined guard of tick_spectrum_batched)"""
+
+    def __init__(self, backend):
+        self.be = backend
+        self.capture_channels = backend.capture_channels
+        self.records, self.cfgs = [], []
+
+    def __getattr__(self, name):
+        return getattr(self.be, name)
+
+    def tick(self, seconds):
+        self.be.tick(seconds)
+        self.records.append(self.be.observe())
+        self.cfgs.append(self.be.cfg)
+
+    def update(self, changes):
+        self.be.update(changes)
+        if self.records:
+            self.records[-1] = self.be.observe()
+            self.cfgs[-1] = self.be.cfg
+
+    def observe(self):
+        return None
+
+
 WIDE_SEEDS = range(400)    # the reference's full slider ranges (draw_wide)
 
 
@@ -690,9 +754,12 @@ def run_dropin_case(seed, family):
         sync_ms = 0
     elif family == "wave":
         cfg_dict, steps, sync_ms = draw_wave(seed)
+    elif family == "update":
+        _, cfg_dict, steps, sync_ms = draw_update(seed)
     else:
         cfg_dict, steps, sync_ms = draw(seed, family)
     cfg_dict = dict(cfg_dict)   # (vertices stay: WAVSourceHIP::render draws the plugin's vertex buffer from the device's)
+    in_force = _configs_in_force(cfg_dict, steps)
     cfg = scenarios.make_config(cfg_dict)
     sc = dict(cfg=cfg_dict, steps=steps, record="all", sync_ms=sync_ms)
     before = wfref.hip_fallback_ticks()
@@ -710,6 +777,10 @@ def run_dropin_case(seed, family):
     truth = scenarios.play(scenarios.OracleBackend(cfg, exact=True), sc) if family == "meter" else [None] * len(want)
     for t, (g, w, x) in enumerate(zip(got, want, truth)):
         what = f"drop-in {family} case {seed} tick {t} ({cfg_dict}, sync {sync_ms} ms)"
+        if family == "update":  # each record under the configuration in force at its tick
+            ct = scenarios.make_config(in_force[t])
+            _compare([g], [w], _undo_db(ct), what + f" (in force: {in_force[t]})", cfg_stepped=in_force[t].get("vertices") == 3, cfg=ct)
+            continue
         if family == "meter":
             # the criterion of the batch fuzz (helpers.assert_levels_close): within tolerance of the reference, or no farther
             # from the exactly summed level than the reference's own sequential float sum is
@@ -736,7 +807,10 @@ def run_dropin_batched_case(seed, family):
     import os
     os.environ["WF_HIP_LIBRARY"] = str(Path(__file__).resolve().parent.parent / "waveform_amd" / "libwaveform_hip.so")
     os.environ["WF_HIP_BATCHED"] = "1"
-    cfg_dict, steps, sync_ms = draw(seed, family)
+    if family == "update":
+        _, cfg_dict, steps, sync_ms = draw_update(seed)
+    else:
+        cfg_dict, steps, sync_ms = draw(seed, family)
     cfg_dict = dict(cfg_dict)
     cfg = scenarios.make_config(cfg_dict)
     sc = dict(cfg=cfg_dict, steps=steps, record="all", sync_ms=sync_ms)
@@ -747,13 +821,16 @@ def run_dropin_batched_case(seed, family):
     scenarios.play(late, sc)
     got = late.finish()
     assert late.be.src.using_hip and wfref.hip_fallback_ticks() == before, "fell back to the CPU class"
-    tg._check_renders(wfref, cfg, drawn, on_host)
-    want = scenarios.play(scenarios.RefBackend(cfg, isa="generic"), sc)
+    tg._check_renders(wfref, cfg, drawn, on_host, joins=sum(st[0] == "update" for st in steps))
+    twin = _ObservedAtUpdate(scenarios.RefBackend(cfg, isa="generic"))
+    scenarios.play(twin, sc)
+    want, in_force = twin.records, twin.cfgs
     assert len(got) == len(want), (len(got), len(want))
-    undo = _undo_db(cfg)
     for t, (g, w) in enumerate(zip(got, want)):
         what = f"batched drop-in {family} case {seed} tick {t} ({cfg_dict}, sync {sync_ms} ms)"
-        _compare([g], [w], undo, what, cfg_stepped=cfg_dict.get("vertices") == 3, cfg=cfg)  # rows, bars / curve, vertex buffers: one frame late
+        ct = in_force[t]
+        # rows, bars / curve, vertex buffers: one frame late, each under the configuration in force
+        _compare([g], [w], _undo_db(ct), what, cfg_stepped=ct.vertices == 3, cfg=ct)
 
 
 
@@ -815,7 +892,7 @@ def run_dropin_batched_wave_case(seed):
         assert_db_close(g["db"], w["db"], what + " rows", lin_eps=None)
 
 
-DROPIN_SEEDS = {"pow2": range(0, 80), "any": range(0, 40), "meter": range(0, 60), "wave": range(0, 60)}
+DROPIN_SEEDS = {"pow2": range(0, 80), "any": range(0, 40), "meter": range(0, 60), "wave": range(0, 60), "update": range(0, 30)}
 
 
 @pytest.mark.gpu
@@ -850,7 +927,7 @@ def test_reference_plugin_with_batched_hip_waveform_on_random_case(seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("family,seed", [(k, s) for k, r in (("pow2", range(0, 60)), ("any", range(0, 30))) for s in r])
+@pytest.mark.parametrize("family,seed", [(k, s) for k, r in (("pow2", range(0, 60)), ("any", range(0, 30)), ("update", range(0, 30))) for s in r])
 def test_reference_plugin_with_batched_hip_tick_on_random_case(family, seed):
     """the batched plugin mode (sources share a handle, rows read one frame late) on consecutive seeds"""
     from oracle import wfref

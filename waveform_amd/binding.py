@@ -366,6 +366,13 @@ class SpectrumBatch:
         dst = Readback(bars=pinned.ptr)
         self._ck(self.L.wf_hip_read_async(self.h, first, count, C.byref(dst), slot))
 
+    def read_async(self, slot: int, first: int = 0, count: int | None = None, **pinned: "PinnedBuffer"):
+        """wf_hip_read_async without waiting: `pinned` names the destinations by Readback field (rows, last_silent, bars,
+        premirror, vertices, vertex_counts, input_rms, meter); readback_done(slot) waits for them"""
+        count = self.streams - first if count is None else count
+        dst = Readback(**{k: v.ptr for k, v in pinned.items()})
+        self._ck(self.L.wf_hip_read_async(self.h, first, count, C.byref(dst), slot))
+
     def readback_done(self, slot: int):
         self._ck(self.L.wf_hip_readback_done(self.h, slot))
 

@@ -672,7 +672,17 @@ int wf_hip_reset(wf_hip *h, uint32_t first, uint32_t count)
             hipLaunchKernelGGL(wf::fill_f32_kernel, dim3(((size_t)count * h->disp_ch + 255) / 256), dim3(256), 0, h->stream,
                                h->d_bars_pre + (size_t)first * h->disp_ch, (size_t)count * h->disp_ch, h->tab.border_bottom);
     }
+    if(h->d_verts) {
+        // no geometry until the first tick, as after create
+        const size_t pv = (size_t)h->disp_ch * h->vtab.per_row;
+        WF_HIP_TRY(h, hipMemsetAsync(h->d_verts + (size_t)first * pv, 0, (size_t)count * pv * sizeof(wf::f4), h->stream));
+        WF_HIP_TRY(h, hipMemsetAsync(h->d_vert_counts + (size_t)first * h->disp_ch, 0, (size_t)count * h->disp_ch * sizeof(uint32_t), h->stream));
+    }
     WF_HIP_TRY(h, hipGetLastError());
+    // the mirror set being written holds the bars of the ticks before this reset: the next hand-over copies the handle's own bars
+    // (the reset state of these streams) in, as it does before any tick
+    if(h->mirror_n)
+        h->mirror_fresh = false;
     int rrc = reset_rms_producer(h, first, count);
     if(rrc)
         return rrc;
@@ -1594,17 +1604,9 @@ static int read_rows_async(wf_hip *h, uint32_t first, uint32_t count, float *pin
     return WF_HIP_OK;
 }
 
+// The riders below copy behind the rows' copy on the readback stream; check_riders has validated them before the rows went out
 static int read_premirror_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_out, uint32_t slot)
 {
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
-    if(slot > 1 || pinned_out == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL or slot is not 0 / 1");
-    if(h->d_bars_pre == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "the configuration has no mirrored display (cfg.mirror_freq_axis == 0, or no bars / curve)");
-    if(!h->rows_in_flight[slot] || h->read_stream == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: premirror rides behind rows");
     WF_HIP_TRY(h, hipSetDevice(h->device));
     WF_HIP_TRY(h, hipMemcpyAsync(pinned_out, h->d_bars_pre + (size_t)first * h->disp_ch, (size_t)count * h->disp_ch * sizeof(float), hipMemcpyDeviceToHost,
                                  h->read_stream));
@@ -1615,17 +1617,6 @@ static int read_premirror_async(wf_hip *h, uint32_t first, uint32_t count, float
 static int read_display_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_bars, float *pinned_vertices, uint32_t *pinned_counts,
                               uint32_t slot)
 {
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
-    if(slot > 1)
-        return fail(h, WF_HIP_ERR_INVALID, "slot is not 0 / 1");
-    if(h->d_bars == nullptr || h->meter)
-        return fail(h, WF_HIP_ERR_INVALID, "the configuration displays neither bars nor a curve (cfg.bars == 0 and cfg.curve == 0)");
-    if((pinned_vertices != nullptr || pinned_counts != nullptr) && h->d_verts == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "configuration has no vertex fill (cfg.vertices == 0)");
-    if(!h->rows_in_flight[slot] || h->read_stream == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: bars / vertices ride behind rows");
     WF_HIP_TRY(h, hipSetDevice(h->device));
     // behind the rows' copy on the readback stream (which already waits for the tick, its bars and its vertex fill on every lane);
     // the next tick waits, on the device, for this slot's event before it overwrites any of them
@@ -1701,11 +1692,25 @@ static int read_meter_async(wf_hip *h, uint32_t first, uint32_t count, float *pi
 // m_input_rms behind the rows' copy on the readback stream (which already waits for the tick)
 static int read_input_rms_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_out, uint32_t slot)
 {
-    if(h->d_input_rms == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "the device RMS producer is not enabled (wf_hip_enable_input_rms)");
     WF_HIP_TRY(h, hipSetDevice(h->device));
     WF_HIP_TRY(h, hipMemcpyAsync(pinned_out, h->d_input_rms + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
     WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
+    return WF_HIP_OK;
+}
+
+// the outputs that ride behind the rows of one wf_hip_read_async: each one the batch must have
+static int check_riders(wf_hip *h, const wf_hip_readback *dst)
+{
+    if(h->meter)
+        return fail(h, WF_HIP_ERR_INVALID, "meter batch: there is no m_decibels");
+    if(dst->input_rms && h->d_input_rms == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "the device RMS producer is not enabled (wf_hip_enable_input_rms)");
+    if((dst->bars || dst->vertices || dst->vertex_counts) && h->d_bars == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "the configuration displays neither bars nor a curve (cfg.bars == 0 and cfg.curve == 0)");
+    if((dst->vertices || dst->vertex_counts) && h->d_verts == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "configuration has no vertex fill (cfg.vertices == 0)");
+    if(dst->premirror && h->d_bars_pre == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "the configuration has no mirrored display (cfg.mirror_freq_axis == 0, or no bars / curve)");
     return WF_HIP_OK;
 }
 
@@ -1729,6 +1734,10 @@ int wf_hip_read_async(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_re
     }
     if(dst->last_silent == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: rows go with last_silent");
+    // every rider is checked before the rows are enqueued: a refused call leaves no copy in flight and the slot as it was
+    rc = check_riders(h, dst);
+    if(rc)
+        return rc;
     rc = read_rows_async(h, first, count, dst->rows, dst->last_silent, slot);
     if(rc == WF_HIP_OK && dst->input_rms)
         rc = read_input_rms_async(h, first, count, dst->input_rms, slot);
