@@ -36,6 +36,8 @@
  *                        when read
  *   WF_HIP_OUT_SIGNAL    not in the reference: level, DC, clipping and stereo phase correlation of every stream's newest
  *                        window of audio, measured on the device when read
+ *   WF_HIP_OUT_PITCH     not in the reference: the fundamental frequency of every stream's newest window of audio (YIN),
+ *                        estimated on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -370,9 +372,12 @@ typedef enum wf_hip_output {
                                   pushes issued so far; 0 bytes while the producer is off */
     WF_HIP_OUT_PEAKS,          /* wf_hip_peaks [output_channels]             the strongest peaks of each m_decibels row as of the newest tick
                                   (spectrum batches; definition below) */
-    WF_HIP_OUT_SIGNAL          /* wf_hip_signal                              level, DC, clipping and stereo phase of the newest
+    WF_HIP_OUT_SIGNAL,         /* wf_hip_signal                              level, DC, clipping and stereo phase of the newest
                                   wf_hip_fft_size() frames in the rings as of the pushes issued so far (spectrum and meter
                                   batches; definition below) */
+    WF_HIP_OUT_PITCH           /* wf_hip_pitch                               fundamental frequency (YIN) of the newest
+                                  min(wf_hip_fft_size(), 4096) frames in the rings as of the pushes issued so far (spectrum
+                                  and meter batches; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -437,6 +442,51 @@ typedef struct wf_hip_signal {
     float mid_db;                /* 10 log10(Smid / W), mid  = (l + r) / 2 */
     float side_db;               /* 10 log10(Sside / W), side = (l - r) / 2 */
 } wf_hip_signal;                               /* 48 bytes */
+/* ---- pitch (WF_HIP_OUT_PITCH) ----------------------------------------------------------------------------------------------
+ * Per stream, the fundamental frequency by YIN (de Cheveigne and Kawahara, "YIN, a fundamental frequency estimator for speech
+ * and music", JASA 111 (4), 2002, steps 1 to 5).  sr = cfg.sample_rate, W = wf_hip_fft_size().
+ *   window         P = min(W, WF_HIP_PITCH_MAX_WINDOW) frames, H = P / 2 (integer division): the newest P frames of each
+ *                  captured channel's ring, positions (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of
+ *                  WF_HIP_OUT_SIGNAL: every push issued before the read counts whatever its path, the A/V-sync delay is not
+ *                  applied, the zeros of create and wf_hip_reset count as samples.
+ *   signal         x[i], i < P, in float64: the sample of a one-channel capture, (l + r) / 2 of a two-channel capture (exact
+ *                  in float64, and a value of at most 25 bits, so every product of two of them is exact as well).
+ *   difference     the paper's eq. 7 for tau = 0 .. H:
+ *                      r(tau) = sum_{j<H} x[j] x[j+tau],  e(tau) = sum_{j<H} x[j+tau]^2,
+ *                      d(tau) = max(e(0) + e(tau) - 2 r(tau), 0),  d(0) = 0.
+ *                  r(tau) and e(tau) are direct sums per lag in float64, both added in the order of j: every product is
+ *                  exact and only the additions round, in an order fixed by the window and the same for every lag.  So
+ *                  d(tau) is exactly 0 wherever x[j+tau] == x[j] for all j < H (a constant; a period of whole frames), and
+ *                  the same ring contents read bit-identically; there are no atomics.
+ *   normalisation  d'(0) = 1, d'(tau) = d(tau) tau / sum_{t=1..tau} d(t), and 1 where that running sum is 0 (the cumulative
+ *                  mean normalised difference).
+ *   search         over tau in [WF_HIP_PITCH_MIN_LAG, H - 1], so hz <= sr / 8 (6 kHz at 48 kHz) and the lowest pitch that
+ *                  can be reported is about sr / (H - 1) (23.4 Hz at 48 kHz with P = 4096).  The first tau with
+ *                  d'(tau) < WF_HIP_PITCH_THRESHOLD, then forward while tau + 1 <= H - 1 and d'(tau + 1) < d'(tau): that
+ *                  lag, voiced = 1.  If no lag is under the threshold: the lag of the smallest d' in the range, the lower
+ *                  lag on ties, voiced = 0 (a best guess: noise, a chord, a pitch outside the range).
+ *   interpolation  a = d'(lag - 1), b = d'(lag), c = d'(lag + 1); den = a - 2 b + c;
+ *                  p = den > 0 ? clamp(0.5 (a - c) / den, -0.5, 0.5) : 0; hz = sr / (lag + p); clarity = clamp(1 - b, 0, 1);
+ *                  in float64, each rounded to float32 once.
+ *   nothing to report   when sum_{t=1..H} d(t) == 0 (digital silence, a constant, a stereo pair with l = -r):
+ *                  hz = 0, clarity = 0, lag = 0, voiced = 0.
+ * Accuracy is the estimator's: the parabola through d' reads high at short lags.  Pure sines at 48 kHz with P = 4096 read
+ * within 0.0002 % up to 110 Hz, +0.004 % at 440 Hz (lag 109), +0.02 % at 1 kHz (lag 48), +0.19 % at 3 kHz (lag 16) and
+ * +0.7 % at 6 kHz (lag 8).  There is no state between reads: smoothing, octave-error correction and note names are the
+ * host's.  Computed when read, by one kernel on the handle's stream behind the pushes issued so far (about H^2 float64
+ * multiply-adds per stream for r and as many for e: compute-bound, unlike the other outputs; INTEGRATION.md, "Pitch"), into a
+ * block the first read allocates: a handle that never reads it allocates and launches nothing new.  Handles with W < 64 and
+ * waveform batches: wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it
+ * through wf_hip_multi_read. */
+#define WF_HIP_PITCH_MIN_LAG 8
+#define WF_HIP_PITCH_THRESHOLD 0.15
+#define WF_HIP_PITCH_MAX_WINDOW 4096
+typedef struct wf_hip_pitch {
+    float hz;        /* sr / (lag + p); 0: nothing to report */
+    float clarity;   /* 1 - d'(lag): 1 = perfectly periodic */
+    uint32_t lag;    /* the integer lag chosen, frames */
+    uint32_t voiced; /* 1: a lag under the threshold was found; 0: the best guess, or nothing */
+} wf_hip_pitch;      /* 16 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL = range(13)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH = range(14)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -131,6 +131,13 @@ FULL_SCALE = np.float32(0.999969482421875)  # WF_HIP_FULL_SCALE, 32767 / 32768: 
 CHANNEL_SIGNAL_DTYPE = np.dtype([("rms_db", np.float32), ("peak_db", np.float32), ("dc", np.float32), ("clipped", np.uint32)])
 SIGNAL_DTYPE = np.dtype([("ch", CHANNEL_SIGNAL_DTYPE, (2,)), ("correlation", np.float32), ("balance_db", np.float32),
                          ("mid_db", np.float32), ("side_db", np.float32)])
+
+
+# struct wf_hip_pitch (include/wf_hip.h): YIN over one stream's newest min(fft_size, PITCH_MAX_WINDOW) frames
+PITCH_MIN_LAG = 8  # WF_HIP_PITCH_MIN_LAG: the shortest lag searched, so hz <= sample_rate / 8
+PITCH_THRESHOLD = 0.15  # WF_HIP_PITCH_THRESHOLD: the first lag whose normalised difference is under it is voiced
+PITCH_MAX_WINDOW = 4096  # WF_HIP_PITCH_MAX_WINDOW
+PITCH_DTYPE = np.dtype([("hz", np.float32), ("clarity", np.float32), ("lag", np.uint32), ("voiced", np.uint32)])
 
 
 class Readback(C.Structure):
@@ -355,6 +362,11 @@ class SpectrumBatch:
         """[count] structured array of wf_hip_signal (SIGNAL_DTYPE): level, DC, clipping and stereo phase of each stream's
         newest fft_size frames as of the pushes issued so far, measured on the device when read"""
         return self._read(OUT_SIGNAL, first, count, (), SIGNAL_DTYPE)
+
+    def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_pitch (PITCH_DTYPE): fundamental frequency, clarity, lag and voiced flag of each
+        stream's newest min(fft_size, PITCH_MAX_WINDOW) frames as of the pushes issued so far, by YIN on the device when read"""
+        return self._read(OUT_PITCH, first, count, (), PITCH_DTYPE)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -723,6 +735,12 @@ class MultiBatch:
         count = self.streams - first if count is None else count
         out = np.empty(count, SIGNAL_DTYPE)
         self._ck(self.L.wf_hip_multi_read(self.m, OUT_SIGNAL, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = self.streams - first if count is None else count
+        out = np.empty(count, PITCH_DTYPE)
+        self._ck(self.L.wf_hip_multi_read(self.m, OUT_PITCH, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:

@@ -23,6 +23,7 @@
 #include "wf_loudness.hpp"
 #include "wf_peaks.hpp"
 #include "wf_signal.hpp"
+#include "wf_pitch.hpp"
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
@@ -1806,6 +1807,11 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         if(h->wave) { *why = "waveform batch: signal statistics belong to spectrum and meter batches (a window of fft_size frames)"; return nullptr; }
         *per_stream = sizeof(wf_hip_signal);
         return h->d_ring;
+    case WF_HIP_OUT_PITCH: // (computed from the rings when read, into a block the first read allocates: read_pitch)
+        if(h->wave) { *why = "waveform batch: the pitch belongs to spectrum and meter batches (a window of fft_size frames)"; return nullptr; }
+        if(h->N < 64) { *why = "the pitch needs a window of at least 64 frames"; return nullptr; }
+        *per_stream = sizeof(wf_hip_pitch);
+        return h->d_ring;
     }
     *why = "unknown output";
     return nullptr;
@@ -1853,6 +1859,30 @@ static int read_signal(wf_hip *h, uint32_t first, uint32_t count, void *out)
     return read_back(h, a.out, out, (size_t)count * sizeof(wf_hip_signal));
 }
 
+// WF_HIP_OUT_PITCH of streams [first, first+count): one workgroup per stream over its newest min(fft_size, 4096) frames, on
+// `stream` behind the pushes issued
+static int read_pitch(wf_hip *h, uint32_t first, uint32_t count, void *out)
+{
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    if(h->d_pitch == nullptr)
+        WF_TRY_RC(dev_alloc(h, &h->d_pitch, (size_t)h->n_streams));
+    wf::PitchArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = h->d_pitch + first;
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.P = std::min<uint32_t>(h->N, WF_HIP_PITCH_MAX_WINDOW); // (a multiple of 16 on spectrum and meter batches; <= ring_cap)
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::pitch_read_kernel<2>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::pitch_read_kernel<1>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
+    WF_HIP_TRY(h, hipGetLastError());
+    return read_back(h, a.out, out, (size_t)count * sizeof(wf_hip_pitch));
+}
+
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
 {
     if(h == nullptr)
@@ -1884,6 +1914,8 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
         return read_peaks(h, first, count, out);
     if(what == WF_HIP_OUT_SIGNAL)
         return read_signal(h, first, count, out);
+    if(what == WF_HIP_OUT_PITCH)
+        return read_pitch(h, first, count, out);
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
         rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));

@@ -151,6 +151,7 @@ struct wf_hip {
     wf::LoudCoefs loud_k{};
     wf_hip_peaks *d_peaks = nullptr;              // [n_streams][out_ch] WF_HIP_OUT_PEAKS, allocated by its first read (wf_peaks.hpp)
     wf_hip_signal *d_signal = nullptr;            // [n_streams] WF_HIP_OUT_SIGNAL, allocated by its first read (wf_signal.hpp)
+    wf_hip_pitch *d_pitch = nullptr;              // [n_streams] WF_HIP_OUT_PITCH, allocated by its first read (wf_pitch.hpp)
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;
