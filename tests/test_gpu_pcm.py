@@ -146,6 +146,44 @@ def test_ragged_async(dtype, interleaved, capture):
             p.close()
 
 
+@pytest.mark.parametrize("entry", ["float", "pcm"])
+def test_one_slot_grows_while_in_use(entry):
+    """The ordering rule of an ingest slot, on its own: every push goes through slot 0 and none waits for the one before.  A
+    small plain push, a ragged push with more streams and more frames (the staging block is outgrown and the frame counts
+    appear while the plain push may still read the slot), a small plain push, a ragged push beyond 64 streams (both blocks are
+    outgrown, the page-locked counts are rewritten) and a small plain push again; a tick behind each.  Every push has a host
+    buffer of its own, so wf_hip_ingest_done is not needed in between.  The twin takes the same frames through wf_hip_push_audio."""
+    streams, cap = 100, 2
+    steps = [(2, 64, False), (40, 300, True), (2, 64, False), (streams, 403, True), (3, 65, False)]  # (count, frames, ragged)
+    rng = np.random.default_rng(29)
+    with wf.SpectrumBatch(_cfg(cap), streams) as b, wf.SpectrumBatch(_cfg(cap), streams) as twin:
+        pins, counts = [], []
+        for count, frames, ragged in steps:
+            pin = wf.PinnedBuffer((count, cap, frames))
+            pin.array[...] = random_packet(rng, np.float32, count, cap, frames, False)
+            f = rng.integers(0, frames + 1, count).astype(np.uint32) if ragged else np.full(count, frames, np.uint32)
+            if ragged:
+                f[0], f[1] = frames, 0
+            pins.append(pin)
+            counts.append(f)
+        for (count, frames, ragged), pin, f in zip(steps, pins, counts):
+            if entry == "pcm":
+                b.push_pcm(pin, interleaved=False, frames=f if ragged else None, slot=0)
+            elif ragged:
+                b.push_audio_ragged_async(pin, f, frames, 0)
+            else:
+                b.push_audio_async(pin, count, frames, 0)
+            b.tick()
+        for pin, f in zip(pins, counts):
+            for s in np.flatnonzero(f):
+                twin.push_audio(pin.array[s:s + 1, :, :f[s]], first=int(s))
+            twin.tick()
+        _assert_same(b, twin, f"one slot, {entry} entry points")
+        b.sync()
+        for p in pins:
+            p.close()
+
+
 def test_volume_normalisation_and_ragged_refused():
     streams, frames = 4, 800
     cfg = _cfg(2, normalize_volume=1)

@@ -342,22 +342,27 @@ void dev_release(wf_hip *h, void *p)
 // staging blocks grow geometrically and the outgrown block is released once the stream has drained it
 size_t grown(size_t have, size_t need) { return std::max(need, have + have / 2); }
 
+// replaces *d by a block of at least `floats` (the caller has made sure that nothing enqueued still uses the old one)
+int grow_stage(wf_hip *h, float **d, size_t *have, size_t floats)
+{
+    dev_release(h, *d);
+    *d = nullptr;
+    const size_t want = grown(*have, floats);
+    *have = 0;
+    float *p = nullptr;
+    WF_TRY_RC(dev_alloc(h, &p, want));
+    *d = p;
+    *have = want;
+    return WF_HIP_OK;
+}
+
+// the blocking pushes' block: every use of it is on `stream`, so draining the stream frees it
 int ensure_stage(wf_hip *h, size_t floats)
 {
     if(h->stage_floats >= floats)
         return WF_HIP_OK;
     WF_HIP_TRY(h, hipStreamSynchronize(h->stream)); // the old block may still feed a ring append
-    dev_release(h, h->d_stage);
-    h->d_stage = nullptr;
-    const size_t want = grown(h->stage_floats, floats);
-    h->stage_floats = 0;
-    float *p = nullptr;
-    int rc = dev_alloc(h, &p, want);
-    if(rc)
-        return rc;
-    h->d_stage = p;
-    h->stage_floats = want;
-    return WF_HIP_OK;
+    return grow_stage(h, &h->d_stage, &h->stage_floats, floats);
 }
 
 // the squared-peak ring follows the pushed audio (wf_hip_enable_input_rms) -- as opposed to being fed by the host
@@ -405,6 +410,40 @@ void loudness_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t fra
         hipLaunchKernelGGL(wf::loudness_push_kernel<1>, dim3(count), dim3(64), 0, h->stream, a);
 }
 
+// What a uniform push of `frames` must satisfy, and a ragged one of `count` streams (frames[i] capped at max_frames): checked by
+// the float, PCM and synth entry points alike
+int check_uniform_push(wf_hip *h, uint32_t frames)
+{
+    if(rms_follows_audio(h) && frames > h->rms_cap)
+        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", frames, h->rms_cap);
+    return loudness_check(h, frames);
+}
+
+int check_ragged_push(wf_hip *h, uint32_t count, const uint32_t *frames, uint32_t max_frames)
+{
+    if(rms_follows_audio(h))
+        return fail(h, WF_HIP_ERR_INVALID, "ragged pushes are not available while the device RMS producer follows the audio (wf_hip_enable_input_rms)");
+    if(count > 65535u)
+        return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
+    for(uint32_t i = 0; i < count; ++i)
+        WF_TRY_RC(loudness_check(h, std::min(frames[i], max_frames)));
+    return WF_HIP_OK;
+}
+
+// The end of every append, behind the kernels that wrote the rings: the write positions advance (a ragged push's kernel has
+// advanced them itself: d_frames != nullptr), then the loudness producer follows
+int finish_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, const uint32_t *d_frames)
+{
+    if(d_frames == nullptr)
+        hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
+                           h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
+    loudness_after_push(h, first, count, frames, d_frames);
+    WF_HIP_TRY(h, hipGetLastError());
+    if(d_frames == nullptr && frames % 4u)
+        h->all_aligned = false; // (a ragged push: its caller, from the counts -- fill_counts)
+    return WF_HIP_OK;
+}
+
 // d_src feeds the audio rings (nullptr: zeros); d_rms_src feeds the squared-peak ring when the producer is enabled
 // (capture_audio takes the RMS from the packet even when it is muted, src/source.cpp:1842-1871 vs :1879-1880)
 int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, const float *d_rms_src, uint32_t frames)
@@ -412,9 +451,7 @@ int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, c
     if(frames == 0)
         return WF_HIP_OK;
     // a packet longer than the ring keeps its newest ring_cap frames, as CircularBuffer + capture_audio's trimming would
-    if(rms_follows_audio(h) && frames > h->rms_cap)
-        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", frames, h->rms_cap);
-    WF_TRY_RC(loudness_check(h, frames));
+    WF_TRY_RC(check_uniform_push(h, frames));
     // the kernels index (stream, channel) rows by blockIdx.y (at most 65535): larger batches go in slices
     for(uint32_t off = 0; off < count; off += PUSH_SLICE) {
         const uint32_t cnt = std::min(PUSH_SLICE, count - off);
@@ -428,12 +465,90 @@ int push_common(wf_hip *h, uint32_t first, uint32_t count, const float *d_src, c
             rms_after_push(h, first + off, cnt, frames);
         }
     }
-    hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
-                       h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
-    loudness_after_push(h, first, count, frames, nullptr);
-    WF_HIP_TRY(h, hipGetLastError());
-    if(frames % 4u)
-        h->all_aligned = false;
+    return finish_push(h, first, count, frames, nullptr);
+}
+
+// ---- pipelined ingest ---------------------------------------------------------------------------------------------------
+// A push from page-locked memory goes through one of two slots (wf_hip::IngestSlot): the copy stream fills the slot's staging
+// block, ev_copied[slot] hands it to `stream`, whose kernels read it, and the slot's ev_consumed says that they have.  The audio
+// pushes (float, PCM; uniform or ragged) use h->ingest_slot[], the squared-peak feed h->sq_slot[]; every one of them reads:
+// validate, slot_ready, copy, hand_over, launch, slot_consumed.
+int ensure_copy_stream(wf_hip *h)
+{
+    if(h->copy_stream != nullptr)
+        return WF_HIP_OK;
+    WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    for(int i = 0; i < 2; ++i) {
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ingest_slot[i].ev_consumed, hipEventDisableTiming));
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->sq_slot[i].ev_consumed, hipEventDisableTiming));
+    }
+    return WF_HIP_OK;
+}
+
+// Makes the slot ready for a copy of `floats` into its staging block and, for a ragged push, for `counts` > 0 frame counts.
+// The ordering rule of the slots: what the slot's last push enqueued may still read its staging.  Where this push is about to
+// touch the slot from the HOST -- a ragged push rewrites the page-locked counts that the last H2D copy reads, a block that is
+// too small is released -- the host waits for ev_consumed.  Otherwise only device memory is reused, by the copy this push puts
+// on the copy stream: the copy stream waits, the host does not.
+int slot_ready(wf_hip *h, wf_hip::IngestSlot &s, size_t floats, uint32_t counts)
+{
+    const bool from_host = counts != 0 || s.stage_floats < floats;
+    if(s.used && from_host)
+        WF_HIP_TRY(h, hipEventSynchronize(s.ev_consumed));
+    else if(s.used)
+        WF_HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, s.ev_consumed, 0));
+    if(s.stage_floats < floats)
+        WF_TRY_RC(grow_stage(h, &s.d_stage, &s.stage_floats, floats));
+    if(s.frames_cap < counts) {
+        dev_release(h, s.d_frames);
+        s.d_frames = nullptr;
+        if(s.h_frames)
+            (void)hipHostFree(s.h_frames);
+        s.h_frames = nullptr;
+        s.frames_cap = 0;
+        const size_t want = std::max<size_t>(counts, 64);
+        WF_TRY_RC(dev_alloc(h, &s.d_frames, want));
+        WF_HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&s.h_frames), want * sizeof(uint32_t), hipHostMallocDefault));
+        s.frames_cap = want;
+    }
+    return WF_HIP_OK;
+}
+
+// the caller's frame counts, none above `clamp`, into the slot's page-locked block (behind slot_ready); what the callers
+// derive from them
+struct SlotCounts {
+    bool aligned = true;  // every count is a multiple of 4 (wf_hip::all_aligned)
+    uint32_t longest = 0;
+};
+constexpr uint32_t NO_CLAMP = 0xffffffffu;
+SlotCounts fill_counts(wf_hip::IngestSlot &s, const uint32_t *frames, uint32_t count, uint32_t clamp)
+{
+    SlotCounts c;
+    for(uint32_t i = 0; i < count; ++i) {
+        s.h_frames[i] = std::min(frames[i], clamp);
+        c.aligned = c.aligned && (s.h_frames[i] % 4u) == 0;
+        c.longest = std::max(c.longest, s.h_frames[i]);
+    }
+    return c;
+}
+
+// behind the copy of the samples: the `counts` frame counts of a ragged push follow them, `copied` (ev_copied[slot]) marks the
+// end of the slot's copies and the compute stream waits for it; whatever is enqueued behind (the tick) is ordered by the stream
+int hand_over(wf_hip *h, wf_hip::IngestSlot &s, hipEvent_t copied, uint32_t counts)
+{
+    if(counts)
+        WF_HIP_TRY(h, hipMemcpyAsync(s.d_frames, s.h_frames, (size_t)counts * sizeof(uint32_t), hipMemcpyHostToDevice, h->copy_stream));
+    WF_HIP_TRY(h, hipEventRecord(copied, h->copy_stream));
+    WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, copied, 0));
+    return WF_HIP_OK;
+}
+
+// behind the kernels that read the slot's staging
+int slot_consumed(wf_hip *h, wf_hip::IngestSlot &s)
+{
+    WF_HIP_TRY(h, hipEventRecord(s.ev_consumed, h->stream));
+    s.used = true;
     return WF_HIP_OK;
 }
 
@@ -487,29 +602,9 @@ int pcm_check(wf_hip *h, uint32_t count, const wf_hip_pcm *pcm)
     if(pcm->frames_per_stream) {
         if(pcm->memory != WF_HIP_PCM_PINNED || pcm->frames == 0)
             return fail(h, WF_HIP_ERR_INVALID, "a ragged push needs WF_HIP_PCM_PINNED memory and frames (max_frames) > 0");
-        if(rms_follows_audio(h))
-            return fail(h, WF_HIP_ERR_INVALID, "ragged pushes are not available while the device RMS producer follows the audio (wf_hip_enable_input_rms)");
-        if(count > 65535u)
-            return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
-        for(uint32_t i = 0; i < count; ++i)
-            WF_TRY_RC(loudness_check(h, std::min(pcm->frames_per_stream[i], pcm->frames)));
-    } else if(rms_follows_audio(h) && pcm->frames > h->rms_cap)
-        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", pcm->frames, h->rms_cap);
-    else
-        WF_TRY_RC(loudness_check(h, pcm->frames));
-    return WF_HIP_OK;
-}
-
-int ensure_copy_stream(wf_hip *h)
-{
-    if(h->copy_stream != nullptr)
-        return WF_HIP_OK;
-    WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    for(int i = 0; i < 2; ++i) {
-        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
-        WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_consumed[i], hipEventDisableTiming));
+        return check_ragged_push(h, count, pcm->frames_per_stream, pcm->frames);
     }
-    return WF_HIP_OK;
+    return check_uniform_push(h, pcm->frames);
 }
 
 // the H2D copy of a host packet into `dst`: interleaved (or every plane captured) in one piece; planar with more channels than
@@ -554,9 +649,7 @@ int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm,
         a.first = first;
         a.src = static_cast<const unsigned char *>(d_src);
         launch(dim3(1, count), h->stream, a);
-        loudness_after_push(h, first, count, frames, d_frames);
-        WF_HIP_TRY(h, hipGetLastError());
-        return WF_HIP_OK;
+        return finish_push(h, first, count, frames, d_frames);
     }
     const uint32_t tile = pcm->format <= WF_HIP_PCM_F32 ? wf::PCM_TILE / (channels * bps) : wf::PCM_TILE / bps;
     const uint32_t tiles = (uint32_t)std::min<size_t>(((size_t)frames + tile - 1) / tile, 64);
@@ -568,13 +661,7 @@ int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm,
         if(a.rms_ring)
             rms_after_push(h, first + off, cnt, frames);
     }
-    hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
-                       h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
-    loudness_after_push(h, first, count, frames, nullptr);
-    WF_HIP_TRY(h, hipGetLastError());
-    if(frames % 4u)
-        h->all_aligned = false;
-    return WF_HIP_OK;
+    return finish_push(h, first, count, frames, nullptr);
 }
 
 } // namespace
@@ -730,7 +817,7 @@ int wf_hip_push_audio(wf_hip *h, uint32_t first, uint32_t count, const float *sa
 
 int wf_hip_push_audio_muted(wf_hip *h, uint32_t first, uint32_t count, const float *samples, uint32_t frames)
 {
-    if(samples != nullptr && h != nullptr && h->d_rms_ring != nullptr && !h->rms_feed)
+    if(samples != nullptr && h != nullptr && rms_follows_audio(h))
         return push_host(h, first, count, samples, frames, true); // the RMS producer takes the packet's samples
     // a packet without data, or nobody to read it: CircularBuffer::push_back_zero
     int rc = check_range(h, first, count);
@@ -748,41 +835,14 @@ int wf_hip_push_audio_async(wf_hip *h, uint32_t first, uint32_t count, const flo
     if(pinned_samples == nullptr || slot > 1)
         return fail(h, WF_HIP_ERR_INVALID, "samples is NULL or slot is not 0 / 1");
     WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->copy_stream == nullptr) {
-        WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for(int i = 0; i < 2; ++i) {
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_consumed[i], hipEventDisableTiming));
-        }
-    }
+    wf_hip::IngestSlot &s = h->ingest_slot[slot];
     const size_t n = (size_t)count * h->cap_ch * frames;
-    if(h->stage_async_floats[slot] < n) {
-        if(h->slot_used[slot])
-            WF_HIP_TRY(h, hipEventSynchronize(h->ev_consumed[slot])); // the old block may still feed an append
-        dev_release(h, h->d_stage_async[slot]);
-        h->d_stage_async[slot] = nullptr;
-        const size_t want = grown(h->stage_async_floats[slot], n);
-        h->stage_async_floats[slot] = 0;
-        float *p = nullptr;
-        rc = dev_alloc(h, &p, want);
-        if(rc)
-            return rc;
-        h->d_stage_async[slot] = p;
-        h->stage_async_floats[slot] = want;
-    }
-    // copy stream: wait until the previous append from this slot's staging block is done, then copy
-    if(h->slot_used[slot])
-        WF_HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_consumed[slot], 0));
-    WF_HIP_TRY(h, hipMemcpyAsync(h->d_stage_async[slot], pinned_samples, n * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_copied[slot], h->copy_stream));
-    // compute stream: the append waits for the copy; whatever is enqueued behind it (the tick) is ordered by the stream
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
-    rc = push_common(h, first, count, h->d_stage_async[slot], h->d_stage_async[slot], frames);
-    if(rc)
-        return rc;
-    WF_HIP_TRY(h, hipEventRecord(h->ev_consumed[slot], h->stream));
-    h->slot_used[slot] = true;
-    return WF_HIP_OK;
+    WF_TRY_RC(ensure_copy_stream(h));
+    WF_TRY_RC(slot_ready(h, s, n, 0));
+    WF_HIP_TRY(h, hipMemcpyAsync(s.d_stage, pinned_samples, n * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+    WF_TRY_RC(hand_over(h, s, h->ev_copied[slot], 0));
+    WF_TRY_RC(push_common(h, first, count, s.d_stage, s.d_stage, frames));
+    return slot_consumed(h, s);
 }
 
 int wf_hip_push_audio_ragged_async(wf_hip *h, uint32_t first, uint32_t count, const float *pinned_samples, const uint32_t *frames,
@@ -793,67 +853,21 @@ int wf_hip_push_audio_ragged_async(wf_hip *h, uint32_t first, uint32_t count, co
         return rc;
     if(pinned_samples == nullptr || frames == nullptr || slot > 1 || max_frames == 0)
         return fail(h, WF_HIP_ERR_INVALID, "samples or frames is NULL, max_frames is 0 or slot is not 0 / 1");
-    if(rms_follows_audio(h))
-        return fail(h, WF_HIP_ERR_INVALID, "ragged pushes are not available while the device RMS producer follows the audio (wf_hip_enable_input_rms)");
-    if(count > 65535u)
-        return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
-    for(uint32_t i = 0; i < count; ++i)
-        WF_TRY_RC(loudness_check(h, std::min(frames[i], max_frames)));
+    WF_TRY_RC(check_ragged_push(h, count, frames, max_frames));
     WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->copy_stream == nullptr) {
-        WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for(int i = 0; i < 2; ++i) {
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_consumed[i], hipEventDisableTiming));
-        }
-    }
+    wf_hip::IngestSlot &s = h->ingest_slot[slot];
     const size_t n = (size_t)count * h->cap_ch * max_frames;
-    if(h->slot_used[slot])
-        WF_HIP_TRY(h, hipEventSynchronize(h->ev_consumed[slot])); // the slot's staging (samples and counts) is free again
-    if(h->stage_async_floats[slot] < n) {
-        dev_release(h, h->d_stage_async[slot]);
-        h->d_stage_async[slot] = nullptr;
-        const size_t want = grown(h->stage_async_floats[slot], n);
-        h->stage_async_floats[slot] = 0;
-        float *p = nullptr;
-        rc = dev_alloc(h, &p, want);
-        if(rc)
-            return rc;
-        h->d_stage_async[slot] = p;
-        h->stage_async_floats[slot] = want;
-    }
-    if(h->frames_async_cap[slot] < count) {
-        dev_release(h, h->d_frames_async[slot]);
-        h->d_frames_async[slot] = nullptr;
-        if(h->h_frames_async[slot])
-            (void)hipHostFree(h->h_frames_async[slot]);
-        h->h_frames_async[slot] = nullptr;
-        h->frames_async_cap[slot] = 0;
-        const size_t want = std::max<size_t>(count, 64);
-        rc = dev_alloc(h, &h->d_frames_async[slot], want);
-        if(rc)
-            return rc;
-        WF_HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_frames_async[slot]), want * sizeof(uint32_t), hipHostMallocDefault));
-        h->frames_async_cap[slot] = want;
-    }
-    bool aligned = true;
-    for(uint32_t i = 0; i < count; ++i) {
-        h->h_frames_async[slot][i] = frames[i];
-        aligned = aligned && (frames[i] % 4u) == 0;
-    }
-    WF_HIP_TRY(h, hipMemcpyAsync(h->d_stage_async[slot], pinned_samples, n * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
-    WF_HIP_TRY(h, hipMemcpyAsync(h->d_frames_async[slot], h->h_frames_async[slot], (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                 h->copy_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_copied[slot], h->copy_stream));
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
+    WF_TRY_RC(ensure_copy_stream(h));
+    WF_TRY_RC(slot_ready(h, s, n, count));
+    const SlotCounts c = fill_counts(s, frames, count, NO_CLAMP);
+    WF_HIP_TRY(h, hipMemcpyAsync(s.d_stage, pinned_samples, n * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+    WF_TRY_RC(hand_over(h, s, h->ev_copied[slot], count));
     hipLaunchKernelGGL(wf::ring_push_ragged_kernel, dim3(1, count), dim3(256), 0, h->stream, h->d_ring, h->d_wpos,
-                       h->d_flags + (size_t)h->flag_cur * h->n_streams, h->ring_cap, h->ring_stride, h->cap_ch, first, h->d_stage_async[slot],
-                       h->d_frames_async[slot], max_frames);
-    loudness_after_push(h, first, count, max_frames, h->d_frames_async[slot]);
-    WF_HIP_TRY(h, hipGetLastError());
-    WF_HIP_TRY(h, hipEventRecord(h->ev_consumed[slot], h->stream));
-    h->slot_used[slot] = true;
-    if(!aligned)
+                       h->d_flags + (size_t)h->flag_cur * h->n_streams, h->ring_cap, h->ring_stride, h->cap_ch, first, s.d_stage, s.d_frames,
+                       max_frames);
+    WF_TRY_RC(finish_push(h, first, count, max_frames, s.d_frames));
+    WF_TRY_RC(slot_consumed(h, s));
+    if(!c.aligned)
         h->all_aligned = false;
     return WF_HIP_OK;
 }
@@ -862,7 +876,7 @@ int wf_hip_ingest_done(wf_hip *h, uint32_t slot)
 {
     if(h == nullptr || slot > 1)
         return WF_HIP_ERR_INVALID;
-    if(!h->slot_used[slot] && !h->sq_slot_used[slot])
+    if(!h->ingest_slot[slot].used && !h->sq_slot[slot].used)
         return WF_HIP_OK;
     WF_HIP_TRY(h, hipSetDevice(h->device));
     WF_HIP_TRY(h, hipEventSynchronize(h->ev_copied[slot])); // the slot's last H2D copy (samples or squared peaks)
@@ -904,9 +918,7 @@ int wf_hip_push_synth(wf_hip *h, uint32_t first, uint32_t count, uint64_t seed, 
         return rc;
     if(frames == 0)
         return WF_HIP_OK;
-    if(rms_follows_audio(h) && frames > h->rms_cap)
-        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", frames, h->rms_cap);
-    WF_TRY_RC(loudness_check(h, frames));
+    WF_TRY_RC(check_uniform_push(h, frames));
     WF_HIP_TRY(h, hipSetDevice(h->device));
     const uint32_t gx = std::min<uint32_t>((frames + 255) / 256, 256);
     for(uint32_t off = 0; off < count; off += PUSH_SLICE) {
@@ -919,13 +931,7 @@ int wf_hip_push_synth(wf_hip *h, uint32_t first, uint32_t count, uint64_t seed, 
             rms_after_push(h, first + off, cnt, frames);
         }
     }
-    hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
-                       h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
-    loudness_after_push(h, first, count, frames, nullptr);
-    WF_HIP_TRY(h, hipGetLastError());
-    if(frames % 4u)
-        h->all_aligned = false;
-    return WF_HIP_OK;
+    return finish_push(h, first, count, frames, nullptr);
 }
 
 int wf_hip_push_pcm(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm)
@@ -952,54 +958,17 @@ int wf_hip_push_pcm(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm 
         WF_HIP_TRY(h, hipStreamSynchronize(h->stream)); // `data` is borrowed for the call only
         return WF_HIP_OK;
     }
-    // WF_HIP_PCM_PINNED: wf_hip_push_audio_async's pipeline (copy stream, the slot's staging block and events)
-    const uint32_t slot = pcm->slot;
+    // WF_HIP_PCM_PINNED: wf_hip_push_audio_async's pipeline
+    wf_hip::IngestSlot &s = h->ingest_slot[pcm->slot];
+    const uint32_t counts = ragged ? count : 0;
     WF_TRY_RC(ensure_copy_stream(h));
-    if(ragged && h->slot_used[slot])
-        WF_HIP_TRY(h, hipEventSynchronize(h->ev_consumed[slot])); // the slot's frame counts are free again
-    if(h->stage_async_floats[slot] < floats) {
-        if(h->slot_used[slot])
-            WF_HIP_TRY(h, hipEventSynchronize(h->ev_consumed[slot])); // the old block may still feed an append
-        dev_release(h, h->d_stage_async[slot]);
-        h->d_stage_async[slot] = nullptr;
-        const size_t want = grown(h->stage_async_floats[slot], floats);
-        h->stage_async_floats[slot] = 0;
-        float *p = nullptr;
-        WF_TRY_RC(dev_alloc(h, &p, want));
-        h->d_stage_async[slot] = p;
-        h->stage_async_floats[slot] = want;
-    }
-    bool aligned = true;
-    if(ragged) {
-        if(h->frames_async_cap[slot] < count) {
-            dev_release(h, h->d_frames_async[slot]);
-            h->d_frames_async[slot] = nullptr;
-            if(h->h_frames_async[slot])
-                (void)hipHostFree(h->h_frames_async[slot]);
-            h->h_frames_async[slot] = nullptr;
-            h->frames_async_cap[slot] = 0;
-            const size_t want = std::max<size_t>(count, 64);
-            WF_TRY_RC(dev_alloc(h, &h->d_frames_async[slot], want));
-            WF_HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_frames_async[slot]), want * sizeof(uint32_t), hipHostMallocDefault));
-            h->frames_async_cap[slot] = want;
-        }
-        for(uint32_t i = 0; i < count; ++i) {
-            h->h_frames_async[slot][i] = pcm->frames_per_stream[i];
-            aligned = aligned && (pcm->frames_per_stream[i] % 4u) == 0;
-        }
-    }
-    if(h->slot_used[slot])
-        WF_HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_consumed[slot], 0));
-    WF_HIP_TRY(h, pcm_copy(h, h->d_stage_async[slot], pcm, count, h->copy_stream, &channels, &base));
-    if(ragged)
-        WF_HIP_TRY(h, hipMemcpyAsync(h->d_frames_async[slot], h->h_frames_async[slot], (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                     h->copy_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_copied[slot], h->copy_stream));
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
-    WF_TRY_RC(pcm_append(h, first, count, pcm, h->d_stage_async[slot], channels, base, ragged ? h->d_frames_async[slot] : nullptr));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_consumed[slot], h->stream));
-    h->slot_used[slot] = true;
-    if(!aligned)
+    WF_TRY_RC(slot_ready(h, s, floats, counts));
+    const SlotCounts c = fill_counts(s, pcm->frames_per_stream, counts, NO_CLAMP);
+    WF_HIP_TRY(h, pcm_copy(h, s.d_stage, pcm, count, h->copy_stream, &channels, &base));
+    WF_TRY_RC(hand_over(h, s, h->ev_copied[pcm->slot], counts));
+    WF_TRY_RC(pcm_append(h, first, count, pcm, s.d_stage, channels, base, ragged ? s.d_frames : nullptr));
+    WF_TRY_RC(slot_consumed(h, s));
+    if(!c.aligned)
         h->all_aligned = false;
     return WF_HIP_OK;
 }
@@ -1409,69 +1378,25 @@ int wf_hip_push_rms_ragged_async(wf_hip *h, uint32_t first, uint32_t count, cons
     if(max_frames > h->rms_size)
         return fail(h, WF_HIP_ERR_INVALID, "a feed of %u values per stream exceeds the RMS window (%u)", max_frames, h->rms_size);
     WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->copy_stream == nullptr) {
-        WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for(int i = 0; i < 2; ++i) {
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_consumed[i], hipEventDisableTiming));
-        }
-    }
-    if(h->ev_sq_consumed[0] == nullptr)
-        for(int i = 0; i < 2; ++i)
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_sq_consumed[i], hipEventDisableTiming));
-    if(h->sq_slot_used[slot])
-        WF_HIP_TRY(h, hipEventSynchronize(h->ev_sq_consumed[slot])); // the slot's staging is free again (two feeds ago)
+    wf_hip::IngestSlot &s = h->sq_slot[slot];
     const size_t n = (size_t)count * max_frames;
-    if(h->sq_stage_floats[slot] < n) {
-        dev_release(h, h->d_sq_stage[slot]);
-        h->d_sq_stage[slot] = nullptr;
-        const size_t want = grown(h->sq_stage_floats[slot], n);
-        h->sq_stage_floats[slot] = 0;
-        float *p = nullptr;
-        rc = dev_alloc(h, &p, want);
-        if(rc)
-            return rc;
-        h->d_sq_stage[slot] = p;
-        h->sq_stage_floats[slot] = want;
-    }
-    if(h->sq_frames_cap[slot] < count) {
-        dev_release(h, h->d_sq_frames[slot]);
-        h->d_sq_frames[slot] = nullptr;
-        if(h->h_sq_frames[slot])
-            (void)hipHostFree(h->h_sq_frames[slot]);
-        h->h_sq_frames[slot] = nullptr;
-        h->sq_frames_cap[slot] = 0;
-        const size_t want = std::max<size_t>(count, 64);
-        rc = dev_alloc(h, &h->d_sq_frames[slot], want);
-        if(rc)
-            return rc;
-        WF_HIP_TRY(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_sq_frames[slot]), want * sizeof(uint32_t), hipHostMallocDefault));
-        h->sq_frames_cap[slot] = want;
-    }
-    uint32_t longest = 0;
-    for(uint32_t i = 0; i < count; ++i) {
-        h->h_sq_frames[slot][i] = std::min(frames[i], max_frames);
-        longest = std::max(longest, h->h_sq_frames[slot][i]);
-    }
-    if(longest == 0)
+    WF_TRY_RC(ensure_copy_stream(h));
+    WF_TRY_RC(slot_ready(h, s, n, count)); // (in use two feeds ago)
+    const SlotCounts c = fill_counts(s, frames, count, max_frames);
+    if(c.longest == 0)
         return WF_HIP_OK; // nothing to consume this frame (sync_rms_buffer returns false for every stream)
     // rows are max_frames apart; only the part any stream uses crosses the bus when the rows are short
-    if(longest == max_frames || count == 1)
-        WF_HIP_TRY(h, hipMemcpyAsync(h->d_sq_stage[slot], pinned_sq, (count == 1 ? (size_t)longest : n) * sizeof(float), hipMemcpyHostToDevice,
-                                     h->copy_stream));
+    if(c.longest == max_frames || count == 1)
+        WF_HIP_TRY(h, hipMemcpyAsync(s.d_stage, pinned_sq, (count == 1 ? (size_t)c.longest : n) * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
     else
-        WF_HIP_TRY(h, hipMemcpy2DAsync(h->d_sq_stage[slot], (size_t)max_frames * sizeof(float), pinned_sq, (size_t)max_frames * sizeof(float),
-                                       (size_t)longest * sizeof(float), count, hipMemcpyHostToDevice, h->copy_stream));
-    WF_HIP_TRY(h, hipMemcpyAsync(h->d_sq_frames[slot], h->h_sq_frames[slot], (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                 h->copy_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_copied[slot], h->copy_stream));
+        WF_HIP_TRY(h, hipMemcpy2DAsync(s.d_stage, (size_t)max_frames * sizeof(float), pinned_sq, (size_t)max_frames * sizeof(float),
+                                       (size_t)c.longest * sizeof(float), count, hipMemcpyHostToDevice, h->copy_stream));
     WF_TRY_RC(join_lanes(h));
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied[slot], 0));
+    WF_TRY_RC(hand_over(h, s, h->ev_copied[slot], count));
     hipLaunchKernelGGL(wf::rms_feed_ragged_kernel, dim3(count), dim3(256), 0, h->stream, h->d_rms_ring, h->d_rms_bsum, h->d_rend, h->rms_cap, first,
-                       h->d_sq_stage[slot], h->d_sq_frames[slot], max_frames);
+                       s.d_stage, s.d_frames, max_frames);
     WF_HIP_TRY(h, hipGetLastError());
-    WF_HIP_TRY(h, hipEventRecord(h->ev_sq_consumed[slot], h->stream));
-    h->sq_slot_used[slot] = true;
+    WF_TRY_RC(slot_consumed(h, s));
     h->main_dirty = true;
     return WF_HIP_OK;
 }

@@ -37,13 +37,22 @@ struct wf_hip {
     hipEvent_t ev_lane[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr}, ev_fork = nullptr;
     bool lanes_pending = false; // a lane holds work `stream` has not waited for
     bool main_dirty = true;     // `stream` holds work the lanes have not waited for
-    // pipelined ingest (wf_hip_push_audio_async): a copy stream, per-slot staging blocks and events
+    // pipelined ingest (wf_hip_push_audio_async and the other pushes from page-locked memory; wf_hip.hip, "pipelined ingest"):
+    // a copy stream and two slots, used alternately by the caller
+    struct IngestSlot {
+        float *d_stage = nullptr;         // device staging block: filled on the copy stream, read by the kernels on `stream`
+        size_t stage_floats = 0;
+        uint32_t *d_frames = nullptr;     // ragged pushes: per-stream frame counts ...
+        uint32_t *h_frames = nullptr;     // ... and the page-locked copy their H2D reads from
+        size_t frames_cap = 0;
+        hipEvent_t ev_consumed = nullptr; // the kernels that read the slot's staging have finished
+        bool used = false;                // ev_consumed has been recorded
+    };
     hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copied[2] = {nullptr, nullptr};   // the H2D copy of the slot has finished (host buffer free, staging full)
-    hipEvent_t ev_consumed[2] = {nullptr, nullptr}; // the ring append that read the slot's staging block has finished
-    float *d_stage_async[2] = {nullptr, nullptr};
-    size_t stage_async_floats[2] = {0, 0};
-    bool slot_used[2] = {false, false};
+    hipEvent_t ev_copied[2] = {nullptr, nullptr}; // the slot's last H2D copy, of samples or of squared peaks, has finished (host
+                                                  // buffer free, staging full): wf_hip_ingest_done waits for it
+    IngestSlot ingest_slot[2];                    // audio, float or PCM
+    IngestSlot sq_slot[2];                        // the squared peaks of wf_hip_push_rms_ragged_async ([count][max_frames])
     // pipelined readback (wf_hip_read_bars_async): a stream for the D2H copies, a device snapshot and two events per slot
     hipStream_t read_stream = nullptr;
     hipEvent_t ev_snap[2] = {nullptr, nullptr}, ev_read[2] = {nullptr, nullptr};
@@ -51,9 +60,6 @@ struct wf_hip {
     size_t snap_floats[2] = {0, 0};
     bool read_used[2] = {false, false};
     bool rows_in_flight[2] = {false, false}; // wf_hip_read_rows_async copies straight from m_decibels: the next tick waits for them
-    uint32_t *d_frames_async[2] = {nullptr, nullptr}; // ragged ingest: per-stream frame counts of the slot
-    uint32_t *h_frames_async[2] = {nullptr, nullptr}; // (page-locked host copy)
-    size_t frames_async_cap[2] = {0, 0};
     uint8_t *d_silent_bytes[2] = {nullptr, nullptr};  // rows readback: m_last_silent as bytes
     size_t silent_bytes_cap[2] = {0, 0};
     uint32_t n_streams = 0;
@@ -136,13 +142,6 @@ struct wf_hip {
     float *d_rms_bsum = nullptr;     // [n_streams][rms_cap / RMS_BLOCK]
     uint32_t *d_rend = nullptr;      // [n_streams] consumption point of sync_rms_buffer
     bool rms_feed = false;           // the squared peaks come from the host (wf_hip_push_rms_ragged_async), not from the pushed audio
-    float *d_sq_stage[2] = {nullptr, nullptr};      // feed staging per ingest slot: [count][max_frames] squared peaks ...
-    size_t sq_stage_floats[2] = {0, 0};
-    uint32_t *d_sq_frames[2] = {nullptr, nullptr};  // ... and their counts
-    uint32_t *h_sq_frames[2] = {nullptr, nullptr};  // page-locked copy the H2D reads from
-    size_t sq_frames_cap[2] = {0, 0};
-    hipEvent_t ev_sq_consumed[2] = {nullptr, nullptr};
-    bool sq_slot_used[2] = {false, false};
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), nullptr while it is off
     struct wf::LoudState *d_loud = nullptr;       // [n_streams]

@@ -852,7 +852,10 @@ void wf_hip_destroy(wf_hip *h)
         (void)hipStreamSynchronize(h->copy_stream);
     for(int i = 0; i < 2; ++i) {
         if(h->ev_copied[i]) (void)hipEventDestroy(h->ev_copied[i]);
-        if(h->ev_consumed[i]) (void)hipEventDestroy(h->ev_consumed[i]);
+        for(wf_hip::IngestSlot *s : {&h->ingest_slot[i], &h->sq_slot[i]}) { // (their device blocks went with h->allocs)
+            if(s->ev_consumed) (void)hipEventDestroy(s->ev_consumed);
+            if(s->h_frames) (void)hipHostFree(s->h_frames);
+        }
     }
     if(h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if(h->read_stream)
@@ -862,11 +865,6 @@ void wf_hip_destroy(wf_hip *h)
         if(h->ev_read[i]) (void)hipEventDestroy(h->ev_read[i]);
     }
     if(h->read_stream) (void)hipStreamDestroy(h->read_stream);
-    for(int i = 0; i < 2; ++i) {
-        if(h->h_frames_async[i]) (void)hipHostFree(h->h_frames_async[i]);
-        if(h->h_sq_frames[i]) (void)hipHostFree(h->h_sq_frames[i]);
-        if(h->ev_sq_consumed[i]) (void)hipEventDestroy(h->ev_sq_consumed[i]);
-    }
     for(auto e : h->ev_bars_lane)
         if(e) (void)hipEventDestroy(e);
     for(int i = 0; i < 2; ++i) {
