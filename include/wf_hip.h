@@ -38,6 +38,8 @@
  *                        window of audio, measured on the device when read
  *   WF_HIP_OUT_PITCH     not in the reference: the fundamental frequency of every stream's newest window of audio (YIN),
  *                        estimated on the device when read
+ *   WF_HIP_OUT_BANDS     not in the reference: third-octave band levels (IEC 61260-1) and the Z / A / C weighted level
+ *                        (IEC 61672-1) of every m_decibels row, summed on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -375,9 +377,11 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_SIGNAL,         /* wf_hip_signal                              level, DC, clipping and stereo phase of the newest
                                   wf_hip_fft_size() frames in the rings as of the pushes issued so far (spectrum and meter
                                   batches; definition below) */
-    WF_HIP_OUT_PITCH           /* wf_hip_pitch                               fundamental frequency (YIN) of the newest
+    WF_HIP_OUT_PITCH,          /* wf_hip_pitch                               fundamental frequency (YIN) of the newest
                                   min(wf_hip_fft_size(), 4096) frames in the rings as of the pushes issued so far (spectrum
                                   and meter batches; definition below) */
+    WF_HIP_OUT_BANDS           /* wf_hip_bands [output_channels]             third-octave band levels and the Z / A / C weighted level
+                                  of each m_decibels row as of the newest tick (spectrum batches; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -487,6 +491,54 @@ typedef struct wf_hip_pitch {
     uint32_t lag;    /* the integer lag chosen, frames */
     uint32_t voiced; /* 1: a lag under the threshold was found; 0: the best guess, or nothing */
 } wf_hip_pitch;      /* 16 bytes */
+/* ---- band levels (WF_HIP_OUT_BANDS) ---------------------------------------------------------------------------------------
+ * Per stream and output channel, the levels a real-time analyser shows: 31 third-octave bands and the broadband level
+ * unweighted (Z), A-weighted and C-weighted.  sr = cfg.sample_rate, N = wf_hip_fft_size(), M = N / 2, d[0..M-1] the row exactly
+ * as WF_HIP_OUT_DECIBELS returns it.  Everything below is float64 unless it says otherwise.
+ *   power          P[k] = 10^(d[k] / 10) from the float32 value; P[k] = 0 where d[k] <= wf_hip_db_min(); P[0] = 0 (the DC bin is
+ *                  left out: its magnitude carries the factor 2 of the one-sided spectrum, and no band reaches it).
+ *   ENBW           the window's equivalent noise bandwidth in bins, N sum(w^2) / (sum w)^2, both sums over the float32 table
+ *                  WF_HIP_TABLE_WINDOW in index order; 1 for WF_WINDOW_NONE (an empty table).  Computed on the host.  The
+ *                  rows hold |X| 2 / window_sum, so a sine of amplitude A has the power sum A^2 ENBW over its main lobe
+ *                  wherever it falls between bins (Parseval); dividing by ENBW makes every level below read 20 log10 A for a
+ *                  sine of amplitude A, the convention of the rows themselves.
+ *   band grid      IEC 61260-1, base ten: band b = 0 .. WF_HIP_NUM_BANDS - 1 has the centre 1000 * 10^((b - 17) / 10) Hz
+ *                  (nominal 20 Hz .. 20 kHz) and lies between the edges e[b] and e[b + 1],
+ *                  e[j] = 1000 * 10^((2 (j - 17) - 1) / 20) Hz, j = 0 .. 31.  In bins: E[j] = e[j] N / sr.
+ *   bin to band    bin k >= 1 stands for the interval [k - 0.5, k + 0.5] in bins.  Its weight in band b is the length of the
+ *                  overlap of that interval with [E[b], E[b + 1]]:
+ *                  weight(b, k) = max(min(k + 0.5, E[b + 1]) - max(k - 0.5, E[b]), 0), 0 to 1.  A bin an edge cuts is shared by
+ *                  the two bands, its two weights adding to 1.
+ *                  band power(b) = sum_k weight(b, k) P[k] / ENBW, band_db[b] = 10 log10(band power), rounded to float32 once.
+ *   covered        bit b is set when E[b] >= 0.5 and E[b + 1] <= M - 0.5: the band lies wholly inside the row's frequency
+ *                  range.  A band only partly inside still reports what lies inside; a band with no overlap, or with power
+ *                  0, reads -INFINITY.  Bit 31 is 0.  `covered` depends on N and sr alone, never on the row.
+ *   totals         total = sum_{k=1..M-1} P[k] / ENBW; a and c are the same sum with P[k] multiplied by the squared
+ *                  IEC 61672-1 weighting at f = k sr / N, normalised to exactly 1 at 1000 Hz (not the rounded +2.00 / +0.06 dB):
+ *                  RA(f) = 12194^2 f^4 / ((f^2 + 20.6^2) sqrt((f^2 + 107.7^2) (f^2 + 737.9^2)) (f^2 + 12194^2)),
+ *                  RC(f) = 12194^2 f^2 / ((f^2 + 20.6^2) (f^2 + 12194^2)), weight (R(f) / R(1000))^2.
+ *                  Each total is 10 log10 of its sum, -INFINITY for 0, rounded to float32 once.
+ *   determinism    no atomics; the order of every sum depends on M and the edges alone, never on the data or on timing: the
+ *                  same rows read bit-identically.  A host that restates the sums in another order, or with another exp10,
+ *                  differs by rounding only: below 2e-11 dB before the one rounding to float32, so by at most one float32 ulp.
+ * The levels describe the rows the batch displays: after slope, smoothing, volume normalisation and roll-off, over the whole
+ * row and not only the cutoff range.  A host that wants calibrated levels configures slope 0, no volume normalisation and no
+ * roll-off.  Rows at DB_MIN -- hidden, freshly created or reset streams -- read -INFINITY in every level, with `covered` as
+ * always.  After WF_HIP_TICK_NO_DECIBELS ticks the levels are as stale as the rows.  Every legal FFT size and sample rate is
+ * served; a short FFT simply leaves the low bands uncovered.  Octave bands are the sums of three third-octave powers.
+ * Computed when read, by one kernel behind the ticks issued so far, into a block the first read allocates together with
+ * the tables of the band edges and of the bins' A and C weights: a handle whose bands are never read allocates and launches nothing new.  Meter and waveform batches:
+ * wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads them through
+ * wf_hip_multi_read. */
+#define WF_HIP_NUM_BANDS 31
+typedef struct wf_hip_bands {
+    float band_db[WF_HIP_NUM_BANDS]; /* third-octave band levels, band 0 = 20 Hz ... band 30 = 20 kHz */
+    uint32_t covered;                /* bit b set: band b lies wholly inside the row's frequency range */
+    float total_db;                  /* Z (unweighted) level of the whole row */
+    float a_db;                      /* A-weighted level of the whole row (IEC 61672-1) */
+    float c_db;                      /* C-weighted level of the whole row */
+    uint32_t reserved;               /* 0 */
+} wf_hip_bands;                      /* 144 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

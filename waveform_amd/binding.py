@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH = range(14)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS = range(15)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -138,6 +138,13 @@ PITCH_MIN_LAG = 8  # WF_HIP_PITCH_MIN_LAG: the shortest lag searched, so hz <= s
 PITCH_THRESHOLD = 0.15  # WF_HIP_PITCH_THRESHOLD: the first lag whose normalised difference is under it is voiced
 PITCH_MAX_WINDOW = 4096  # WF_HIP_PITCH_MAX_WINDOW
 PITCH_DTYPE = np.dtype([("hz", np.float32), ("clarity", np.float32), ("lag", np.uint32), ("voiced", np.uint32)])
+
+
+# struct wf_hip_bands (include/wf_hip.h): third-octave band levels and the Z / A / C weighted level of one m_decibels row
+NUM_BANDS = 31  # WF_HIP_NUM_BANDS
+BANDS_DTYPE = np.dtype([("band_db", np.float32, (NUM_BANDS,)), ("covered", np.uint32), ("total_db", np.float32), ("a_db", np.float32),
+                        ("c_db", np.float32), ("reserved", np.uint32)])
+BAND_CENTRES_HZ = 1000.0 * 10.0 ** ((np.arange(NUM_BANDS) - 17) / 10.0)  # IEC 61260-1, base ten: 19.95 Hz .. 19.95 kHz
 
 
 class Readback(C.Structure):
@@ -367,6 +374,11 @@ class SpectrumBatch:
         """[count] structured array of wf_hip_pitch (PITCH_DTYPE): fundamental frequency, clarity, lag and voiced flag of each
         stream's newest min(fft_size, PITCH_MAX_WINDOW) frames as of the pushes issued so far, by YIN on the device when read"""
         return self._read(OUT_PITCH, first, count, (), PITCH_DTYPE)
+
+    def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count, output_channels] structured array of wf_hip_bands (BANDS_DTYPE): the third-octave band levels and the Z / A / C
+        weighted level of each m_decibels row as of the newest tick, summed on the device when read"""
+        return self._read(OUT_BANDS, first, count, (self.output_channels,), BANDS_DTYPE)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -741,6 +753,12 @@ class MultiBatch:
         count = self.streams - first if count is None else count
         out = np.empty(count, PITCH_DTYPE)
         self._ck(self.L.wf_hip_multi_read(self.m, OUT_PITCH, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        count = self.streams - first if count is None else count
+        out = np.empty((count, self.output_channels), BANDS_DTYPE)
+        self._ck(self.L.wf_hip_multi_read(self.m, OUT_BANDS, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:

@@ -24,6 +24,7 @@
 #include "wf_peaks.hpp"
 #include "wf_signal.hpp"
 #include "wf_pitch.hpp"
+#include "wf_bands.hpp"
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
@@ -1737,6 +1738,10 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         if(h->N < 64) { *why = "the pitch needs a window of at least 64 frames"; return nullptr; }
         *per_stream = sizeof(wf_hip_pitch);
         return h->d_ring;
+    case WF_HIP_OUT_BANDS: // (computed from the rows when read, into a block the first read allocates: read_bands)
+        if(h->meter || h->wave) { *why = "meter / waveform batch: band levels belong to spectrum batches"; return nullptr; }
+        *per_stream = (size_t)h->out_ch * sizeof(wf_hip_bands);
+        return h->d_decibels;
     }
     *why = "unknown output";
     return nullptr;
@@ -1808,6 +1813,73 @@ static int read_pitch(wf_hip *h, uint32_t first, uint32_t count, void *out)
     return read_back(h, a.out, out, (size_t)count * sizeof(wf_hip_pitch));
 }
 
+// the first read of WF_HIP_OUT_BANDS: the output block, and what follows from the configuration alone -- the band edges in
+// bins (IEC 61260-1, base ten), which bands lie wholly inside the row, the window's equivalent noise bandwidth, the A and C
+// weights of every bin
+static int setup_bands(wf_hip *h)
+{
+    std::vector<double> edges(WF_HIP_NUM_BANDS + 1);
+    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
+        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)h->N / (double)h->cfg.sample_rate;
+    h->bands_covered = 0;
+    for(int b = 0; b < WF_HIP_NUM_BANDS; ++b)
+        if(edges[b] >= 0.5 && edges[b + 1] <= (double)h->M - 0.5)
+            h->bands_covered |= 1u << b;
+    h->bands_enbw = 1.0;
+    if(!h->tab.window.empty()) {
+        double s1 = 0.0, s2 = 0.0;
+        for(const float w : h->tab.window) {
+            s1 += (double)w;
+            s2 += (double)w * (double)w;
+        }
+        h->bands_enbw = (double)h->N * s2 / (s1 * s1);
+    }
+    // (R(f) / R(1000))^2 of IEC 61672-1's RA and RC at every bin's frequency
+    const auto ra = [](double f) {
+        const double f2 = f * f;
+        return 12194.0 * 12194.0 * f2 * f2 /
+               ((f2 + 20.6 * 20.6) * std::sqrt((f2 + 107.7 * 107.7) * (f2 + 737.9 * 737.9)) * (f2 + 12194.0 * 12194.0));
+    };
+    const auto rc = [](double f) {
+        const double f2 = f * f;
+        return 12194.0 * 12194.0 * f2 / ((f2 + 20.6 * 20.6) * (f2 + 12194.0 * 12194.0));
+    };
+    std::vector<double> weights((size_t)h->M * 2);
+    for(uint32_t k = 0; k < h->M; ++k) {
+        const double f = (double)k * (double)h->cfg.sample_rate / (double)h->N;
+        const double a = ra(f) / ra(1000.0), c = rc(f) / rc(1000.0);
+        weights[2 * (size_t)k] = a * a;
+        weights[2 * (size_t)k + 1] = c * c;
+    }
+    if(h->d_band_edges == nullptr)
+        WF_TRY_RC(upload(h, &h->d_band_edges, edges)); // (pageable memory: staged before the call returns)
+    if(h->d_band_weights == nullptr)
+        WF_TRY_RC(upload(h, &h->d_band_weights, weights));
+    return dev_alloc(h, &h->d_bands, (size_t)h->n_streams * h->out_ch); // (last: d_bands says that all of this is in place)
+}
+
+// WF_HIP_OUT_BANDS of streams [first, first+count): one wavefront per m_decibels row, on `stream` behind the ticks issued
+static int read_bands(wf_hip *h, uint32_t first, uint32_t count, void *out)
+{
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    if(h->d_bands == nullptr)
+        WF_TRY_RC(setup_bands(h));
+    wf::BandsArgs a{};
+    a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
+    a.out = h->d_bands + (size_t)first * h->out_ch;
+    a.edges = h->d_band_edges;
+    a.n_rows = count * h->out_ch;
+    a.M = h->M;
+    a.covered = h->bands_covered;
+    a.db_min = wf::db_min();
+    a.enbw = h->bands_enbw;
+    a.weights = h->d_band_weights;
+    hipLaunchKernelGGL(wf::bands_read_kernel, dim3((a.n_rows + wf::WF_BANDS_WAVES - 1) / wf::WF_BANDS_WAVES), dim3(64 * wf::WF_BANDS_WAVES),
+                       0, h->stream, a);
+    WF_HIP_TRY(h, hipGetLastError());
+    return read_back(h, a.out, out, (size_t)a.n_rows * sizeof(wf_hip_bands));
+}
+
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
 {
     if(h == nullptr)
@@ -1841,6 +1913,8 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
         return read_signal(h, first, count, out);
     if(what == WF_HIP_OUT_PITCH)
         return read_pitch(h, first, count, out);
+    if(what == WF_HIP_OUT_BANDS)
+        return read_bands(h, first, count, out);
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
         rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));

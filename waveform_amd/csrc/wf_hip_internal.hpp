@@ -151,6 +151,11 @@ struct wf_hip {
     wf_hip_peaks *d_peaks = nullptr;              // [n_streams][out_ch] WF_HIP_OUT_PEAKS, allocated by its first read (wf_peaks.hpp)
     wf_hip_signal *d_signal = nullptr;            // [n_streams] WF_HIP_OUT_SIGNAL, allocated by its first read (wf_signal.hpp)
     wf_hip_pitch *d_pitch = nullptr;              // [n_streams] WF_HIP_OUT_PITCH, allocated by its first read (wf_pitch.hpp)
+    wf_hip_bands *d_bands = nullptr;              // [n_streams][out_ch] WF_HIP_OUT_BANDS, allocated by its first read (wf_bands.hpp)
+    double *d_band_edges = nullptr;               // [WF_HIP_NUM_BANDS + 1] the band edges in bins, uploaded by that read
+    uint32_t bands_covered = 0;                   // wf_hip_bands::covered of this batch
+    double bands_enbw = 1.0;                      // the window's equivalent noise bandwidth in bins
+    double *d_band_weights = nullptr;             // [M][2] the squared A and C weights of every bin, uploaded by that read
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;
