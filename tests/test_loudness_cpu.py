@@ -2,8 +2,6 @@
 float64 reference (tests/loudness_ref.py) against analytic truth, the new exports, the ctypes mirror of struct
 wf_hip_loudness against the C layout, and a gfx950 compile of the new kernels with no scratch."""
 import ctypes as C
-import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -13,6 +11,7 @@ import pytest
 import waveform_amd as wf
 from waveform_amd import binding
 import loudness_ref as ref
+from kernel_usage import kernel_usage
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -113,25 +112,6 @@ def test_new_symbols_exported_and_null_handle_refused(so):
 
 
 def test_loudness_kernels_have_no_scratch():
-    csrc = ROOT / "waveform_amd" / "csrc"
-    hipcc = Path("/opt/rocm/bin/hipcc")
-    if not hipcc.exists():
-        found = shutil.which("hipcc")
-        if found is None:
-            pytest.skip("hipcc not found")
-        hipcc = Path(found)
-    r = subprocess.run([str(hipcc), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-slp-vectorize", "-I", str(ROOT / "include"),
-                        "-I", str(csrc), "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", "-c", str(csrc / "wf_hip.hip"),
-                        "-o", "/dev/null"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    scratch = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and "loudness_" in name:
-            scratch[name] = int(m.group(1))
+    scratch = {name: r.get("ScratchSize [bytes/lane]") for name, r in kernel_usage("wf_hip_measure", "loudness_").items()}
     assert len(scratch) == 3, sorted(scratch)  # the push kernel for 1 and 2 channels, the read kernel
     assert all(v == 0 for v in scratch.values()), scratch

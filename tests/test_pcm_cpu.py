@@ -12,6 +12,7 @@ import pytest
 import waveform_amd as wf
 from waveform_amd import binding
 from pcm_convert import to_float, captured
+from kernel_usage import kernel_usage
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -79,26 +80,6 @@ def test_new_symbols_exported_and_null_handle_refused():
 
 
 def test_append_kernel_has_no_scratch():
-    csrc = ROOT / "waveform_amd" / "csrc"
-    hipcc = Path("/opt/rocm/bin/hipcc")
-    if not hipcc.exists():
-        import shutil
-        found = shutil.which("hipcc")
-        if found is None:
-            pytest.skip("hipcc not found")
-        hipcc = Path(found)
-    r = subprocess.run([str(hipcc), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-slp-vectorize", "-I", str(ROOT / "include"),
-                        "-I", str(csrc), "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", "-c", str(csrc / "wf_hip.hip"),
-                        "-o", "/dev/null"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    scratch = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and "ring_push_pcm_kernel" in name:
-            scratch[name] = int(m.group(1))
+    scratch = {name: r.get("ScratchSize [bytes/lane]") for name, r in kernel_usage("wf_hip", "ring_push_pcm_kernel").items()}
     assert len(scratch) == 16, sorted(scratch)  # 4 sample types x interleaved / planar x ragged or not
     assert all(v == 0 for v in scratch.values()), scratch

@@ -1,8 +1,6 @@
 """Spectral peaks (WF_HIP_OUT_PEAKS) without a device: the structured dtype against the C layout, the appended output number,
 the export count, the float64 reference (tests/peaks_ref.py) against exact parabolas and hand-built rows, and a gfx950 compile
 of the read kernel with no scratch."""
-import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -12,6 +10,7 @@ import pytest
 import waveform_amd as wf
 from waveform_amd import binding
 import peaks_ref as ref
+from kernel_usage import kernel_usage
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -85,24 +84,8 @@ def test_reference_tie_and_threshold_rules():
 
 
 def test_peaks_kernel_has_no_scratch():
-    csrc = ROOT / "waveform_amd" / "csrc"
-    hipcc = Path("/opt/rocm/bin/hipcc")
-    if not hipcc.exists():
-        found = shutil.which("hipcc")
-        if found is None:
-            pytest.skip("hipcc not found")
-        hipcc = Path(found)
-    r = subprocess.run([str(hipcc), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-slp-vectorize", "-I", str(ROOT / "include"),
-                        "-I", str(csrc), "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", "-c", str(csrc / "wf_hip.hip"),
-                        "-o", "/dev/null"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name and "peaks_read_kernel" in name:
-            res[m.group(1)] = int(m.group(2))
+    found = kernel_usage("wf_hip_measure", "peaks_read_kernel")
+    assert len(found) == 1, found
+    (res,) = found.values()
     assert res.get("ScratchSize [bytes/lane]") == 0 and res.get("VGPRs Spill") == 0, res
     assert res.get("Occupancy [waves/SIMD]") == 8, res  # one row per wavefront: 8192 rows fill 256 CUs x 4 SIMDs x 8 at once

@@ -1,8 +1,6 @@
 """Pitch (WF_HIP_OUT_PITCH) without a device: the structured dtype against the C layout, the appended output number, the export
 count, the float64 reference (tests/pitch_ref.py) against analytic cases, every seeded input of the GPU tests shown to be well
 conditioned for the reference alone, and a gfx950 compile of the read kernel with no scratch."""
-import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -14,6 +12,7 @@ from waveform_amd import binding
 import pitch_cases as cases
 import pitch_ref as ref
 from signal_ref import History
+from kernel_usage import kernel_usage
 
 ROOT = Path(__file__).resolve().parents[1]
 SR = cases.SR
@@ -138,25 +137,7 @@ def test_fuzz_inputs_are_well_conditioned(fft, cap, kw, ring):
 
 
 def test_pitch_kernel_has_no_scratch():
-    csrc = ROOT / "waveform_amd" / "csrc"
-    hipcc = Path("/opt/rocm/bin/hipcc")
-    if not hipcc.exists():
-        found = shutil.which("hipcc")
-        if found is None:
-            pytest.skip("hipcc not found")
-        hipcc = Path(found)
-    r = subprocess.run([str(hipcc), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-slp-vectorize", "-I", str(ROOT / "include"),
-                        "-I", str(csrc), "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", "-c", str(csrc / "wf_hip.hip"),
-                        "-o", "/dev/null"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name and "pitch_read_kernel" in name:
-            res.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    res = kernel_usage("wf_hip_measure", "pitch_read_kernel")
     assert len(res) == 2, res  # mono and stereo capture
     for name, r in res.items():
         assert r.get("ScratchSize [bytes/lane]") == 0 and r.get("VGPRs Spill") == 0, (name, r)

@@ -146,6 +146,22 @@ BANDS_DTYPE = np.dtype([("band_db", np.float32, (NUM_BANDS,)), ("covered", np.ui
                         ("c_db", np.float32), ("reserved", np.uint32)])
 BAND_CENTRES_HZ = 1000.0 * 10.0 ** ((np.arange(NUM_BANDS) - 17) / 10.0)  # IEC 61260-1, base ten: 19.95 Hz .. 19.95 kHz
 
+# the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
+# row -- output_channels per stream -- rather than one per stream)
+MEASURES = {
+    "loudness": (OUT_LOUDNESS, LOUDNESS_DTYPE, False),
+    "peaks": (OUT_PEAKS, PEAKS_DTYPE, True),
+    "signal": (OUT_SIGNAL, SIGNAL_DTYPE, False),
+    "pitch": (OUT_PITCH, PITCH_DTYPE, False),
+    "bands": (OUT_BANDS, BANDS_DTYPE, True),
+}
+
+
+def _read_measure(batch, name: str, first: int, count: int | None) -> np.ndarray:
+    """the reader `name` of a SpectrumBatch or MultiBatch: [count] or [count, output_channels] entries"""
+    what, dtype, per_row = MEASURES[name]
+    return batch._read(what, first, count, (batch.output_channels,) if per_row else (), dtype)
+
 
 class Readback(C.Structure):
     """wf_hip_readback: the page-locked destinations of one wf_hip_read_async (NULL leaves an output out)"""
@@ -342,7 +358,6 @@ class SpectrumBatch:
         self._ck(self.L.wf_hip_enable_input_rms(self.h, 0))
 
     def input_rms(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
         return self._read(OUT_INPUT_RMS, first, count, (), np.float32)
 
     def enable_loudness(self):
@@ -358,27 +373,27 @@ class SpectrumBatch:
 
     def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array with the fields of wf_hip_loudness (LOUDNESS_DTYPE)"""
-        return self._read(OUT_LOUDNESS, first, count, (), LOUDNESS_DTYPE)
+        return _read_measure(self, "loudness", first, count)
 
     def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count, output_channels] structured array of wf_hip_peaks (PEAKS_DTYPE): the strongest peaks of each m_decibels row
         as of the newest tick, found on the device when read"""
-        return self._read(OUT_PEAKS, first, count, (self.output_channels,), PEAKS_DTYPE)
+        return _read_measure(self, "peaks", first, count)
 
     def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_signal (SIGNAL_DTYPE): level, DC, clipping and stereo phase of each stream's
         newest fft_size frames as of the pushes issued so far, measured on the device when read"""
-        return self._read(OUT_SIGNAL, first, count, (), SIGNAL_DTYPE)
+        return _read_measure(self, "signal", first, count)
 
     def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_pitch (PITCH_DTYPE): fundamental frequency, clarity, lag and voiced flag of each
         stream's newest min(fft_size, PITCH_MAX_WINDOW) frames as of the pushes issued so far, by YIN on the device when read"""
-        return self._read(OUT_PITCH, first, count, (), PITCH_DTYPE)
+        return _read_measure(self, "pitch", first, count)
 
     def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count, output_channels] structured array of wf_hip_bands (BANDS_DTYPE): the third-octave band levels and the Z / A / C
         weighted level of each m_decibels row as of the newest tick, summed on the device when read"""
-        return self._read(OUT_BANDS, first, count, (self.output_channels,), BANDS_DTYPE)
+        return _read_measure(self, "bands", first, count)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -472,7 +487,6 @@ class SpectrumBatch:
 
     # -- results ------------------------------------------------------------------------
     def decibels(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
         return self._read(OUT_DECIBELS, first, count, (self.output_channels, self.bins), np.float32)
 
     def _read(self, what: int, first: int, count: int | None, shape, dtype) -> np.ndarray:
@@ -703,17 +717,18 @@ class MultiBatch:
     def sync(self):
         self._ck(self.L.wf_hip_multi_sync(self.m))
 
-    def decibels(self, first: int = 0, count: int | None = None) -> np.ndarray:
+    def _read(self, what: int, first: int, count: int | None, shape, dtype) -> np.ndarray:
+        """wf_hip_multi_read: output `what` of streams [first, first+count) as [count, *shape]"""
         count = self.streams - first if count is None else count
-        out = np.empty((count, self.output_channels, self.bins), np.float32)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_DECIBELS, first, count, out.ctypes.data_as(C.c_void_p)))
+        out = np.empty((count,) + tuple(shape), dtype)
+        self._ck(self.L.wf_hip_multi_read(self.m, what, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def decibels(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        return self._read(OUT_DECIBELS, first, count, (self.output_channels, self.bins), np.float32)
+
     def bars(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty((count, self.display_channels, self.num_bars), np.float32)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_BARS, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._read(OUT_BARS, first, count, (self.display_channels, self.num_bars), np.float32)
 
     def _loudness_on_shards(self, first: int, count: int):
         """wf_hip_enable_loudness on every shard the global range overlaps, with local indices"""
@@ -732,40 +747,22 @@ class MultiBatch:
         self._loudness_on_shards(first, count)
 
     def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty(count, LOUDNESS_DTYPE)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_LOUDNESS, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _read_measure(self, "loudness", first, count)
 
     def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty((count, self.output_channels), PEAKS_DTYPE)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_PEAKS, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _read_measure(self, "peaks", first, count)
 
     def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty(count, SIGNAL_DTYPE)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_SIGNAL, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _read_measure(self, "signal", first, count)
 
     def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty(count, PITCH_DTYPE)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_PITCH, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _read_measure(self, "pitch", first, count)
 
     def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty((count, self.output_channels), BANDS_DTYPE)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_BANDS, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _read_measure(self, "bands", first, count)
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        count = self.streams - first if count is None else count
-        out = np.empty(count, np.uint8)
-        self._ck(self.L.wf_hip_multi_read(self.m, OUT_LAST_SILENT, first, count, out.ctypes.data_as(C.c_void_p)))
-        return out.astype(bool)
+        return self._read(OUT_LAST_SILENT, first, count, (), np.uint8).astype(bool)
 
     def allgather_bars(self):
         """asynchronous: enqueued behind the ticks so far on every device's gather stream"""

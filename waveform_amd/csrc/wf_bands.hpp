@@ -1,4 +1,4 @@
-// wf_bands.hpp -- gfx950 read kernel of WF_HIP_OUT_BANDS (device code only; hipcc).
+// wf_bands.hpp -- gfx950 read kernel of WF_HIP_OUT_BANDS (device code only; hipcc; included by wf_hip_measure.hip alone).
 //
 // Not in the reference: the 31 third-octave band levels (IEC 61260-1) and the Z / A / C weighted level (IEC 61672-1) of every
 // m_decibels row, as float64 power sums of the row's bins (the definition is in include/wf_hip.h, "band levels").  wf_hip_read
@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -45,15 +46,6 @@ __device__ __forceinline__ double bands_tenth(double x)
 {
     const double q = x * 0.1;
     return fma(fma(-10.0, q, x), 0.1, q);
-}
-
-// the same sum in every lane (a butterfly: every lane adds the same pairs, and the addition commutes)
-__device__ __forceinline__ double bands_wave_sum(double v)
-{
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // a value every lane holds, moved to scalar registers: what is decided from it branches for the whole wavefront
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(64 * WF_BANDS_WAVES, WF_BANDS_OCC) void bands_read_
                 }
                 if(hi > c_hi)
                     break; // the band goes on in the next chunk
-                const double s = bands_wave_sum(acc);
+                const double s = wave_sum(acc);
                 if(lane == band)
                     mine = s;
                 acc = 0.0;
@@ -143,13 +135,13 @@ __global__ __launch_bounds__(64 * WF_BANDS_WAVES, WF_BANDS_OCC) void bands_read_
             cur[u] = nxt[u];
     }
     if(band < WF_HIP_NUM_BANDS) { // the band the row ends in; the bands above it keep 0
-        const double s = bands_wave_sum(acc);
+        const double s = wave_sum(acc);
         if(lane == band)
             mine = s;
     }
-    tot = bands_wave_sum(tot);
-    tot_a = bands_wave_sum(tot_a);
-    tot_c = bands_wave_sum(tot_c);
+    tot = wave_sum(tot);
+    tot_a = wave_sum(tot_a);
+    tot_c = wave_sum(tot_c);
 
     // the struct as 36 words: band_db[31], covered, total_db, a_db, c_db, reserved -- one store per lane
     const double s = lane < WF_HIP_NUM_BANDS ? mine : lane == 32u ? tot : lane == 33u ? tot_a : tot_c;

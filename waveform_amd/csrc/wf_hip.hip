@@ -1,6 +1,6 @@
-// wf_hip.hip -- the entry points of the C ABI in include/wf_hip.h other than create / destroy (wf_hip_plan.hip): audio
-// ingest, the tick, per-stream settings, readbacks, measurement -- host side + the launches of the small kernels (rings,
-// level meter, waveform display, RMS, vertex fill).  The fused spectrum kernel is launched through wf_hip::launch
+// wf_hip.hip -- the entry points of the C ABI in include/wf_hip.h other than create / destroy (wf_hip_plan.hip) and the
+// measurement outputs (wf_hip_measure.hip): audio ingest, the tick, per-stream settings, readbacks, timing -- host side + the
+// launches of the small kernels (rings, level meter, waveform display, RMS, vertex fill).  The fused spectrum kernel is launched through wf_hip::launch
 // (wf_tick_geom.hip, wf_big_dispatch.hip).  gfx950 only.  There is no CPU fallback: every entry point either drives the
 // device or fails.
 #include <hip/hip_runtime.h>
@@ -20,11 +20,6 @@
 #include "wf_pcm.hpp"
 #include "wf_meter.hpp"
 #include "wf_rms.hpp"
-#include "wf_loudness.hpp"
-#include "wf_peaks.hpp"
-#include "wf_signal.hpp"
-#include "wf_pitch.hpp"
-#include "wf_bands.hpp"
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
@@ -262,21 +257,7 @@ void launch_input_rms(wf_hip *h, const wf_hip_tick_params *p)
     hipLaunchKernelGGL(wf::input_rms_kernel, dim3(h->n_streams), dim3(64), 0, h->stream, r);
 }
 
-// Every entry point other than wf_hip_tick: `stream` waits for what the lanes hold, and the next tick's lanes will wait for
-// what this call enqueues on `stream`.
-int join_lanes(wf_hip *h)
-{
-    if(h->lanes_pending) {
-        WF_HIP_TRY(h, hipSetDevice(h->device));
-        for(int l = 1; l < h->n_lanes; ++l)
-            WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_lane[l], 0));
-        h->lanes_pending = false;
-    }
-    h->main_dirty = true;
-    return WF_HIP_OK;
-}
-
-// wf_hip_read_rows_async copies straight out of m_decibels on the readback stream: whatever is about to overwrite rows (a
+// wf_hip_read_async copies the rows straight out of m_decibels on the readback stream: whatever is about to overwrite rows (a
 // tick of a spectrum or waveform batch, wf_hip_reset) first makes `stream` wait -- on the device -- for copies in flight
 int wait_rows_in_flight(wf_hip *h)
 {
@@ -289,7 +270,21 @@ int wait_rows_in_flight(wf_hip *h)
     return WF_HIP_OK;
 }
 
-int check_range(wf_hip *h, uint32_t first, uint32_t count)
+} // namespace
+
+int wf::host::join_lanes(wf_hip *h)
+{
+    if(h->lanes_pending) {
+        WF_HIP_TRY(h, hipSetDevice(h->device));
+        for(int l = 1; l < h->n_lanes; ++l)
+            WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_lane[l], 0));
+        h->lanes_pending = false;
+    }
+    h->main_dirty = true;
+    return WF_HIP_OK;
+}
+
+int wf::host::check_range(wf_hip *h, uint32_t first, uint32_t count)
 {
     if(h == nullptr)
         return WF_HIP_ERR_INVALID;
@@ -298,7 +293,15 @@ int check_range(wf_hip *h, uint32_t first, uint32_t count)
     return join_lanes(h);
 }
 
-} // namespace
+int wf::host::read_back(wf_hip *h, const void *d, void *out, size_t bytes)
+{
+    if(out == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL");
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    WF_HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
+    WF_HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return WF_HIP_OK;
+}
 
 int wf::host::upload_words(wf_hip *h, void *d_dst, const void *src, size_t bytes)
 {
@@ -378,46 +381,13 @@ void rms_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames)
                        h->d_rms_bsum, h->d_wpos, h->rms_cap, first, frames);
 }
 
-// the loudness producer (wf_hip_enable_loudness) follows every push: one launch behind the write positions' advance over
-// the frames the push appended, ring[wpos - n, wpos) (d_frames: a ragged push's per-stream counts, capped at `frames`)
-inline bool loudness_on(const wf_hip *h) { return h->d_loud != nullptr; }
-
-// ring trimming would drop frames from the measurement: while the producer is on, nothing longer than the ring is taken
-int loudness_check(wf_hip *h, uint32_t frames)
-{
-    if(loudness_on(h) && frames > h->ring_cap)
-        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the ring capacity %u while the loudness producer is on", frames, h->ring_cap);
-    return WF_HIP_OK;
-}
-
-void loudness_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, const uint32_t *d_frames)
-{
-    if(!loudness_on(h) || frames == 0)
-        return;
-    wf::LoudPushArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
-    a.frames_per_stream = d_frames;
-    a.state = h->d_loud;
-    a.hist = h->d_loud_hist;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
-    a.first = first;
-    a.frames = frames;
-    a.k = h->loud_k;
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::loudness_push_kernel<2>, dim3(count), dim3(128), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::loudness_push_kernel<1>, dim3(count), dim3(64), 0, h->stream, a);
-}
-
 // What a uniform push of `frames` must satisfy, and a ragged one of `count` streams (frames[i] capped at max_frames): checked by
 // the float, PCM and synth entry points alike
 int check_uniform_push(wf_hip *h, uint32_t frames)
 {
     if(rms_follows_audio(h) && frames > h->rms_cap)
         return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the RMS ring capacity %u", frames, h->rms_cap);
-    return loudness_check(h, frames);
+    return measure_check_push(h, frames);
 }
 
 int check_ragged_push(wf_hip *h, uint32_t count, const uint32_t *frames, uint32_t max_frames)
@@ -427,7 +397,7 @@ int check_ragged_push(wf_hip *h, uint32_t count, const uint32_t *frames, uint32_
     if(count > 65535u)
         return fail(h, WF_HIP_ERR_INVALID, "at most 65535 streams per ragged push");
     for(uint32_t i = 0; i < count; ++i)
-        WF_TRY_RC(loudness_check(h, std::min(frames[i], max_frames)));
+        WF_TRY_RC(measure_check_push(h, std::min(frames[i], max_frames)));
     return WF_HIP_OK;
 }
 
@@ -438,7 +408,7 @@ int finish_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, cons
     if(d_frames == nullptr)
         hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
                            h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
-    loudness_after_push(h, first, count, frames, d_frames);
+    measure_after_push(h, first, count, frames, d_frames);
     WF_HIP_TRY(h, hipGetLastError());
     if(d_frames == nullptr && frames % 4u)
         h->all_aligned = false; // (a ragged push: its caller, from the counts -- fill_counts)
@@ -1286,8 +1256,6 @@ int wf_hip_set_input_rms(wf_hip *h, uint32_t first, uint32_t count, const float 
     return WF_HIP_OK;
 }
 
-static int read_back(wf_hip *h, const void *d, void *out, size_t bytes);
-
 static int enable_rms_producer(wf_hip *h, bool feed)
 {
     if(h == nullptr)
@@ -1328,43 +1296,6 @@ static int enable_rms_producer(wf_hip *h, bool feed)
 }
 
 int wf_hip_enable_input_rms(wf_hip *h, int feed) { return enable_rms_producer(h, feed != 0); }
-
-static int clear_loudness(wf_hip *h, uint32_t first, uint32_t count)
-{
-    WF_HIP_TRY(h, hipMemsetAsync(h->d_loud + first, 0, (size_t)count * sizeof(wf::LoudState), h->stream));
-    WF_HIP_TRY(h, hipMemsetAsync(h->d_loud_hist + (size_t)first * 2, 0, (size_t)count * 2 * sizeof(wf::LoudHist), h->stream));
-    return WF_HIP_OK;
-}
-
-int wf_hip_enable_loudness(wf_hip *h, uint32_t first, uint32_t count)
-{
-    WF_TRY_RC(check_range(h, first, count));
-    if(h->d_loud) { // on already: restart the range
-        WF_HIP_TRY(h, hipSetDevice(h->device));
-        WF_TRY_RC(clear_loudness(h, first, count));
-        h->main_dirty = true;
-        return WF_HIP_OK;
-    }
-    if(h->cfg.sample_rate % 10 != 0 || h->cfg.sample_rate == 0)
-        return fail(h, WF_HIP_ERR_INVALID, "sample_rate %u: the loudness producer's 100 ms step must be whole frames", h->cfg.sample_rate);
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    WF_TRY_RC(join_lanes(h));
-    wf::LoudState *st = nullptr;
-    wf::LoudHist *hist = nullptr;
-    wf_hip_loudness *out = nullptr;
-    int rc = dev_alloc(h, &st, h->n_streams);
-    if(rc == WF_HIP_OK) rc = dev_alloc(h, &hist, (size_t)h->n_streams * 2);
-    if(rc == WF_HIP_OK) rc = dev_alloc(h, &out, h->n_streams);
-    if(rc)
-        return rc;
-    h->loud_k = wf::host::loudness_coefs(h->cfg.sample_rate);
-    h->d_loud = st;
-    h->d_loud_hist = hist;
-    h->d_loud_out = out; // from here on every push feeds the producer
-    WF_TRY_RC(clear_loudness(h, 0, h->n_streams));
-    h->main_dirty = true;
-    return WF_HIP_OK;
-}
 
 int wf_hip_push_rms_ragged_async(wf_hip *h, uint32_t first, uint32_t count, const float *pinned_sq, const uint32_t *frames, uint32_t max_frames,
                                  uint32_t slot)
@@ -1414,16 +1345,6 @@ int wf_hip_sync(wf_hip *h)
         if(h->read_stream) WF_HIP_TRY(h, hipStreamSynchronize(h->read_stream));
         return check_canaries(h);
     }
-    return WF_HIP_OK;
-}
-
-static int read_back(wf_hip *h, const void *d, void *out, size_t bytes)
-{
-    if(out == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL");
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    WF_HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    WF_HIP_TRY(h, hipStreamSynchronize(h->stream));
     return WF_HIP_OK;
 }
 
@@ -1480,7 +1401,7 @@ static int read_bars_snapshot_async(wf_hip *h, uint32_t first, uint32_t count, f
     return WF_HIP_OK;
 }
 
-// m_last_silent of streams [first, first+count) as bytes (for the D2H copy of wf_hip_read_rows_async)
+// m_last_silent of streams [first, first+count) as bytes (for the D2H copy of wf_hip_read_async's rows)
 __global__ void silent_bytes_kernel(const uint32_t *flags, uint32_t first, uint32_t count, uint8_t *out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1675,7 +1596,8 @@ int wf_hip_read_async(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_re
     return rc;
 }
 
-// where an output lives on the device and how large it is per stream; nullptr + a text when the batch has none
+// where an output other than a measurement lives on the device and how large it is per stream; nullptr + a text when the
+// batch has none
 static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *per_stream, const char **why)
 {
     *per_stream = 0;
@@ -1722,162 +1644,14 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         *per_stream = sizeof(uint64_t);
         return h->d_wts;
     case WF_HIP_OUT_LOUDNESS:
-        if(h->d_loud_out == nullptr) { *why = "the loudness producer is not enabled (wf_hip_enable_loudness)"; return nullptr; }
-        *per_stream = sizeof(wf_hip_loudness);
-        return h->d_loud_out;
-    case WF_HIP_OUT_PEAKS: // (computed from the rows when read, into a block the first read allocates: read_peaks)
-        if(h->meter || h->wave) { *why = "meter / waveform batch: spectral peaks belong to spectrum batches"; return nullptr; }
-        *per_stream = (size_t)h->out_ch * sizeof(wf_hip_peaks);
-        return h->d_decibels;
-    case WF_HIP_OUT_SIGNAL: // (computed from the rings when read, into a block the first read allocates: read_signal)
-        if(h->wave) { *why = "waveform batch: signal statistics belong to spectrum and meter batches (a window of fft_size frames)"; return nullptr; }
-        *per_stream = sizeof(wf_hip_signal);
-        return h->d_ring;
-    case WF_HIP_OUT_PITCH: // (computed from the rings when read, into a block the first read allocates: read_pitch)
-        if(h->wave) { *why = "waveform batch: the pitch belongs to spectrum and meter batches (a window of fft_size frames)"; return nullptr; }
-        if(h->N < 64) { *why = "the pitch needs a window of at least 64 frames"; return nullptr; }
-        *per_stream = sizeof(wf_hip_pitch);
-        return h->d_ring;
-    case WF_HIP_OUT_BANDS: // (computed from the rows when read, into a block the first read allocates: read_bands)
-        if(h->meter || h->wave) { *why = "meter / waveform batch: band levels belong to spectrum batches"; return nullptr; }
-        *per_stream = (size_t)h->out_ch * sizeof(wf_hip_bands);
-        return h->d_decibels;
+    case WF_HIP_OUT_PEAKS:
+    case WF_HIP_OUT_SIGNAL:
+    case WF_HIP_OUT_PITCH:
+    case WF_HIP_OUT_BANDS:
+        break; // (never asked here: measure_source answers for them)
     }
     *why = "unknown output";
     return nullptr;
-}
-
-// WF_HIP_OUT_PEAKS of streams [first, first+count): one wavefront per m_decibels row, on `stream` behind the ticks issued
-static int read_peaks(wf_hip *h, uint32_t first, uint32_t count, void *out)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->d_peaks == nullptr)
-        WF_TRY_RC(dev_alloc(h, &h->d_peaks, (size_t)h->n_streams * h->out_ch));
-    wf::PeaksArgs a{};
-    a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
-    a.out = h->d_peaks + (size_t)first * h->out_ch;
-    a.n_rows = count * h->out_ch;
-    a.M = h->M;
-    a.floor_db = (float)h->cfg.floor_db;
-    a.hz_per_bin = (double)h->cfg.sample_rate / (double)h->N;
-    hipLaunchKernelGGL(wf::peaks_read_kernel, dim3((a.n_rows + wf::WF_PEAKS_WAVES - 1) / wf::WF_PEAKS_WAVES), dim3(64 * wf::WF_PEAKS_WAVES), 0,
-                       h->stream, a);
-    WF_HIP_TRY(h, hipGetLastError());
-    return read_back(h, a.out, out, (size_t)a.n_rows * sizeof(wf_hip_peaks));
-}
-
-// WF_HIP_OUT_SIGNAL of streams [first, first+count): one workgroup per stream over its newest fft_size frames, on `stream`
-// behind the pushes issued
-static int read_signal(wf_hip *h, uint32_t first, uint32_t count, void *out)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->d_signal == nullptr)
-        WF_TRY_RC(dev_alloc(h, &h->d_signal, (size_t)h->n_streams));
-    wf::SignalArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
-    a.out = h->d_signal + first;
-    a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
-    a.W = h->N; // (<= ring_cap: wf_hip_create sizes the ring from it)
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::signal_read_kernel<2>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::signal_read_kernel<1>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
-    WF_HIP_TRY(h, hipGetLastError());
-    return read_back(h, a.out, out, (size_t)count * sizeof(wf_hip_signal));
-}
-
-// WF_HIP_OUT_PITCH of streams [first, first+count): one workgroup per stream over its newest min(fft_size, 4096) frames, on
-// `stream` behind the pushes issued
-static int read_pitch(wf_hip *h, uint32_t first, uint32_t count, void *out)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->d_pitch == nullptr)
-        WF_TRY_RC(dev_alloc(h, &h->d_pitch, (size_t)h->n_streams));
-    wf::PitchArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
-    a.out = h->d_pitch + first;
-    a.sample_rate = (double)h->cfg.sample_rate;
-    a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
-    a.P = std::min<uint32_t>(h->N, WF_HIP_PITCH_MAX_WINDOW); // (a multiple of 16 on spectrum and meter batches; <= ring_cap)
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::pitch_read_kernel<2>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::pitch_read_kernel<1>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
-    WF_HIP_TRY(h, hipGetLastError());
-    return read_back(h, a.out, out, (size_t)count * sizeof(wf_hip_pitch));
-}
-
-// the first read of WF_HIP_OUT_BANDS: the output block, and what follows from the configuration alone -- the band edges in
-// bins (IEC 61260-1, base ten), which bands lie wholly inside the row, the window's equivalent noise bandwidth, the A and C
-// weights of every bin
-static int setup_bands(wf_hip *h)
-{
-    std::vector<double> edges(WF_HIP_NUM_BANDS + 1);
-    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
-        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)h->N / (double)h->cfg.sample_rate;
-    h->bands_covered = 0;
-    for(int b = 0; b < WF_HIP_NUM_BANDS; ++b)
-        if(edges[b] >= 0.5 && edges[b + 1] <= (double)h->M - 0.5)
-            h->bands_covered |= 1u << b;
-    h->bands_enbw = 1.0;
-    if(!h->tab.window.empty()) {
-        double s1 = 0.0, s2 = 0.0;
-        for(const float w : h->tab.window) {
-            s1 += (double)w;
-            s2 += (double)w * (double)w;
-        }
-        h->bands_enbw = (double)h->N * s2 / (s1 * s1);
-    }
-    // (R(f) / R(1000))^2 of IEC 61672-1's RA and RC at every bin's frequency
-    const auto ra = [](double f) {
-        const double f2 = f * f;
-        return 12194.0 * 12194.0 * f2 * f2 /
-               ((f2 + 20.6 * 20.6) * std::sqrt((f2 + 107.7 * 107.7) * (f2 + 737.9 * 737.9)) * (f2 + 12194.0 * 12194.0));
-    };
-    const auto rc = [](double f) {
-        const double f2 = f * f;
-        return 12194.0 * 12194.0 * f2 / ((f2 + 20.6 * 20.6) * (f2 + 12194.0 * 12194.0));
-    };
-    std::vector<double> weights((size_t)h->M * 2);
-    for(uint32_t k = 0; k < h->M; ++k) {
-        const double f = (double)k * (double)h->cfg.sample_rate / (double)h->N;
-        const double a = ra(f) / ra(1000.0), c = rc(f) / rc(1000.0);
-        weights[2 * (size_t)k] = a * a;
-        weights[2 * (size_t)k + 1] = c * c;
-    }
-    if(h->d_band_edges == nullptr)
-        WF_TRY_RC(upload(h, &h->d_band_edges, edges)); // (pageable memory: staged before the call returns)
-    if(h->d_band_weights == nullptr)
-        WF_TRY_RC(upload(h, &h->d_band_weights, weights));
-    return dev_alloc(h, &h->d_bands, (size_t)h->n_streams * h->out_ch); // (last: d_bands says that all of this is in place)
-}
-
-// WF_HIP_OUT_BANDS of streams [first, first+count): one wavefront per m_decibels row, on `stream` behind the ticks issued
-static int read_bands(wf_hip *h, uint32_t first, uint32_t count, void *out)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->d_bands == nullptr)
-        WF_TRY_RC(setup_bands(h));
-    wf::BandsArgs a{};
-    a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
-    a.out = h->d_bands + (size_t)first * h->out_ch;
-    a.edges = h->d_band_edges;
-    a.n_rows = count * h->out_ch;
-    a.M = h->M;
-    a.covered = h->bands_covered;
-    a.db_min = wf::db_min();
-    a.enbw = h->bands_enbw;
-    a.weights = h->d_band_weights;
-    hipLaunchKernelGGL(wf::bands_read_kernel, dim3((a.n_rows + wf::WF_BANDS_WAVES - 1) / wf::WF_BANDS_WAVES), dim3(64 * wf::WF_BANDS_WAVES),
-                       0, h->stream, a);
-    WF_HIP_TRY(h, hipGetLastError());
-    return read_back(h, a.out, out, (size_t)a.n_rows * sizeof(wf_hip_bands));
 }
 
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
@@ -1886,6 +1660,8 @@ size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
         return 0;
     size_t per = 0;
     const char *why = nullptr;
+    if(measure_source(h, what, &per, &why))
+        return per;
     return output_source(h, what, &per, &why) ? per : 0;
 }
 
@@ -1896,25 +1672,13 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
         return rc;
     size_t per = 0;
     const char *why = nullptr;
+    if(measure_source(h, what, &per, &why))
+        return measure_read(h, what, first, count, out);
     const void *src = output_source(h, what, &per, &why);
     if(src == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "%s", why);
     if(out == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL");
-    if(what == WF_HIP_OUT_LOUDNESS) { // the readings are made from the state when asked for, behind the pushes issued so far
-        WF_HIP_TRY(h, hipSetDevice(h->device));
-        hipLaunchKernelGGL(wf::loudness_read_kernel, dim3(count), dim3(64), 0, h->stream, h->d_loud, h->d_loud_hist, h->d_loud_out, first,
-                           h->loud_k.sub_frames);
-        WF_HIP_TRY(h, hipGetLastError());
-    }
-    if(what == WF_HIP_OUT_PEAKS)
-        return read_peaks(h, first, count, out);
-    if(what == WF_HIP_OUT_SIGNAL)
-        return read_signal(h, first, count, out);
-    if(what == WF_HIP_OUT_PITCH)
-        return read_pitch(h, first, count, out);
-    if(what == WF_HIP_OUT_BANDS)
-        return read_bands(h, first, count, out);
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
         rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));

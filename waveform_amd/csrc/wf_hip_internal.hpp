@@ -1,5 +1,5 @@
 // wf_hip_internal.hpp -- what the translation units of libwaveform_hip.so share: the handle, the error helpers and the
-// functions by which the plan (wf_hip_plan.hip), the entry points (wf_hip.hip) and the kernel dispatch (wf_tick_geom.hip, one
+// functions by which the plan (wf_hip_plan.hip), the entry points (wf_hip.hip; the measurement outputs: wf_hip_measure.hip) and the kernel dispatch (wf_tick_geom.hip, one
 // object per FFT geometry; wf_big_dispatch.hip for the transforms beyond a CU's LDS) call each other.  Not installed: the
 // library's interface is include/wf_hip.h.
 #pragma once
@@ -12,7 +12,7 @@
 
 #include "wf_hip.h"
 
-namespace wf { struct LoudState; struct LoudHist; }
+namespace wf { struct LoudState; struct LoudHist; } // (wf_loudness.hpp: device code, seen by wf_hip_measure.hip alone)
 #include "wf_dev_guard.hpp"
 #include "wf_host_tables.hpp"
 #include "wf_loudness_tables.hpp"
@@ -53,13 +53,13 @@ struct wf_hip {
                                                   // buffer free, staging full): wf_hip_ingest_done waits for it
     IngestSlot ingest_slot[2];                    // audio, float or PCM
     IngestSlot sq_slot[2];                        // the squared peaks of wf_hip_push_rms_ragged_async ([count][max_frames])
-    // pipelined readback (wf_hip_read_bars_async): a stream for the D2H copies, a device snapshot and two events per slot
+    // pipelined readback (wf_hip_read_async): a stream for the D2H copies, a device snapshot and two events per slot
     hipStream_t read_stream = nullptr;
     hipEvent_t ev_snap[2] = {nullptr, nullptr}, ev_read[2] = {nullptr, nullptr};
     float *d_snap[2] = {nullptr, nullptr};
     size_t snap_floats[2] = {0, 0};
     bool read_used[2] = {false, false};
-    bool rows_in_flight[2] = {false, false}; // wf_hip_read_rows_async copies straight from m_decibels: the next tick waits for them
+    bool rows_in_flight[2] = {false, false}; // wf_hip_read_async copies the rows straight from m_decibels: the next tick waits for them
     uint8_t *d_silent_bytes[2] = {nullptr, nullptr};  // rows readback: m_last_silent as bytes
     size_t silent_bytes_cap[2] = {0, 0};
     uint32_t n_streams = 0;
@@ -143,19 +143,23 @@ struct wf_hip {
     uint32_t *d_rend = nullptr;      // [n_streams] consumption point of sync_rms_buffer
     bool rms_feed = false;           // the squared peaks come from the host (wf_hip_push_rms_ragged_async), not from the pushed audio
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
-    // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), nullptr while it is off
-    struct wf::LoudState *d_loud = nullptr;       // [n_streams]
-    struct wf::LoudHist *d_loud_hist = nullptr;   // [n_streams][2]: integrated, range
-    wf_hip_loudness *d_loud_out = nullptr;        // [n_streams] what the last wf_hip_read(WF_HIP_OUT_LOUDNESS) computed
-    wf::LoudCoefs loud_k{};
-    wf_hip_peaks *d_peaks = nullptr;              // [n_streams][out_ch] WF_HIP_OUT_PEAKS, allocated by its first read (wf_peaks.hpp)
-    wf_hip_signal *d_signal = nullptr;            // [n_streams] WF_HIP_OUT_SIGNAL, allocated by its first read (wf_signal.hpp)
-    wf_hip_pitch *d_pitch = nullptr;              // [n_streams] WF_HIP_OUT_PITCH, allocated by its first read (wf_pitch.hpp)
-    wf_hip_bands *d_bands = nullptr;              // [n_streams][out_ch] WF_HIP_OUT_BANDS, allocated by its first read (wf_bands.hpp)
-    double *d_band_edges = nullptr;               // [WF_HIP_NUM_BANDS + 1] the band edges in bins, uploaded by that read
-    uint32_t bands_covered = 0;                   // wf_hip_bands::covered of this batch
-    double bands_enbw = 1.0;                      // the window's equivalent noise bandwidth in bins
-    double *d_band_weights = nullptr;             // [M][2] the squared A and C weights of every bin, uploaded by that read
+    // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
+    // [n_streams][out_ch], allocated by the output's first read
+    static constexpr int N_MEASURES = 5;
+    char *d_measure[N_MEASURES] = {};
+    // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
+    struct Loudness {
+        wf::LoudState *d_state = nullptr;         // [n_streams]
+        wf::LoudHist *d_hist = nullptr;           // [n_streams][2]: integrated, range
+        wf::LoudCoefs k{};
+    } loud;
+    // what WF_HIP_OUT_BANDS derives from the configuration (setup_bands, at its first read; wf_bands.hpp)
+    struct Bands {
+        double *d_edges = nullptr;                // [WF_HIP_NUM_BANDS + 1] the band edges in bins
+        double *d_weights = nullptr;              // [M][2] the squared A and C weights of every bin
+        uint32_t covered = 0;                     // wf_hip_bands::covered of this batch
+        double enbw = 1.0;                        // the window's equivalent noise bandwidth in bins
+    } bands;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;
@@ -281,6 +285,21 @@ inline uint32_t next_pow2(uint32_t v)
 // `bytes` of per-stream words from a borrowed host array to `d_dst`, without waiting for the stream: through one of the handle's
 // two page-locked staging blocks (wf_hip.hip)
 int upload_words(wf_hip *h, void *d_dst, const void *src, size_t bytes);
+
+// wf_hip.hip, for the entry points that live elsewhere.  join_lanes: what every entry point other than wf_hip_tick starts with --
+// `stream` waits for what the lanes hold, and the next tick's lanes will wait for what the call enqueues on `stream`
+int join_lanes(wf_hip *h);
+int check_range(wf_hip *h, uint32_t first, uint32_t count);        // refuses a stream range outside the batch, then joins the lanes
+int read_back(wf_hip *h, const void *d, void *out, size_t bytes); // device to host on `stream`; returns when the bytes have arrived
+
+// wf_hip_measure.hip: the measurement outputs.  The ingest's two hooks -- what a push of `frames` must satisfy while a producer
+// follows the pushes, and that producer's launch behind the advance of the write positions (d_frames: a ragged push's counts)
+int measure_check_push(wf_hip *h, uint32_t frames);
+void measure_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, const uint32_t *d_frames);
+// false: `what` is no measurement output.  Else *why is the refusal's text (*per_stream 0), or nullptr with the bytes per stream
+bool measure_source(const wf_hip *h, wf_hip_output what, size_t *per_stream, const char **why);
+// wf_hip_read of a measurement output: computes streams [first, first+count) on `stream` and copies them to `out`
+int measure_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, void *out);
 
 // ---- kernel dispatch -----------------------------------------------------------------------------------------------------
 // One object file per geometry (wf_tick_geom.hip compiled with -DWF_TU_GEOM=<N>): picks the spectrum_tick_kernel instantiation

@@ -1,0 +1,289 @@
+// wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH
+// and _BANDS.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is and how it is
+// launched; one reader (measure_read) does the rest.  The loudness producer alone also keeps state between reads: it follows
+// every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip) and is switched on by
+// wf_hip_enable_loudness.  gfx950 only.
+//
+// A new measurement output: its kernel in a header of its own, included here and nowhere else; a launch function, a refusal
+// function and a row of MEASURES below; a row of MEASURES in waveform_amd/binding.py.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "wf_hip_internal.hpp"
+#include "wf_dev_guard.hpp"
+#include "wf_loudness.hpp"
+#include "wf_peaks.hpp"
+#include "wf_signal.hpp"
+#include "wf_pitch.hpp"
+#include "wf_bands.hpp"
+
+namespace {
+
+using namespace wf::host;
+
+inline bool loudness_on(const wf_hip *h) { return h->loud.d_state != nullptr; }
+
+int clear_loudness(wf_hip *h, uint32_t first, uint32_t count)
+{
+    WF_HIP_TRY(h, hipMemsetAsync(h->loud.d_state + first, 0, (size_t)count * sizeof(wf::LoudState), h->stream));
+    WF_HIP_TRY(h, hipMemsetAsync(h->loud.d_hist + (size_t)first * 2, 0, (size_t)count * 2 * sizeof(wf::LoudHist), h->stream));
+    return WF_HIP_OK;
+}
+
+// One launch function per output: the entries of streams [first, first+count) into d_block, the output's whole block.
+// Loudness: the readings are made from the state when asked for, behind the pushes issued so far
+int launch_loudness(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    hipLaunchKernelGGL(wf::loudness_read_kernel, dim3(count), dim3(64), 0, h->stream, h->loud.d_state, h->loud.d_hist,
+                       static_cast<wf_hip_loudness *>(d_block), first, h->loud.k.sub_frames);
+    return WF_HIP_OK;
+}
+
+// one wavefront per m_decibels row, behind the ticks issued
+int launch_peaks(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    wf::PeaksArgs a{};
+    a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
+    a.out = static_cast<wf_hip_peaks *>(d_block) + (size_t)first * h->out_ch;
+    a.n_rows = count * h->out_ch;
+    a.M = h->M;
+    a.floor_db = (float)h->cfg.floor_db;
+    a.hz_per_bin = (double)h->cfg.sample_rate / (double)h->N;
+    hipLaunchKernelGGL(wf::peaks_read_kernel, dim3((a.n_rows + wf::WF_PEAKS_WAVES - 1) / wf::WF_PEAKS_WAVES), dim3(64 * wf::WF_PEAKS_WAVES), 0,
+                       h->stream, a);
+    return WF_HIP_OK;
+}
+
+// one workgroup per stream over its newest fft_size frames, behind the pushes issued
+int launch_signal(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    wf::SignalArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = static_cast<wf_hip_signal *>(d_block) + first;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.W = h->N; // (<= ring_cap: wf_hip_create sizes the ring from it)
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::signal_read_kernel<2>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::signal_read_kernel<1>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
+    return WF_HIP_OK;
+}
+
+// one workgroup per stream over its newest min(fft_size, 4096) frames, behind the pushes issued
+int launch_pitch(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    wf::PitchArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = static_cast<wf_hip_pitch *>(d_block) + first;
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.P = std::min<uint32_t>(h->N, WF_HIP_PITCH_MAX_WINDOW); // (a multiple of 16 on spectrum and meter batches; <= ring_cap)
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::pitch_read_kernel<2>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::pitch_read_kernel<1>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
+    return WF_HIP_OK;
+}
+
+// what the band levels derive from the configuration alone, made by their first read: the band edges in bins (IEC 61260-1,
+// base ten), which bands lie wholly inside the row, the window's equivalent noise bandwidth, the A and C weights of every bin
+int setup_bands(wf_hip *h)
+{
+    wf_hip::Bands &b = h->bands;
+    std::vector<double> edges(WF_HIP_NUM_BANDS + 1);
+    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
+        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)h->N / (double)h->cfg.sample_rate;
+    b.covered = 0;
+    for(int j = 0; j < WF_HIP_NUM_BANDS; ++j)
+        if(edges[j] >= 0.5 && edges[j + 1] <= (double)h->M - 0.5)
+            b.covered |= 1u << j;
+    b.enbw = 1.0;
+    if(!h->tab.window.empty()) {
+        double s1 = 0.0, s2 = 0.0;
+        for(const float w : h->tab.window) {
+            s1 += (double)w;
+            s2 += (double)w * (double)w;
+        }
+        b.enbw = (double)h->N * s2 / (s1 * s1);
+    }
+    // (R(f) / R(1000))^2 of IEC 61672-1's RA and RC at every bin's frequency
+    const auto ra = [](double f) {
+        const double f2 = f * f;
+        return 12194.0 * 12194.0 * f2 * f2 /
+               ((f2 + 20.6 * 20.6) * std::sqrt((f2 + 107.7 * 107.7) * (f2 + 737.9 * 737.9)) * (f2 + 12194.0 * 12194.0));
+    };
+    const auto rc = [](double f) {
+        const double f2 = f * f;
+        return 12194.0 * 12194.0 * f2 / ((f2 + 20.6 * 20.6) * (f2 + 12194.0 * 12194.0));
+    };
+    std::vector<double> weights((size_t)h->M * 2);
+    for(uint32_t k = 0; k < h->M; ++k) {
+        const double f = (double)k * (double)h->cfg.sample_rate / (double)h->N;
+        const double a = ra(f) / ra(1000.0), c = rc(f) / rc(1000.0);
+        weights[2 * (size_t)k] = a * a;
+        weights[2 * (size_t)k + 1] = c * c;
+    }
+    if(b.d_edges == nullptr)
+        WF_TRY_RC(upload(h, &b.d_edges, edges)); // (pageable memory: staged before the call returns)
+    return upload(h, &b.d_weights, weights);     // (last: d_weights says that all of this is in place)
+}
+
+// one wavefront per m_decibels row, behind the ticks issued
+int launch_bands(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    if(h->bands.d_weights == nullptr)
+        WF_TRY_RC(setup_bands(h));
+    wf::BandsArgs a{};
+    a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
+    a.out = static_cast<wf_hip_bands *>(d_block) + (size_t)first * h->out_ch;
+    a.edges = h->bands.d_edges;
+    a.n_rows = count * h->out_ch;
+    a.M = h->M;
+    a.covered = h->bands.covered;
+    a.db_min = wf::db_min();
+    a.enbw = h->bands.enbw;
+    a.weights = h->bands.d_weights;
+    hipLaunchKernelGGL(wf::bands_read_kernel, dim3((a.n_rows + wf::WF_BANDS_WAVES - 1) / wf::WF_BANDS_WAVES), dim3(64 * wf::WF_BANDS_WAVES),
+                       0, h->stream, a);
+    return WF_HIP_OK;
+}
+
+// why a batch has no such output (nullptr: it has)
+const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
+const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
+const char *why_no_bands(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: band levels belong to spectrum batches" : nullptr; }
+const char *why_no_signal(const wf_hip *h)
+{
+    return h->wave ? "waveform batch: signal statistics belong to spectrum and meter batches (a window of fft_size frames)" : nullptr;
+}
+const char *why_no_pitch(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the pitch belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->N < 64 ? "the pitch needs a window of at least 64 frames" : nullptr;
+}
+
+struct Measure {
+    wf_hip_output what;
+    size_t entry_bytes;
+    bool per_row; // one entry per m_decibels row (out_ch per stream), not one per stream
+    const char *(*why_not)(const wf_hip *);
+    int (*launch)(wf_hip *, uint32_t first, uint32_t count, void *d_block);
+};
+
+// row i's block is wf_hip::d_measure[i]
+constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
+    {WF_HIP_OUT_LOUDNESS, sizeof(wf_hip_loudness), false, why_no_loudness, launch_loudness},
+    {WF_HIP_OUT_PEAKS, sizeof(wf_hip_peaks), true, why_no_peaks, launch_peaks},
+    {WF_HIP_OUT_SIGNAL, sizeof(wf_hip_signal), false, why_no_signal, launch_signal},
+    {WF_HIP_OUT_PITCH, sizeof(wf_hip_pitch), false, why_no_pitch, launch_pitch},
+    {WF_HIP_OUT_BANDS, sizeof(wf_hip_bands), true, why_no_bands, launch_bands},
+};
+
+int measure_row(wf_hip_output what) // -1: not a measurement output
+{
+    for(int i = 0; i < wf_hip::N_MEASURES; ++i)
+        if(MEASURES[i].what == what)
+            return i;
+    return -1;
+}
+
+size_t bytes_per_stream(const wf_hip *h, const Measure &m) { return m.entry_bytes * (m.per_row ? h->out_ch : 1u); }
+
+} // namespace
+
+// ring trimming would drop frames from the measurement: while the producer is on, nothing longer than the ring is taken
+int wf::host::measure_check_push(wf_hip *h, uint32_t frames)
+{
+    if(loudness_on(h) && frames > h->ring_cap)
+        return fail(h, WF_HIP_ERR_INVALID, "push of %u frames exceeds the ring capacity %u while the loudness producer is on", frames, h->ring_cap);
+    return WF_HIP_OK;
+}
+
+// the loudness producer follows every push: one launch behind the write positions' advance over the frames the push
+// appended, ring[wpos - n, wpos) (d_frames: a ragged push's per-stream counts, capped at `frames`)
+void wf::host::measure_after_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, const uint32_t *d_frames)
+{
+    if(!loudness_on(h) || frames == 0)
+        return;
+    wf::LoudPushArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.frames_per_stream = d_frames;
+    a.state = h->loud.d_state;
+    a.hist = h->loud.d_hist;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.first = first;
+    a.frames = frames;
+    a.k = h->loud.k;
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::loudness_push_kernel<2>, dim3(count), dim3(128), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::loudness_push_kernel<1>, dim3(count), dim3(64), 0, h->stream, a);
+}
+
+bool wf::host::measure_source(const wf_hip *h, wf_hip_output what, size_t *per_stream, const char **why)
+{
+    const int i = measure_row(what);
+    if(i < 0)
+        return false;
+    *why = MEASURES[i].why_not(h);
+    *per_stream = *why ? 0 : bytes_per_stream(h, MEASURES[i]);
+    return true;
+}
+
+int wf::host::measure_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, void *out)
+{
+    const int i = measure_row(what);
+    const Measure &m = MEASURES[i];
+    if(const char *why = m.why_not(h))
+        return fail(h, WF_HIP_ERR_INVALID, "%s", why);
+    if(out == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL");
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    const size_t per = bytes_per_stream(h, m);
+    // (the first read may be of a slice: the block is for every stream)
+    if(h->d_measure[i] == nullptr)
+        WF_TRY_RC(dev_alloc(h, &h->d_measure[i], (size_t)h->n_streams * per));
+    WF_TRY_RC(m.launch(h, first, count, h->d_measure[i]));
+    WF_HIP_TRY(h, hipGetLastError());
+    return read_back(h, h->d_measure[i] + (size_t)first * per, out, (size_t)count * per);
+}
+
+int wf_hip_enable_loudness(wf_hip *h, uint32_t first, uint32_t count)
+{
+    WF_TRY_RC(check_range(h, first, count));
+    if(loudness_on(h)) { // on already: restart the range
+        WF_HIP_TRY(h, hipSetDevice(h->device));
+        WF_TRY_RC(clear_loudness(h, first, count));
+        h->main_dirty = true;
+        return WF_HIP_OK;
+    }
+    if(h->cfg.sample_rate % 10 != 0 || h->cfg.sample_rate == 0)
+        return fail(h, WF_HIP_ERR_INVALID, "sample_rate %u: the loudness producer's 100 ms step must be whole frames", h->cfg.sample_rate);
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    WF_TRY_RC(join_lanes(h));
+    wf::LoudState *st = nullptr;
+    wf::LoudHist *hist = nullptr;
+    int rc = dev_alloc(h, &st, h->n_streams);
+    if(rc == WF_HIP_OK) rc = dev_alloc(h, &hist, (size_t)h->n_streams * 2);
+    if(rc)
+        return rc;
+    h->loud.k = wf::host::loudness_coefs(h->cfg.sample_rate);
+    h->loud.d_hist = hist;
+    h->loud.d_state = st; // from here on every push feeds the producer
+    WF_TRY_RC(clear_loudness(h, 0, h->n_streams));
+    h->main_dirty = true;
+    return WF_HIP_OK;
+}

@@ -1,5 +1,5 @@
 // wf_loudness.hpp -- gfx950 kernels of the loudness producer (include/wf_hip.h, "loudness"; device code only; hipcc; included
-// by wf_hip.hip alone).
+// by wf_hip_measure.hip alone).
 //
 //   loudness_push_kernel<CapCh>   runs behind every push, once the write positions have advanced: measures the frames the
 //                                 push appended, ring[wpos - n, wpos) of each captured channel
@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "wf_hip.h"
 #include "wf_loudness_tables.hpp"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -54,35 +55,6 @@ struct LoudPushArgs {
 };
 
 #define WF_LOUD_DEV __device__ __forceinline__
-
-WF_LOUD_DEV float loud_wave_sum(float v)
-{
-#pragma unroll
-    for(int m = 1; m < 64; m <<= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
-}
-WF_LOUD_DEV float loud_wave_max(float v)
-{
-#pragma unroll
-    for(int m = 1; m < 64; m <<= 1)
-        v = __builtin_fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-WF_LOUD_DEV double loud_wave_sum_d(double v)
-{
-#pragma unroll
-    for(int m = 1; m < 64; m <<= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
-}
-WF_LOUD_DEV uint32_t loud_wave_sum_u(uint32_t v)
-{
-#pragma unroll
-    for(int m = 1; m < 64; m <<= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // one step of the K-weighting cascade: state s (shelf s1, s2, high-pass s1, s2), input x -> output
 WF_LOUD_DEV double k_step(const LoudCoefs &k, double s[4], double x)
@@ -226,9 +198,9 @@ __global__ __launch_bounds__(64 * CapCh) void loudness_push_kernel(LoudPushArgs 
 #pragma unroll
         for(int j = 0; j < 4; ++j)
             S[j] = __shfl(v[j], last, 64);
-        ea = loud_wave_sum(ea);
-        eb = loud_wave_sum(eb);
-        pk = loud_wave_max(pk);
+        ea = wave_sum<WAVE_UP>(ea);
+        eb = wave_sum<WAVE_UP>(eb);
+        pk = wave_max<WAVE_UP>(pk);
         if(lane == 0) {
             red[ch][0] = ea;
             red[ch][1] = eb;
@@ -292,8 +264,8 @@ __global__ __launch_bounds__(64) void loudness_read_kernel(const LoudState *stat
             e += hg.energy[b];
             c += hg.count[b];
         }
-        e = loud_wave_sum_d(e);
-        c = loud_wave_sum_u(c);
+        e = wave_sum<WAVE_UP>(e);
+        c = wave_sum<WAVE_UP>(c);
         gated[w] = ninf;
         if(c == 0)
             continue;
@@ -307,8 +279,8 @@ __global__ __launch_bounds__(64) void loudness_read_kernel(const LoudState *stat
                 c2 += hg.count[b];
             }
         const uint32_t mine = c2;
-        e2 = loud_wave_sum_d(e2);
-        c2 = loud_wave_sum_u(c2);
+        e2 = wave_sum<WAVE_UP>(e2);
+        c2 = wave_sum<WAVE_UP>(c2);
         if(c2 == 0)
             continue;
         gated[w] = (float)(-0.691 + 10.0 * log10(e2 / c2));
@@ -338,7 +310,7 @@ __global__ __launch_bounds__(64) void loudness_read_kernel(const LoudState *stat
                         }
                     }
             }
-            pct[1][p] = loud_wave_sum(found); // (exactly one lane holds it)
+            pct[1][p] = wave_sum<WAVE_UP>(found); // (exactly one lane holds it)
         }
         any_range = true;
     }

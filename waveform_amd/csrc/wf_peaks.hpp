@@ -1,4 +1,4 @@
-// wf_peaks.hpp -- gfx950 read kernel of WF_HIP_OUT_PEAKS (device code only; hipcc).
+// wf_peaks.hpp -- gfx950 read kernel of WF_HIP_OUT_PEAKS (device code only; hipcc; included by wf_hip_measure.hip alone).
 //
 // Not in the reference: the WF_HIP_MAX_PEAKS strongest local maxima of every m_decibels row, with the parabola through
 // each maximum and its two neighbours (the definition is in include/wf_hip.h).  wf_hip_read launches it on the handle's

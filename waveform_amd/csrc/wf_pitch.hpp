@@ -1,4 +1,4 @@
-// wf_pitch.hpp -- gfx950 read kernel of WF_HIP_OUT_PITCH (device code only; hipcc; included by wf_hip.hip alone).
+// wf_pitch.hpp -- gfx950 read kernel of WF_HIP_OUT_PITCH (device code only; hipcc; included by wf_hip_measure.hip alone).
 //
 // Not in the reference: the fundamental frequency of the newest P = min(fft_size, 4096) frames in each stream's rings by YIN
 // (de Cheveigne and Kawahara 2002, steps 1 to 5; the definition is in include/wf_hip.h, "pitch").  wf_hip_read launches it on

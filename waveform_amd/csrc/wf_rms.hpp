@@ -18,20 +18,12 @@
 #include <hip/hip_runtime.h>
 #include "wf_tick_phases.hpp"
 #include "wf_synth.h"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
 constexpr uint32_t RMS_BLOCK = 256;      // frames per stored partial sum
 constexpr uint32_t RMS_BLOCK_SHIFT = 8;
-
-// fixed-order sum over a wavefront
-WF_DEV float wave_sum(float v)
-{
-#pragma unroll
-    for(int m = 32; m >= 1; m >>= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // src: [count*cap_ch][frames] (nullptr: silence); squared peaks of streams [first, first+count) at wpos.. (before wpos advances)
 __global__ void rms_push_kernel(float *rms_ring, const uint32_t *wpos, uint32_t rms_cap, uint32_t cap_ch, uint32_t first,
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(64) void rms_block_kernel(const float *rms_ring, fl
         bsum[(size_t)stream * (rms_cap >> RMS_BLOCK_SHIFT) + (k & ((rms_cap >> RMS_BLOCK_SHIFT) - 1))] = sum;
 }
 
-// Feed mode (wf_hip_enable_input_rms_feed): the host hands over the squared peaks themselves -- what sync_rms_buffer moves
+// Feed mode (wf_hip_enable_input_rms(h, 1)): the host hands over the squared peaks themselves -- what sync_rms_buffer moves
 // from m_rms_sync_buf into m_input_rms_buf this tick (src/source.cpp:810-835) -- a different number of values per stream.
 // sq: [count][max_frames], frames[count].  One workgroup per stream appends them at the stream's consumption point
 // `rend`, stores the sums of the blocks that became complete, and advances rend.

@@ -1,4 +1,4 @@
-// wf_signal.hpp -- gfx950 read kernel of WF_HIP_OUT_SIGNAL (device code only; hipcc; included by wf_hip.hip alone).
+// wf_signal.hpp -- gfx950 read kernel of WF_HIP_OUT_SIGNAL (device code only; hipcc; included by wf_hip_measure.hip alone).
 //
 // Not in the reference: level, DC, clipping and stereo phase of the newest W = fft_size frames in each captured channel's
 // ring (the definition is in include/wf_hip.h).  wf_hip_read launches it on the handle's stream, behind every push issued so
@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -106,14 +107,6 @@ __device__ __forceinline__ void signal_run(SignalAcc<CH> &a, const float *r0, co
         signal_add4<CH>(a, p0[i], CH == 2 ? p1[i] : p0[i]);
 }
 
-__device__ __forceinline__ double signal_wave_sum(double v)
-{
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __device__ __forceinline__ float signal_db(double ratio, double scale)
 {
     return ratio > 0.0 ? (float)(scale * log10(ratio)) : -INFINITY;
@@ -162,7 +155,7 @@ __global__ __launch_bounds__(WF_SIGNAL_THREADS, WF_SIGNAL_OCC) void signal_read_
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 #pragma unroll
     for(int k = 0; k < ND; ++k)
-        d[k] = signal_wave_sum(d[k]);
+        d[k] = wave_sum(d[k]);
     float mx[CH];
     uint32_t clip[CH];
 #pragma unroll
