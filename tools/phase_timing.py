@@ -44,6 +44,15 @@ for i, nm in enumerate(names):
     print(f"{nm:18s} mean {d[:, i].mean():9.1f}  ({100 * d[:, i].mean() / tot.mean():5.1f} %)   p90 {np.percentile(d[:, i], 90):9.1f}")
 
 print("after stamp 10 (flags store, bars if any) until the end of the kernel: mean %.0f ticks" % (s[:, 13] - s[:, 10]).mean())
+# the kernels without a display also leave the cycle counter of the wavefront's first instruction (slot 14): the prologue = kernel
+# arguments, per-stream scalar words and whatever is requested in front of stamp 0
+entry = None if (extra or not s[:, 14].any()) else s[:, 14]
+if entry is not None:
+    pro = s[:, 0] - entry
+    print("entry -> stamp 0 (kernel arguments + per-stream words): mean %.0f  p50 %.0f  p90 %.0f  (%.1f %% of entry -> stamp 10)" %
+          (pro.mean(), np.percentile(pro, 50), np.percentile(pro, 90), 100 * pro.mean() / (s[:, 10] - entry).mean()))
+    f1 = s[:, 1] - entry
+    print("entry -> stamp 1 (the whole fetch burst has returned): mean %.0f  p50 %.0f  p90 %.0f" % (f1.mean(), np.percentile(f1, 50), np.percentile(f1, 90)))
 if os.environ.get("WF_BENCH_CURVE"):
     print("curve: row->LDS+syncs %.0f | points + mapping + stores %.0f" % ((s[:, 12] - s[:, 10]).mean(), (s[:, 13] - s[:, 12]).mean()))
 if os.environ.get("WF_BENCH_BARS") and os.environ.get("WF_HIP_BAR_PS", "1") != "0":
@@ -53,14 +62,15 @@ elif os.environ.get("WF_BENCH_BARS"):
     print("bars: row->LDS+syncs %.0f | A products+sync %.0f | B1 segment sums+sync %.0f | B2 bar sums+stores %.0f" %
           ((s[:, 12] - s[:, 10]).mean(), (s[:, 14] - s[:, 12]).mean(), (s[:, 15] - s[:, 14]).mean(), (s[:, 13] - s[:, 15]).mean()))
 # ---- where and when: per-CU residency from HW_ID (slot 11) / XCC_ID (slot 12) ------------------------------
-hw, xcc = s[:, 11], 0 * s[:, 11]
+hw, xcc = s[:, 11], (s[:, 12] & 0xF if entry is not None else 0 * s[:, 11])  # (slot 12 holds XCC_ID unless the display phase stamps it)
 cu = ((xcc << 12) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xF))
 # the cycle counters of different CUs are not synchronised: normalise per CU (the launch ramp is not visible this way)
 ids = np.unique(cu)
 start, end = np.zeros(nblk), np.zeros(nblk)
 for i in ids:
     m = cu == i
-    start[m], end[m] = s[m, 0] - s[m, 0].min(), s[m, 10] - s[m, 0].min()
+    t0 = s[m, 0].min()
+    start[m], end[m] = (s[m, 0] if entry is None else entry[m]) - t0, s[m, (10 if entry is None else 13)] - t0
 span = np.median([end[cu == i].max() for i in ids])
 print(f"CUs seen: {len(ids)}  workgroups per CU: min {min((cu == i).sum() for i in ids)} max {max((cu == i).sum() for i in ids)}")
 print("per-CU span (first start -> last stamp-10): p10 %.0f p50 %.0f p90 %.0f ticks" %
@@ -77,5 +87,8 @@ for i in ids:
         gaps.append(st[slots + k] - en[k])
 print("mean resident workgroups per CU over the kernel span: %.2f" % np.mean(conc))
 if gaps:
-    print("slot refill gap (next start - freed end, stamp 10 is before the final stores drain): mean %.0f  p50 %.0f  p90 %.0f" %
-          (np.mean(gaps), np.percentile(gaps, 50), np.percentile(gaps, 90)))
+    what = "next start - freed end, stamp 10 is before the final stores drain" if entry is None else "next workgroup's first instruction - freed workgroup's last stamp"
+    print("slot refill gap (%s): mean %.0f  p50 %.0f  p90 %.0f" % (what, np.mean(gaps), np.percentile(gaps, 50), np.percentile(gaps, 90)))
+    life = (end - start).mean()
+    print("workgroup life by the same two stamps: mean %.0f  -> an empty slot for %.1f %% of life + gap (by the mean gap), %.1f %% (by the median)" %
+          (life, 100 * np.mean(gaps) / (life + np.mean(gaps)), 100 * np.percentile(gaps, 50) / (life + np.percentile(gaps, 50))))

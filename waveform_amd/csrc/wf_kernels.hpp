@@ -193,6 +193,9 @@ template<class G, Variant V> constexpr int tick_waves_per_simd()
 template<class G, Variant V>
 __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void spectrum_tick_kernel(const TickArgs a)
 {
+#ifdef WF_PHASE_TIMING
+    const unsigned long long clock_entry = __builtin_readcyclecounter(); // the wavefront's first instruction (stored with stamp 0, slot 14)
+#endif
     constexpr int SPW = V.spw, DEC = V.dec, DISP = V.disp, PLAN = V.plan;
     constexpr bool ALIGNED = V.aligned, SPLIT = V.split, TLDS = V.tlds, BLU = V.blu, BOTH = V.both, MR = V.mr, MRS = V.mrs, MIR = V.mir;
     static_assert(!MRS || (MR && G::T <= 256 && G::P > 8), "the small-radix instantiation belongs to the containers of one, two and four wavefronts");
@@ -278,6 +281,10 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
 
     WF_STAMP(0);
     WF_STAMP_HWID();
+#ifdef WF_PHASE_TIMING
+    if(DISP == 2 && threadIdx.x == 0 && a.phase_clock) // (slot 14 belongs to the display phase's stamps in the other instantiations)
+        a.phase_clock[(size_t)blockIdx.x * 16 + 14] = clock_entry;
+#endif
     // ---- fetch the window; per-wavefront facts for the silence state machine (reference :55-95) ----------
     // (hidden streams are fetched too: the flags word is not waited for before the loads are issued)
     P1Regs<G> r1;
