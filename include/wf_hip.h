@@ -40,6 +40,8 @@
  *                        estimated on the device when read
  *   WF_HIP_OUT_BANDS     not in the reference: third-octave band levels (IEC 61260-1) and the Z / A / C weighted level
  *                        (IEC 61672-1) of every m_decibels row, summed on the device when read
+ *   WF_HIP_OUT_STEREO    not in the reference: correlation, coherence, phase and balance between the two captured channels in
+ *                        each third-octave band, from a float64 transform of every stream's newest window on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -380,8 +382,11 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_PITCH,          /* wf_hip_pitch                               fundamental frequency (YIN) of the newest
                                   min(wf_hip_fft_size(), 4096) frames in the rings as of the pushes issued so far (spectrum
                                   and meter batches; definition below) */
-    WF_HIP_OUT_BANDS           /* wf_hip_bands [output_channels]             third-octave band levels and the Z / A / C weighted level
+    WF_HIP_OUT_BANDS,          /* wf_hip_bands [output_channels]             third-octave band levels and the Z / A / C weighted level
                                   of each m_decibels row as of the newest tick (spectrum batches; definition below) */
+    WF_HIP_OUT_STEREO          /* wf_hip_stereo                              correlation, coherence, phase and balance per third-octave
+                                  band between captured channels 0 and 1, over the newest frames in the rings as of the pushes
+                                  issued so far (spectrum and meter batches with two captured channels; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -539,6 +544,59 @@ typedef struct wf_hip_bands {
     float c_db;                      /* C-weighted level of the whole row */
     uint32_t reserved;               /* 0 */
 } wf_hip_bands;                      /* 144 bytes */
+/* ---- stereo image (WF_HIP_OUT_STEREO) ---------------------------------------------------------------------------------------
+ * Per stream, what a correlation meter by band shows: how captured channels 0 (l) and 1 (r) relate in each of the 31
+ * third-octave bands.  WF_HIP_OUT_SIGNAL's one broadband correlation cannot tell a bass that cancels in mono from a wide reverb
+ * tail, and the tick keeps magnitudes only, so the output takes a complex transform of its own when read.  sr = cfg.sample_rate,
+ * W = wf_hip_fft_size().  Everything below is float64 unless it says otherwise.
+ *   window         P = the largest power of two <= min(W, WF_HIP_STEREO_MAX_WINDOW) frames: the newest P frames of both rings,
+ *                  positions (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of WF_HIP_OUT_SIGNAL: every push
+ *                  issued before the read counts whatever its path, the A/V-sync delay is not applied, the zeros of create and
+ *                  wf_hip_reset count as samples.  Hidden and paused streams are read like any other.
+ *   transform      w[i] = 0.5 - 0.5 cos(2 pi i / P) (periodic Hann; a table made on the host), z[i] = w[i] (l[i] + j r[i]) from
+ *                  the float32 samples, Z = the forward DFT of z with the kernel e^(-j 2 pi i k / P), twiddles from a host-made
+ *                  table of cos / sin.  For k = 1 .. P/2 - 1:
+ *                      L[k] = (Z[k] + conj Z[P - k]) / 2,   R[k] = (Z[k] - conj Z[P - k]) / (2j):
+ *                  one complex transform serves both channels.
+ *   per bin        Pll = |L|^2, Prr = |R|^2, C = L conj(R): the phase of C is positive when the left channel leads.
+ *   bands          the grid, the edges e[j] and the bin-to-band overlap weights of WF_HIP_OUT_BANDS with N replaced by P:
+ *                  E[j] = e[j] P / sr, weight(b, k) = max(min(k + 0.5, E[b + 1]) - max(k - 0.5, E[b]), 0).  For band b,
+ *                      A = sum_k weight Pll,  B = sum_k weight Prr,  X = sum_k weight C     (k = 1 .. P/2 - 1).
+ *                  `covered` is defined as there, with M = P / 2.
+ *   fields         per band, each rounded to float32 once:
+ *                  correlation[b] = Re X / sqrt(A B), clamped to [-1, 1]: +1 mono, 0 unrelated or in quadrature, -1 out of phase
+ *                  coherence[b]   = |X| / sqrt(A B), clamped to [0, 1]: 1 where one fixed phase and gain relate the channels
+ *                                   over the band, small where the phase wanders (decorrelated: reverb, independent sources)
+ *                  phase_deg[b]   = atan2(Im X, Re X) 180 / pi, in (-180, 180]; a rounded -180 is reported as +180
+ *                  balance_db[b]  = 10 log10(B / A), positive when the right channel is louder
+ *                  When A or B is 0, or the band has no overlap with the bins: correlation, coherence and phase read 0, and
+ *                  balance_db reads 0 if both are 0 and +-INFINITY if one is (wf_hip_signal's rule).  L and R come out of one
+ *                  transform, so a channel of exact zeros leaves a sum of the other's rounding errors, some 310 dB under it,
+ *                  not 0: a sum below WF_HIP_STEREO_DEAD_RATIO (2^-80, -240.8 dB) times the other counts as 0, so that a dead
+ *                  channel reads as one.  No pair of float32 signals that means anything lies that far apart.
+ *   determinism    no atomics; the order of every sum depends on P and the edges alone: the same ring contents read
+ *                  bit-identically.  A host that restates the transform with another FFT differs by float64 rounding only,
+ *                  below 1e-12 in every field before the one rounding to float32 (phase: wherever coherence >= 0.01; below
+ *                  that the phase of a sum that nearly cancels is not a number to rely on).
+ * A short window leaves the low bands uncovered (`covered`); no state is kept between reads: averaging over time is the
+ * host's.  Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup per stream,
+ * the transform in 16 P bytes of LDS), into a block the first read allocates together with the window, twiddle and edge
+ * tables: a handle that never reads it allocates and launches nothing new.  Measured on an MI355X, 4096 stereo streams at FFT
+ * 4096: 0.275 ms per read, against 2.36 ms to copy the windows to the host (profiles/stereo_kernel_stats.json; INTEGRATION.md,
+ * "Stereo image").  Spectrum and meter batches with two captured
+ * channels are served whatever cfg.stereo says (a mono mixdown still captures two).  One captured channel, W < 64 and
+ * waveform batches: wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through
+ * wf_hip_multi_read. */
+#define WF_HIP_STEREO_MAX_WINDOW 4096
+#define WF_HIP_STEREO_DEAD_RATIO 8.271806125530277e-25 /* 2^-80, exact */
+typedef struct wf_hip_stereo {
+    float correlation[WF_HIP_NUM_BANDS]; /* Re X / sqrt(A B), -1 .. 1 */
+    float coherence[WF_HIP_NUM_BANDS];   /* |X| / sqrt(A B), 0 .. 1 */
+    float phase_deg[WF_HIP_NUM_BANDS];   /* phase of X in degrees, (-180, 180]: positive when the left channel leads */
+    float balance_db[WF_HIP_NUM_BANDS];  /* 10 log10(B / A): positive means right is louder */
+    uint32_t covered;                    /* as wf_hip_bands::covered, for P and sr */
+    uint32_t window;                     /* P */
+} wf_hip_stereo;                         /* 504 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS = range(15)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO = range(16)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -146,6 +146,13 @@ BANDS_DTYPE = np.dtype([("band_db", np.float32, (NUM_BANDS,)), ("covered", np.ui
                         ("c_db", np.float32), ("reserved", np.uint32)])
 BAND_CENTRES_HZ = 1000.0 * 10.0 ** ((np.arange(NUM_BANDS) - 17) / 10.0)  # IEC 61260-1, base ten: 19.95 Hz .. 19.95 kHz
 
+# struct wf_hip_stereo (include/wf_hip.h): correlation, coherence, phase and balance between captured channels 0 and 1 in each
+# third-octave band, over one stream's newest window of at most STEREO_MAX_WINDOW frames
+STEREO_MAX_WINDOW = 4096  # WF_HIP_STEREO_MAX_WINDOW
+STEREO_DTYPE = np.dtype([("correlation", np.float32, (NUM_BANDS,)), ("coherence", np.float32, (NUM_BANDS,)),
+                         ("phase_deg", np.float32, (NUM_BANDS,)), ("balance_db", np.float32, (NUM_BANDS,)), ("covered", np.uint32),
+                         ("window", np.uint32)])
+
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
 MEASURES = {
@@ -154,6 +161,7 @@ MEASURES = {
     "signal": (OUT_SIGNAL, SIGNAL_DTYPE, False),
     "pitch": (OUT_PITCH, PITCH_DTYPE, False),
     "bands": (OUT_BANDS, BANDS_DTYPE, True),
+    "stereo": (OUT_STEREO, STEREO_DTYPE, False),
 }
 
 
@@ -394,6 +402,12 @@ class SpectrumBatch:
         """[count, output_channels] structured array of wf_hip_bands (BANDS_DTYPE): the third-octave band levels and the Z / A / C
         weighted level of each m_decibels row as of the newest tick, summed on the device when read"""
         return _read_measure(self, "bands", first, count)
+
+    def stereo(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_stereo (STEREO_DTYPE): correlation, coherence, phase and balance between captured
+        channels 0 and 1 in each third-octave band, over each stream's newest window (the largest power of two <=
+        min(fft_size, STEREO_MAX_WINDOW) frames) as of the pushes issued so far, transformed on the device when read"""
+        return _read_measure(self, "stereo", first, count)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -760,6 +774,9 @@ class MultiBatch:
 
     def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return _read_measure(self, "bands", first, count)
+
+    def stereo(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        return _read_measure(self, "stereo", first, count)
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return self._read(OUT_LAST_SILENT, first, count, (), np.uint8).astype(bool)

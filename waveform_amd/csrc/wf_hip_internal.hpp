@@ -145,7 +145,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read
-    static constexpr int N_MEASURES = 5;
+    static constexpr int N_MEASURES = 6;
     char *d_measure[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
@@ -160,6 +160,12 @@ struct wf_hip {
         uint32_t covered = 0;                     // wf_hip_bands::covered of this batch
         double enbw = 1.0;                        // the window's equivalent noise bandwidth in bins
     } bands;
+    // what WF_HIP_OUT_STEREO derives from the configuration (setup_stereo, at its first read; wf_stereo.hpp)
+    struct Stereo {
+        double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_NUM_BANDS + 1] band edges in bins of P
+        uint32_t P = 0, log2p = 0;                // the window: a power of two
+        uint32_t covered = 0;                     // wf_hip_stereo::covered of this batch
+    } stereo;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

@@ -1,5 +1,5 @@
-// wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH
-// and _BANDS.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
+// _BANDS and _STEREO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is and how it is
 // launched; one reader (measure_read) does the rest.  The loudness producer alone also keeps state between reads: it follows
 // every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip) and is switched on by
@@ -20,6 +20,7 @@
 #include "wf_signal.hpp"
 #include "wf_pitch.hpp"
 #include "wf_bands.hpp"
+#include "wf_stereo.hpp"
 
 namespace {
 
@@ -158,6 +159,70 @@ int launch_bands(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// the stereo image's window: the largest power of two <= min(fft_size, WF_HIP_STEREO_MAX_WINDOW) (<= ring_cap)
+uint32_t stereo_window(const wf_hip *h)
+{
+    uint32_t p = 1;
+    while(2 * p <= std::min<uint32_t>(h->N, WF_HIP_STEREO_MAX_WINDOW))
+        p *= 2;
+    return p;
+}
+
+// what the stereo image derives from the configuration alone, made by its first read: the periodic Hann window and the
+// twiddles e^(-j 2 pi m / P) in float64, the band edges in bins of P and which bands lie wholly inside the spectrum -- one
+// block [P window][P / 2 twiddles, re im][WF_HIP_NUM_BANDS + 1 edges]
+int setup_stereo(wf_hip *h)
+{
+    wf_hip::Stereo &s = h->stereo;
+    const uint32_t P = stereo_window(h);
+    std::vector<double> tab((size_t)2 * P + WF_HIP_NUM_BANDS + 1);
+    for(uint32_t i = 0; i < P; ++i)
+        tab[i] = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)P);
+    for(uint32_t m = 0; m < P / 2; ++m) {
+        const double x = 2.0 * M_PI * (double)m / (double)P;
+        tab[P + 2 * (size_t)m] = std::cos(x);
+        tab[P + 2 * (size_t)m + 1] = -std::sin(x);
+    }
+    double *edges = tab.data() + 2 * (size_t)P;
+    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
+        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)P / (double)h->cfg.sample_rate;
+    s.covered = 0;
+    for(int j = 0; j < WF_HIP_NUM_BANDS; ++j)
+        if(edges[j] >= 0.5 && edges[j + 1] <= (double)(P / 2) - 0.5)
+            s.covered |= 1u << j;
+    s.P = P;
+    s.log2p = 0;
+    while((1u << s.log2p) < P)
+        ++s.log2p;
+    // (64 KB at P = 4096: the most a workgroup gets without asking; asked for all the same, so that the limit is stated here)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::stereo_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)(WF_HIP_STEREO_MAX_WINDOW * sizeof(double2))));
+    return upload(h, &s.d_tab, tab); // (pageable memory: staged before the call returns; d_tab says that all of this is in place)
+}
+
+// one workgroup per stream over its newest P frames of both channels, behind the pushes issued
+int launch_stereo(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    if(h->stereo.d_tab == nullptr)
+        WF_TRY_RC(setup_stereo(h));
+    const wf_hip::Stereo &s = h->stereo;
+    wf::StereoArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = static_cast<wf_hip_stereo *>(d_block) + first;
+    a.window = s.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(s.d_tab + s.P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.edges = s.d_tab + 2 * (size_t)s.P;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.P = s.P;
+    a.log2p = s.log2p;
+    a.covered = s.covered;
+    hipLaunchKernelGGL(wf::stereo_read_kernel, dim3(count), dim3(wf::WF_STEREO_THREADS), (size_t)s.P * sizeof(double2), h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -171,6 +236,15 @@ const char *why_no_pitch(const wf_hip *h)
     if(h->wave)
         return "waveform batch: the pitch belongs to spectrum and meter batches (a window of fft_size frames)";
     return h->N < 64 ? "the pitch needs a window of at least 64 frames" : nullptr;
+}
+
+const char *why_no_stereo(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the stereo image belongs to spectrum and meter batches (a window of fft_size frames)";
+    if(h->cap_ch != 2)
+        return "one captured channel: the stereo image needs two (capture_channels == 2)";
+    return h->N < 64 ? "the stereo image needs a window of at least 64 frames" : nullptr;
 }
 
 struct Measure {
@@ -188,6 +262,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_SIGNAL, sizeof(wf_hip_signal), false, why_no_signal, launch_signal},
     {WF_HIP_OUT_PITCH, sizeof(wf_hip_pitch), false, why_no_pitch, launch_pitch},
     {WF_HIP_OUT_BANDS, sizeof(wf_hip_bands), true, why_no_bands, launch_bands},
+    {WF_HIP_OUT_STEREO, sizeof(wf_hip_stereo), false, why_no_stereo, launch_stereo},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
