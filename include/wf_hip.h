@@ -42,6 +42,8 @@
  *                        (IEC 61672-1) of every m_decibels row, summed on the device when read
  *   WF_HIP_OUT_STEREO    not in the reference: correlation, coherence, phase and balance between the two captured channels in
  *                        each third-octave band, from a float64 transform of every stream's newest window on the device when read
+ *   WF_HIP_OUT_CQ        not in the reference: a constant-Q spectrum, one level per semitone from C0 to B9, of every stream's
+ *                        newest audio in the rings, correlated in float64 on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -384,9 +386,12 @@ typedef enum wf_hip_output {
                                   and meter batches; definition below) */
     WF_HIP_OUT_BANDS,          /* wf_hip_bands [output_channels]             third-octave band levels and the Z / A / C weighted level
                                   of each m_decibels row as of the newest tick (spectrum batches; definition below) */
-    WF_HIP_OUT_STEREO          /* wf_hip_stereo                              correlation, coherence, phase and balance per third-octave
+    WF_HIP_OUT_STEREO,         /* wf_hip_stereo                              correlation, coherence, phase and balance per third-octave
                                   band between captured channels 0 and 1, over the newest frames in the rings as of the pushes
                                   issued so far (spectrum and meter batches with two captured channels; definition below) */
+    WF_HIP_OUT_CQ              /* wf_hip_cq                                  constant-Q spectrum: one level per semitone and captured
+                                  channel, each over its own Q periods of the newest frames in the rings as of the pushes issued
+                                  so far (spectrum and meter batches; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -597,6 +602,56 @@ typedef struct wf_hip_stereo {
     uint32_t covered;                    /* as wf_hip_bands::covered, for P and sr */
     uint32_t window;                     /* P */
 } wf_hip_stereo;                         /* 504 bytes */
+/* ---- constant-Q spectrum (WF_HIP_OUT_CQ) -------------------------------------------------------------------------------------
+ * Per stream and captured channel, one level per semitone: the "notes" display, from which hosts sum chroma, chord and key
+ * displays.  Every other spectral output is a view of the tick's rows and has their one resolution, sr / fft_size per bin --
+ * 11.7 Hz at FFT 4096 and 48 kHz, where semitones lie 6 Hz apart at 100 Hz -- so this one analyses the audio in the rings
+ * itself, with a window of Q periods per note: long in the bass, short in the treble, the same relative resolution everywhere.
+ * sr = cfg.sample_rate.  Everything below is float64 unless it says otherwise.
+ *   bins           WF_HIP_CQ_BINS = 120 semitones; bin b has the centre f_b = 440 * 2^((b - 57) / 12) Hz: b = 0 is C0
+ *                  (16.35 Hz), b = 57 is A4, b = 119 is B9 (15 804 Hz); bin b is MIDI note 12 + b.  Q = 1 / (2^(1/12) - 1), about
+ *                  16.817.
+ *   windows        Lmax = min(wf_hip_ring_frames(), WF_HIP_CQ_MAX_WINDOW), L_b = min(ceil(Q sr / f_b), Lmax).  Bin b analyses
+ *                  the newest L_b frames of each captured channel's ring, positions (wpos - L_b .. wpos - 1) mod the ring's
+ *                  capacity: all bins end at the newest frame.  The rules are WF_HIP_OUT_SIGNAL's: every push issued before
+ *                  the read counts whatever its path, the A/V-sync delay is not applied, the zeros of create and wf_hip_reset
+ *                  count as samples.  Hidden and paused streams are read like any other.
+ *   value          w_b[n] = 0.5 - 0.5 cos(2 pi n / L_b) (periodic Hann), x[n] frame n of the window as float32,
+ *                      S_b = sum_{n < L_b} w_b[n] x[n] e^(-j 2 pi f_b n / sr),   a_b = 4 |S_b| / L_b,
+ *                  db = 20 log10 a_b, rounded to float32 once; -INFINITY when a_b is 0.  A sine of amplitude A at f_b reads
+ *                  20 log10 A, the convention of the rows and of WF_HIP_OUT_BANDS; its semitone neighbours read about 6 dB
+ *                  lower, the usual overlap of a Hann constant-Q bank.
+ *   covered        bin b is covered when f_b 2^(1/24) < sr / 2: its upper edge lies under the Nyquist frequency.  The covered
+ *                  bins are a prefix, `end_covered` is their count; the others read -INFINITY and are not computed.
+ *   resolved       `first_resolved` is the lowest b with ceil(Q sr / f_b) <= Lmax (WF_HIP_CQ_BINS when there is none).  Bins
+ *                  below it use Lmax frames and are wider than a semitone; a host that wants resolved notes further down
+ *                  creates the handle with a larger `ring_frames` (16384 frames at 48 kHz resolve from G#1, 51.9 Hz).  Both
+ *                  fields depend on sr and the ring alone, never on the audio.
+ *   channels       db[c] is captured channel c; with one captured channel db[1] reads -INFINITY throughout.
+ *   determinism    no atomics; every sum in an order fixed by L_b alone: the same ring contents read bit-identically, across
+ *                  push paths, repeated reads, slices and shards.  On the device the carrier and the window's phasor start from
+ *                  float64 values made on the host for the first 64 frames and advance by a complex multiplication per 64
+ *                  frames, at most 256 times.  A host that restates the sums directly differs by float64 rounding: phase
+ *                  rounding of 2 pi f_b n / sr (at most 2 pi Q, 106 rad), the 256-step recurrence and the order of the sums,
+ *                  about 1e-11 of the window's largest |x| in a_b by derivation; the tests hold it to 1e-10 of that, and to two
+ *                  float32 ulps of db wherever a_b is at least 1e-3 of it.  Measured on an MI355X over the tests' shapes: every
+ *                  such bin equal to the restatement's float32, every other covered bin within two ulps of it.
+ * No state is kept between reads: smoothing over time is the host's.  Computed when read, by one kernel on the handle's stream
+ * behind the pushes issued so far (one workgroup per stream, the newest Lmax frames of each channel staged in LDS, one
+ * wavefront per bin), into a block the first read allocates together with the per-bin constants (about 250 KB): a handle that
+ * never reads it allocates and launches nothing new.  Measured on an MI355X, 4096 stereo streams at FFT 4096: 1.28 ms per read at
+ * Lmax 8192 against 4.71 ms to copy the windows to the host, 2.24 ms against 11.28 ms at Lmax 16384 (profiles/cq_kernel_stats.json;
+ * INTEGRATION.md, "Constant-Q spectrum").  Spectrum and meter batches are served; on waveform batches wf_hip_read
+ * returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_CQ_BINS 120
+#define WF_HIP_CQ_MAX_WINDOW 16384
+typedef struct wf_hip_cq {
+    float db[2][WF_HIP_CQ_BINS]; /* captured channels 0 and 1 */
+    uint32_t end_covered;        /* covered bins: b < end_covered */
+    uint32_t first_resolved;     /* lowest bin with its full Q sr / f window */
+    uint32_t max_window;         /* Lmax */
+    uint32_t reserved;           /* 0 */
+} wf_hip_cq;                     /* 976 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

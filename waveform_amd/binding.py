@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO = range(16)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ = range(17)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -153,6 +153,14 @@ STEREO_DTYPE = np.dtype([("correlation", np.float32, (NUM_BANDS,)), ("coherence"
                          ("phase_deg", np.float32, (NUM_BANDS,)), ("balance_db", np.float32, (NUM_BANDS,)), ("covered", np.uint32),
                          ("window", np.uint32)])
 
+# struct wf_hip_cq (include/wf_hip.h): the constant-Q spectrum, one level per semitone (bin b: MIDI note 12 + b) and captured
+# channel, each over its own Q periods of the newest frames in the ring, at most CQ_MAX_WINDOW of them
+CQ_BINS = 120  # WF_HIP_CQ_BINS
+CQ_MAX_WINDOW = 16384  # WF_HIP_CQ_MAX_WINDOW
+CQ_DTYPE = np.dtype([("db", np.float32, (2, CQ_BINS)), ("end_covered", np.uint32), ("first_resolved", np.uint32),
+                     ("max_window", np.uint32), ("reserved", np.uint32)])
+CQ_CENTRES_HZ = 440.0 * 2.0 ** ((np.arange(CQ_BINS) - 57) / 12.0)  # C0 16.35 Hz .. B9 15.8 kHz
+
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
 MEASURES = {
@@ -162,6 +170,7 @@ MEASURES = {
     "pitch": (OUT_PITCH, PITCH_DTYPE, False),
     "bands": (OUT_BANDS, BANDS_DTYPE, True),
     "stereo": (OUT_STEREO, STEREO_DTYPE, False),
+    "cq": (OUT_CQ, CQ_DTYPE, False),
 }
 
 
@@ -408,6 +417,12 @@ class SpectrumBatch:
         channels 0 and 1 in each third-octave band, over each stream's newest window (the largest power of two <=
         min(fft_size, STEREO_MAX_WINDOW) frames) as of the pushes issued so far, transformed on the device when read"""
         return _read_measure(self, "stereo", first, count)
+
+    def cq(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_cq (CQ_DTYPE): the constant-Q spectrum, db[channel][semitone] from C0 to B9, each
+        bin over the newest min(ceil(Q sr / f), ring_frames, CQ_MAX_WINDOW) frames of the ring as of the pushes issued so far,
+        correlated on the device when read"""
+        return _read_measure(self, "cq", first, count)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -777,6 +792,9 @@ class MultiBatch:
 
     def stereo(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return _read_measure(self, "stereo", first, count)
+
+    def cq(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        return _read_measure(self, "cq", first, count)
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return self._read(OUT_LAST_SILENT, first, count, (), np.uint8).astype(bool)

@@ -145,7 +145,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read
-    static constexpr int N_MEASURES = 6;
+    static constexpr int N_MEASURES = 7;
     char *d_measure[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
@@ -166,6 +166,13 @@ struct wf_hip {
         uint32_t P = 0, log2p = 0;                // the window: a power of two
         uint32_t covered = 0;                     // wf_hip_stereo::covered of this batch
     } stereo;
+    // what WF_HIP_OUT_CQ derives from the configuration and the ring (setup_cq, at its first read; wf_cq.hpp)
+    struct Cq {
+        double *d_tab = nullptr;                  // [end_covered][WF_CQ_BIN_DOUBLES] steps, 4 / L_b, L_b and the lanes' start values
+        uint32_t *d_sched = nullptr;              // [WF_CQ_SCHED_WORDS] which wave takes which bins, in which order
+        uint32_t max_window = 0;                  // Lmax
+        uint32_t end_covered = 0, first_resolved = 0;
+    } cq;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS and _STEREO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO and _CQ.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is and how it is
 // launched; one reader (measure_read) does the rest.  The loudness producer alone also keeps state between reads: it follows
 // every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip) and is switched on by
@@ -21,6 +21,7 @@
 #include "wf_pitch.hpp"
 #include "wf_bands.hpp"
 #include "wf_stereo.hpp"
+#include "wf_cq.hpp"
 
 namespace {
 
@@ -223,6 +224,108 @@ int launch_stereo(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the constant-Q spectrum derives from the sample rate and the ring alone, made by its first read: L_b, which bins are
+// covered and resolved, and per covered bin the constants of wf_cq.hpp's table -- the carrier e^(-j 2 pi f_b n / sr) and the
+// window's phasor e^(j 2 pi n / L_b) at n = 0 .. 63 and their steps of 64 frames, from long double arguments so that the device's
+// recurrence starts from correctly rounded values -- and the order in which the kernel's waves take the bins
+int setup_cq(wf_hip *h)
+{
+    wf_hip::Cq &q = h->cq;
+    const double sr = (double)h->cfg.sample_rate;
+    const double Q = 1.0 / (std::pow(2.0, 1.0 / 12.0) - 1.0);
+    const uint32_t Lmax = std::min<uint32_t>(h->ring_cap, WF_HIP_CQ_MAX_WINDOW); // (a power of two >= 128: a multiple of 64)
+    uint32_t L[WF_HIP_CQ_BINS];
+    q.max_window = Lmax;
+    q.end_covered = 0;
+    q.first_resolved = WF_HIP_CQ_BINS;
+    for(uint32_t b = 0; b < WF_HIP_CQ_BINS; ++b) {
+        const double f = 440.0 * std::pow(2.0, ((double)b - 57.0) / 12.0);
+        if(f * std::pow(2.0, 1.0 / 24.0) < sr / 2.0 && q.end_covered == b)
+            q.end_covered = b + 1;
+        const double full = std::ceil(Q * sr / f);
+        if(full <= (double)Lmax && q.first_resolved == WF_HIP_CQ_BINS)
+            q.first_resolved = b;
+        L[b] = full <= (double)Lmax ? (uint32_t)full : Lmax;
+    }
+    std::vector<double> tab((size_t)q.end_covered * wf::WF_CQ_BIN_DOUBLES, 0.0);
+    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
+    for(uint32_t b = 0; b < q.end_covered; ++b) {
+        const long double wc = -two_pi * 440.0L * std::pow(2.0L, ((long double)b - 57.0L) / 12.0L) / (long double)h->cfg.sample_rate;
+        const long double wh = two_pi / (long double)L[b];
+        double *t = tab.data() + (size_t)b * wf::WF_CQ_BIN_DOUBLES;
+        t[0] = (double)std::cos(64.0L * wc);
+        t[1] = (double)std::sin(64.0L * wc);
+        t[2] = (double)std::cos(64.0L * wh);
+        t[3] = (double)std::sin(64.0L * wh);
+        t[4] = 4.0 / (double)L[b];
+        t[5] = (double)L[b];
+        for(uint32_t l = 0; l < 64; ++l) {
+            double *v = t + wf::WF_CQ_BIN_HEAD + 4 * (size_t)l;
+            v[0] = (double)std::cos((long double)l * wc);
+            v[1] = (double)std::sin((long double)l * wc);
+            v[2] = (double)std::cos((long double)l * wh);
+            v[3] = (double)std::sin((long double)l * wh);
+        }
+    }
+    // the longest bin first, each to the wave with the least work so far (ties: the lower bin, the lower wave); a bin costs its
+    // iterations plus a constant for its table, its reduction and its logarithm
+    std::vector<uint32_t> lists[wf::WF_CQ_WAVES];
+    uint32_t load[wf::WF_CQ_WAVES] = {};
+    std::vector<uint32_t> by_cost(q.end_covered);
+    for(uint32_t b = 0; b < q.end_covered; ++b)
+        by_cost[b] = b;
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](uint32_t x, uint32_t y) { return L[x] > L[y]; });
+    for(const uint32_t b : by_cost) {
+        const uint32_t w = (uint32_t)(std::min_element(load, load + wf::WF_CQ_WAVES) - load);
+        lists[w].push_back(b);
+        load[w] += (L[b] + 63u) / 64u + 8u;
+    }
+    std::vector<uint32_t> sched;
+    sched.reserve(wf::WF_CQ_SCHED_WORDS);
+    uint32_t at = 0;
+    for(uint32_t w = 0; w < wf::WF_CQ_WAVES; ++w) {
+        sched.push_back(at);
+        at += (uint32_t)lists[w].size();
+    }
+    sched.push_back(at);
+    for(uint32_t w = 0; w < wf::WF_CQ_WAVES; ++w)
+        sched.insert(sched.end(), lists[w].begin(), lists[w].end());
+    sched.resize(wf::WF_CQ_SCHED_WORDS, 0u);
+    // (128 KB at the cap with two channels: more than a workgroup gets without asking)
+    const int lds = (int)(WF_HIP_CQ_MAX_WINDOW * 2 * sizeof(float));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::cq_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds / 2));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::cq_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if(q.d_sched == nullptr)
+        WF_TRY_RC(upload(h, &q.d_sched, sched)); // (pageable memory: staged before the call returns)
+    return upload(h, &q.d_tab, tab);             // (last: d_tab says that all of this is in place)
+}
+
+// one workgroup per stream over the newest Lmax frames of its captured channels, behind the pushes issued
+int launch_cq(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    if(h->cq.d_tab == nullptr)
+        WF_TRY_RC(setup_cq(h));
+    const wf_hip::Cq &q = h->cq;
+    wf::CqArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = static_cast<wf_hip_cq *>(d_block) + first;
+    a.tab = q.d_tab;
+    a.sched = q.d_sched;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.Lmax = q.max_window;
+    a.end_covered = q.end_covered;
+    a.first_resolved = q.first_resolved;
+    const size_t lds = (size_t)h->cap_ch * q.max_window * sizeof(float);
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::cq_read_kernel<2>, dim3(count), dim3(wf::WF_CQ_THREADS), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::cq_read_kernel<1>, dim3(count), dim3(wf::WF_CQ_THREADS), lds, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -247,6 +350,11 @@ const char *why_no_stereo(const wf_hip *h)
     return h->N < 64 ? "the stereo image needs a window of at least 64 frames" : nullptr;
 }
 
+const char *why_no_cq(const wf_hip *h)
+{
+    return h->wave ? "waveform batch: the constant-Q spectrum belongs to spectrum and meter batches" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -263,6 +371,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_PITCH, sizeof(wf_hip_pitch), false, why_no_pitch, launch_pitch},
     {WF_HIP_OUT_BANDS, sizeof(wf_hip_bands), true, why_no_bands, launch_bands},
     {WF_HIP_OUT_STEREO, sizeof(wf_hip_stereo), false, why_no_stereo, launch_stereo},
+    {WF_HIP_OUT_CQ, sizeof(wf_hip_cq), false, why_no_cq, launch_cq},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
