@@ -44,6 +44,8 @@
  *                        each third-octave band, from a float64 transform of every stream's newest window on the device when read
  *   WF_HIP_OUT_CQ        not in the reference: a constant-Q spectrum, one level per semitone from C0 to B9, of every stream's
  *                        newest audio in the rings, correlated in float64 on the device when read
+ *   WF_HIP_OUT_SCOPE     not in the reference (its "waveform" mode is a level history, not the wave): a triggered oscilloscope
+ *                        trace of every stream's newest window of audio, triggered and reduced to columns on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -389,9 +391,12 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_STEREO,         /* wf_hip_stereo                              correlation, coherence, phase and balance per third-octave
                                   band between captured channels 0 and 1, over the newest frames in the rings as of the pushes
                                   issued so far (spectrum and meter batches with two captured channels; definition below) */
-    WF_HIP_OUT_CQ              /* wf_hip_cq                                  constant-Q spectrum: one level per semitone and captured
+    WF_HIP_OUT_CQ,             /* wf_hip_cq                                  constant-Q spectrum: one level per semitone and captured
                                   channel, each over its own Q periods of the newest frames in the rings as of the pushes issued
                                   so far (spectrum and meter batches; definition below) */
+    WF_HIP_OUT_SCOPE           /* wf_hip_scope                               oscilloscope: the smallest and largest sample per display
+                                  column of a triggered view of the newest min(wf_hip_fft_size(), 8192) frames in the rings as of
+                                  the pushes issued so far (spectrum and meter batches; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -652,6 +657,59 @@ typedef struct wf_hip_cq {
     uint32_t max_window;         /* Lmax */
     uint32_t reserved;           /* 0 */
 } wf_hip_cq;                     /* 976 bytes */
+/* ---- oscilloscope (WF_HIP_OUT_SCOPE) ------------------------------------------------------------------------------------------
+ * Per stream, the wave itself against time: a min/max trace of WF_HIP_SCOPE_COLUMNS columns per captured channel, over a view
+ * that starts at a trigger point, so that a periodic signal stands still from read to read.  W = wf_hip_fft_size().  Everything
+ * below consists of comparisons, exact float64 operations and single correctly rounded IEEE operations: a host that restates it
+ * reproduces every field bit for bit.
+ *   window         P = min(W, WF_HIP_SCOPE_MAX_WINDOW) frames: the newest P frames of each captured channel's ring, positions
+ *                  (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of WF_HIP_OUT_SIGNAL: every push issued before
+ *                  the read counts whatever its path, the A/V-sync delay is not applied, the zeros of create and wf_hip_reset
+ *                  count as samples.  Hidden and paused streams are read like any other.  x_c[i], i < P, is the float32 sample
+ *                  of channel c.
+ *   view           V = P / 2 (integer division) frames are drawn, in K = min(WF_HIP_SCOPE_COLUMNS, V) columns.
+ *   trigger signal in float64: t[i] = x_0[i] with one captured channel, x_0[i] + x_1[i] with two (exact).
+ *   level          an automatic 50 % trigger, so that a DC offset does not stop the scope from triggering: tmax = max t and
+ *                  tmin = min t over all P frames, level = (tmax + tmin) * 0.5, hyst = (tmax - tmin) * 0.125,
+ *                  u[i] = t[i] - level; each one IEEE float64 operation followed by an exact scaling.
+ *   classes        frame i is LOW when u[i] <= -hyst and HIGH when u[i] >= 0; otherwise it is neither.
+ *   triggers       walk i upwards from 0, starting unarmed: a LOW frame arms, a HIGH frame met while armed is a trigger and
+ *                  disarms.  So i is a trigger iff it is HIGH and the nearest earlier frame that is LOW or HIGH is LOW; then
+ *                  i >= 1 and u[i-1] < 0 <= u[i].  The hysteresis rejects the extra zero crossings of a harmonic-rich wave whose
+ *                  excursion stays within an eighth of the swing.
+ *   selection      `start` is the largest trigger with start <= P - V, so that the view [start, start + V) lies inside the
+ *                  window; triggered = 1; period = start - j with j the largest trigger below start, 0 when there is none;
+ *                  frac = u[start-1] / (u[start-1] - u[start]), computed in float64 and rounded to float32 once, in (0, 1]: the
+ *                  interpolated crossing lies at start - 1 + frac, and a host draws frame start + k at x = k + (1 - frac), the
+ *                  crossing at x = 0, for a picture that is steady to less than a sample.  If tmax == tmin (silence, a constant, l = -r) or no trigger lies at or
+ *                  below P - V: start = P - V, triggered = 0, period = 0, frac = 0 -- the scope free-runs on the newest V frames.
+ *   trace          column c < K covers frames start + floor(c V / K) .. start + floor((c + 1) V / K) - 1 (never empty, K <= V);
+ *                  lo[ch][c] and hi[ch][c] are the smallest and largest x_ch among them, as float32.  Columns c >= K and the rows
+ *                  of a channel that is not captured read 0.  Behaviour for non-finite samples is not defined.
+ *   determinism    no atomics; the result depends on the ring contents alone and reads bit-identically across push paths,
+ *                  repeated reads, slices and shards.
+ * sample_rate / period is the scope's "frequency" read-out; the time base is the FFT size's (V = fft_size / 2 frames across the
+ * picture) and is capped at WF_HIP_SCOPE_MAX_WINDOW frames.  No state is kept between reads.  Computed when read, by one kernel on
+ * the handle's stream behind the pushes issued so far (one workgroup per stream, the window of each channel staged in LDS once,
+ * the trigger search as a scan over ballots of 64 frames), into a block the first read allocates: a handle that never reads it
+ * allocates and launches nothing new.  Cost on an MI355X, 4096 stereo streams: unmeasured (tools/scope_bench.py measures it against
+ * copying the windows to the host; INTEGRATION.md, "Oscilloscope").  Spectrum and meter batches are served; on waveform
+ * batches and on handles with W < 64, wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group
+ * reads it through wf_hip_multi_read. */
+#define WF_HIP_SCOPE_MAX_WINDOW 8192
+#define WF_HIP_SCOPE_COLUMNS 256
+typedef struct wf_hip_scope {
+    float lo[2][WF_HIP_SCOPE_COLUMNS]; /* captured channels 0 and 1: the smallest sample of each column */
+    float hi[2][WF_HIP_SCOPE_COLUMNS]; /* the largest */
+    uint32_t window;                   /* P */
+    uint32_t view;                     /* V */
+    uint32_t columns;                  /* K */
+    uint32_t start;     /* first frame of the view inside the window; the view ends P - start - V frames before the newest */
+    uint32_t triggered; /* 1: start is a trigger; 0: free run */
+    uint32_t period;    /* frames back to the trigger before, 0: none (sample_rate / period is a scope's "frequency" read-out) */
+    float frac;         /* see above */
+    uint32_t reserved;  /* 0 */
+} wf_hip_scope;         /* 4128 bytes */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ = range(17)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE = range(18)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -161,6 +161,14 @@ CQ_DTYPE = np.dtype([("db", np.float32, (2, CQ_BINS)), ("end_covered", np.uint32
                      ("max_window", np.uint32), ("reserved", np.uint32)])
 CQ_CENTRES_HZ = 440.0 * 2.0 ** ((np.arange(CQ_BINS) - 57) / 12.0)  # C0 16.35 Hz .. B9 15.8 kHz
 
+# struct wf_hip_scope (include/wf_hip.h): the oscilloscope, the smallest and largest sample per column and captured channel of a
+# triggered view of V = P / 2 frames inside the newest P = min(fft_size, SCOPE_MAX_WINDOW) frames of the ring
+SCOPE_MAX_WINDOW = 8192  # WF_HIP_SCOPE_MAX_WINDOW
+SCOPE_COLUMNS = 256  # WF_HIP_SCOPE_COLUMNS
+SCOPE_DTYPE = np.dtype([("lo", np.float32, (2, SCOPE_COLUMNS)), ("hi", np.float32, (2, SCOPE_COLUMNS)), ("window", np.uint32),
+                        ("view", np.uint32), ("columns", np.uint32), ("start", np.uint32), ("triggered", np.uint32),
+                        ("period", np.uint32), ("frac", np.float32), ("reserved", np.uint32)])
+
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
 MEASURES = {
@@ -171,6 +179,7 @@ MEASURES = {
     "bands": (OUT_BANDS, BANDS_DTYPE, True),
     "stereo": (OUT_STEREO, STEREO_DTYPE, False),
     "cq": (OUT_CQ, CQ_DTYPE, False),
+    "scope": (OUT_SCOPE, SCOPE_DTYPE, False),
 }
 
 
@@ -423,6 +432,13 @@ class SpectrumBatch:
         bin over the newest min(ceil(Q sr / f), ring_frames, CQ_MAX_WINDOW) frames of the ring as of the pushes issued so far,
         correlated on the device when read"""
         return _read_measure(self, "cq", first, count)
+
+    def scope(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_scope (SCOPE_DTYPE): the oscilloscope, lo / hi[channel][column] over a view of
+        fft_size / 2 frames that starts at the last rising 50 % crossing of the newest min(fft_size, SCOPE_MAX_WINDOW) frames of the
+        ring as of the pushes issued so far, with the trigger's position, sub-sample fraction and period; made on the device
+        when read"""
+        return _read_measure(self, "scope", first, count)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -795,6 +811,9 @@ class MultiBatch:
 
     def cq(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return _read_measure(self, "cq", first, count)
+
+    def scope(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        return _read_measure(self, "scope", first, count)
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return self._read(OUT_LAST_SILENT, first, count, (), np.uint8).astype(bool)

@@ -1650,6 +1650,7 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
     case WF_HIP_OUT_BANDS:
     case WF_HIP_OUT_STEREO:
     case WF_HIP_OUT_CQ:
+    case WF_HIP_OUT_SCOPE:
         break; // (never asked here: measure_source answers for them)
     }
     *why = "unknown output";

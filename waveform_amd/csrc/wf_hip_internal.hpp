@@ -145,7 +145,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read
-    static constexpr int N_MEASURES = 7;
+    static constexpr int N_MEASURES = 8;
     char *d_measure[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
@@ -173,6 +173,7 @@ struct wf_hip {
         uint32_t max_window = 0;                  // Lmax
         uint32_t end_covered = 0, first_resolved = 0;
     } cq;
+    bool scope_ready = false;                     // WF_HIP_OUT_SCOPE: its kernel's dynamic LDS has been asked for (launch_scope; wf_scope.hpp)
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO and _CQ.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ and _SCOPE.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is and how it is
 // launched; one reader (measure_read) does the rest.  The loudness producer alone also keeps state between reads: it follows
 // every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip) and is switched on by
@@ -22,6 +22,7 @@
 #include "wf_bands.hpp"
 #include "wf_stereo.hpp"
 #include "wf_cq.hpp"
+#include "wf_scope.hpp"
 
 namespace {
 
@@ -326,6 +327,39 @@ int launch_cq(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// the oscilloscope's window: the newest min(fft_size, WF_HIP_SCOPE_MAX_WINDOW) frames (<= ring_cap)
+uint32_t scope_window(const wf_hip *h) { return std::min<uint32_t>(h->N, WF_HIP_SCOPE_MAX_WINDOW); }
+
+// one workgroup per stream over its newest P frames of every captured channel, behind the pushes issued
+int launch_scope(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    if(!h->scope_ready) {
+        // (about 71 KB at the cap with two channels, the windows and the kernel's working set behind them: more than a workgroup
+        // gets without asking, and two workgroups to a CU)
+        WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)wf::scope_lds_bytes(1, WF_HIP_SCOPE_MAX_WINDOW)));
+        WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)wf::scope_lds_bytes(2, WF_HIP_SCOPE_MAX_WINDOW)));
+        h->scope_ready = true;
+    }
+    wf::ScopeArgs a{};
+    a.ring = h->d_ring;
+    a.wpos = h->d_wpos;
+    a.out = static_cast<wf_hip_scope *>(d_block) + first;
+    a.first = first;
+    a.ring_cap = h->ring_cap;
+    a.ring_stride = h->ring_stride;
+    a.P = scope_window(h);
+    a.V = a.P / 2;
+    a.K = std::min<uint32_t>(WF_HIP_SCOPE_COLUMNS, a.V);
+    const size_t lds = wf::scope_lds_bytes(h->cap_ch, a.P);
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::scope_read_kernel<2>, dim3(count), dim3(wf::WF_SCOPE_THREADS), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::scope_read_kernel<1>, dim3(count), dim3(wf::WF_SCOPE_THREADS), lds, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -355,6 +389,13 @@ const char *why_no_cq(const wf_hip *h)
     return h->wave ? "waveform batch: the constant-Q spectrum belongs to spectrum and meter batches" : nullptr;
 }
 
+const char *why_no_scope(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the oscilloscope belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->N < 64 ? "the oscilloscope needs a window of at least 64 frames" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -372,6 +413,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_BANDS, sizeof(wf_hip_bands), true, why_no_bands, launch_bands},
     {WF_HIP_OUT_STEREO, sizeof(wf_hip_stereo), false, why_no_stereo, launch_stereo},
     {WF_HIP_OUT_CQ, sizeof(wf_hip_cq), false, why_no_cq, launch_cq},
+    {WF_HIP_OUT_SCOPE, sizeof(wf_hip_scope), false, why_no_scope, launch_scope},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
