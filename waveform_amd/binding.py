@@ -240,6 +240,7 @@ def lib():
     L.wf_hip_multi_push_pcm.argtypes = [vp, u32, u32, C.POINTER(Pcm)]
     L.wf_hip_push_audio_muted.argtypes = [vp, u32, u32, fp, u32]
     L.wf_hip_enable_input_rms.argtypes = [vp, C.c_int]
+    L.wf_hip_push_rms_ragged_async.argtypes = [vp, u32, u32, vp, C.POINTER(u32), u32, u32]
     L.wf_hip_enable_loudness.argtypes = [vp, u32, u32]
     L.wf_hip_tick.argtypes = [vp, C.POINTER(TickParams)]
     L.wf_hip_set_hidden.argtypes = [vp, u32, u32, C.POINTER(C.c_uint8)]
@@ -379,9 +380,16 @@ class SpectrumBatch:
         assert s.ndim == 3 and s.shape[1] == self.capture_channels, s.shape
         self._ck(self.L.wf_hip_push_audio_muted(self.h, first, s.shape[0], s.ctypes.data_as(C.POINTER(C.c_float)), s.shape[2]))
 
-    def enable_input_rms(self):
-        """update_input_rms on the device from now on (cfg.normalize_volume)"""
-        self._ck(self.L.wf_hip_enable_input_rms(self.h, 0))
+    def enable_input_rms(self, feed: bool = False):
+        """update_input_rms on the device from now on (cfg.normalize_volume); feed: the squared peaks come from
+        push_rms_ragged_async instead of the pushed audio"""
+        self._ck(self.L.wf_hip_enable_input_rms(self.h, 1 if feed else 0))
+
+    def push_rms_ragged_async(self, pinned: "PinnedBuffer", frames, max_frames: int, slot: int, first: int = 0):
+        """wf_hip_push_rms_ragged_async: pinned [count, max_frames] float32 squared peaks, frames[count] per stream"""
+        f = np.ascontiguousarray(frames, dtype=np.uint32)
+        self._ck(self.L.wf_hip_push_rms_ragged_async(self.h, first, len(f), C.c_void_p(pinned.ptr), f.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      max_frames, slot))
 
     def input_rms(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return self._read(OUT_INPUT_RMS, first, count, (), np.float32)
