@@ -325,7 +325,55 @@ def _copy(ptr, n, dtype=np.float32):
     return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True)
 
 
-class SpectrumBatch:
+class _MeasureReaders:
+    """The readers of the measurement outputs (MEASURES), shared by SpectrumBatch and MultiBatch: each goes through the batch's own
+    _read."""
+
+    def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array with the fields of wf_hip_loudness (LOUDNESS_DTYPE)"""
+        return _read_measure(self, "loudness", first, count)
+
+    def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count, output_channels] structured array of wf_hip_peaks (PEAKS_DTYPE): the strongest peaks of each m_decibels row
+        as of the newest tick, found on the device when read"""
+        return _read_measure(self, "peaks", first, count)
+
+    def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_signal (SIGNAL_DTYPE): level, DC, clipping and stereo phase of each stream's
+        newest fft_size frames as of the pushes issued so far, measured on the device when read"""
+        return _read_measure(self, "signal", first, count)
+
+    def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_pitch (PITCH_DTYPE): fundamental frequency, clarity, lag and voiced flag of each
+        stream's newest min(fft_size, PITCH_MAX_WINDOW) frames as of the pushes issued so far, by YIN on the device when read"""
+        return _read_measure(self, "pitch", first, count)
+
+    def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count, output_channels] structured array of wf_hip_bands (BANDS_DTYPE): the third-octave band levels and the Z / A / C
+        weighted level of each m_decibels row as of the newest tick, summed on the device when read"""
+        return _read_measure(self, "bands", first, count)
+
+    def stereo(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_stereo (STEREO_DTYPE): correlation, coherence, phase and balance between captured
+        channels 0 and 1 in each third-octave band, over each stream's newest window (the largest power of two <=
+        min(fft_size, STEREO_MAX_WINDOW) frames) as of the pushes issued so far, transformed on the device when read"""
+        return _read_measure(self, "stereo", first, count)
+
+    def cq(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_cq (CQ_DTYPE): the constant-Q spectrum, db[channel][semitone] from C0 to B9, each
+        bin over the newest min(ceil(Q sr / f), ring_frames, CQ_MAX_WINDOW) frames of the ring as of the pushes issued so far,
+        correlated on the device when read"""
+        return _read_measure(self, "cq", first, count)
+
+    def scope(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_scope (SCOPE_DTYPE): the oscilloscope, lo / hi[channel][column] over a view of
+        fft_size / 2 frames that starts at the last rising 50 % crossing of the newest min(fft_size, SCOPE_MAX_WINDOW) frames of the
+        ring as of the pushes issued so far, with the trigger's position, sub-sample fraction and period; made on the device
+        when read"""
+        return _read_measure(self, "scope", first, count)
+
+
+class SpectrumBatch(_MeasureReaders):
     """A batch of `streams` independent sources sharing one configuration, resident on one GPU."""
 
     def __init__(self, cfg: Config, streams: int, device: int = 0, ring_frames: int = 0):
@@ -404,49 +452,6 @@ class SpectrumBatch:
         if int(self.L.wf_hip_output_bytes(self.h, OUT_LOUDNESS)) == 0:
             raise WfHipError(-1, "the loudness producer is not enabled (enable_loudness)")
         self._ck(self.L.wf_hip_enable_loudness(self.h, first, count))
-
-    def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count] structured array with the fields of wf_hip_loudness (LOUDNESS_DTYPE)"""
-        return _read_measure(self, "loudness", first, count)
-
-    def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count, output_channels] structured array of wf_hip_peaks (PEAKS_DTYPE): the strongest peaks of each m_decibels row
-        as of the newest tick, found on the device when read"""
-        return _read_measure(self, "peaks", first, count)
-
-    def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count] structured array of wf_hip_signal (SIGNAL_DTYPE): level, DC, clipping and stereo phase of each stream's
-        newest fft_size frames as of the pushes issued so far, measured on the device when read"""
-        return _read_measure(self, "signal", first, count)
-
-    def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count] structured array of wf_hip_pitch (PITCH_DTYPE): fundamental frequency, clarity, lag and voiced flag of each
-        stream's newest min(fft_size, PITCH_MAX_WINDOW) frames as of the pushes issued so far, by YIN on the device when read"""
-        return _read_measure(self, "pitch", first, count)
-
-    def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count, output_channels] structured array of wf_hip_bands (BANDS_DTYPE): the third-octave band levels and the Z / A / C
-        weighted level of each m_decibels row as of the newest tick, summed on the device when read"""
-        return _read_measure(self, "bands", first, count)
-
-    def stereo(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count] structured array of wf_hip_stereo (STEREO_DTYPE): correlation, coherence, phase and balance between captured
-        channels 0 and 1 in each third-octave band, over each stream's newest window (the largest power of two <=
-        min(fft_size, STEREO_MAX_WINDOW) frames) as of the pushes issued so far, transformed on the device when read"""
-        return _read_measure(self, "stereo", first, count)
-
-    def cq(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count] structured array of wf_hip_cq (CQ_DTYPE): the constant-Q spectrum, db[channel][semitone] from C0 to B9, each
-        bin over the newest min(ceil(Q sr / f), ring_frames, CQ_MAX_WINDOW) frames of the ring as of the pushes issued so far,
-        correlated on the device when read"""
-        return _read_measure(self, "cq", first, count)
-
-    def scope(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        """[count] structured array of wf_hip_scope (SCOPE_DTYPE): the oscilloscope, lo / hi[channel][column] over a view of
-        fft_size / 2 frames that starts at the last rising 50 % crossing of the newest min(fft_size, SCOPE_MAX_WINDOW) frames of the
-        ring as of the pushes issued so far, with the trigger's position, sub-sample fraction and period; made on the device
-        when read"""
-        return _read_measure(self, "scope", first, count)
 
     def push_audio_async(self, pinned: "PinnedBuffer", count: int, frames: int, slot: int, first: int = 0):
         """pipelined ingest from page-locked memory (see wf_hip_push_audio_async); does not wait"""
@@ -687,7 +692,7 @@ class PinnedBuffer:
             pass
 
 
-class MultiBatch:
+class MultiBatch(_MeasureReaders):
     """One batch of `streams` sources sharded contiguously over several devices of one node, single process, one host thread
     per device (wf_hip_multi_*); all stream indices are global.  allgather_bars() leaves every stream's bars on every device."""
 
@@ -798,30 +803,6 @@ class MultiBatch:
         if int(self.L.wf_hip_output_bytes(self.shards[0][0], OUT_LOUDNESS)) == 0:
             raise WfHipError(-1, "the loudness producer is not enabled (enable_loudness)")
         self._loudness_on_shards(first, count)
-
-    def loudness(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "loudness", first, count)
-
-    def peaks(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "peaks", first, count)
-
-    def signal(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "signal", first, count)
-
-    def pitch(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "pitch", first, count)
-
-    def bands(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "bands", first, count)
-
-    def stereo(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "stereo", first, count)
-
-    def cq(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "cq", first, count)
-
-    def scope(self, first: int = 0, count: int | None = None) -> np.ndarray:
-        return _read_measure(self, "scope", first, count)
 
     def last_silent(self, first: int = 0, count: int | None = None) -> np.ndarray:
         return self._read(OUT_LAST_SILENT, first, count, (), np.uint8).astype(bool)

@@ -23,28 +23,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_cq_sizes.hpp" // WF_CQ_THREADS, WF_CQ_WAVES and the sizes of the host's tables
+#include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
 
 namespace wf {
 
-constexpr uint32_t WF_CQ_THREADS = 1024;
-constexpr uint32_t WF_CQ_WAVES = WF_CQ_THREADS / 64;
-// the host's table per bin, in doubles: [0..3] the 64-frame steps of carrier and window phasor (re, im each), [4] 4 / L_b,
-// [5] L_b, [6..7] unused, then per lane l < 64 the values at n = l: carrier re, im, window phasor re, im
-constexpr uint32_t WF_CQ_BIN_HEAD = 8;
-constexpr uint32_t WF_CQ_BIN_DOUBLES = WF_CQ_BIN_HEAD + 64 * 4;
-// the schedule, in words: [0 .. WF_CQ_WAVES] where each wave's list starts in the order (the last: its end), then the order
-constexpr uint32_t WF_CQ_SCHED_WORDS = WF_CQ_WAVES + 1 + WF_HIP_CQ_BINS;
-
 struct CqArgs {
-    const float *ring;       // d_ring: [n_streams][CH][ring_stride]
-    const uint32_t *wpos;    // [n_streams] write positions
+    RingView rings;
     wf_hip_cq *out;          // [count] the entry of stream `first`
     const double *tab;       // [end_covered][WF_CQ_BIN_DOUBLES], 16-byte aligned
     const uint32_t *sched;   // [WF_CQ_SCHED_WORDS]: bins < end_covered, each once
     uint32_t first;          // first stream read
-    uint32_t ring_cap;       // power of two
-    uint32_t ring_stride;    // floats between consecutive rings
     uint32_t Lmax;           // frames staged: a multiple of 64, <= min(ring_cap, WF_HIP_CQ_MAX_WINDOW); every L_b <= Lmax
     uint32_t end_covered, first_resolved;
 };
@@ -63,14 +53,14 @@ __global__ __launch_bounds__(WF_CQ_THREADS) void cq_read_kernel(const CqArgs a)
     const uint32_t t = threadIdx.x, lane = t & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const uint32_t stream = a.first + blockIdx.x;
-    const uint32_t mask = a.ring_cap - 1u;
-    const uint32_t s = a.wpos[stream] - a.Lmax; // (uint32 wrap of the write position included: the mask takes it)
-    const float *r0 = a.ring + (size_t)stream * CH * a.ring_stride;
+    const uint32_t mask = a.rings.ring_cap - 1u;
+    const uint32_t s = window_start(a.rings, stream, a.Lmax);
+    const float *r0 = channel_ring(a.rings, stream, 0, CH);
     for(uint32_t i = t; i < a.Lmax; i += WF_CQ_THREADS) {
         const uint32_t at = (s + i) & mask;
         cq_x[i] = r0[at];
         if constexpr(CH == 2)
-            cq_x[a.Lmax + i] = r0[a.ring_stride + at];
+            cq_x[a.Lmax + i] = r0[a.rings.ring_stride + at];
     }
     // what no wave computes: the uncovered bins and the channel that was not captured read -INFINITY; the geometry
     uint32_t *words = reinterpret_cast<uint32_t *>(a.out + blockIdx.x);

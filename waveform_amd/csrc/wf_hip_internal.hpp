@@ -144,36 +144,36 @@ struct wf_hip {
     bool rms_feed = false;           // the squared peaks come from the host (wf_hip_push_rms_ragged_async), not from the pushed audio
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
-    // [n_streams][out_ch], allocated by the output's first read
+    // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
     static constexpr int N_MEASURES = 8;
     char *d_measure[N_MEASURES] = {};
+    bool measure_ready[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
         wf::LoudState *d_state = nullptr;         // [n_streams]
         wf::LoudHist *d_hist = nullptr;           // [n_streams][2]: integrated, range
         wf::LoudCoefs k{};
     } loud;
-    // what WF_HIP_OUT_BANDS derives from the configuration (setup_bands, at its first read; wf_bands.hpp)
+    // what WF_HIP_OUT_BANDS derives from the configuration (setup_bands, at its first read: wf::host::bands_tables; wf_bands.hpp)
     struct Bands {
         double *d_edges = nullptr;                // [WF_HIP_NUM_BANDS + 1] the band edges in bins
         double *d_weights = nullptr;              // [M][2] the squared A and C weights of every bin
         uint32_t covered = 0;                     // wf_hip_bands::covered of this batch
         double enbw = 1.0;                        // the window's equivalent noise bandwidth in bins
     } bands;
-    // what WF_HIP_OUT_STEREO derives from the configuration (setup_stereo, at its first read; wf_stereo.hpp)
+    // what WF_HIP_OUT_STEREO derives from the configuration (setup_stereo, at its first read: wf::host::stereo_tables; wf_stereo.hpp)
     struct Stereo {
         double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_NUM_BANDS + 1] band edges in bins of P
         uint32_t P = 0, log2p = 0;                // the window: a power of two
         uint32_t covered = 0;                     // wf_hip_stereo::covered of this batch
     } stereo;
-    // what WF_HIP_OUT_CQ derives from the configuration and the ring (setup_cq, at its first read; wf_cq.hpp)
+    // what WF_HIP_OUT_CQ derives from the configuration and the ring (setup_cq, at its first read: wf::host::cq_tables; wf_cq.hpp)
     struct Cq {
         double *d_tab = nullptr;                  // [end_covered][WF_CQ_BIN_DOUBLES] steps, 4 / L_b, L_b and the lanes' start values
         uint32_t *d_sched = nullptr;              // [WF_CQ_SCHED_WORDS] which wave takes which bins, in which order
         uint32_t max_window = 0;                  // Lmax
         uint32_t end_covered = 0, first_resolved = 0;
     } cq;
-    bool scope_ready = false;                     // WF_HIP_OUT_SCOPE: its kernel's dynamic LDS has been asked for (launch_scope; wf_scope.hpp)
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

@@ -1,12 +1,15 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
 // _BANDS, _STEREO, _CQ and _SCOPE.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
-// of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is and how it is
-// launched; one reader (measure_read) does the rest.  The loudness producer alone also keeps state between reads: it follows
-// every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip) and is switched on by
-// wf_hip_enable_loudness.  gfx950 only.
+// of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
+// sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
+// is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
+// keeps state between reads: it follows every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip)
+// and is switched on by wf_hip_enable_loudness.  gfx950 only.
 //
-// A new measurement output: its kernel in a header of its own, included here and nowhere else; a launch function, a refusal
-// function and a row of MEASURES below; a row of MEASURES in waveform_amd/binding.py.
+// A new measurement output: its kernel in a header of its own, included here and nowhere else, with a wf::RingView in its
+// arguments if it reads the rings; if it needs tables, a builder in wf_measure_tables.cpp that sees no handle and no HIP, and a
+// setup function here that calls it, keeps the scalars on the handle and uploads; a launch function, a refusal function and a
+// row of MEASURES below; a row of MEASURES and a reader on _MeasureReaders in waveform_amd/binding.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +18,7 @@
 
 #include "wf_hip_internal.hpp"
 #include "wf_dev_guard.hpp"
+#include "wf_measure_tables.hpp"
 #include "wf_loudness.hpp"
 #include "wf_peaks.hpp"
 #include "wf_signal.hpp"
@@ -36,6 +40,9 @@ int clear_loudness(wf_hip *h, uint32_t first, uint32_t count)
     WF_HIP_TRY(h, hipMemsetAsync(h->loud.d_hist + (size_t)first * 2, 0, (size_t)count * 2 * sizeof(wf::LoudHist), h->stream));
     return WF_HIP_OK;
 }
+
+// how the kernels that read the rings see them
+wf::RingView ring_view(const wf_hip *h) { return wf::RingView{h->d_ring, h->d_wpos, h->ring_cap, h->ring_stride}; }
 
 // One launch function per output: the entries of streams [first, first+count) into d_block, the output's whole block.
 // Loudness: the readings are made from the state when asked for, behind the pushes issued so far
@@ -65,12 +72,9 @@ int launch_peaks(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 int launch_signal(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
     wf::SignalArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
+    a.rings = ring_view(h);
     a.out = static_cast<wf_hip_signal *>(d_block) + first;
     a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
     a.W = h->N; // (<= ring_cap: wf_hip_create sizes the ring from it)
     if(h->cap_ch == 2)
         hipLaunchKernelGGL(wf::signal_read_kernel<2>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
@@ -83,13 +87,10 @@ int launch_signal(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 int launch_pitch(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
     wf::PitchArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
+    a.rings = ring_view(h);
     a.out = static_cast<wf_hip_pitch *>(d_block) + first;
     a.sample_rate = (double)h->cfg.sample_rate;
     a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
     a.P = std::min<uint32_t>(h->N, WF_HIP_PITCH_MAX_WINDOW); // (a multiple of 16 on spectrum and meter batches; <= ring_cap)
     if(h->cap_ch == 2)
         hipLaunchKernelGGL(wf::pitch_read_kernel<2>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
@@ -98,54 +99,22 @@ int launch_pitch(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
-// what the band levels derive from the configuration alone, made by their first read: the band edges in bins (IEC 61260-1,
-// base ten), which bands lie wholly inside the row, the window's equivalent noise bandwidth, the A and C weights of every bin
+// what the band levels derive from the configuration alone (wf::host::bands_tables)
 int setup_bands(wf_hip *h)
 {
     wf_hip::Bands &b = h->bands;
-    std::vector<double> edges(WF_HIP_NUM_BANDS + 1);
-    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
-        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)h->N / (double)h->cfg.sample_rate;
-    b.covered = 0;
-    for(int j = 0; j < WF_HIP_NUM_BANDS; ++j)
-        if(edges[j] >= 0.5 && edges[j + 1] <= (double)h->M - 0.5)
-            b.covered |= 1u << j;
-    b.enbw = 1.0;
-    if(!h->tab.window.empty()) {
-        double s1 = 0.0, s2 = 0.0;
-        for(const float w : h->tab.window) {
-            s1 += (double)w;
-            s2 += (double)w * (double)w;
-        }
-        b.enbw = (double)h->N * s2 / (s1 * s1);
-    }
-    // (R(f) / R(1000))^2 of IEC 61672-1's RA and RC at every bin's frequency
-    const auto ra = [](double f) {
-        const double f2 = f * f;
-        return 12194.0 * 12194.0 * f2 * f2 /
-               ((f2 + 20.6 * 20.6) * std::sqrt((f2 + 107.7 * 107.7) * (f2 + 737.9 * 737.9)) * (f2 + 12194.0 * 12194.0));
-    };
-    const auto rc = [](double f) {
-        const double f2 = f * f;
-        return 12194.0 * 12194.0 * f2 / ((f2 + 20.6 * 20.6) * (f2 + 12194.0 * 12194.0));
-    };
-    std::vector<double> weights((size_t)h->M * 2);
-    for(uint32_t k = 0; k < h->M; ++k) {
-        const double f = (double)k * (double)h->cfg.sample_rate / (double)h->N;
-        const double a = ra(f) / ra(1000.0), c = rc(f) / rc(1000.0);
-        weights[2 * (size_t)k] = a * a;
-        weights[2 * (size_t)k + 1] = c * c;
-    }
+    const BandsTables t = bands_tables(h->cfg.sample_rate, h->N, h->M, h->tab.window);
+    b.covered = t.covered;
+    b.enbw = t.enbw;
+    // (pageable memory: staged before the call returns, so `t` may go.  A retry after a failed second upload keeps the first)
     if(b.d_edges == nullptr)
-        WF_TRY_RC(upload(h, &b.d_edges, edges)); // (pageable memory: staged before the call returns)
-    return upload(h, &b.d_weights, weights);     // (last: d_weights says that all of this is in place)
+        WF_TRY_RC(upload(h, &b.d_edges, t.edges));
+    return upload(h, &b.d_weights, t.weights);
 }
 
 // one wavefront per m_decibels row, behind the ticks issued
 int launch_bands(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
-    if(h->bands.d_weights == nullptr)
-        WF_TRY_RC(setup_bands(h));
     wf::BandsArgs a{};
     a.rows = h->d_decibels + (size_t)first * h->out_ch * h->M;
     a.out = static_cast<wf_hip_bands *>(d_block) + (size_t)first * h->out_ch;
@@ -161,63 +130,31 @@ int launch_bands(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
-// the stereo image's window: the largest power of two <= min(fft_size, WF_HIP_STEREO_MAX_WINDOW) (<= ring_cap)
-uint32_t stereo_window(const wf_hip *h)
-{
-    uint32_t p = 1;
-    while(2 * p <= std::min<uint32_t>(h->N, WF_HIP_STEREO_MAX_WINDOW))
-        p *= 2;
-    return p;
-}
-
-// what the stereo image derives from the configuration alone, made by its first read: the periodic Hann window and the
-// twiddles e^(-j 2 pi m / P) in float64, the band edges in bins of P and which bands lie wholly inside the spectrum -- one
-// block [P window][P / 2 twiddles, re im][WF_HIP_NUM_BANDS + 1 edges]
+// what the stereo image derives from the configuration alone (wf::host::stereo_tables), in one block
 int setup_stereo(wf_hip *h)
 {
     wf_hip::Stereo &s = h->stereo;
-    const uint32_t P = stereo_window(h);
-    std::vector<double> tab((size_t)2 * P + WF_HIP_NUM_BANDS + 1);
-    for(uint32_t i = 0; i < P; ++i)
-        tab[i] = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)P);
-    for(uint32_t m = 0; m < P / 2; ++m) {
-        const double x = 2.0 * M_PI * (double)m / (double)P;
-        tab[P + 2 * (size_t)m] = std::cos(x);
-        tab[P + 2 * (size_t)m + 1] = -std::sin(x);
-    }
-    double *edges = tab.data() + 2 * (size_t)P;
-    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
-        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)P / (double)h->cfg.sample_rate;
-    s.covered = 0;
-    for(int j = 0; j < WF_HIP_NUM_BANDS; ++j)
-        if(edges[j] >= 0.5 && edges[j + 1] <= (double)(P / 2) - 0.5)
-            s.covered |= 1u << j;
-    s.P = P;
-    s.log2p = 0;
-    while((1u << s.log2p) < P)
-        ++s.log2p;
+    const StereoTables t = stereo_tables(h->cfg.sample_rate, h->N);
+    s.P = t.P;
+    s.log2p = t.log2p;
+    s.covered = t.covered;
     // (64 KB at P = 4096: the most a workgroup gets without asking; asked for all the same, so that the limit is stated here)
     WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::stereo_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)(WF_HIP_STEREO_MAX_WINDOW * sizeof(double2))));
-    return upload(h, &s.d_tab, tab); // (pageable memory: staged before the call returns; d_tab says that all of this is in place)
+    return upload(h, &s.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
 
 // one workgroup per stream over its newest P frames of both channels, behind the pushes issued
 int launch_stereo(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
-    if(h->stereo.d_tab == nullptr)
-        WF_TRY_RC(setup_stereo(h));
     const wf_hip::Stereo &s = h->stereo;
     wf::StereoArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
+    a.rings = ring_view(h);
     a.out = static_cast<wf_hip_stereo *>(d_block) + first;
     a.window = s.d_tab;
     a.tw = reinterpret_cast<const double2 *>(s.d_tab + s.P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
     a.edges = s.d_tab + 2 * (size_t)s.P;
     a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
     a.P = s.P;
     a.log2p = s.log2p;
     a.covered = s.covered;
@@ -225,97 +162,34 @@ int launch_stereo(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
-// what the constant-Q spectrum derives from the sample rate and the ring alone, made by its first read: L_b, which bins are
-// covered and resolved, and per covered bin the constants of wf_cq.hpp's table -- the carrier e^(-j 2 pi f_b n / sr) and the
-// window's phasor e^(j 2 pi n / L_b) at n = 0 .. 63 and their steps of 64 frames, from long double arguments so that the device's
-// recurrence starts from correctly rounded values -- and the order in which the kernel's waves take the bins
+// what the constant-Q spectrum derives from the sample rate and the ring alone (wf::host::cq_tables)
 int setup_cq(wf_hip *h)
 {
     wf_hip::Cq &q = h->cq;
-    const double sr = (double)h->cfg.sample_rate;
-    const double Q = 1.0 / (std::pow(2.0, 1.0 / 12.0) - 1.0);
-    const uint32_t Lmax = std::min<uint32_t>(h->ring_cap, WF_HIP_CQ_MAX_WINDOW); // (a power of two >= 128: a multiple of 64)
-    uint32_t L[WF_HIP_CQ_BINS];
-    q.max_window = Lmax;
-    q.end_covered = 0;
-    q.first_resolved = WF_HIP_CQ_BINS;
-    for(uint32_t b = 0; b < WF_HIP_CQ_BINS; ++b) {
-        const double f = 440.0 * std::pow(2.0, ((double)b - 57.0) / 12.0);
-        if(f * std::pow(2.0, 1.0 / 24.0) < sr / 2.0 && q.end_covered == b)
-            q.end_covered = b + 1;
-        const double full = std::ceil(Q * sr / f);
-        if(full <= (double)Lmax && q.first_resolved == WF_HIP_CQ_BINS)
-            q.first_resolved = b;
-        L[b] = full <= (double)Lmax ? (uint32_t)full : Lmax;
-    }
-    std::vector<double> tab((size_t)q.end_covered * wf::WF_CQ_BIN_DOUBLES, 0.0);
-    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
-    for(uint32_t b = 0; b < q.end_covered; ++b) {
-        const long double wc = -two_pi * 440.0L * std::pow(2.0L, ((long double)b - 57.0L) / 12.0L) / (long double)h->cfg.sample_rate;
-        const long double wh = two_pi / (long double)L[b];
-        double *t = tab.data() + (size_t)b * wf::WF_CQ_BIN_DOUBLES;
-        t[0] = (double)std::cos(64.0L * wc);
-        t[1] = (double)std::sin(64.0L * wc);
-        t[2] = (double)std::cos(64.0L * wh);
-        t[3] = (double)std::sin(64.0L * wh);
-        t[4] = 4.0 / (double)L[b];
-        t[5] = (double)L[b];
-        for(uint32_t l = 0; l < 64; ++l) {
-            double *v = t + wf::WF_CQ_BIN_HEAD + 4 * (size_t)l;
-            v[0] = (double)std::cos((long double)l * wc);
-            v[1] = (double)std::sin((long double)l * wc);
-            v[2] = (double)std::cos((long double)l * wh);
-            v[3] = (double)std::sin((long double)l * wh);
-        }
-    }
-    // the longest bin first, each to the wave with the least work so far (ties: the lower bin, the lower wave); a bin costs its
-    // iterations plus a constant for its table, its reduction and its logarithm
-    std::vector<uint32_t> lists[wf::WF_CQ_WAVES];
-    uint32_t load[wf::WF_CQ_WAVES] = {};
-    std::vector<uint32_t> by_cost(q.end_covered);
-    for(uint32_t b = 0; b < q.end_covered; ++b)
-        by_cost[b] = b;
-    std::stable_sort(by_cost.begin(), by_cost.end(), [&](uint32_t x, uint32_t y) { return L[x] > L[y]; });
-    for(const uint32_t b : by_cost) {
-        const uint32_t w = (uint32_t)(std::min_element(load, load + wf::WF_CQ_WAVES) - load);
-        lists[w].push_back(b);
-        load[w] += (L[b] + 63u) / 64u + 8u;
-    }
-    std::vector<uint32_t> sched;
-    sched.reserve(wf::WF_CQ_SCHED_WORDS);
-    uint32_t at = 0;
-    for(uint32_t w = 0; w < wf::WF_CQ_WAVES; ++w) {
-        sched.push_back(at);
-        at += (uint32_t)lists[w].size();
-    }
-    sched.push_back(at);
-    for(uint32_t w = 0; w < wf::WF_CQ_WAVES; ++w)
-        sched.insert(sched.end(), lists[w].begin(), lists[w].end());
-    sched.resize(wf::WF_CQ_SCHED_WORDS, 0u);
+    const CqTables t = cq_tables(h->cfg.sample_rate, h->ring_cap);
+    q.max_window = t.max_window;
+    q.end_covered = t.end_covered;
+    q.first_resolved = t.first_resolved;
     // (128 KB at the cap with two channels: more than a workgroup gets without asking)
     const int lds = (int)(WF_HIP_CQ_MAX_WINDOW * 2 * sizeof(float));
     WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::cq_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds / 2));
     WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::cq_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    // (pageable memory: staged before the call returns, so `t` may go.  A retry after a failed second upload keeps the first)
     if(q.d_sched == nullptr)
-        WF_TRY_RC(upload(h, &q.d_sched, sched)); // (pageable memory: staged before the call returns)
-    return upload(h, &q.d_tab, tab);             // (last: d_tab says that all of this is in place)
+        WF_TRY_RC(upload(h, &q.d_sched, t.sched));
+    return upload(h, &q.d_tab, t.tab);
 }
 
 // one workgroup per stream over the newest Lmax frames of its captured channels, behind the pushes issued
 int launch_cq(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
-    if(h->cq.d_tab == nullptr)
-        WF_TRY_RC(setup_cq(h));
     const wf_hip::Cq &q = h->cq;
     wf::CqArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
+    a.rings = ring_view(h);
     a.out = static_cast<wf_hip_cq *>(d_block) + first;
     a.tab = q.d_tab;
     a.sched = q.d_sched;
     a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
     a.Lmax = q.max_window;
     a.end_covered = q.end_covered;
     a.first_resolved = q.first_resolved;
@@ -330,25 +204,25 @@ int launch_cq(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 // the oscilloscope's window: the newest min(fft_size, WF_HIP_SCOPE_MAX_WINDOW) frames (<= ring_cap)
 uint32_t scope_window(const wf_hip *h) { return std::min<uint32_t>(h->N, WF_HIP_SCOPE_MAX_WINDOW); }
 
+// the oscilloscope has no tables: its kernels' dynamic LDS is all its first read asks for
+int setup_scope(wf_hip *h)
+{
+    // (about 71 KB at the cap with two channels, the windows and the kernel's working set behind them: more than a workgroup
+    // gets without asking, and two workgroups to a CU)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::scope_lds_bytes(1, WF_HIP_SCOPE_MAX_WINDOW)));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::scope_lds_bytes(2, WF_HIP_SCOPE_MAX_WINDOW)));
+    return WF_HIP_OK;
+}
+
 // one workgroup per stream over its newest P frames of every captured channel, behind the pushes issued
 int launch_scope(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
-    if(!h->scope_ready) {
-        // (about 71 KB at the cap with two channels, the windows and the kernel's working set behind them: more than a workgroup
-        // gets without asking, and two workgroups to a CU)
-        WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)wf::scope_lds_bytes(1, WF_HIP_SCOPE_MAX_WINDOW)));
-        WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)wf::scope_lds_bytes(2, WF_HIP_SCOPE_MAX_WINDOW)));
-        h->scope_ready = true;
-    }
     wf::ScopeArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
+    a.rings = ring_view(h);
     a.out = static_cast<wf_hip_scope *>(d_block) + first;
     a.first = first;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
     a.P = scope_window(h);
     a.V = a.P / 2;
     a.K = std::min<uint32_t>(WF_HIP_SCOPE_COLUMNS, a.V);
@@ -401,19 +275,20 @@ struct Measure {
     size_t entry_bytes;
     bool per_row; // one entry per m_decibels row (out_ch per stream), not one per stream
     const char *(*why_not)(const wf_hip *);
+    int (*setup)(wf_hip *); // what the output's first read makes before its first launch (nullptr: nothing)
     int (*launch)(wf_hip *, uint32_t first, uint32_t count, void *d_block);
 };
 
-// row i's block is wf_hip::d_measure[i]
+// row i's block is wf_hip::d_measure[i], and wf_hip::measure_ready[i] says that its setup has been done
 constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
-    {WF_HIP_OUT_LOUDNESS, sizeof(wf_hip_loudness), false, why_no_loudness, launch_loudness},
-    {WF_HIP_OUT_PEAKS, sizeof(wf_hip_peaks), true, why_no_peaks, launch_peaks},
-    {WF_HIP_OUT_SIGNAL, sizeof(wf_hip_signal), false, why_no_signal, launch_signal},
-    {WF_HIP_OUT_PITCH, sizeof(wf_hip_pitch), false, why_no_pitch, launch_pitch},
-    {WF_HIP_OUT_BANDS, sizeof(wf_hip_bands), true, why_no_bands, launch_bands},
-    {WF_HIP_OUT_STEREO, sizeof(wf_hip_stereo), false, why_no_stereo, launch_stereo},
-    {WF_HIP_OUT_CQ, sizeof(wf_hip_cq), false, why_no_cq, launch_cq},
-    {WF_HIP_OUT_SCOPE, sizeof(wf_hip_scope), false, why_no_scope, launch_scope},
+    {WF_HIP_OUT_LOUDNESS, sizeof(wf_hip_loudness), false, why_no_loudness, nullptr, launch_loudness},
+    {WF_HIP_OUT_PEAKS, sizeof(wf_hip_peaks), true, why_no_peaks, nullptr, launch_peaks},
+    {WF_HIP_OUT_SIGNAL, sizeof(wf_hip_signal), false, why_no_signal, nullptr, launch_signal},
+    {WF_HIP_OUT_PITCH, sizeof(wf_hip_pitch), false, why_no_pitch, nullptr, launch_pitch},
+    {WF_HIP_OUT_BANDS, sizeof(wf_hip_bands), true, why_no_bands, setup_bands, launch_bands},
+    {WF_HIP_OUT_STEREO, sizeof(wf_hip_stereo), false, why_no_stereo, setup_stereo, launch_stereo},
+    {WF_HIP_OUT_CQ, sizeof(wf_hip_cq), false, why_no_cq, setup_cq, launch_cq},
+    {WF_HIP_OUT_SCOPE, sizeof(wf_hip_scope), false, why_no_scope, setup_scope, launch_scope},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
@@ -443,13 +318,10 @@ void wf::host::measure_after_push(wf_hip *h, uint32_t first, uint32_t count, uin
     if(!loudness_on(h) || frames == 0)
         return;
     wf::LoudPushArgs a{};
-    a.ring = h->d_ring;
-    a.wpos = h->d_wpos;
+    a.rings = ring_view(h);
     a.frames_per_stream = d_frames;
     a.state = h->loud.d_state;
     a.hist = h->loud.d_hist;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
     a.first = first;
     a.frames = frames;
     a.k = h->loud.k;
@@ -482,6 +354,12 @@ int wf::host::measure_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32
     // (the first read may be of a slice: the block is for every stream)
     if(h->d_measure[i] == nullptr)
         WF_TRY_RC(dev_alloc(h, &h->d_measure[i], (size_t)h->n_streams * per));
+    // (the flag only behind a setup that succeeded: a first read that failed is set up again by the next)
+    if(!h->measure_ready[i]) {
+        if(m.setup)
+            WF_TRY_RC(m.setup(h));
+        h->measure_ready[i] = true;
+    }
     WF_TRY_RC(m.launch(h, first, count, h->d_measure[i]));
     WF_HIP_TRY(h, hipGetLastError());
     return read_back(h, h->d_measure[i] + (size_t)first * per, out, (size_t)count * per);

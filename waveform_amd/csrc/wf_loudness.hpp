@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "wf_hip.h"
 #include "wf_loudness_tables.hpp"
+#include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
 
 namespace wf {
@@ -45,12 +46,11 @@ struct LoudHist {
 };
 
 struct LoudPushArgs {
-    const float *ring;
-    const uint32_t *wpos;             // already advanced past the push
+    RingView rings;                   // (wpos: already advanced past the push)
     const uint32_t *frames_per_stream; // ragged pushes: [count] (capped at `frames`), else nullptr
     LoudState *state;
     LoudHist *hist;                   // [n_streams][2]: integrated, range
-    uint32_t ring_cap, ring_stride, first, frames;
+    uint32_t first, frames;
     LoudCoefs k;
 };
 
@@ -106,8 +106,8 @@ __global__ __launch_bounds__(64 * CapCh) void loudness_push_kernel(LoudPushArgs 
         return;
     LoudState &st = a.state[stream];
     LoudHist *hist = a.hist + (size_t)stream * 2;
-    const float *row = a.ring + ((size_t)stream * CapCh + ch) * a.ring_stride;
-    const uint32_t start = a.wpos[stream] - n, mask = a.ring_cap - 1u;
+    const float *row = channel_ring(a.rings, stream, ch, CapCh);
+    const uint32_t start = window_start(a.rings, stream, n), mask = a.rings.ring_cap - 1u; // (the frames the push appended)
     const uint32_t B = a.k.sub_frames, T = B < LOUD_TILE ? B : LOUD_TILE;
     float *x = xs[ch];
     if(lane < LOUD_HISTORY)

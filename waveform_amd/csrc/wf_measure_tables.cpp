@@ -1,0 +1,159 @@
+// wf_measure_tables.cpp -- the host tables of the measurement outputs (wf_measure_tables.hpp).  Plain C++.
+#include "wf_measure_tables.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace wf::host {
+
+namespace {
+// The sine of an argument whose cosine is taken beside it.  g++ turns such a pair into one sincos call, and the C library's
+// sincos does not give its sin in every last bit (2 pi 1955 / 4096 is one argument where it does not); the device's results
+// depend on every bit of these tables, so the two stay the two calls they are written as, whichever compiler builds this.
+template<class T> [[gnu::noinline]] T sin_alone(T x) { return std::sin(x); }
+} // namespace
+
+uint32_t third_octave_edges(uint32_t sample_rate, uint32_t n, uint32_t m, double edges[WF_HIP_NUM_BANDS + 1])
+{
+    for(int j = 0; j <= WF_HIP_NUM_BANDS; ++j)
+        edges[j] = 1000.0 * std::pow(10.0, (double)(2 * (j - 17) - 1) / 20.0) * (double)n / (double)sample_rate;
+    uint32_t covered = 0;
+    for(int j = 0; j < WF_HIP_NUM_BANDS; ++j)
+        if(edges[j] >= 0.5 && edges[j + 1] <= (double)m - 0.5)
+            covered |= 1u << j;
+    return covered;
+}
+
+BandsTables bands_tables(uint32_t sample_rate, uint32_t N, uint32_t M, const std::vector<float> &window)
+{
+    BandsTables b;
+    b.edges.resize(WF_HIP_NUM_BANDS + 1);
+    b.covered = third_octave_edges(sample_rate, N, M, b.edges.data());
+    b.enbw = 1.0;
+    if(!window.empty()) {
+        double s1 = 0.0, s2 = 0.0;
+        for(const float w : window) {
+            s1 += (double)w;
+            s2 += (double)w * (double)w;
+        }
+        b.enbw = (double)N * s2 / (s1 * s1);
+    }
+    // (R(f) / R(1000))^2 of IEC 61672-1's RA and RC at every bin's frequency
+    const auto ra = [](double f) {
+        const double f2 = f * f;
+        return 12194.0 * 12194.0 * f2 * f2 /
+               ((f2 + 20.6 * 20.6) * std::sqrt((f2 + 107.7 * 107.7) * (f2 + 737.9 * 737.9)) * (f2 + 12194.0 * 12194.0));
+    };
+    const auto rc = [](double f) {
+        const double f2 = f * f;
+        return 12194.0 * 12194.0 * f2 / ((f2 + 20.6 * 20.6) * (f2 + 12194.0 * 12194.0));
+    };
+    b.weights.resize((size_t)M * 2);
+    for(uint32_t k = 0; k < M; ++k) {
+        const double f = (double)k * (double)sample_rate / (double)N;
+        const double a = ra(f) / ra(1000.0), c = rc(f) / rc(1000.0);
+        b.weights[2 * (size_t)k] = a * a;
+        b.weights[2 * (size_t)k + 1] = c * c;
+    }
+    return b;
+}
+
+uint32_t stereo_window(uint32_t fft_size)
+{
+    uint32_t p = 1;
+    while(2 * p <= std::min<uint32_t>(fft_size, WF_HIP_STEREO_MAX_WINDOW))
+        p *= 2;
+    return p;
+}
+
+StereoTables stereo_tables(uint32_t sample_rate, uint32_t N)
+{
+    StereoTables s;
+    const uint32_t P = stereo_window(N);
+    std::vector<double> &tab = s.tab;
+    tab.resize((size_t)2 * P + WF_HIP_NUM_BANDS + 1);
+    for(uint32_t i = 0; i < P; ++i)
+        tab[i] = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)P);
+    for(uint32_t m = 0; m < P / 2; ++m) {
+        const double x = 2.0 * M_PI * (double)m / (double)P;
+        tab[P + 2 * (size_t)m] = std::cos(x);
+        tab[P + 2 * (size_t)m + 1] = -sin_alone(x);
+    }
+    s.covered = third_octave_edges(sample_rate, P, P / 2, tab.data() + 2 * (size_t)P);
+    s.P = P;
+    s.log2p = 0;
+    while((1u << s.log2p) < P)
+        ++s.log2p;
+    return s;
+}
+
+// (2^x is exp2 throughout: pow(2.0, x) is not the same function in every last bit -- 2^(11/12) is one value where the C
+// library's two differ -- and exp2 is what these tables have always been made with)
+CqTables cq_tables(uint32_t sample_rate, uint32_t ring_cap)
+{
+    CqTables q;
+    const double sr = (double)sample_rate;
+    const double Q = 1.0 / (std::exp2(1.0 / 12.0) - 1.0);
+    const uint32_t Lmax = std::min<uint32_t>(ring_cap, WF_HIP_CQ_MAX_WINDOW); // (a power of two >= 128: a multiple of 64)
+    uint32_t L[WF_HIP_CQ_BINS];
+    q.max_window = Lmax;
+    q.end_covered = 0;
+    q.first_resolved = WF_HIP_CQ_BINS;
+    for(uint32_t b = 0; b < WF_HIP_CQ_BINS; ++b) {
+        const double f = 440.0 * std::exp2(((double)b - 57.0) / 12.0);
+        if(f * std::exp2(1.0 / 24.0) < sr / 2.0 && q.end_covered == b)
+            q.end_covered = b + 1;
+        const double full = std::ceil(Q * sr / f);
+        if(full <= (double)Lmax && q.first_resolved == WF_HIP_CQ_BINS)
+            q.first_resolved = b;
+        L[b] = full <= (double)Lmax ? (uint32_t)full : Lmax;
+    }
+    std::vector<double> &tab = q.tab;
+    tab.assign((size_t)q.end_covered * WF_CQ_BIN_DOUBLES, 0.0);
+    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
+    for(uint32_t b = 0; b < q.end_covered; ++b) {
+        const long double wc = -two_pi * 440.0L * std::exp2(((long double)b - 57.0L) / 12.0L) / (long double)sample_rate;
+        const long double wh = two_pi / (long double)L[b];
+        double *t = tab.data() + (size_t)b * WF_CQ_BIN_DOUBLES;
+        t[0] = (double)std::cos(64.0L * wc);
+        t[1] = (double)sin_alone(64.0L * wc);
+        t[2] = (double)std::cos(64.0L * wh);
+        t[3] = (double)sin_alone(64.0L * wh);
+        t[4] = 4.0 / (double)L[b];
+        t[5] = (double)L[b];
+        for(uint32_t l = 0; l < 64; ++l) {
+            double *v = t + WF_CQ_BIN_HEAD + 4 * (size_t)l;
+            v[0] = (double)std::cos((long double)l * wc);
+            v[1] = (double)sin_alone((long double)l * wc);
+            v[2] = (double)std::cos((long double)l * wh);
+            v[3] = (double)sin_alone((long double)l * wh);
+        }
+    }
+    // the longest bin first, each to the wave with the least work so far (ties: the lower bin, the lower wave); a bin costs its
+    // iterations plus a constant for its table, its reduction and its logarithm
+    std::vector<uint32_t> lists[WF_CQ_WAVES];
+    uint32_t load[WF_CQ_WAVES] = {};
+    std::vector<uint32_t> by_cost(q.end_covered);
+    for(uint32_t b = 0; b < q.end_covered; ++b)
+        by_cost[b] = b;
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](uint32_t x, uint32_t y) { return L[x] > L[y]; });
+    for(const uint32_t b : by_cost) {
+        const uint32_t w = (uint32_t)(std::min_element(load, load + WF_CQ_WAVES) - load);
+        lists[w].push_back(b);
+        load[w] += (L[b] + 63u) / 64u + 8u;
+    }
+    std::vector<uint32_t> &sched = q.sched;
+    sched.reserve(WF_CQ_SCHED_WORDS);
+    uint32_t at = 0;
+    for(uint32_t w = 0; w < WF_CQ_WAVES; ++w) {
+        sched.push_back(at);
+        at += (uint32_t)lists[w].size();
+    }
+    sched.push_back(at);
+    for(uint32_t w = 0; w < WF_CQ_WAVES; ++w)
+        sched.insert(sched.end(), lists[w].begin(), lists[w].end());
+    sched.resize(WF_CQ_SCHED_WORDS, 0u);
+    return q;
+}
+
+} // namespace wf::host

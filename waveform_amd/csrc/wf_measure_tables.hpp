@@ -1,0 +1,51 @@
+// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO and _CQ derive from the configuration alone,
+// built on the host (wf_measure_tables.cpp) at the output's first read and uploaded by wf_hip_measure.hip.  Plain C++: no HIP
+// and no handle, so the arithmetic also compiles into a program of its own (tests/test_measure_tables_cpu.py).  The sizes of
+// the constant-Q tables are in wf_cq_sizes.hpp, shared with the kernel (wf_cq.hpp).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "wf_hip.h"
+#include "wf_cq_sizes.hpp"
+
+namespace wf::host {
+
+// the third-octave band edges (IEC 61260-1, base ten) in bins of an n-point transform; returns the mask of the bands that lie
+// wholly inside a spectrum of m bins (wf_hip_bands::covered, wf_hip_stereo::covered)
+uint32_t third_octave_edges(uint32_t sample_rate, uint32_t n, uint32_t m, double edges[WF_HIP_NUM_BANDS + 1]);
+
+// WF_HIP_OUT_BANDS (wf_bands.hpp) of an N-point transform with M bins per row
+struct BandsTables {
+    std::vector<double> edges;   // [WF_HIP_NUM_BANDS + 1] the band edges in bins
+    std::vector<double> weights; // [M][2] the squared A and C weights of every bin (IEC 61672-1)
+    uint32_t covered = 0;
+    double enbw = 1.0;           // the window's equivalent noise bandwidth in bins (an empty window: none, 1)
+};
+BandsTables bands_tables(uint32_t sample_rate, uint32_t N, uint32_t M, const std::vector<float> &window);
+
+// the stereo image's window: the largest power of two <= min(fft_size, WF_HIP_STEREO_MAX_WINDOW) (<= ring_cap)
+uint32_t stereo_window(uint32_t fft_size);
+
+// WF_HIP_OUT_STEREO (wf_stereo.hpp): the periodic Hann window and the twiddles e^(-j 2 pi m / P) in float64, the band edges in
+// bins of P and which bands lie wholly inside the spectrum
+struct StereoTables {
+    uint32_t P = 0, log2p = 0;
+    uint32_t covered = 0;
+    std::vector<double> tab; // one block [P window][P / 2 twiddles, re im][WF_HIP_NUM_BANDS + 1 edges]
+};
+StereoTables stereo_tables(uint32_t sample_rate, uint32_t N);
+
+// WF_HIP_OUT_CQ (wf_cq.hpp): L_b, which bins are covered and resolved, and per covered bin the constants of the table above --
+// the carrier e^(-j 2 pi f_b n / sr) and the window's phasor e^(j 2 pi n / L_b) at n = 0 .. 63 and their steps of 64 frames, from
+// long double arguments so that the device's recurrence starts from correctly rounded values -- and the order in which the
+// kernel's waves take the bins
+struct CqTables {
+    uint32_t max_window = 0; // Lmax = min(ring_cap, WF_HIP_CQ_MAX_WINDOW)
+    uint32_t end_covered = 0, first_resolved = 0;
+    std::vector<double> tab;     // [end_covered][WF_CQ_BIN_DOUBLES]
+    std::vector<uint32_t> sched; // [WF_CQ_SCHED_WORDS]
+};
+CqTables cq_tables(uint32_t sample_rate, uint32_t ring_cap);
+
+} // namespace wf::host

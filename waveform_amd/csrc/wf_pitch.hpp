@@ -25,17 +25,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_ring_view.hpp"
 
 namespace wf {
 
 struct PitchArgs {
-    const float *ring;       // d_ring: [n_streams][cap_ch][ring_stride]
-    const uint32_t *wpos;    // [n_streams] write positions
+    RingView rings;
     wf_hip_pitch *out;       // [count] the entry of stream `first`
     double sample_rate;
     uint32_t first;          // first stream read
-    uint32_t ring_cap;       // power of two
-    uint32_t ring_stride;    // floats between consecutive rings
     uint32_t P;              // window frames: a multiple of 16, 64 <= P <= min(ring_cap, WF_HIP_PITCH_MAX_WINDOW)
 };
 
@@ -122,10 +120,10 @@ __global__ __launch_bounds__(WF_PITCH_THREADS, WF_PITCH_OCC) void pitch_read_ker
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     const uint32_t stream = a.first + blockIdx.x;
     const uint32_t P = a.P, H = P / 2u;
-    const uint32_t mask = a.ring_cap - 1u;
-    const uint32_t s = a.wpos[stream] - P; // (uint32 wrap of the write position included: the capacity divides 2^32)
-    const float *r0 = a.ring + (size_t)stream * CH * a.ring_stride;
-    const float *r1 = CH == 2 ? r0 + a.ring_stride : r0;
+    const uint32_t mask = a.rings.ring_cap - 1u;
+    const uint32_t s = window_start(a.rings, stream, P);
+    const float *r0 = channel_ring(a.rings, stream, 0, CH);
+    const float *r1 = CH == 2 ? channel_ring(a.rings, stream, 1, CH) : r0;
 
     // ---- stage: x[i], i < P, and zeros up to the end of the image
     for(uint32_t i = t; i < WF_PITCH_X; i += WF_PITCH_THREADS) {

@@ -26,16 +26,14 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_ring_view.hpp"
 
 namespace wf {
 
 struct ScopeArgs {
-    const float *ring;       // d_ring: [n_streams][CH][ring_stride]
-    const uint32_t *wpos;    // [n_streams] write positions
+    RingView rings;          // (ring_cap a multiple of 4)
     wf_hip_scope *out;       // [count] the entry of stream `first` (16-byte aligned: a hipMalloc'ed block of 4128-byte entries)
     uint32_t first;          // first stream read
-    uint32_t ring_cap;       // power of two, a multiple of 4
-    uint32_t ring_stride;    // floats between consecutive rings (a multiple of 4)
     uint32_t P, V, K;        // window <= min(ring_cap, WF_HIP_SCOPE_MAX_WINDOW), view P / 2, columns min(WF_HIP_SCOPE_COLUMNS, V) >= 1
 };
 
@@ -127,16 +125,17 @@ __global__ __launch_bounds__(WF_SCOPE_THREADS, WF_SCOPE_OCC) void scope_read_ker
     const uint32_t P = a.P, V = a.V, K = a.K;
     const uint32_t S = scope_lds_stride(P);
     ScopeWork &w = *reinterpret_cast<ScopeWork *>(scope_x + (size_t)CH * S);
-    const uint32_t s = (a.wpos[stream] - P) & (a.ring_cap - 1u); // (uint32 wrap of the write position included)
+    const uint32_t ring_cap = a.rings.ring_cap;
+    const uint32_t s = window_start(a.rings, stream, P) & (ring_cap - 1u);
     const uint32_t o = s & 3u;
-    const float *r0 = a.ring + (size_t)stream * CH * a.ring_stride;
-    const float *r1 = CH == 2 ? r0 + a.ring_stride : r0;
+    const float *r0 = channel_ring(a.rings, stream, 0, CH);
+    const float *r1 = CH == 2 ? channel_ring(a.rings, stream, 1, CH) : r0;
     const float *x0 = scope_x + o, *x1 = x0 + S; // x_c[i]
 
     const uint32_t end = s + P; // <= 2 ring_cap
-    scope_stage<CH>(scope_x, S, r0, r1, s, end < a.ring_cap ? end : a.ring_cap, o - s);
-    if(end > a.ring_cap)
-        scope_stage<CH>(scope_x, S, r0, r1, 0u, end - a.ring_cap, o + (a.ring_cap - s));
+    scope_stage<CH>(scope_x, S, r0, r1, s, end < ring_cap ? end : ring_cap, o - s);
+    if(end > ring_cap)
+        scope_stage<CH>(scope_x, S, r0, r1, 0u, end - ring_cap, o + (ring_cap - s));
     for(uint32_t i = t; i < sizeof(wf_hip_scope) / 4u; i += WF_SCOPE_THREADS)
         w.image[i] = 0u;
     __syncthreads();

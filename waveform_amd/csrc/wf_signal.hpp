@@ -17,17 +17,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
 
 namespace wf {
 
 struct SignalArgs {
-    const float *ring;       // d_ring: [n_streams][cap_ch][ring_stride]
-    const uint32_t *wpos;    // [n_streams] write positions
+    RingView rings;
     wf_hip_signal *out;      // [count] the entry of stream `first`
     uint32_t first;          // first stream read
-    uint32_t ring_cap;       // power of two
-    uint32_t ring_stride;    // floats between consecutive rings (a multiple of 4)
     uint32_t W;              // window frames, <= ring_cap
 };
 
@@ -122,10 +120,10 @@ __global__ __launch_bounds__(WF_SIGNAL_THREADS, WF_SIGNAL_OCC) void signal_read_
     __shared__ uint32_t lds_c[WF_SIGNAL_WAVES][CH];
 
     const uint32_t stream = a.first + blockIdx.x;
-    const uint32_t mask = a.ring_cap - 1u;
-    const uint32_t s = (a.wpos[stream] - a.W) & mask; // (uint32 wrap of the write position included)
-    const float *r0 = a.ring + (size_t)stream * CH * a.ring_stride;
-    const float *r1 = CH == 2 ? r0 + a.ring_stride : r0;
+    const uint32_t ring_cap = a.rings.ring_cap;
+    const uint32_t s = window_start(a.rings, stream, a.W) & (ring_cap - 1u);
+    const float *r0 = channel_ring(a.rings, stream, 0, CH);
+    const float *r1 = CH == 2 ? channel_ring(a.rings, stream, 1, CH) : r0;
 
     SignalAcc<CH> acc;
 #pragma unroll
@@ -137,9 +135,9 @@ __global__ __launch_bounds__(WF_SIGNAL_THREADS, WF_SIGNAL_OCC) void signal_read_
     }
     acc.slr = acc.sum2 = acc.dif2 = 0.0;
     const uint32_t end = s + a.W; // <= 2 ring_cap
-    signal_run<CH>(acc, r0, r1, s, end < a.ring_cap ? end : a.ring_cap);
-    if(end > a.ring_cap)
-        signal_run<CH>(acc, r0, r1, 0u, end - a.ring_cap);
+    signal_run<CH>(acc, r0, r1, s, end < ring_cap ? end : ring_cap);
+    if(end > ring_cap)
+        signal_run<CH>(acc, r0, r1, 0u, end - ring_cap);
 
     double d[ND];
 #pragma unroll

@@ -26,20 +26,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
 
 namespace wf {
 
 struct StereoArgs {
-    const float *ring;       // d_ring: [n_streams][2][ring_stride]
-    const uint32_t *wpos;    // [n_streams] write positions
+    RingView rings;          // (two captured channels)
     wf_hip_stereo *out;      // [count] the entry of stream `first`
     const double *window;    // [P] periodic Hann
     const double2 *tw;       // [P / 2] e^(-j 2 pi m / P)
     const double *edges;     // [WF_HIP_NUM_BANDS + 1] band edges in bins of P, ascending
     uint32_t first;          // first stream read
-    uint32_t ring_cap;       // power of two
-    uint32_t ring_stride;    // floats between consecutive rings
     uint32_t P;              // window frames: a power of two, 64 <= P <= min(ring_cap, WF_HIP_STEREO_MAX_WINDOW)
     uint32_t log2p;
     uint32_t covered;        // wf_hip_stereo::covered, the same for every stream
@@ -79,10 +77,10 @@ __global__ __launch_bounds__(WF_STEREO_THREADS) void stereo_read_kernel(const St
     const uint32_t t = threadIdx.x;
     const uint32_t stream = a.first + blockIdx.x;
     const uint32_t P = a.P, cb = a.log2p - 4u;
-    const uint32_t mask = a.ring_cap - 1u;
-    const uint32_t s = a.wpos[stream] - P; // (uint32 wrap of the write position included)
-    const float *r0 = a.ring + (size_t)stream * 2u * a.ring_stride;
-    const float *r1 = r0 + a.ring_stride;
+    const uint32_t mask = a.rings.ring_cap - 1u;
+    const uint32_t s = window_start(a.rings, stream, P);
+    const float *r0 = channel_ring(a.rings, stream, 0, 2);
+    const float *r1 = channel_ring(a.rings, stream, 1, 2);
 
     // load: the 16-point transform of frames c' + m P/16 in registers
     const uint32_t n16 = P >> 4;
