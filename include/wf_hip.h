@@ -251,7 +251,9 @@ int wf_hip_tick(wf_hip *h, const wf_hip_tick_params *p);
 #define WF_HIP_HIDDEN_TIMEOUT 2  /* m_tick_ts - m_capture_ts > CAPTURE_TIMEOUT */
 #define WF_HIP_PAUSED 3          /* the source was not ticked in this video frame (OBS ticks only active sources; a waveform source whose buffers
                                     hold no more than the A/V-sync reserve returns before it touches anything, src/source_generic.cpp:293-295) --
-                                    the next wf_hip_tick leaves the stream exactly as it is; cleared by any other value */
+                                    the next wf_hip_tick leaves the stream exactly as it is, the device RMS producer's m_input_rms and
+                                    its sync_rms_buffer position included (update_input_rms belongs to the tick); cleared by any other
+                                    value */
 #define WF_HIP_STARVED 4         /* spectrum batches whose host keeps the sources' own buffers (the plugin binding): the source holds fewer
                                     samples than window + A/V-sync delay (src/source_generic.cpp:55-61: every channel is skipped) -- the
                                     next wf_hip_tick processes no channel of the stream but still runs the reference's end-of-tick pass

@@ -5,6 +5,7 @@ the plugin (audio packets in, video ticks, show/hide).  The same script can be p
   * RefBackend     the reference itself (oracle/_ref/libwfref.so)     -> tools/make_golden.py
   * OracleBackend  the CPU restatement (oracle/libwforacle.so)         -> CPU tests
   * HipBackend     libwaveform_hip.so through its C ABI               -> GPU tests
+  * HipBatch / OracleBatch  S scripts on the S streams of ONE batch (play_batch, draw_mixed) -> tests/test_gpu_mixed_states.py
 and every backend records the same observables after each tick:
   db    float32 [display_channels, fft_size/2]   m_decibels
   bars  float32 [display_channels, num_bars]     m_interp_bufs after render_bars / render_curve (if cfg.bars or cfg.curve;
@@ -293,14 +294,16 @@ def config_with(cfg, changes: dict):
 
 
 class _Feeder:
-    """turns ('noise', n) etc. into sample blocks; the stream index in the hash is always 0"""
+    """turns ('noise', n) etc. into sample blocks; `stream` is the stream index in the hash (0 unless the scenario carries a
+    noise_id: the streams of a mixed batch each hear their own noise)"""
 
-    def __init__(self, channels):
+    def __init__(self, channels, stream=0):
         self.channels = channels
+        self.stream = int(stream)
         self.pos = 0
 
     def block(self, kind, frames, amp=1.0):
-        a = synth.block(SEED, 0, 1, 2, self.pos, frames)[0]
+        a = synth.block(SEED, self.stream, 1, 2, self.pos, frames)[0]
         self.pos += frames
         if kind == "silence" or kind == "mute":
             a[:] = 0.0
@@ -338,34 +341,85 @@ def no_vertex_buffer(cfg) -> bool:
     return steps == 0
 
 
+def _apply(backend, feeder, step):
+    """every step but the tick"""
+    op = step[0]
+    if op in ("noise", "silence", "noise_ch0_only", "noise_ch1_only"):
+        backend.push(feeder.block(op, step[1]), muted=False)
+    elif op == "noise_amp":
+        backend.push(feeder.block(op, step[1], step[2]), muted=False)
+    elif op == "timeout":
+        backend.timeout()  # no packet for more than CAPTURE_TIMEOUT (500 ms); the next packet ends it
+    elif op in ("mute", "mute_noise"):
+        backend.push(feeder.block(op, step[1]), muted=True)
+    elif op == "hide":
+        backend.set_hidden(True)
+    elif op == "show":
+        backend.set_hidden(False)
+    elif op == "update":
+        backend.update(step[1])  # WAVSource::update() mid-stream with these wf_config fields changed (an empty dict: the same settings)
+    else:
+        raise ValueError(op)
+
+
+def tick_seconds(step) -> float:
+    return step[1] if len(step) > 1 else 1.0 / 60.0
+
+
+def tick_paused(step) -> bool:
+    """("tick", seconds, "paused"): the source is not ticked in this video frame (OBS ticks only active sources).  Nothing of
+    it moves; its record of that frame is its state as it stands."""
+    return len(step) > 2 and step[2] == "paused"
+
+
 def play(backend, scenario: dict):
     """returns list of per-tick records: dict(db=..., bars=... | None, silent=bool)"""
-    feeder = _Feeder(backend.capture_channels)
+    feeder = _Feeder(backend.capture_channels, scenario.get("noise_id", 0))
     records = []
     if scenario.get("sync_ms"):
         backend.set_sync_ms(int(scenario["sync_ms"]))
     for step in scenario["steps"]:
-        op = step[0]
-        if op in ("noise", "silence", "noise_ch0_only", "noise_ch1_only"):
-            backend.push(feeder.block(op, step[1]), muted=False)
-        elif op == "noise_amp":
-            backend.push(feeder.block(op, step[1], step[2]), muted=False)
-        elif op == "timeout":
-            backend.timeout()  # no packet for more than CAPTURE_TIMEOUT (500 ms); the next packet ends it
-        elif op in ("mute", "mute_noise"):
-            backend.push(feeder.block(op, step[1]), muted=True)
-        elif op == "tick":
-            seconds = step[1] if len(step) > 1 else 1.0 / 60.0
-            backend.tick(seconds)
+        if step[0] == "tick":
+            if not tick_paused(step):
+                backend.tick(tick_seconds(step))
             records.append(backend.observe())
-        elif op == "hide":
-            backend.set_hidden(True)
-        elif op == "show":
-            backend.set_hidden(False)
-        elif op == "update":
-            backend.update(step[1])  # WAVSource::update() mid-stream with these wf_config fields changed (an empty dict: the same settings)
         else:
-            raise ValueError(op)
+            _apply(backend, feeder, step)
+    return records
+
+
+def play_batch(batch, scenarios):
+    """S scripts on the S streams of one batch, in lock step: for tick k every stream runs its steps up to its k-th tick, then
+    the batch ticks once and every stream's view records its slice.  A tick belongs to the batch, so the scripts carry the
+    same number of ticks and the same seconds per tick; a stream whose k-th tick is marked "paused" sits that frame out.
+    Returns one list of per-tick records per stream, as play() would for each script alone."""
+    views = batch.views
+    assert len(views) == len(scenarios), (len(views), len(scenarios))
+    ticks = [[st for st in sc["steps"] if st[0] == "tick"] for sc in scenarios]
+    assert all(len(t) == len(ticks[0]) for t in ticks), "the scripts of a batch carry the same number of ticks"
+    for k in range(len(ticks[0])):
+        assert all(tick_seconds(t[k]) == tick_seconds(ticks[0][k]) for t in ticks), f"tick {k}: one tick, one frame time"
+    feeders = [_Feeder(v.capture_channels, sc.get("noise_id", 0)) for v, sc in zip(views, scenarios)]
+    for v, sc in zip(views, scenarios):
+        if sc.get("sync_ms"):
+            v.set_sync_ms(int(sc["sync_ms"]))
+    at = [0] * len(views)
+    records = [[] for _ in views]
+    for k in range(len(ticks[0])):
+        for i, (v, sc) in enumerate(zip(views, scenarios)):
+            steps = sc["steps"]
+            while steps[at[i]][0] != "tick":
+                _apply(v, feeders[i], steps[at[i]])
+                at[i] += 1
+            if tick_paused(steps[at[i]]):
+                v.pause()
+            else:
+                v.tick(tick_seconds(steps[at[i]]))
+            at[i] += 1
+        batch.tick(tick_seconds(ticks[0][k]))
+        for i, v in enumerate(views):
+            records[i].append(v.observe())
+    assert all(at[i] == len(sc["steps"]) for i, sc in enumerate(scenarios)), "steps behind the last tick would never be seen"
     return records
 
 
@@ -651,3 +705,339 @@ class HipBackend:
         if os.environ.get("WF_HIP_CANARY"):  # the guard bytes behind every device block are compared in wf_hip_sync: a kernel that wrote past a buffer fails the case here
             self.batch.sync()
         self.batch.close()
+
+
+# ---- one batch whose streams are in different states ------------------------------------------------------------------------
+# The backends above play ONE script (HipBackend: identical copies of it).  The two below own S streams that each play a script
+# of their own through play_batch(): views with the backend interface (push, tick, timeout, set_hidden, set_sync_ms, observe,
+# capture_channels) plus pause() for a frame the source is not ticked in.
+WF_HIP_SHOWN, WF_HIP_HIDDEN, WF_HIP_HIDDEN_TIMEOUT, WF_HIP_PAUSED = 0, 1, 2, 3  # include/wf_hip.h
+WF_HIP_TICK_NO_DECIBELS = 1
+
+
+def split_reserves(reserves):
+    """the A/V-sync reserves of the streams of a batch (frames) as a host hands them over: the smallest as the tick's common
+    delay_frames, the remainders per stream (wf_hip_set_stream_delay) -- the kernel adds the two"""
+    common = min(reserves)
+    return common, [r - common for r in reserves]
+
+
+class _StreamClock:
+    """the clock model of RefBackend / OracleBackend / HipBackend for one stream of a batch: packets end "now", ticks happen
+    "now", the A/V-sync reserve follows from the stream's own m_audio_ts and sync offset"""
+
+    def __init__(self, sample_rate):
+        self.sr = int(sample_rate)
+        self.now = 1_000_000_000
+        self.audio_ts = 0
+        self.sync_ns = 0
+
+    def set_sync_ms(self, ms):
+        self.sync_ns = ms * 1_000_000
+
+    def packet(self, frames):
+        self.now += frames * 1_000_000_000 // self.sr + 1
+        self.audio_ts = self.now
+
+    def reserve(self):
+        return sync_reserve_frames(self.audio_ts, self.sync_ns, self.now, self.sr)
+
+
+class HipStreamView:
+    """stream `index` of a HipBatch through the per-stream forms of the C ABI"""
+
+    def __init__(self, batch, index):
+        self.b = batch
+        self.i = index
+        self.capture_channels = batch.batch.capture_channels
+        self.clock = _StreamClock(batch.cfg.sample_rate)
+        self.hidden = self.timed_out = False
+        self.ticked = True
+        self.sent_state, self.sent_delay, self.sent_ts = WF_HIP_SHOWN, 0, None
+
+    def set_sync_ms(self, ms):
+        self.clock.set_sync_ms(ms)
+
+    def push(self, audio, muted):
+        self.clock.packet(audio.shape[1])
+        self.timed_out = False  # a packet ends a capture timeout
+        hb = self.b.batch
+        if muted and self.b.auto_rms:
+            hb.push_audio_muted(audio[None], first=self.i)  # zeros into the rings, the samples into the RMS producer
+        elif muted:
+            hb.push_silence(audio.shape[1], first=self.i, count=1)
+        else:
+            hb.push_audio(audio[None], first=self.i)
+
+    def tick(self, seconds):
+        self.ticked = True
+
+    def pause(self):
+        self.ticked = False
+
+    def timeout(self):
+        self.clock.now += 600_000_000
+        self.timed_out = True
+
+    def set_hidden(self, hidden):
+        self.hidden = hidden
+
+    def state(self):
+        if not self.ticked:
+            return WF_HIP_PAUSED
+        return WF_HIP_HIDDEN_TIMEOUT if self.timed_out else WF_HIP_HIDDEN if self.hidden else WF_HIP_SHOWN
+
+    def update(self, changes):
+        raise NotImplementedError(f"{type(self).__name__}: no mid-stream update()")
+
+    def observe(self):
+        return self.b.record(self.i)
+
+
+class HipBatch:
+    """One SpectrumBatch of `streams` streams, each driven by its own script (play_batch).  rms: None -- no volume
+    normalisation, or the device producer (wf_hip_enable_input_rms) where cfg.normalize_volume; a sequence -- m_input_rms of
+    every stream, fixed (wf_hip_set_input_rms).  flags: WF_HIP_TICK_* of every tick."""
+
+    def __init__(self, cfg, streams, rms=None, flags=0):
+        import waveform_amd as wf
+        self.cfg = cfg
+        self.flags = int(flags)
+        self.batch = wf.SpectrumBatch(cfg, streams)
+        self.streams = streams
+        self.disp = self.batch.display_channels
+        self.auto_rms = bool(cfg.normalize_volume) and not cfg.meter and rms is None
+        if self.auto_rms:
+            self.batch.enable_input_rms()
+        elif rms is not None:
+            assert len(rms) == streams
+            for i, r in enumerate(rms):
+                self.batch.set_input_rms(np.array([r], np.float32), first=i)
+        self.views = [HipStreamView(self, i) for i in range(streams)]
+        self.out = None
+
+    def tick(self, seconds):
+        hb = self.batch
+        for v in self.views:  # show / hide / capture timeout / not ticked in this frame, stream by stream
+            st = v.state()
+            if st != v.sent_state:
+                hb.set_hidden(np.array([st], np.uint8), first=v.i)
+                v.sent_state = st
+        common, rest = split_reserves([v.clock.reserve() for v in self.views])
+        for v, d in zip(self.views, rest):
+            if d != v.sent_delay:
+                hb.set_stream_delay(np.array([d], np.uint32), first=v.i)
+                v.sent_delay = d
+            if self.cfg.waveform and v.clock.audio_ts != v.sent_ts:
+                hb.set_stream_audio_ts(np.array([v.clock.audio_ts], np.uint64), first=v.i)
+                v.sent_ts = v.clock.audio_ts
+        hb.tick(seconds=seconds, delay_frames=common, flags=self.flags)
+        # every output of the whole batch once; the views hand out slices
+        o = dict(silent=hb.last_silent())
+        if self.cfg.meter:
+            o.update(meter=hb.meter(), bars=hb.bars())
+        else:
+            o["db"] = hb.decibels()
+            if self.cfg.waveform:
+                o["wts"] = hb.waveform_ts()
+            elif (self.cfg.bars or self.cfg.curve) and hb.num_bars > 0 and not no_vertex_buffer(self.cfg):
+                o["bars"] = hb.bars()
+                if self.cfg.vertices:
+                    o.update(verts=hb.vertices(), counts=hb.vertex_counts())
+            if self.auto_rms:
+                o["rms"] = hb.input_rms()
+        self.out = o
+
+    def record(self, i):
+        o = self.out
+        if self.cfg.meter:
+            return dict(db=o["meter"][i][None], bars=o["bars"][i], silent=bool(o["silent"][i]))
+        rec = dict(db=o["db"][i][: self.disp], bars=o["bars"][i] if "bars" in o else None, silent=bool(o["silent"][i]))
+        if "wts" in o:
+            rec["wts"] = int(o["wts"][i])
+        if "verts" in o:
+            rec["verts"] = [o["verts"][i][c, : int(o["counts"][i][c])] for c in range(o["verts"].shape[1])]
+        if "rms" in o:
+            rec["rms"] = o["rms"][i]
+        return rec
+
+    def kernel_name(self):
+        return self.batch.kernel_name()
+
+    def close(self):
+        import os
+        if os.environ.get("WF_HIP_CANARY"):
+            self.batch.sync()
+        self.batch.close()
+
+
+class _OracleStream(OracleBackend):
+    """an OracleBackend as one stream of an OracleBatch: its tick waits for the batch's, and the A/V-sync reserve of that tick
+    is what the batch hands over (common part + this stream's remainder) instead of what the backend would compute"""
+
+    ticked = True
+    delay = None
+
+    def _sync(self):
+        if self.delay is None:
+            return super()._sync()
+        if self.cfg.waveform:
+            self.src.set_time(self.audio_ts, self.delay)
+        else:
+            self.src.set_sync_delay(self.delay)
+
+    def tick(self, seconds):
+        self.ticked = True
+
+    def pause(self):
+        self.ticked = False
+
+    def batch_tick(self, seconds, delay):
+        self.delay = delay
+        try:
+            super().tick(seconds)
+        finally:
+            self.delay = None
+
+
+class OracleBatch:
+    """S restated sources behind the interface of HipBatch: what play_batch() does to a batch, with no device.  The reserve
+    goes through split_reserves() like the device's; a stream that is not ticked in a frame is simply not ticked."""
+
+    def __init__(self, cfg, streams, rms=None, exact=False):
+        self.cfg = cfg
+        self.views = [_OracleStream(cfg, input_rms=None if rms is None else float(rms[i]), exact=exact) for i in range(streams)]
+
+    def tick(self, seconds):
+        common, rest = split_reserves([sync_reserve_frames(v.audio_ts, v.sync_ns, v.now, int(self.cfg.sample_rate)) for v in self.views])
+        for v, d in zip(self.views, rest):
+            if v.ticked:
+                v.batch_tick(seconds, common + d)
+
+
+# ---- scripts for such a batch ----------------------------------------------------------------------------------------------
+MIXED_TICKS = 28
+RAGGED_HOPS = (800, 441, 1024, 37, 1600)    # the fuzz's packet sizes
+ALIGNED_HOPS = (800, 440, 1024, 36, 1600)   # multiples of 4 frames: with reserves of 240 / 960 frames the ALIGNED instantiations run
+# role tables by (captured channels, streams): every entry a tuple of traits laid over a stream of noise packets; "twin" is the
+# same script with the same noise as entry 0, half a batch away
+MIXED_ROLES = {
+    (1, 7): [("latches",), ("live",), ("hide_timeout",), ("twin",), ("muted",), ("paused",), ("late",)],
+    (2, 5): [("latches",), ("one_channel",), ("twin",), ("hide_timeout", "late"), ("live", "muted", "paused")],
+    (1, 4): [("latches",), ("live", "late"), ("twin",), ("hide_timeout", "muted", "paused")],
+    (2, 4): [("latches",), ("one_channel", "late"), ("twin",), ("hide_timeout", "muted", "paused")],
+    (1, 3): [("latches",), ("hide_timeout", "late", "paused"), ("twin",)],
+    (2, 3): [("latches",), ("hide_timeout", "late", "paused"), ("twin",)],
+    (2, 6): [("latches",), ("one_channel",), ("hide_timeout",), ("twin",), ("muted", "late"), ("paused",)],
+}
+
+
+def _mixed_script(traits, fill, hop, seconds, window):
+    """one stream's steps: noise packets of `hop` frames before every tick (the first one preceded by `fill` frames, so that the
+    window is full of noise from the start), with the traits' events laid over them.  Tick windows are fixed so that a batch has
+    frames in which one stream is latched silent while others are hidden, fed on one channel only, and live."""
+    T = len(seconds)
+    pre = [[("noise", hop)] for _ in range(T)]
+    paused = [False] * T
+    long = max(window + 400, hop)  # enough frames to replace the whole window at once
+    if "late" not in traits and fill:
+        pre[0].insert(0, ("noise", fill))
+    if "latches" in traits:  # silence until the display has decayed below floor - 10 and m_last_silent latches, then noise again
+        for k in range(3, 18):
+            pre[k] = [("silence", long if k == 3 else hop)]
+    if "one_channel" in traits:
+        for k in range(3, 15):
+            pre[k] = [("noise_ch0_only", long if k == 3 else hop)]
+        for k in range(15, T):
+            pre[k] = [("noise_ch1_only", long if k == 15 else hop)]
+    if "hide_timeout" in traits:
+        pre[9].insert(0, ("hide",))
+        pre[16].insert(0, ("show",))
+        pre[21], pre[22] = [("timeout",)], []  # no packet for 600 ms; the packet before tick 23 ends it
+    if "muted" in traits:
+        for k in (6, 7, 20):
+            pre[k] = [("mute", hop)]
+        for k in (12, 13):
+            pre[k] = [("mute_noise", hop)]
+    if "paused" in traits:  # not ticked in these frames while its packets keep arriving
+        for k in (4, 5, 11, 12, 13, 19):
+            paused[k] = True
+    steps = []
+    for k in range(T):
+        steps += pre[k]
+        steps.append(("tick", seconds[k], "paused") if paused[k] else ("tick", seconds[k]))
+    return steps
+
+
+def draw_mixed(seed: int, cfg, S: int, aligned: bool = False, base_sync_ms: int | None = None):
+    """S scripts for the S streams of one batch of configuration `cfg` (a wf_config struct), each with its own noise, packet
+    size and role; the roles' positions rotate with the seed.  Returns scenario dicts (steps, sync_ms, noise_id, role) for
+    play() / play_batch().  aligned: packets and reserves are multiples of 4 frames."""
+    r = np.random.default_rng(4242000 + seed)
+    cap = int(cfg.capture_channels)
+    roles = MIXED_ROLES[(cap, S)]
+    hops = ALIGNED_HOPS if aligned else RAGGED_HOPS
+    seconds = [float(np.float32(r.choice([1 / 60, 1 / 30, 1 / 144]))) for _ in range(MIXED_TICKS)]
+    # what one analysis looks at: the FFT window, or the meter's buffer (a waveform display has no latch to reach)
+    window = int(cfg.sample_rate) * int(cfg.meter_ms) // 1000 if cfg.meter else 0 if cfg.waveform else int(cfg.fft_size)
+    fill = 0 if (cfg.meter or cfg.waveform) else window + 400
+    # every stream runs ahead of the video by the same few ms in half of the draws (the tick's common delay_frames is then not
+    # zero), the late starter by 20 ms: its first ticks hold less than window + reserve
+    if base_sync_ms is None:
+        base_sync_ms = int(r.choice([0, 5]))
+    out = [None] * S
+    for ri, traits in enumerate(roles):
+        src = 0 if "twin" in traits else ri
+        tr = roles[src]
+        hop = hops[(src + seed) % len(hops)]
+        if "late" in tr:
+            hop = hops[1] if hop > 960 // 2 else hop  # small packets: more than one tick short of the reserve
+        out[(ri + seed) % S] = dict(steps=_mixed_script(tr, fill, hop, seconds, window), sync_ms=20 if "late" in tr else base_sync_ms,
+                                    noise_id=src + 1, role="+".join(traits), twin_of=(src + seed) % S if "twin" in traits else None)
+    return out
+
+
+def script_states(steps):
+    """per tick of a script: dict(hidden, timed_out, paused, one_channel) as the script itself says"""
+    hidden = timed_out = False
+    one = False
+    out = []
+    for st in steps:
+        op = st[0]
+        if op == "hide":
+            hidden = True
+        elif op == "show":
+            hidden = False
+        elif op == "timeout":
+            timed_out = True
+        elif op == "tick":
+            out.append(dict(hidden=hidden, timed_out=timed_out, paused=tick_paused(st), one_channel=one))
+        else:  # a packet
+            timed_out = False
+            one = op in ("noise_ch0_only", "noise_ch1_only")
+    return out
+
+
+def mixed_ticks(cfg, scripts, records, pairs: bool):
+    """the ticks at which the batch really was mixed, judged from the scripts and the reference's own records: some stream is
+    latched silent; a live one (ticked, shown, not silent) sits next to a silent one -- in the same workgroup pair (i ^ 1) where
+    `pairs`, anywhere in the batch otherwise; some stream is hidden; and, with two captured channels, some stream is fed on one
+    channel only -- in a stereo layout its other row must have gone below floor - 10, i.e. the source processes one channel
+    (a mono mixdown tests row 0 for both channels, reference :81: there a half-fed stream keeps processing both)."""
+    states = [script_states(sc["steps"]) for sc in scripts]
+    S, quiet = len(scripts), float(cfg.floor_db) - 10.0
+    hits = []
+    for t in range(len(records[0])):
+        # (a hidden or timed-out source reads m_last_silent too: that is its reset branch, not the latch)
+        silent = [bool(records[i][t]["silent"]) and not states[i][t]["hidden"] and not states[i][t]["timed_out"] for i in range(S)]
+        live = [not records[i][t]["silent"] and not states[i][t]["hidden"] and not states[i][t]["timed_out"] and not states[i][t]["paused"] for i in range(S)]
+        near = any(silent[i] and ((i ^ 1) < S and live[i ^ 1] if pairs else any(live)) for i in range(S))
+        hid = any(states[i][t]["hidden"] and not states[i][t]["paused"] for i in range(S))
+        half = cfg.capture_channels < 2
+        for i in range(S):
+            if cfg.capture_channels == 2 and states[i][t]["one_channel"] and live[i]:
+                db = records[i][t]["db"]
+                half = half or not (cfg.stereo and not cfg.meter and not cfg.waveform) or float(min(db[0].max(), db[1].max())) <= quiet
+        if any(silent) and near and hid and half:
+            hits.append(t)
+    return hits

@@ -242,6 +242,7 @@ void launch_input_rms(wf_hip *h, const wf_hip_tick_params *p)
     r.rms_ring = h->d_rms_ring;
     r.bsum = h->d_rms_bsum;
     r.wpos = h->d_wpos;
+    r.flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
     r.rend = h->d_rend;
     r.rms_cap = h->rms_cap;
     r.size = h->rms_size;

@@ -120,6 +120,7 @@ struct RmsArgs {
     const float *rms_ring;     // [n_streams][rms_cap] squared peaks
     const float *bsum;         // [n_streams][rms_cap / RMS_BLOCK] sums of completed blocks
     const uint32_t *wpos;      // [n_streams]
+    const uint32_t *flags;     // [n_streams] WF_STREAM_* as the tick behind this kernel reads them
     uint32_t *rend;            // [n_streams] consumption point of sync_rms_buffer
     uint32_t rms_cap;
     uint32_t size;             // m_input_rms_size
@@ -137,6 +138,10 @@ __global__ __launch_bounds__(64) void input_rms_kernel(const RmsArgs a)
 {
     const uint32_t stream = blockIdx.x;
     const uint32_t lane = threadIdx.x;
+    // a source that is not ticked in this frame does not run update_input_rms either (WAVSource::tick, src/source.cpp:1330-1331):
+    // m_input_rms stays, and sync_rms_buffer consumes nothing -- the sync point of a frame the source sat out must not count
+    if(a.flags[stream] & WF_STREAM_PAUSED)
+        return;
     const uint32_t wpos = a.wpos[stream];
     uint32_t rend = a.rend[stream];
     const uint32_t delay = a.delay + (a.delay_stream ? a.delay_stream[stream] : 0u);
