@@ -1,6 +1,7 @@
 // wf_hip.hip -- the entry points of the C ABI in include/wf_hip.h other than create / destroy (wf_hip_plan.hip) and the
 // measurement outputs (wf_hip_measure.hip): audio ingest, the tick, per-stream settings, readbacks, timing -- host side + the
 // launches of the small kernels (rings, level meter, waveform display, RMS, vertex fill).  The fused spectrum kernel is launched through wf_hip::launch
+// with the arguments of tick_args(): the handle's constant wf_hip::tick + the per-tick part
 // (wf_tick_geom.hip, wf_big_dispatch.hip).  gfx950 only.  There is no CPU fallback: every entry point either drives the
 // device or fails.
 #include <hip/hip_runtime.h>
@@ -23,28 +24,110 @@
 #include "wf_wave.hpp"
 #include "wf_vertex.hpp"
 
+// the small kernels' argument structs of a handle (wf_hip::small); this unit alone includes the headers that define them
+struct wf::host::SmallArgs {
+    wf::MeterArgs meter{};   // level-meter batches
+    wf::WaveArgs wave{};     // waveform batches
+    wf::VertexArgs vertex{}; // cfg.vertices; per_row == 0: no vertex fill
+    wf::RmsArgs rms{};       // wf_hip_enable_input_rms
+};
+
+namespace wf::host {
+
+static SmallArgs &small_args(wf_hip *h)
+{
+    if(!h->small)
+        h->small = std::make_shared<SmallArgs>();
+    return *h->small;
+}
+
+void fill_meter_args(wf_hip *h)
+{
+    wf::MeterArgs &m = small_args(h).meter;
+    m.ring_cap = h->ring_cap;
+    m.ring_stride = h->ring_stride;
+    m.ring_mask = h->ring_cap - 1;
+    m.size = h->N;
+    m.db_min = wf::db_min();
+    m.silent_floor = (float)(h->cfg.floor_db - 10);
+    m.border_top = h->tab.border_top;
+    m.border_bottom = h->tab.border_bottom;
+    m.ceiling = (float)h->cfg.ceiling_db;
+    m.dbrange = (float)(h->cfg.ceiling_db - h->cfg.floor_db);
+    m.n_streams = h->n_streams;
+    m.cap_ch = h->cap_ch;
+    m.rms = h->cfg.meter_rms ? 1u : 0u;
+    m.tsmooth = (h->cfg.tsmoothing != WF_TSMOOTH_NONE) ? 1u : 0u;
+    m.fast_peaks = h->cfg.fast_peaks ? 1u : 0u;
+}
+
+void fill_wave_args(wf_hip *h, uint32_t wave_samples)
+{
+    wf::WaveArgs &w = small_args(h).wave;
+    w.ring_mask = h->ring_cap - 1;
+    w.ring_stride = h->ring_stride;
+    w.step_ns = ((unsigned long long)h->cfg.meter_ms * 1000000ull) / h->N; // src/source_generic.cpp:299
+    w.waveform_samples = wave_samples; // m_waveform_samples
+    w.width = h->N;
+    w.sample_rate = h->cfg.sample_rate;
+    w.n_streams = h->n_streams;
+    w.cap_ch = h->cap_ch;
+    w.out_ch = h->out_ch;
+    w.stereo = h->cfg.stereo ? 1u : 0u;
+    w.normalize = h->cfg.normalize_volume ? 1u : 0u;
+    w.db_min = wf::db_min();
+}
+
+void fill_vertex_args(wf_hip *h, const wf::VertexTables &vt, const float *d_cap_xy)
+{
+    wf::VertexArgs &v = small_args(h).vertex;
+    v.cap_xy = d_cap_xy;
+    v.disp_ch = h->disp_ch;
+    v.num_bars = (int)h->num_bars;
+    v.per_row = vt.per_row;
+    v.per_bar = vt.per_bar;
+    v.mode = vt.mode;
+    v.bar_stride = vt.bar_stride;
+    v.bar_width = h->cfg.bar_width;
+    v.cpos = vt.cpos;
+    v.bottom = vt.bottom;
+    v.channel_offset = vt.channel_offset;
+    v.cap_radius = vt.cap_radius;
+    v.rounded = h->cfg.rounded_caps ? 1 : 0;
+    v.cap_tris = vt.cap_tris;
+    v.bottom_caps = vt.bottom_caps;
+    v.radial = vt.radial;
+    v.bot_offset = vt.bot_offset;
+    v.step_width = h->cfg.step_width;
+    v.step_stride = vt.step_stride;
+    v.max_steps = vt.max_steps;
+}
+
+} // namespace wf::host
+
 namespace {
 
 using namespace wf::host;
 
-wf::TickArgs make_args(wf_hip *h, const wf_hip_tick_params *p)
+// volume_compensation, reference src/source_generic.cpp:163 (:381 for the waveform) with dbfs() of src/source.hpp:293-299
+float volume_compensation(const wf_hip *h, float rms)
 {
-    wf::TickArgs a{};
+    const float rms_db = (rms > 0.0f) ? 20.0f * std::log10(rms) : wf::db_min();
+    return std::min(h->cfg.volume_target - rms_db, h->cfg.max_gain);
+}
+
+// The arguments of one tick: the handle's constant part (h->tick, written by wf_hip_create where each value is decided) + what
+// can change between ticks -- the tick's own parameters, the state other entry points own, the flag rotation, the mirrors.
+// stream_base / stream_count are the whole batch here; wf_hip_tick narrows them per lane.
+wf::TickArgs tick_args(const wf_hip *h, const wf_hip_tick_params *p)
+{
+    wf::TickArgs a = h->tick;
     a.ring = h->d_ring;
     a.wpos = h->d_wpos;
-    a.ring_cap = h->ring_cap;
-    a.ring_stride = h->ring_stride;
-    a.ring_mask = h->ring_cap - 1;
-    a.delay = p->delay_frames;
-    a.delay_stream = h->d_delay;
-    a.window = h->d_window;
-    a.tw1 = h->d_tw1;
-    a.tw2 = h->d_tw2;
-    a.tws = h->d_tws;
-    a.slope = h->d_slope;
-    a.rolloff = h->d_rolloff;
     a.tsmooth = h->d_tsmooth;
     a.decibels = h->d_decibels;
+    a.delay = p->delay_frames;
+    a.delay_stream = h->d_delay;
     a.stream_flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
     if(h->split) {
         const uint32_t nxt = (h->flag_cur + 1) % 3, clr = (h->flag_cur + 2) % 3;
@@ -57,179 +140,71 @@ wf::TickArgs make_args(wf_hip *h, const wf_hip_tick_params *p)
     // mono mixdown keeps storing its row: the silence quirk adds the stale row to the partner's magnitudes (wf_kernels.hpp)
     const bool mono_mix_rows = !h->cfg.stereo && h->cap_ch > 1;
     a.skip_decibels = ((p->flags & WF_HIP_TICK_NO_DECIBELS) && !mono_mix_rows) ? 1u : 0u;
-    a.split_ch = 0xffffffffu;
     a.bars_only = h->d_bars_only;
     a.stale_row = h->d_stale_row;
-    a.bar = wf::BarArgs{};
     if(h->d_bars) {
-        a.bar.coef = h->d_bar_coef;
-        a.bar.bin = h->d_bar_bin;
-        a.bar.off = h->d_bar_off;
-        a.bar.count = h->d_band_widths;
-        a.bar.big_task = h->d_big_task;
-        a.bar.big_bar_task = h->d_big_bar_task;
-        a.bar.big_num_tasks = h->big_num_tasks;
-        a.bar.chunk = h->d_bar_chunk;
-        a.bar.num_chunks = h->bar_chunks;
-        a.bar.lane_coef = h->d_lane_coef;
-        a.bar.lane_base = h->d_lane_base;
-        a.bar.bar_seg = h->d_bar_seg;
-        a.bar.seg_group = h->d_seg_group;
-        a.bar.lead_bar = h->d_lead_bar;
-        a.bar.lead_end = h->d_lead_end;
-        a.bar.wave_local = h->bar_wave_local ? 1 : 0;
-        a.bar.piece_mode = h->bar_piece_mode ? 1 : 0;
-        a.bar.ps_tab = h->d_ps_tab;
-        a.bar.ps_lanes = h->bar_ps_lanes;
-        a.bar.num_segs = h->bar_segs;
-        a.bar.lane_blocks = h->bar_blocks;
-        a.bar.cur_coef = h->d_cur_coef;
-        a.bar.cur_base = h->d_cur_base;
-        a.bar.cur_x = h->d_cur_x;
-        a.bar.curve = h->curve ? (h->curve_catrom ? 2 : 1) : 0;
-        a.bar.stream_steps = h->stream_steps ? 1 : 0;
-        a.bar.both_subs = h->curve_both ? 1 : 0;
-        a.bar.out_steps = h->out_steps;
-        a.bar.gauss = h->d_gauss;
-        a.bar.gauss_wsum = h->d_gauss_wsum;
-        a.bar.gauss_radius = h->tab.gauss_radius;
-        a.bar.stage_off = h->bar_stage_off;
-        a.bar.entries = (int)h->tab.bar_coef.size();
-        a.bar.lanes_per_bar = h->bar_lpb;
         a.bar.out = h->d_bars;
         a.bar.pre_out = h->d_bars_pre;
         a.bar.out2_n = (int)h->mirror_n;
         for(uint32_t j = 0; j < h->mirror_n; ++j)
             a.bar.out2_delta[j] = (long long)(h->bars_mirror[h->mirror_next][j] - h->d_bars);
-        a.bar.num_bars = (int)h->num_bars;
-        a.bar.mirror = h->cfg.mirror_freq_axis ? 1 : 0;
-        a.bar.border_top = h->tab.border_top;
-        a.bar.border_bottom = h->tab.border_bottom;
-        a.bar.ceiling = (float)h->cfg.ceiling_db;
-        a.bar.dbrange = (float)(h->cfg.ceiling_db - h->cfg.floor_db);
-        a.bar.inv_dbrange = 1.0f / a.bar.dbrange;
-        a.bar.lerp_mixed = ((a.bar.border_top <= 0 && a.bar.border_bottom >= 0) || (a.bar.border_top >= 0 && a.bar.border_bottom <= 0)) ? 1 : 0;
-        a.bar.disp_ch = h->disp_ch;
     }
-    a.half_coef = 0.5f * (2.0f / h->tab.window_sum); // mag_coefficient (reference src/source_generic.cpp:110), halved: the
-                                                     // kernel produces 2X[k] from the real split
-    a.slope_step = h->tab.slope.empty() ? 0.0f : (float)(3.0 * (double)h->cfg.slope / (double)(h->M - 1));
-    a.row_bins = h->M;
-    if(h->blu) {
-        a.blu_a = h->d_blu_a;
-        a.blu_b = h->d_blu_b;
-        a.blu_n = h->N;
-        a.blu_q = h->d_blu_q;
-        a.blu_qr = h->d_blu_qr;
-        a.blu_w = h->d_blu_w;
-        a.mr.passes = h->mr_passes;
-        for(int i = 0; i < 4; ++i) {
-            a.mr.radix[i] = h->mr_radix[i];
-            a.mr.tw_off[i] = h->mr_tw_off[i];
-        }
-        a.mr.tw = h->d_mr_tw;
-        a.mr.wp = h->d_mr_wp;
-        a.mr.half = h->mr_half;
-        a.mr.s3 = h->mr_s3;
-        a.mr.lds_cf = h->mr_lds_cf;
-        if(h->big_l) // direct form: |c_k| / L, times mag_coefficient (the packed form's tables carry the 1 / L, and its real split the 1 / 2)
-            a.half_coef = (2.0f / h->tab.window_sum) / (float)h->big_l;
-    }
-    if(h->big_mr) {
-        a.mr.passes = h->mr_passes;
-        for(int i = 0; i < 4; ++i) {
-            a.mr.radix[i] = h->mr_radix[i];
-            a.mr.tw_off[i] = h->mr_tw_off[i];
-        }
-        a.mr.tw = h->d_mr_tw;
-        a.mr.wp = h->d_mr_wp;
-        a.mr.half = (int)wf::GBig::M / 2; // (the rows kernel's two halves of the 132 KB buffer; its Z goes to device memory)
-        a.mr.s3 = h->big_mrw ? a.mr.half / 4 + 4 : 0; // (big_mr_whole_kernel leaves a row's Z in the buffer: mr_z_addr's four planes)
-        a.mr.lds_cf = 0;
-        a.big_c = h->big_rows;
-        a.big_r = h->M / h->big_rows;
-        a.big_wc = h->d_big_wc;
-    }
-    if(h->big_br) { // rows by Bluestein inside LDS: the container geometry's tables in place of the batch geometry's
-        a.tw1 = h->d_br_tw1;
-        a.tw2 = h->d_br_tw2;
-        a.blu_b = h->d_br_bhat;
-        a.blu_q = h->d_br_q;
-        a.big_c = h->big_rows;
-        a.big_r = h->M / h->big_rows;
-    }
-    if(h->big_l) {
-        a.big_z = h->d_big_z;
-        a.big_tws = h->d_big_tws;
-        a.big_tw = h->d_big_tw;
-        a.big_nz_out = h->d_big_nz;
-        a.big_nz = h->d_big_nz;
-        a.big_m = h->blu ? 0u : h->N / 2;
-        a.big_l = h->big_br ? h->big_rows * h->br_rs : h->big_l;
-        a.big_rs = h->br_rs;
-        a.blu_n = h->N; // the window length the underflow test compares with
-    }
-    a.half_coef *= 1.0f / h->in_scale; // the window tables on the device carry in_scale
     a.g = wf::gravity_for(h->cfg, p->seconds);
     a.g2 = 1.0f - a.g;
-    a.db_min = wf::db_min();
-    a.silent_floor = (float)(h->cfg.floor_db - 10);
-    a.vol_comp = 0.0f;
-    a.n_streams = h->n_streams;
-    a.stream_base = 0;
-    a.stream_count = h->n_streams;
-    a.cap_ch = h->cap_ch;
-    a.out_ch = h->out_ch;
-    uint32_t mode = 0;
-    if(h->cfg.tsmoothing != WF_TSMOOTH_NONE) mode |= wf::WF_MODE_TSMOOTH;
-    if(h->cfg.fast_peaks) mode |= wf::WF_MODE_FAST_PEAKS;
-    if(h->cfg.stereo) mode |= wf::WF_MODE_STEREO;
-    if(!h->tab.slope.empty()) mode |= wf::WF_MODE_SLOPE;
-    if(h->d_rolloff) mode |= wf::WF_MODE_ROLLOFF;
-    if(!h->tab.window.empty()) mode |= wf::WF_MODE_WINDOW;
-    if(!h->cfg.stereo && h->cap_ch > 1) mode |= wf::WF_MODE_MONO_MIX;
     if(h->cfg.normalize_volume) {
-        mode |= wf::WF_MODE_NORMALIZE;
-        // volume_compensation, reference src/source_generic.cpp:163
-        const float rms_db = (p->input_rms > 0.0f) ? 20.0f * std::log10(p->input_rms) : wf::db_min();
-        a.vol_comp = std::min(h->cfg.volume_target - rms_db, h->cfg.max_gain);
+        a.vol_comp = volume_compensation(h, p->input_rms);
         a.vol_comp_stream = h->d_vol_comp; // per-stream values once wf_hip_set_input_rms has been used
     }
-    a.mode = mode;
-    a.phase_clock = h->d_phase_clock;
     return a;
 }
 
-wf::MeterArgs make_meter_args(wf_hip *h, const wf_hip_tick_params *p)
+wf::MeterArgs meter_args(const wf_hip *h, const wf_hip_tick_params *p)
 {
-    wf::MeterArgs m{};
+    wf::MeterArgs m = h->small->meter;
     m.ring = h->d_ring;
     m.wpos = h->d_wpos;
     m.mend = h->d_mend;
-    m.ring_cap = h->ring_cap;
-    m.ring_stride = h->ring_stride;
-    m.ring_mask = h->ring_cap - 1;
-    m.delay = p->delay_frames;
-    m.delay_stream = h->d_delay;
-    m.size = h->N;
     m.meter_buf = h->d_meter_buf;
     m.meter_val = h->d_meter_val;
     m.stream_flags = h->d_flags;
     m.bars = h->d_bars;
+    m.delay = p->delay_frames;
+    m.delay_stream = h->d_delay;
     m.g = wf::gravity_for(h->cfg, p->seconds);
     m.g2 = 1.0f - m.g;
-    m.db_min = wf::db_min();
-    m.silent_floor = (float)(h->cfg.floor_db - 10);
-    m.border_top = h->tab.border_top;
-    m.border_bottom = h->tab.border_bottom;
-    m.ceiling = (float)h->cfg.ceiling_db;
-    m.dbrange = (float)(h->cfg.ceiling_db - h->cfg.floor_db);
-    m.n_streams = h->n_streams;
-    m.cap_ch = h->cap_ch;
-    m.rms = h->cfg.meter_rms ? 1u : 0u;
-    m.tsmooth = (h->cfg.tsmoothing != WF_TSMOOTH_NONE) ? 1u : 0u;
-    m.fast_peaks = h->cfg.fast_peaks ? 1u : 0u;
     return m;
+}
+
+wf::WaveArgs wave_args(const wf_hip *h, const wf_hip_tick_params *p)
+{
+    wf::WaveArgs w = h->small->wave;
+    w.ring = h->d_ring;
+    w.wpos = h->d_wpos;
+    w.cend = h->d_cend;
+    w.wts = h->d_wts;
+    w.rows = h->d_decibels;
+    w.stream_flags = h->d_flags;
+    w.delay = p->delay_frames;
+    w.delay_stream = h->d_delay;
+    w.audio_ts = p->audio_ts_ns;
+    w.audio_ts_stream = h->d_audio_ts;
+    if(w.normalize) {
+        w.vol_comp = volume_compensation(h, p->input_rms);
+        w.vol_comp_stream = h->d_vol_comp;
+    }
+    return w;
+}
+
+// the vertex fill of streams [lo, hi), behind their bars
+wf::VertexArgs vertex_args(const wf_hip *h, uint32_t lo, uint32_t hi)
+{
+    wf::VertexArgs v = h->small->vertex;
+    v.bars = h->d_bars;
+    v.verts = h->d_verts;
+    v.counts = h->d_vert_counts;
+    v.stream_base = lo;
+    v.stream_count = hi - lo;
+    return v;
 }
 
 // update_input_rms of every stream (what WAVSource::tick does first, src/source.cpp:1330-1331); leaves the per-stream volume
@@ -238,23 +213,16 @@ void launch_input_rms(wf_hip *h, const wf_hip_tick_params *p)
 {
     if(h->d_rms_ring == nullptr)
         return;
-    wf::RmsArgs r{};
+    wf::RmsArgs r = h->small->rms; // (the producer's constants: enable_rms_producer)
     r.rms_ring = h->d_rms_ring;
     r.bsum = h->d_rms_bsum;
     r.wpos = h->d_wpos;
     r.flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
     r.rend = h->d_rend;
-    r.rms_cap = h->rms_cap;
-    r.size = h->rms_size;
     r.delay = p->delay_frames;
     r.delay_stream = h->d_delay;
     r.input_rms = h->d_input_rms;
     r.vol_comp = h->d_vol_comp;
-    r.volume_target = h->cfg.volume_target;
-    r.max_gain = h->cfg.max_gain;
-    r.db_min = wf::db_min();
-    r.n_streams = h->n_streams;
-    r.feed = h->rms_feed ? 1u : 0u;
     hipLaunchKernelGGL(wf::input_rms_kernel, dim3(h->n_streams), dim3(64), 0, h->stream, r);
 }
 
@@ -734,7 +702,7 @@ int wf_hip_reset(wf_hip *h, uint32_t first, uint32_t count)
     }
     if(h->d_verts) {
         // no geometry until the first tick, as after create
-        const size_t pv = (size_t)h->disp_ch * h->vtab.per_row;
+        const size_t pv = (size_t)h->disp_ch * h->small->vertex.per_row;
         WF_HIP_TRY(h, hipMemsetAsync(h->d_verts + (size_t)first * pv, 0, (size_t)count * pv * sizeof(wf::f4), h->stream));
         WF_HIP_TRY(h, hipMemsetAsync(h->d_vert_counts + (size_t)first * h->disp_ch, 0, (size_t)count * h->disp_ch * sizeof(uint32_t), h->stream));
     }
@@ -994,7 +962,7 @@ static int wf_hip_tick_impl(wf_hip *h, const wf_hip_tick_params *p)
 {
     if(h == nullptr || p == nullptr)
         return WF_HIP_ERR_INVALID;
-    if((uint64_t)p->delay_frames + h->max_stream_delay + (h->wave ? h->wave_samples : h->N) > h->ring_cap)
+    if((uint64_t)p->delay_frames + h->max_stream_delay + (h->wave ? h->small->wave.waveform_samples : h->N) > h->ring_cap)
         return fail(h, WF_HIP_ERR_INVALID, "delay_frames %u (+ per-stream %u) + fft_size %u exceeds the ring capacity %u", p->delay_frames,
                     h->max_stream_delay, h->N, h->ring_cap);
     if((p->flags & WF_HIP_TICK_NO_DECIBELS) && h->num_bars == 0)
@@ -1003,47 +971,20 @@ static int wf_hip_tick_impl(wf_hip *h, const wf_hip_tick_params *p)
     if(h->wave) {
         WF_TRY_RC(wait_rows_in_flight(h)); // the waveform rows are read back the same way
         launch_input_rms(h, p);
-        wf::WaveArgs w{};
-        w.ring = h->d_ring;
-        w.wpos = h->d_wpos;
-        w.cend = h->d_cend;
-        w.wts = h->d_wts;
-        w.ring_mask = h->ring_cap - 1;
-        w.ring_stride = h->ring_stride;
-        w.delay = p->delay_frames;
-        w.delay_stream = h->d_delay;
-        w.rows = h->d_decibels;
-        w.stream_flags = h->d_flags;
-        w.audio_ts = p->audio_ts_ns;
-        w.audio_ts_stream = h->d_audio_ts;
-        w.step_ns = ((unsigned long long)h->cfg.meter_ms * 1000000ull) / h->N; // src/source_generic.cpp:299
-        w.waveform_samples = h->wave_samples;
-        w.width = h->N;
-        w.sample_rate = h->cfg.sample_rate;
-        w.n_streams = h->n_streams;
-        w.cap_ch = h->cap_ch;
-        w.out_ch = h->out_ch;
-        w.stereo = h->cfg.stereo ? 1u : 0u;
-        w.normalize = h->cfg.normalize_volume ? 1u : 0u;
-        if(w.normalize) {
-            const float rms_db = (p->input_rms > 0.0f) ? 20.0f * std::log10(p->input_rms) : wf::db_min();
-            w.vol_comp = std::min(h->cfg.volume_target - rms_db, h->cfg.max_gain); // src/source_generic.cpp:381
-            w.vol_comp_stream = h->d_vol_comp;
-        }
-        w.db_min = wf::db_min();
+        const wf::WaveArgs w = wave_args(h, p);
         hipLaunchKernelGGL(wf::waveform_tick_kernel, dim3((h->n_streams + wf::WAVE_STREAMS - 1) / wf::WAVE_STREAMS), dim3(wf::WAVE_THREADS), 0, h->stream, w);
         WF_HIP_TRY(h, hipGetLastError());
         return WF_HIP_OK;
     }
     if(h->meter) {
-        const wf::MeterArgs m = make_meter_args(h, p);
+        const wf::MeterArgs m = meter_args(h, p);
         hipLaunchKernelGGL(wf::meter_tick_kernel, dim3(h->n_streams), dim3(wf::METER_THREADS), 0, h->stream, m);
         WF_HIP_TRY(h, hipGetLastError());
         return WF_HIP_OK;
     }
     const bool mono_mix_rows = !h->cfg.stereo && h->cap_ch > 1;
     wf_hip_tick_params p_rows;
-    if((p->flags & WF_HIP_TICK_NO_DECIBELS) && (h->big_l || h->ext_outputs)) {
+    if((p->flags & WF_HIP_TICK_NO_DECIBELS) && (h->plan.big_l || h->disp.ext_outputs)) {
         // the outputs of this batch are derived from the stored rows (big_outputs_kernel): the rows are stored regardless --
         // the flag only ever promised that they MAY be stale
         p_rows = *p;
@@ -1074,7 +1015,7 @@ static int wf_hip_tick_impl(wf_hip *h, const wf_hip_tick_params *p)
     if(h->d_rms_ring)
         WF_TRY_RC(join_lanes(h)); // (never pending: the RMS producer keeps the batch on one lane)
     launch_input_rms(h, p);
-    wf::TickArgs a = make_args(h, p);
+    wf::TickArgs a = tick_args(h, p);
     const bool aligned = h->all_aligned && h->stream_delays_aligned && (p->delay_frames % 4u) == 0;
     const int lanes = h->d_rms_ring ? 1 : h->n_lanes; // update_input_rms runs on `stream` ahead of every tick: one lane
     if(lanes > 1 && h->main_dirty) {
@@ -1087,48 +1028,18 @@ static int wf_hip_tick_impl(wf_hip *h, const wf_hip_tick_params *p)
         const uint32_t lo = (uint32_t)((uint64_t)h->n_streams * l / lanes), hi = (uint32_t)((uint64_t)h->n_streams * (l + 1) / lanes);
         a.stream_base = lo;
         a.stream_count = hi - lo;
-        h->launch_stream = l == 0 ? h->stream : h->lane_stream[l];
-        h->launch_rc = WF_HIP_OK;
-        if(h->ext_outputs) {
+        hipStream_t st = l == 0 ? h->stream : h->lane_stream[l];
+        if(h->disp.ext_outputs) {
             // the tick kernel stores rows only; the display comes from them, one workgroup per displayed row
             wf::TickArgs rows_only = a;
             rows_only.bar.out = nullptr;
-            h->launch(h, rows_only, aligned);
+            WF_TRY_RC(h->launch(h, rows_only, aligned, st));
             if(hi > lo)
-                big_outputs_launch(h, a, (hi - lo) * h->disp_ch, h->launch_stream);
+                big_outputs_launch(h, a, (hi - lo) * h->disp_ch, st);
         } else
-            h->launch(h, a, aligned);
-        if(h->launch_rc != WF_HIP_OK)
-            return h->launch_rc;
-        if(h->d_verts && hi > lo) { // the vertex fill of this slice, behind its bars
-            wf::VertexArgs v{};
-            v.bars = h->d_bars;
-            v.verts = h->d_verts;
-            v.cap_xy = h->d_cap_xy;
-            v.stream_base = lo;
-            v.stream_count = hi - lo;
-            v.disp_ch = h->disp_ch;
-            v.num_bars = (int)h->num_bars;
-            v.per_row = h->vtab.per_row;
-            v.per_bar = h->vtab.per_bar;
-            v.mode = h->vtab.mode;
-            v.bar_stride = h->vtab.bar_stride;
-            v.bar_width = h->cfg.bar_width;
-            v.cpos = h->vtab.cpos;
-            v.bottom = h->vtab.bottom;
-            v.channel_offset = h->vtab.channel_offset;
-            v.cap_radius = h->vtab.cap_radius;
-            v.rounded = h->cfg.rounded_caps ? 1 : 0;
-            v.cap_tris = h->vtab.cap_tris;
-            v.bottom_caps = h->vtab.bottom_caps;
-            v.radial = h->vtab.radial;
-            v.bot_offset = h->vtab.bot_offset;
-            v.step_width = h->cfg.step_width;
-            v.step_stride = h->vtab.step_stride;
-            v.max_steps = h->vtab.max_steps;
-            v.counts = h->d_vert_counts;
-            hipLaunchKernelGGL(wf::vertex_fill_kernel, dim3((hi - lo) * h->disp_ch), dim3(256), 0, h->launch_stream, v);
-        }
+            WF_TRY_RC(h->launch(h, a, aligned, st));
+        if(h->d_verts && hi > lo)
+            hipLaunchKernelGGL(wf::vertex_fill_kernel, dim3((hi - lo) * h->disp_ch), dim3(256), 0, st, vertex_args(h, lo, hi));
         if(l > 0)
             WF_HIP_TRY(h, hipEventRecord(h->ev_lane[l], h->lane_stream[l]));
     }
@@ -1189,7 +1100,7 @@ int wf_hip_set_stream_delay(wf_hip *h, uint32_t first, uint32_t count, const uin
         mx = std::max(mx, delay_frames[i]);
         al = al && (delay_frames[i] % 4u) == 0;
     }
-    const uint32_t window = h->wave ? h->wave_samples : h->N; // the same capacity term as wf_hip_tick
+    const uint32_t window = h->wave ? h->small->wave.waveform_samples : h->N; // the same capacity term as wf_hip_tick
     if((uint64_t)mx + window > h->ring_cap)
         return fail(h, WF_HIP_ERR_INVALID, "stream delay %u + window %u exceeds the ring capacity %u", mx, window, h->ring_cap);
     WF_HIP_TRY(h, hipSetDevice(h->device));
@@ -1236,22 +1147,17 @@ int wf_hip_set_input_rms(wf_hip *h, uint32_t first, uint32_t count, const float 
     if(h->d_rms_ring)
         return fail(h, WF_HIP_ERR_INVALID, "m_input_rms is produced on the device (wf_hip_enable_input_rms); it cannot be set");
     WF_HIP_TRY(h, hipSetDevice(h->device));
-    // volume_compensation of every stream, reference src/source_generic.cpp:163 with dbfs() of src/source.hpp:293-299
-    auto comp = [&](float r) {
-        const float rms_db = (r > 0.0f) ? 20.0f * std::log10(r) : wf::db_min();
-        return std::min(h->cfg.volume_target - rms_db, h->cfg.max_gain);
-    };
     if(h->d_vol_comp == nullptr) {
         rc = dev_alloc(h, &h->d_vol_comp, (size_t)h->n_streams);
         if(rc)
             return rc;
-        const std::vector<float> init(h->n_streams, comp(0.0f));
+        const std::vector<float> init(h->n_streams, volume_compensation(h, 0.0f));
         WF_HIP_TRY(h, hipMemcpyAsync(h->d_vol_comp, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
         WF_HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     std::vector<float> v(count);
     for(uint32_t i = 0; i < count; ++i)
-        v[i] = comp(rms[i]);
+        v[i] = volume_compensation(h, rms[i]); // of every stream
     WF_HIP_TRY(h, hipMemcpyAsync(h->d_vol_comp + first, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     WF_HIP_TRY(h, hipStreamSynchronize(h->stream)); // the staging vector dies here
     return WF_HIP_OK;
@@ -1291,6 +1197,14 @@ static int enable_rms_producer(wf_hip *h, bool feed)
     WF_HIP_TRY(h, hipMemsetAsync(h->d_input_rms, 0, (size_t)h->n_streams * sizeof(float), h->stream));
     h->d_rms_bsum = bsum;
     h->rms_feed = feed;
+    wf::RmsArgs &r = small_args(h).rms;
+    r.rms_cap = h->rms_cap;
+    r.size = h->rms_size;
+    r.volume_target = h->cfg.volume_target;
+    r.max_gain = h->cfg.max_gain;
+    r.db_min = wf::db_min();
+    r.n_streams = h->n_streams;
+    r.feed = feed ? 1u : 0u;
     h->d_rms_ring = ring; // from here on every push feeds it (or, feed mode, wf_hip_push_rms_ragged_async does)
     h->main_dirty = true;
     return WF_HIP_OK;
@@ -1349,7 +1263,7 @@ int wf_hip_sync(wf_hip *h)
     return WF_HIP_OK;
 }
 
-uint32_t wf_hip_num_vertices(const wf_hip *h) { return (h && h->d_verts) ? (uint32_t)h->vtab.per_row : 0u; }
+uint32_t wf_hip_num_vertices(const wf_hip *h) { return (h && h->d_verts) ? (uint32_t)h->small->vertex.per_row : 0u; }
 
 const float *wf_hip_vertices_device(wf_hip *h)
 {
@@ -1473,7 +1387,7 @@ static int read_display_async(wf_hip *h, uint32_t first, uint32_t count, float *
     if(pinned_bars)
         WF_HIP_TRY(h, hipMemcpyAsync(pinned_bars, h->d_bars + first * per, count * per * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
     if(pinned_vertices) {
-        const size_t pv = (size_t)h->disp_ch * h->vtab.per_row;
+        const size_t pv = (size_t)h->disp_ch * h->small->vertex.per_row;
         WF_HIP_TRY(h, hipMemcpyAsync(pinned_vertices, h->d_verts + first * pv, count * pv * sizeof(wf::f4), hipMemcpyDeviceToHost, h->read_stream));
     }
     if(pinned_counts)
@@ -1618,7 +1532,7 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
         return h->d_bars_pre;
     case WF_HIP_OUT_VERTICES:
         if(h->d_verts == nullptr) { *why = "configuration has no vertex fill (cfg.vertices == 0)"; return nullptr; }
-        *per_stream = (size_t)h->disp_ch * h->vtab.per_row * sizeof(wf::f4);
+        *per_stream = (size_t)h->disp_ch * h->small->vertex.per_row * sizeof(wf::f4);
         return h->d_verts;
     case WF_HIP_OUT_VERTEX_COUNTS:
         if(h->d_vert_counts == nullptr) { *why = "configuration has no vertex fill (cfg.vertices == 0)"; return nullptr; }
@@ -1749,7 +1663,7 @@ int wf_hip_set_bars_mirrors(wf_hip *h, uint32_t n, void *const *d_out0, void *co
     if(n > 0) {
         if(h->d_bars == nullptr || h->meter || h->wave)
             return fail(h, WF_HIP_ERR_INVALID, "configuration has no bars (cfg.bars == 0 and cfg.curve == 0, or a level-meter / waveform batch)");
-        if(h->ext_outputs || h->big_l != 0 || h->blu)
+        if(h->disp.ext_outputs || h->plan.big_l != 0 || h->plan.blu)
             return fail(h, WF_HIP_ERR_UNSUPPORTED, "fft_size %u: only the power-of-two sizes up to 32768 whose display the tick kernel finishes itself write further bars buffers; copy the bars with wf_hip_copy_bars_device_async", h->N);
         for(uint32_t j = 0; j < n; ++j)
             if(d_out0[j] == nullptr || d_out1[j] == nullptr || d_out0[j] == d_out1[j] || d_out0[j] == (void *)h->d_bars || d_out1[j] == (void *)h->d_bars)
@@ -1953,7 +1867,7 @@ extern "C" int wf_hip_debug_age(wf_hip *h, uint32_t first, uint32_t count, uint3
 // development aid: copies the per-workgroup s_memtime stamps of the last tick (16 per workgroup)
 extern "C" int wf_hip_debug_phase_clock(wf_hip *h, unsigned long long *out, size_t n)
 {
-    if(hipMemcpy(out, h->d_phase_clock, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
+    if(hipMemcpy(out, h->tick.phase_clock, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
         return WF_HIP_ERR_RUNTIME;
     return WF_HIP_OK;
 }
@@ -1967,7 +1881,7 @@ uint32_t wf_hip_launches_per_tick(const wf_hip *h)
         return 0;
     if(h->wave || h->meter)
         return 1;
-    return (uint32_t)(h->d_rms_ring ? 1 : h->n_lanes) * (h->split_mono ? 2u : 1u);
+    return (uint32_t)(h->d_rms_ring ? 1 : h->n_lanes) * (h->plan.split_mono ? 2u : 1u);
 }
 
 uint64_t wf_hip_algorithmic_bytes_per_tick(const wf_hip *h, uint32_t flags)
@@ -1987,7 +1901,7 @@ uint64_t wf_hip_algorithmic_bytes_per_tick(const wf_hip *h, uint32_t flags)
         bytes += n_spec * 8ull * h->M;
     const bool mono_mix = !h->cfg.stereo && h->cap_ch > 1;
     const uint64_t out_rows = (uint64_t)h->n_streams * (mono_mix ? 1u : h->out_ch);
-    if(!(flags & WF_HIP_TICK_NO_DECIBELS) || mono_mix || h->big_l || h->ext_outputs) // the mono-mixdown row is stored in either mode;
+    if(!(flags & WF_HIP_TICK_NO_DECIBELS) || mono_mix || h->plan.big_l || h->disp.ext_outputs) // the mono-mixdown row is stored in either mode;
                                                                                        // so are rows the outputs are derived from
         bytes += out_rows * 4ull * h->M;
     bytes += (uint64_t)h->n_streams * h->disp_ch * h->num_bars * 4ull;

@@ -1,4 +1,5 @@
-// wf_hip_internal.hpp -- what the translation units of libwaveform_hip.so share: the handle, the error helpers and the
+// wf_hip_internal.hpp -- what the translation units of libwaveform_hip.so share: the handle -- which holds the kernels' argument
+// structs themselves (wf_hip::tick and the four small ones: a value fixed at create lives there and nowhere else) --, the error helpers and the
 // functions by which the plan (wf_hip_plan.hip), the entry points (wf_hip.hip; the measurement outputs: wf_hip_measure.hip) and the kernel dispatch (wf_tick_geom.hip, one
 // object per FFT geometry; wf_big_dispatch.hip for the transforms beyond a CU's LDS) call each other.  Not installed: the
 // library's interface is include/wf_hip.h.
@@ -6,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -13,10 +15,13 @@
 #include "wf_hip.h"
 
 namespace wf { struct LoudState; struct LoudHist; } // (wf_loudness.hpp: device code, seen by wf_hip_measure.hip alone)
+// MeterArgs, WaveArgs, VertexArgs and RmsArgs of this handle: their headers define kernels, so wf_hip.hip alone sees the type
+namespace wf::host { struct SmallArgs; }
 #include "wf_dev_guard.hpp"
 #include "wf_host_tables.hpp"
 #include "wf_loudness_tables.hpp"
 #include "wf_tick_phases.hpp" // TickArgs, BarsOnlyState (plain structs: no kernel is instantiated by including it)
+#include "wf_tick_plan.hpp"
 
 struct wf_hip {
     wf_config cfg{};
@@ -30,7 +35,7 @@ struct wf_hip {
     // tail of one slice's launch overlaps the head of another's (a lone launch leaves the chip draining for a workgroup's
     // lifetime at both ends).  Every other entry point first makes `stream` wait for the lanes (join_lanes) and the next
     // tick makes the lanes wait for `stream`: outside wf_hip_tick the handle behaves as if it had the one stream.
-    static constexpr int MAX_LANES = 4;
+    static constexpr int MAX_LANES = wf::MAX_LANES;
     int n_lanes = 1;
     uint32_t wg_lds = 0, wg_threads = 0; // dynamic LDS and threads of one workgroup of the tick kernel (how many fit a CU)
     hipStream_t lane_stream[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
@@ -69,6 +74,19 @@ struct wf_hip {
     uint32_t cap_ch = 1, out_ch = 1, disp_ch = 1;
     uint32_t num_bars = 0;
     bool all_aligned = true; // every push so far was a multiple of 4 frames
+    // The kernels' arguments.  What is fixed at create and used only as a kernel argument -- tables, layout flags, sizes,
+    // coefficients -- is written into these structs where it is decided or uploaded, and read from them; the handle keeps no
+    // copy.  What can change after create, or is read by other entry points (the d_* fields below, the flag rotation, the
+    // mirrors), stays a handle field and is patched into a copy per tick (wf_hip.hip: tick_args and its kin).
+    wf::TransformPlan plan;          // which transform family runs the batch, decided once (wf_tick_plan.hpp)
+    wf::TickArgs tick{};             // spectrum batches
+    std::shared_ptr<wf::host::SmallArgs> small; // the same for the level meter, the waveform display, the vertex fill and the RMS producer
+    // the display decisions that are no kernel arguments; the second display plan (ext_outputs) starts from a default one
+    struct DisplayPlan {
+        bool ext_outputs = false;    // the outputs are derived from the stored rows by big_outputs_kernel behind the tick kernel
+                                     // (displays whose staging does not fit the tick kernel's exchange buffer)
+        size_t big_out_lds = 0;      // dynamic LDS of big_outputs_kernel
+    } disp;
     // device memory
     float *d_ring = nullptr;
     uint32_t *d_wpos = nullptr;
@@ -85,33 +103,7 @@ struct wf_hip {
     uint32_t waves_per_spectrum = 1;
     bool verdict_tracking = false;
     bool split = false;              // the channels of a stream run in different workgroups (spectrum_tick_kernel<.., SPLIT>)
-    bool split_mono = false;         // ... and, for mono mixdown, in different launches (TickArgs::split_ch)
-    // FFT sizes that are not powers of two: Bluestein over the geometry of geom_n = 2 * L points (spectrum_tick_kernel<.., BLU>)
-    bool blu = false;
-    int mr_half = 0, mr_s3 = 0, mr_lds_cf = 0; // MrPlan::half / s3 / lds_cf: the spectrum's exchange buffer sized by the transform
-    int mr_passes = 0;               // > 0: fft_size = 2^a 3^b 5^c, the transform runs as mixed-radix passes inside the Bluestein instantiation (wf_mixed.hpp)
-    int mr_radix[4] = {0, 0, 0, 0}, mr_tw_off[4] = {0, 0, 0, 0};
-    wf::cf *d_mr_tw = nullptr;       // the passes' twiddle tables (wf::build_mixed_radix_tables)
-    wf::cf *d_mr_wp = nullptr;       // W_p^m of a prime first pass (wf::build_prime_twiddles)
-    uint32_t geom_n = 0;             // the fft size whose geometry runs the batch (N itself for the power-of-two sizes >= 1024)
-    wf::cf *d_blu_a = nullptr, *d_blu_b = nullptr, *d_blu_q = nullptr, *d_blu_qr = nullptr, *d_blu_w = nullptr;
-    // transforms beyond a CU's LDS (wf_big.hpp): big_l = big_rows * 16384 complex points in two steps through device memory
-    uint32_t big_l = 0, big_rows = 0;
-    bool big_mr = false;             // fft sizes above 16384 with small prime factors: big_rows rows of a mixed-radix transform (big_mr_rows_kernel)
-    bool big_mrw = false;            // ... two rows on 512 threads: both rows and the end of the tick in one kernel (big_mr_whole_kernel), no scratch
-    bool big_br = false;             // fft sizes above 16384 with a prime factor no plan takes: big_rows (= 8) rows, each by Bluestein inside LDS (big_br_rows_kernel)
-    uint32_t br_rs = 0;              // ... a row's stride in the scratch buffer: M / big_rows rounded up to even
-    uint32_t br_l = 0;               // ... over br_l complex points (4096 / 8192: the 8192- / 16384-sample geometry as container)
-    wf::cf *d_br_tw1 = nullptr, *d_br_tw2 = nullptr; // the container's pass-1 / pass-2 twiddles
-    wf::cf *d_br_rowtw = nullptr, *d_br_bhat = nullptr, *d_br_q = nullptr; // build_bluestein_rows
-    wf::cf *d_big_wc = nullptr;      // [8][8] W_big_rows^(c k1)
-    bool big_whole = false;          // fft_size 65536: both rows plus the end of the tick in ONE kernel (big_whole_kernel), nothing through device memory
-    wf::cf *d_big_v = nullptr, *d_big_z = nullptr, *d_big_tw = nullptr, *d_big_tws = nullptr;
-    uint32_t *d_big_nz = nullptr;
-    size_t big_out_lds = 0;          // dynamic LDS of big_outputs_kernel
-    int *d_big_task = nullptr, *d_big_bar_task = nullptr; // BarArgs::big_task / big_bar_task
-    int big_num_tasks = 0;
-    int mr_plan_id = 0;              // spectrum_tick_kernel's PLAN: the compile-time mixed-radix plan of this size (0: the run-time plan)
+    wf::cf *d_big_v = nullptr;       // the columns' output of the chain through device memory (development builds: wf_big.hpp BigArgs::v)
     int interp_shape[2] = {0, 0};    // {tab.interp_radius, tab.interp_taps} (WF_HIP_TABLE_INTERP_SHAPE)
     float *d_bars = nullptr;
     float *d_bars_pre = nullptr;    // BarArgs::pre_out: [n_streams][disp_ch], mirrored displays only
@@ -121,17 +113,8 @@ struct wf_hip {
     uint32_t mirror_n = 0;
     uint32_t mirror_next = 0;       // the set the ticks write
     bool mirror_fresh = false;      // a tick has written set mirror_next since it became the write set
-    wf::VertexTables vtab;           // cfg.vertices: the vertex fill behind every tick
     wf::f4 *d_verts = nullptr;
     uint32_t *d_vert_counts = nullptr; // [n_streams][disp_ch] vertices of each row's draw call
-    float *d_cap_xy = nullptr;
-    float *d_window = nullptr, *d_slope = nullptr, *d_rolloff = nullptr;
-    wf::cf *d_tw1 = nullptr, *d_tw2 = nullptr, *d_tws = nullptr;
-    float *d_bar_coef = nullptr;
-    int *d_bar_bin = nullptr, *d_bar_off = nullptr, *d_band_widths = nullptr, *d_bar_chunk = nullptr;
-    int bar_chunks = 0, bar_lpb = 1, bar_segs = 0;
-    int bar_blocks = 0;
-    int bar_stage_off = 0;           // BarArgs::stage_off
     uint32_t *d_delay = nullptr;     // [n_streams] A/V-sync delay per stream (wf_hip_set_stream_delay), or nullptr
     uint32_t max_stream_delay = 0;   // largest value ever set (ring-capacity check of the tick)
     unsigned long long *d_audio_ts = nullptr; // [n_streams] m_audio_ts per stream of a waveform batch (wf_hip_set_stream_audio_ts), or nullptr
@@ -177,7 +160,6 @@ struct wf_hip {
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;
-    uint32_t wave_samples = 0;       // m_waveform_samples
     uint32_t *d_cend = nullptr;      // [n_streams] samples consumed so far
     unsigned long long *d_wts = nullptr; // [n_streams] m_waveform_ts
     // level-meter batches (cfg.meter): N is the meter buffer length, there is no FFT state
@@ -190,27 +172,9 @@ struct wf_hip {
     // the path squares -- then stays representable down to |X| ~ 1e-31 instead of ~1e-19 (hypotf in the reference answers for
     // the whole float range: the first ticks behind a reset through a narrow window, a few samples under sin^16 tails, give
     // |X| ~ 1e-26).  Headroom: N * amplitude * in_scale squared must stay below FLT_MAX; the factor is 2^40 up to 4096 samples and
-    // halves with every doubling beyond (wf_hip_create), which keeps the overflow point at an amplitude of 4096 (+72 dBFS) from
+    // halves with every doubling beyond (wf::plan_transform), which keeps the overflow point at an amplitude of 4096 (+72 dBFS) from
     // 4096 samples up (the reference's hypotf overflows far later still: a stated deviation).  Bluestein
-    // through device memory squares values that still carry its factor L: 2^24 there.
-    float in_scale = 1.0f;
-    bool ext_outputs = false;        // the outputs are derived from the stored rows by big_outputs_kernel behind the tick kernel
-                                     // (displays whose staging does not fit the tick kernel's exchange buffer)
-    bool curve = false;              // the outputs are curve points (render_curve), not bars
-    bool curve_both = false;         // ... finished by the threads of both spectra of a workgroup (mono mixdown)
-    bool curve_catrom = false;       // ... Catmull-Rom: positions only, weights on the device (BarArgs::cur_x)
-    bool stream_steps = false;       // ... more points per thread than OutVals holds (BarArgs::stream_steps)
-    float *d_cur_x = nullptr;
-    int out_steps = 0;               // outputs finished per thread (curve: ceil(width / T); bars in segment form: 1)
-    float *d_cur_coef = nullptr, *d_gauss = nullptr, *d_gauss_wsum = nullptr;
-    int *d_cur_base = nullptr;
-    float *d_lane_coef = nullptr;
-    int *d_lane_base = nullptr, *d_bar_seg = nullptr, *d_seg_group = nullptr, *d_lead_bar = nullptr, *d_lead_end = nullptr;
-    bool bar_wave_local = false;
-    bool bar_piece_mode = false;     // BarArgs::piece_mode (d_seg_group holds BarPieceTables::info, d_bar_seg its bar_piece)
-    float *d_ps_tab = nullptr;       // BarArgs::ps_tab (BarPsTables::tab), prefix-sum layout of the bar reduction
-    int bar_ps_lanes = 0;            // BarArgs::ps_lanes; 0: the layout is not used
-    unsigned long long *d_phase_clock = nullptr; // only allocated by WF_PHASE_TIMING builds
+    // through device memory squares values that still carry its factor L: 2^24 there.  (plan.in_scale)
     uint8_t *d_mask = nullptr;
     size_t mask_bytes = 0;
     float *d_stage = nullptr;
@@ -227,9 +191,7 @@ struct wf_hip {
     std::string last_error;
     std::string kernel_name;
     // launch description, fixed at create
-    void (*launch)(wf_hip *, const wf::TickArgs &, bool aligned) = nullptr;
-    hipStream_t launch_stream = nullptr; // where `launch` enqueues (the lane's stream, set by wf_hip_tick)
-    int launch_rc = 0;                   // status of the last `launch` that can fail before its kernels (the big path's memset)
+    int (*launch)(wf_hip *, const wf::TickArgs &, bool aligned, hipStream_t) = nullptr;
 };
 
 namespace wf::host {
@@ -287,6 +249,29 @@ template<class T> int upload(wf_hip *h, T **out, const std::vector<T> &v)
     WF_HIP_TRY(h, hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
     return WF_HIP_OK;
 }
+// the same into a table pointer of an argument struct (`const float *coef` ...)
+template<class T> int upload(wf_hip *h, const T **out, const std::vector<T> &v)
+{
+    T *p = nullptr;
+    const int rc = upload(h, &p, v);
+    *out = p;
+    return rc;
+}
+// ... and a complex table as the host builders leave it (wf::cfloat and wf::cf: the same two floats)
+inline int upload(wf_hip *h, const wf::cf **out, const std::vector<wf::cfloat> &v)
+{
+    static_assert(sizeof(wf::cfloat) == sizeof(wf::cf), "twiddle layout");
+    wf::cf *p = nullptr;
+    *out = nullptr;
+    if(v.empty())
+        return WF_HIP_OK;
+    const int rc = dev_alloc(h, &p, v.size());
+    if(rc)
+        return rc;
+    WF_HIP_TRY(h, hipMemcpyAsync(p, v.data(), v.size() * sizeof(wf::cf), hipMemcpyHostToDevice, h->stream));
+    *out = p;
+    return WF_HIP_OK;
+}
 
 inline uint32_t next_pow2(uint32_t v)
 {
@@ -305,6 +290,10 @@ int upload_words(wf_hip *h, void *d_dst, const void *src, size_t bytes);
 int join_lanes(wf_hip *h);
 int check_range(wf_hip *h, uint32_t first, uint32_t count);        // refuses a stream range outside the batch, then joins the lanes
 int read_back(wf_hip *h, const void *d, void *out, size_t bytes); // device to host on `stream`; returns when the bytes have arrived
+// the constant part of the small argument structs (h->small), for wf_hip_create
+void fill_meter_args(wf_hip *h);
+void fill_wave_args(wf_hip *h, uint32_t wave_samples);
+void fill_vertex_args(wf_hip *h, const wf::VertexTables &vt, const float *d_cap_xy);
 
 // wf_hip_measure.hip: the measurement outputs.  The ingest's two hooks -- what a push of `frames` must satisfy while a producer
 // follows the pushes, and that producer's launch behind the advance of the write positions (d_frames: a ragged push's counts)
@@ -318,16 +307,17 @@ int measure_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, 
 // ---- kernel dispatch -----------------------------------------------------------------------------------------------------
 // One object file per geometry (wf_tick_geom.hip compiled with -DWF_TU_GEOM=<N>): picks the spectrum_tick_kernel instantiation
 // of this handle's configuration (plain / staged tables / shared curve row / split / zero-padded / Bluestein / mixed radix),
-// sets its dynamic-LDS attribute and leaves h->launch, h->wg_lds, h->wg_threads, h->split, h->flag_bufs, h->kernel_name.
-int setup_tick_512(wf_hip *h, bool want_split);
-int setup_tick_1024(wf_hip *h, bool want_split);
-int setup_tick_2048(wf_hip *h, bool want_split);
-int setup_tick_4096(wf_hip *h, bool want_split);
-int setup_tick_8192(wf_hip *h, bool want_split);
-int setup_tick_16384(wf_hip *h, bool want_split);
-int setup_tick_32768(wf_hip *h, bool want_split);
+// sets its dynamic-LDS attribute and leaves h->launch, h->wg_lds, h->wg_threads, h->split, h->flag_bufs, h->kernel_name
+// (mixed radix: also the exchange buffer's size, h->tick.mr.half / s3 / lds_cf).  h->plan says which family; nothing is planned here.
+int setup_tick_512(wf_hip *h);
+int setup_tick_1024(wf_hip *h);
+int setup_tick_2048(wf_hip *h);
+int setup_tick_4096(wf_hip *h);
+int setup_tick_8192(wf_hip *h);
+int setup_tick_16384(wf_hip *h);
+int setup_tick_32768(wf_hip *h);
 // wf_big_dispatch.hip: fft sizes whose transform does not fit a CU's LDS, and big_outputs_kernel for the displays that are
-// finished behind the tick kernel (h->ext_outputs)
+// finished behind the tick kernel (h->disp.ext_outputs)
 int setup_launch_big(wf_hip *h);
 int big_outputs_set_lds(wf_hip *h);
 void big_outputs_launch(wf_hip *h, const wf::TickArgs &a, uint32_t rows, hipStream_t st);

@@ -1,7 +1,7 @@
 // wf_tick_geom.hip -- kernel dispatch of ONE FFT geometry: compiled once per geometry (-DWF_TU_GEOM=512 ... 32768, see the
 // Makefile), so that the ~70 instantiations of spectrum_tick_kernel build in parallel instead of in one translation unit.
 // Host side: the launch functions wf_hip_tick calls through wf_hip::launch, and setup_tick_<N>() which wf_hip_create
-// (wf_hip_plan.hip) calls to pick one.  gfx950 only.
+// (wf_hip_plan.hip) calls to map the handle's finished plan (wf_hip::plan, wf_tick_plan.hpp) to one of them; nothing is planned here.  gfx950 only.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -102,17 +102,19 @@ int setup_pow2_lds(wf_hip *h, int lds)
     return WF_HIP_OK;
 }
 
-template<class G> void launch_tick_split(wf_hip *h, const wf::TickArgs &a0, bool aligned)
+template<class G> int launch_tick_split(wf_hip *h, const wf::TickArgs &a0, bool aligned, hipStream_t st)
 {
     const dim3 block(G::T);
     const size_t lds = wf::tick_lds_bytes<G, 1>();
     // mono mixdown: channel 1 of every stream, then channel 0 (TickArgs::split_ch); stereo pairs: everything at once
-    for(int pass = 0; pass < (h->split_mono ? 2 : 1); ++pass) {
+    const bool two = h->plan.split_mono;
+    for(int pass = 0; pass < (two ? 2 : 1); ++pass) {
         wf::TickArgs a = a0;
-        a.split_ch = h->split_mono ? (uint32_t)(1 - pass) : 0xffffffffu;
-        const dim3 grid(h->split_mono ? a.stream_count : a.stream_count * a.cap_ch);
-        launch_pow2<G, 1, true, 0, false, false, true>(grid, block, lds, h->launch_stream, a, aligned);
+        a.split_ch = two ? (uint32_t)(1 - pass) : 0xffffffffu;
+        const dim3 grid(two ? a.stream_count : a.stream_count * a.cap_ch);
+        launch_pow2<G, 1, true, 0, false, false, true>(grid, block, lds, st, a, aligned);
     }
+    return WF_HIP_OK;
 }
 
 template<class G> int setup_launch_split(wf_hip *h)
@@ -131,12 +133,13 @@ template<class G> int setup_launch_split(wf_hip *h)
 }
 
 // FFT sizes 256 / 128 on the 512-point geometry, zero-padded (spectrum_tick_kernel<.., DEC>)
-template<class G, int DEC> void launch_tick_dec(wf_hip *h, const wf::TickArgs &a, bool aligned)
+template<class G, int DEC> int launch_tick_dec(wf_hip *, const wf::TickArgs &a, bool aligned, hipStream_t st)
 {
     const uint32_t n_spec = a.stream_count * a.cap_ch;
     const dim3 grid((n_spec + 1) / 2), block(G::T * 2);
     const size_t lds = wf::tick_lds_bytes<G, 2>();
-    launch_pow2<G, 2, false, DEC, false, false, false>(grid, block, lds, h->launch_stream, a, aligned);
+    launch_pow2<G, 2, false, DEC, false, false, false>(grid, block, lds, st, a, aligned);
+    return WF_HIP_OK;
 }
 
 template<class G, int DEC> int setup_launch_dec(wf_hip *h)
@@ -153,30 +156,30 @@ template<class G, int DEC> int setup_launch_dec(wf_hip *h)
 }
 
 // Bluestein path (FFT sizes that are not powers of two): always the scalar fetch
-template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> void launch_tick_blu(wf_hip *h, const wf::TickArgs &a0, bool)
+template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int launch_tick_blu(wf_hip *h, const wf::TickArgs &a0, bool, hipStream_t st)
 {
     const uint32_t n_spec = a0.stream_count * a0.cap_ch;
     const dim3 block(G::T * SPW);
     // (mixed radix: the exchange buffers by the transform's size, MrPlan::lds_cf)
-    const size_t lds = wf::tick_lds_bytes<G, SPW>() - (MR ? (size_t)SPW * ((size_t)G::LDS_CF - (size_t)h->mr_lds_cf) * sizeof(wf::cf) : 0);
-    const bool two = SPLIT && h->split_mono; // mono mixdown in two launches (TickArgs::split_ch)
+    const size_t lds = wf::tick_lds_bytes<G, SPW>() - (MR ? (size_t)SPW * ((size_t)G::LDS_CF - (size_t)a0.mr.lds_cf) * sizeof(wf::cf) : 0);
+    const bool two = SPLIT && h->plan.split_mono; // mono mixdown in two launches (TickArgs::split_ch)
     for(int pass = 0; pass < (two ? 2 : 1); ++pass) {
         wf::TickArgs a = a0;
         a.split_ch = two ? (uint32_t)(1 - pass) : 0xffffffffu;
         const dim3 grid(two ? a.stream_count : (n_spec + SPW - 1) / SPW);
         // (no display: the instantiation without any display code -- spectrum_tick_kernel<.., DISP = 2>; the sizes with a
-        // compile-time plan: the instantiation of that plan alone -- <.., PLAN>, wf_hip::mr_plan_id)
+        // compile-time plan: the instantiation of that plan alone -- <.., PLAN>, TransformPlan::plan_id)
         const bool nodisp = MRS && display_kind(a) == 2; // (the small-radix instantiation only: N = 4160 on the all-radix one measured -1.8 %)
 #define WF_LP(PLAN_)                                                                                                                                            \
     do {                                                                                                                                                       \
         if(nodisp)                                                                                                                                             \
-            hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = 2, .plan = PLAN_}>), grid, block, lds, h->launch_stream, a); \
+            hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = 2, .plan = PLAN_}>), grid, block, lds, st, a); \
         else                                                                                                                                                   \
-            hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .plan = PLAN_}>), grid, block, lds, h->launch_stream, a); \
+            hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .plan = PLAN_}>), grid, block, lds, st, a); \
     } while(0)
         if constexpr(MRS && (G::N == 2048 || G::N == 4096)) {
             constexpr int P0 = G::N == 2048 ? 1 : 5; // the container's four fixed plans (spectrum_tick_kernel's PLAN)
-            switch(h->mr_plan_id - P0) {
+            switch(h->plan.plan_id - P0) {
             case 0: WF_LP(P0); break;
             case 1: WF_LP(P0 + 1); break;
             case 2: WF_LP(P0 + 2); break;
@@ -187,57 +190,11 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> void l
             WF_LP(0);
 #undef WF_LP
     }
+    return WF_HIP_OK;
 }
 
 template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int setup_launch_blu(wf_hip *h)
 {
-    if constexpr(!MR && G::N >= 1024) { // (the smallest container a size that is not a power of two ever gets: wf::bluestein_length)
-        // sizes with small prime factors take the same instantiation's fetch and epilogue around a direct transform
-        bool direct = true;
-#ifdef WF_DEV_BUILD
-        if(const char *off = std::getenv("WF_HIP_NO_MIXED_RADIX")) // (development: A/B against Bluestein)
-            direct = off[0] != '1';
-#endif
-        const int passes = direct ? wf::plan_mixed_radix(h->N / 2, (uint32_t)G::T, h->mr_radix, (uint64_t)G::M) : 0;
-        if(passes > 0) {
-            h->mr_passes = passes;
-#ifdef WF_DEV_BUILD
-            if(const char *e = std::getenv("WF_HIP_MR_PLAN")) { // (development: "25,16" -- another order or split of the same product)
-                int r[4] = {0, 0, 0, 0}, n = 0;
-                uint64_t prod = 1;
-                for(const char *q = e; *q && n < 4;) {
-                    r[n] = std::atoi(q);
-                    prod *= (uint64_t)std::max(r[n], 1);
-                    ++n;
-                    while(*q && *q != ',') ++q;
-                    if(*q == ',') ++q;
-                }
-                bool ok = n >= 2 && prod == h->N / 2 && r[n - 1] <= 16 && (h->N / 2) / (uint32_t)r[n - 1] <= (uint32_t)G::T;
-                for(int i = 0; i < n; ++i) {
-                    const int v = r[i];
-                    ok = ok && (v == 2 || v == 3 || v == 4 || v == 5 || v == 6 || v == 8 || v == 9 || v == 10 || v == 12 || v == 15 || v == 16 || v == 7 || v == 11 || v == 13 ||
-                                (i == 0 && (v == 20 || v == 25 || v == 17 || v == 19 || v == 23 || v == h->mr_radix[0])));
-                }
-                if(ok) {
-                    h->mr_passes = n;
-                    for(int i = 0; i < 4; ++i)
-                        h->mr_radix[i] = r[i];
-                }
-            }
-#endif
-            // one-wavefront containers: plans made of small radices take the instantiation that carries only those (five waves per SIMD)
-            if constexpr(G::T <= 256 && G::P > 8) {
-                bool small = wf::mr_small_radices(h->mr_radix, h->mr_passes);
-#ifdef WF_DEV_BUILD
-                if(const char *e = std::getenv("WF_HIP_MR_SMALL")) // 0: the instantiation with every radix (A/B)
-                    small = small && e[0] != '0';
-#endif
-                if(small)
-                    return setup_launch_blu<G, SPW, SPLIT, true, true>(h);
-            }
-            return setup_launch_blu<G, SPW, SPLIT, true>(h);
-        }
-    }
     int lds = (int)wf::tick_lds_bytes<G, SPW>();
     // (the attribute belongs to the kernel, not to this handle: always the container's size -- another handle of another fft size
     // on the same instantiation may need all of it)
@@ -245,19 +202,9 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int se
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = 2}>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    h->mr_plan_id = 0;
     if constexpr(MRS && (G::N == 2048 || G::N == 4096)) {
-        // the sizes the plugin picks by itself run their plan as compile-time constants, in an instantiation of their own
-        static const int fixed[8][3] = {{5, 10, 8}, {5, 12, 8}, {10, 6, 6}, {11, 5, 8}, {10, 8, 10}, {10, 8, 12}, {10, 10, 10}, {10, 8, 11}};
+        // (the fixed plans of this container: TransformPlan::plan_id picks one per launch)
         constexpr int P0 = G::N == 2048 ? 1 : 5;
-        for(int i = 0; i < 4 && h->mr_passes == 3; ++i)
-            if(h->mr_radix[0] == fixed[P0 - 1 + i][0] && h->mr_radix[1] == fixed[P0 - 1 + i][1] && h->mr_radix[2] == fixed[P0 - 1 + i][2])
-                h->mr_plan_id = P0 + i;
-#ifdef WF_DEV_BUILD
-        if(const char *e = std::getenv("WF_HIP_MR_PLAN_KERNEL")) // 0: the instantiation that carries every plan (A/B)
-            if(e[0] == '0')
-                h->mr_plan_id = 0;
-#endif
 #define WF_AP(PLAN_)                                                                                                                                          \
     WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .plan = PLAN_}>), \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                                                       \
@@ -271,14 +218,15 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int se
     }
     if constexpr(MR) {
         // the spectrum's exchange buffer by the transform's size, not the container's (MrPlan::lds_cf): room for more spectra per CU
-        h->mr_half = (int)wf::mr_exchange_half(h->N / 2);
-        h->mr_lds_cf = (int)wf::mr_exchange_cf(h->N / 2, (uint32_t)G::LDS_CF);
-        h->mr_s3 = h->mr_half / 4 + 4;
+        wf::MrPlan &mr = h->tick.mr;
+        mr.half = (int)wf::mr_exchange_half(h->N / 2);
+        mr.lds_cf = (int)wf::mr_exchange_cf(h->N / 2, (uint32_t)G::LDS_CF);
+        mr.s3 = mr.half / 4 + 4;
         // the compile-time plans of the one-wavefront container run IN PLACE (mr_transform_fixed_inplace): without a display -- whose
         // planner has sized its staging by the two-halves buffer already -- the spectrum needs its points and the four-plane result only
-        if(G::T == 64 && h->mr_plan_id != 0 && h->num_bars == 0)
-            h->mr_lds_cf = std::min(h->mr_lds_cf, std::max(h->mr_half, 4 * h->mr_s3));
-        lds -= SPW * ((int)G::LDS_CF - h->mr_lds_cf) * (int)sizeof(wf::cf);
+        if(G::T == 64 && h->plan.plan_id != 0 && h->num_bars == 0)
+            mr.lds_cf = std::min(mr.lds_cf, std::max(mr.half, 4 * mr.s3));
+        lds -= SPW * ((int)G::LDS_CF - mr.lds_cf) * (int)sizeof(wf::cf);
     }
     h->launch = &launch_tick_blu<G, SPW, SPLIT, MR, MRS>;
     h->wg_lds = (uint32_t)lds;
@@ -288,8 +236,8 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int se
     if(MR) {
         char rad[48];
         int o = 0;
-        for(int i = 0; i < h->mr_passes; ++i)
-            o += snprintf(rad + o, sizeof(rad) - (size_t)o, "%s%d", i ? "x" : "", h->mr_radix[i]);
+        for(int i = 0; i < h->tick.mr.passes; ++i)
+            o += snprintf(rad + o, sizeof(rad) - (size_t)o, "%s%d", i ? "x" : "", h->tick.mr.radix[i]);
         snprintf(name, sizeof(name), "spectrum_tick_kernel<N=%u: %u complex points as mixed radix %s,T=%d,SPW=%d%s>", h->N, h->N / 2, rad, G::T, SPW,
                  SPLIT ? ",split" : "");
     } else
@@ -299,12 +247,29 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int se
     return WF_HIP_OK;
 }
 
-template<class G, int SPW, bool TLDS, bool BOTH = false> void launch_tick(wf_hip *h, const wf::TickArgs &a, bool aligned)
+// Bluestein proper, or -- the plan has passes -- the same instantiation's fetch and epilogue around a direct mixed-radix transform;
+// one-wavefront containers: plans made of small radices take the instantiation that carries only those (five waves per SIMD)
+template<class G, int SPW, bool SPLIT> int setup_blu_family(wf_hip *h)
+{
+    if constexpr(G::N >= 1024) { // (the smallest container a size that is not a power of two ever gets: wf::bluestein_length)
+        if(h->plan.mr_in_lds()) {
+            if constexpr(G::T <= 256 && G::P > 8) {
+                if(h->plan.mr_small)
+                    return setup_launch_blu<G, SPW, SPLIT, true, true>(h);
+            }
+            return setup_launch_blu<G, SPW, SPLIT, true>(h);
+        }
+    }
+    return setup_launch_blu<G, SPW, SPLIT>(h);
+}
+
+template<class G, int SPW, bool TLDS, bool BOTH = false> int launch_tick(wf_hip *, const wf::TickArgs &a, bool aligned, hipStream_t st)
 {
     const uint32_t n_spec = a.stream_count * a.cap_ch;
     const dim3 grid((n_spec + SPW - 1) / SPW), block(G::T * SPW);
     const size_t lds = wf::tick_lds_bytes<G, SPW>();
-    launch_pow2<G, SPW, false, 0, TLDS, BOTH, !BOTH>(grid, block, lds, h->launch_stream, a, aligned);
+    launch_pow2<G, SPW, false, 0, TLDS, BOTH, !BOTH>(grid, block, lds, st, a, aligned);
+    return WF_HIP_OK;
 }
 
 template<class G, int SPW, bool TLDS, bool BOTH = false> int setup_launch_impl(wf_hip *h)
@@ -334,7 +299,7 @@ template<class G, int SPW> int setup_launch(wf_hip *h)
             tlds = e[0] == '1';
 #endif
         // mono mixdown with a curve display: the kernel whose two spectra share the row (a TLDS override keeps the plain one)
-        if(h->curve_both && h->N == (uint32_t)G::N && tlds == (G::P <= 8)) {
+        if(h->tick.bar.both_subs && h->N == (uint32_t)G::N && tlds == (G::P <= 8)) {
             if constexpr(G::P <= 8)
                 return setup_launch_impl<G, 2, true, true>(h);
             else
@@ -347,25 +312,26 @@ template<class G, int SPW> int setup_launch(wf_hip *h)
 }
 
 // the kernel of this handle on geometry G: which of the instantiations above its configuration takes
-template<class G> int setup_tick_geometry(wf_hip *h, bool want_split)
+template<class G> int setup_tick_geometry(wf_hip *h)
 {
     const wf_config *cfg = &h->cfg;
+    const bool want_split = h->plan.want_split;
     h->waves_per_spectrum = G::T / 64;
-    if(h->blu) {
+    if(h->plan.blu) {
         if constexpr(G::N >= 32768) {
             // (the Bluestein and mixed-radix instantiations of this container keep 1024 threads of 16 points: a mixed-radix
             // plan's last pass has one butterfly per thread at most, and 39 sizes have no plan on 512 threads)
             using GB = wf::GBig;
             h->waves_per_spectrum = GB::T / 64;
             if(want_split)
-                return setup_launch_blu<GB, 1, true>(h);
+                return setup_blu_family<GB, 1, true>(h);
             if(cfg->capture_channels == 1)
-                return setup_launch_blu<GB, 1, false>(h);
+                return setup_blu_family<GB, 1, false>(h);
             return fail(h, WF_HIP_ERR_RUNTIME, "fft_size %u: no launch plan", cfg->fft_size);
         } else if constexpr(G::T >= 256)
-            return want_split ? setup_launch_blu<G, 1, true>(h) : (cfg->capture_channels > 1) ? setup_launch_blu<G, 2, false>(h) : setup_launch_blu<G, 1, false>(h);
+            return want_split ? setup_blu_family<G, 1, true>(h) : (cfg->capture_channels > 1) ? setup_blu_family<G, 2, false>(h) : setup_blu_family<G, 1, false>(h);
         else
-            return setup_launch_blu<G, 2, false>(h);
+            return setup_blu_family<G, 2, false>(h);
     } else if constexpr(G::N == 512) {
         switch(h->N) {
         case 256: return setup_launch_dec<G, 1>(h);
@@ -392,13 +358,12 @@ namespace wf::host {
 
 #define WF_CAT2(a, b) a##b
 #define WF_CAT(a, b) WF_CAT2(a, b)
-int WF_CAT(setup_tick_, WF_TU_GEOM)(wf_hip *h, bool want_split)
+int WF_CAT(setup_tick_, WF_TU_GEOM)(wf_hip *h)
 {
-#if defined(WF_GEOM_ONLY) && (WF_GEOM_ONLY != WF_TU_GEOM)
-    (void)want_split; // development builds: one geometry only (tools/variant.sh)
+#if defined(WF_GEOM_ONLY) && (WF_GEOM_ONLY != WF_TU_GEOM) // development builds: one geometry only (tools/variant.sh)
     return fail(h, WF_HIP_ERR_UNSUPPORTED, "development build: only the %d-sample geometry is compiled in", WF_GEOM_ONLY);
 #else
-    return setup_tick_geometry<WF_CAT(wf::G, WF_TU_GEOM)>(h, want_split);
+    return setup_tick_geometry<WF_CAT(wf::G, WF_TU_GEOM)>(h);
 #endif
 }
 
