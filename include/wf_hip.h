@@ -46,6 +46,8 @@
  *                        newest audio in the rings, correlated in float64 on the device when read
  *   WF_HIP_OUT_SCOPE     not in the reference (its "waveform" mode is a level history, not the wave): a triggered oscilloscope
  *                        trace of every stream's newest window of audio, triggered and reduced to columns on the device when read
+ *   WF_HIP_OUT_GONIO     not in the reference: a stereo vectorscope (goniometer), the mid/side Lissajous picture of every stream's
+ *                        newest window of audio as a 64 x 64 image of frame counts, ranged and counted on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -396,9 +398,13 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_CQ,             /* wf_hip_cq                                  constant-Q spectrum: one level per semitone and captured
                                   channel, each over its own Q periods of the newest frames in the rings as of the pushes issued
                                   so far (spectrum and meter batches; definition below) */
-    WF_HIP_OUT_SCOPE           /* wf_hip_scope                               oscilloscope: the smallest and largest sample per display
+    WF_HIP_OUT_SCOPE,          /* wf_hip_scope                               oscilloscope: the smallest and largest sample per display
                                   column of a triggered view of the newest min(wf_hip_fft_size(), 8192) frames in the rings as of
                                   the pushes issued so far (spectrum and meter batches; definition below) */
+    WF_HIP_OUT_GONIO           /* wf_hip_gonio                               vectorscope: how many of the newest
+                                  min(wf_hip_fft_size(), 8192) frames in the rings, as of the pushes issued so far, fall into each
+                                  cell of a 64 x 64 side / mid picture that a power of two magnifies to the peak (spectrum and
+                                  meter batches with two captured channels; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -712,6 +718,59 @@ typedef struct wf_hip_scope {
     float frac;         /* see above */
     uint32_t reserved;  /* 0 */
 } wf_hip_scope;         /* 4128 bytes */
+/* ---- vectorscope (WF_HIP_OUT_GONIO) ------------------------------------------------------------------------------------------
+ * Per stream, the goniometer of a metering suite: the L/R Lissajous picture, turned so that mid points up and side to the right, as
+ * an image of G x G cells that count frames.  W = wf_hip_fft_size(); l and r are captured channels 0 and 1.  Everything below
+ * consists of comparisons, integer counting, exact float64 operations and single correctly rounded IEEE operations: a host that
+ * restates it reproduces every field bit for bit (tests/gonio_ref.py does).
+ *   window         P = min(W, WF_HIP_GONIO_MAX_WINDOW) frames: the newest P frames of both rings, positions
+ *                  (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of WF_HIP_OUT_SIGNAL: every push issued before
+ *                  the read counts whatever its path, the A/V-sync delay is not applied, the zeros of create and wf_hip_reset
+ *                  count as samples.  Hidden and paused streams are read like any other.
+ *   peak           A = the largest |l[i]|, |r[i]| over the window, as float32.
+ *   zoom           an automatic range, by a power of two so that it is exact.  If A == 0 then e = 0; otherwise A = f 2^e with
+ *                  0.5 <= f < 1 (frexp), and e is raised to at least WF_HIP_GONIO_MIN_EXP.  zoom = -e: the picture is magnified
+ *                  by 2^zoom, and the loudest sample lies between half and full deflection for every level from -144 dBFS up to
+ *                  above full scale.  No state is kept between reads: a host that dislikes the range flipping while the peak
+ *                  hovers at a power of two applies its own hysteresis when drawing ("Vectorscope").
+ *   coordinates    in float64: x = (r - l) * 0.5 is the side signal, y = (l + r) * 0.5 the mid signal -- the left channel points
+ *                  up-left and the right channel up-right, the usual orientation --, u = x * 2^-e and v = y * 2^-e.  The
+ *                  subtraction and the addition are one IEEE float64 operation each; every scaling is exact.
+ *   cell           G = WF_HIP_GONIO_GRID.  ix = (int) min(max(floor((u + 1.0) * (G / 2)), 0.0), G - 1.0), and iy the same from
+ *                  v: an addition, then an exact multiplication.  Without the clamp of e every index is in range by construction
+ *                  (|u|, |v| < 1); with it the clamped indices collect on the border.  The min / max is taken in floating point
+ *                  before the conversion to integer, so that whatever the samples hold, no index leaves the grid.  Behaviour
+ *                  for non-finite samples is otherwise not defined.
+ *   image          cell[iy][ix] is the number of frames of the window that fall into the cell (P <= 8192: a uint16 cannot
+ *                  overflow).  Row 0 is v = -1, the bottom of the picture.  The cells always add up to P.
+ *   scalars        window = P; peak = A; mid_peak = max |y| and side_peak = max |x|, each taken in float64 and rounded to
+ *                  float32 once; in_phase = frames with l and r both > 0 or both < 0, out_phase = frames where one is > 0 and the
+ *                  other < 0 (sign comparisons, not a product: a zero sample counts in neither); occupied = the number of
+ *                  non-zero cells.
+ *   determinism    the only accumulation is integer counting, which commutes: the same ring contents read bit-identically
+ *                  across push paths, repeated reads, slices and shards.
+ * Cell (ix, iy) covers side in [(ix - G/2) / (G/2), (ix - G/2 + 1) / (G/2)) * 2^-zoom and mid likewise from iy.  Computed when
+ * read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup per stream, the window of both
+ * channels staged in LDS once, the count by integer LDS atomics that neighbouring lanes of equal cell share), into a block the first
+ * read allocates: a handle that never reads it allocates and launches nothing new.  Cost on an MI355X, 4096 stereo streams, read
+ * into page-locked memory (33.7 MB back): 0.69 / 0.70 / 0.66 ms at W = 4096 for independent noise / a mono source / silence against
+ * 2.36 ms for copying the windows to the host, 0.76 / 0.80 / 0.70 ms against 4.71 ms at W = 16384; into pageable memory the read's
+ * own copy takes about 3 ms (tools/gonio_bench.py, profiles/gonio_kernel_stats.json; INTEGRATION.md, "Vectorscope").
+ * Spectrum and meter batches with two captured channels are served, whatever cfg.stereo says (a mono mixdown still captures two),
+ * and there is no lower limit on W; with one captured channel and on waveform batches wf_hip_read returns WF_HIP_ERR_INVALID and
+ * wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_GONIO_GRID 64
+#define WF_HIP_GONIO_MAX_WINDOW 8192
+#define WF_HIP_GONIO_MIN_EXP (-24)
+typedef struct wf_hip_gonio {
+    uint16_t cell[WF_HIP_GONIO_GRID][WF_HIP_GONIO_GRID]; /* [iy][ix] */
+    uint32_t window;    /* P */
+    int32_t  zoom;      /* the picture is magnified by 2^zoom */
+    float    peak;      /* A */
+    float    mid_peak;  /* max |(l + r) / 2| */
+    float    side_peak; /* max |(r - l) / 2| */
+    uint32_t in_phase, out_phase, occupied;
+} wf_hip_gonio;         /* 8224 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

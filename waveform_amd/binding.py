@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE = range(18)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO = range(19)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -168,6 +168,16 @@ SCOPE_COLUMNS = 256  # WF_HIP_SCOPE_COLUMNS
 SCOPE_DTYPE = np.dtype([("lo", np.float32, (2, SCOPE_COLUMNS)), ("hi", np.float32, (2, SCOPE_COLUMNS)), ("window", np.uint32),
                         ("view", np.uint32), ("columns", np.uint32), ("start", np.uint32), ("triggered", np.uint32),
                         ("period", np.uint32), ("frac", np.float32), ("reserved", np.uint32)])
+
+# struct wf_hip_gonio (include/wf_hip.h): the vectorscope, how many of the newest P = min(fft_size, GONIO_MAX_WINDOW) frames of
+# captured channels 0 and 1 fall into each cell [iy][ix] of a GONIO_GRID x GONIO_GRID picture of side (x) against mid (y), which
+# 2^zoom magnifies so that the loudest sample lies between half and full deflection
+GONIO_GRID = 64  # WF_HIP_GONIO_GRID
+GONIO_MAX_WINDOW = 8192  # WF_HIP_GONIO_MAX_WINDOW
+GONIO_MIN_EXP = -24  # WF_HIP_GONIO_MIN_EXP: zoom <= 24
+GONIO_DTYPE = np.dtype([("cell", np.uint16, (GONIO_GRID, GONIO_GRID)), ("window", np.uint32), ("zoom", np.int32), ("peak", np.float32),
+                        ("mid_peak", np.float32), ("side_peak", np.float32), ("in_phase", np.uint32), ("out_phase", np.uint32),
+                        ("occupied", np.uint32)])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -371,6 +381,15 @@ class _MeasureReaders:
         ring as of the pushes issued so far, with the trigger's position, sub-sample fraction and period; made on the device
         when read"""
         return _read_measure(self, "scope", first, count)
+
+    def gonio(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_gonio (GONIO_DTYPE): the vectorscope, cell[iy][ix] = how many of the newest
+        min(fft_size, GONIO_MAX_WINDOW) frames of captured channels 0 and 1, as of the pushes issued so far, fall into each cell
+        of the side (x) / mid (y) picture magnified by 2^zoom, with the peaks, the phase counts and the number of occupied cells;
+        counted on the device when read (batches with two captured channels)"""
+        # (not through _read_measure: MEASURES keeps the eight keys tests/test_measure_tables_cpu.py pins; folding this reader
+        # into the table is for a change that may touch that test)
+        return self._read(OUT_GONIO, first, count, (), GONIO_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

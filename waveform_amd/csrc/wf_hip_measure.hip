@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ and _SCOPE.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE and _GONIO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -27,6 +27,7 @@
 #include "wf_stereo.hpp"
 #include "wf_cq.hpp"
 #include "wf_scope.hpp"
+#include "wf_gonio.hpp"
 
 namespace {
 
@@ -234,6 +235,31 @@ int launch_scope(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// the vectorscope's window: the newest min(fft_size, WF_HIP_GONIO_MAX_WINDOW) frames (<= ring_cap)
+uint32_t gonio_window(const wf_hip *h) { return std::min<uint32_t>(h->N, WF_HIP_GONIO_MAX_WINDOW); }
+
+// the vectorscope has no tables either: its kernel's dynamic LDS is all its first read asks for
+int setup_gonio(wf_hip *h)
+{
+    // (about 74 KB at the cap, both windows and the entry's image behind them: more than a workgroup gets without asking, and two
+    // workgroups to a CU)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::gonio_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::gonio_lds_bytes(WF_HIP_GONIO_MAX_WINDOW)));
+    return WF_HIP_OK;
+}
+
+// one workgroup per stream over its newest P frames of both captured channels, behind the pushes issued
+int launch_gonio(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    wf::GonioArgs a{};
+    a.rings = ring_view(h);
+    a.out = static_cast<wf_hip_gonio *>(d_block) + first;
+    a.first = first;
+    a.P = gonio_window(h);
+    hipLaunchKernelGGL(wf::gonio_read_kernel, dim3(count), dim3(wf::WF_GONIO_THREADS), wf::gonio_lds_bytes(a.P), h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -270,6 +296,13 @@ const char *why_no_scope(const wf_hip *h)
     return h->N < 64 ? "the oscilloscope needs a window of at least 64 frames" : nullptr;
 }
 
+const char *why_no_gonio(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the vectorscope belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->cap_ch != 2 ? "one captured channel: the vectorscope needs two (capture_channels == 2)" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -289,6 +322,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_STEREO, sizeof(wf_hip_stereo), false, why_no_stereo, setup_stereo, launch_stereo},
     {WF_HIP_OUT_CQ, sizeof(wf_hip_cq), false, why_no_cq, setup_cq, launch_cq},
     {WF_HIP_OUT_SCOPE, sizeof(wf_hip_scope), false, why_no_scope, setup_scope, launch_scope},
+    {WF_HIP_OUT_GONIO, sizeof(wf_hip_gonio), false, why_no_gonio, setup_gonio, launch_gonio},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
