@@ -48,6 +48,9 @@
  *                        trace of every stream's newest window of audio, triggered and reduced to columns on the device when read
  *   WF_HIP_OUT_GONIO     not in the reference: a stereo vectorscope (goniometer), the mid/side Lissajous picture of every stream's
  *                        newest window of audio as a 64 x 64 image of frame counts, ranged and counted on the device when read
+ *   WF_HIP_OUT_SONO      not in the reference: a spectrogram (sonogram) of every stream's newest audio in the rings, up to 64
+ *                        columns 256 frames apart by 64 bands of an eighth of an octave, the columns anchored to the stream's
+ *                        sample counter, transformed in float64 on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -401,10 +404,14 @@ typedef enum wf_hip_output {
     WF_HIP_OUT_SCOPE,          /* wf_hip_scope                               oscilloscope: the smallest and largest sample per display
                                   column of a triggered view of the newest min(wf_hip_fft_size(), 8192) frames in the rings as of
                                   the pushes issued so far (spectrum and meter batches; definition below) */
-    WF_HIP_OUT_GONIO           /* wf_hip_gonio                               vectorscope: how many of the newest
+    WF_HIP_OUT_GONIO,          /* wf_hip_gonio                               vectorscope: how many of the newest
                                   min(wf_hip_fft_size(), 8192) frames in the rings, as of the pushes issued so far, fall into each
                                   cell of a 64 x 64 side / mid picture that a power of two magnifies to the peak (spectrum and
                                   meter batches with two captured channels; definition below) */
+    WF_HIP_OUT_SONO            /* wf_hip_sono                                sonogram: the level in 64 bands of an eighth of an
+                                  octave of up to 64 windows of 1024 frames, 256 frames apart and anchored to the sample counter,
+                                  of the audio in the rings as of the pushes issued so far (spectrum and meter batches with a ring
+                                  of at least 2048 frames; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -771,6 +778,70 @@ typedef struct wf_hip_gonio {
     float    side_peak; /* max |(r - l) / 2| */
     uint32_t in_phase, out_phase, occupied;
 } wf_hip_gonio;         /* 8224 bytes, a multiple of 16 */
+/* ---- sonogram (WF_HIP_OUT_SONO) ---------------------------------------------------------------------------------------------
+ * Per stream, the spectrogram of a metering suite: level against time and frequency, from the audio the rings hold.  Every other
+ * spectral output is a view of one tick's rows, with the tick's time step (a video frame, about 800 frames of audio) and its smear
+ * (one FFT window, 85 ms at 4096); this one has a step of 256 frames and a window of 1024, so that a consonant, a click, a
+ * drop-out or a drum hit shows.  sr = cfg.sample_rate; everything is float64 unless it says otherwise.
+ *   constants      P = WF_HIP_SONO_WINDOW = 1024 frames, H = WF_HIP_SONO_HOP = 256 frames, WF_HIP_SONO_COLUMNS = 64,
+ *                  WF_HIP_SONO_BANDS = 64.
+ *   columns        wpos is the stream's uint32 write counter as of the pushes issued so far, with the rules of WF_HIP_OUT_SIGNAL:
+ *                  every push counts whatever its path, the A/V-sync delay is not applied, the zeros of create and wf_hip_reset
+ *                  count as samples, hidden and paused streams are read like any other.  newest = wpos / H (integer division) is
+ *                  the absolute index of the newest complete column, and column index n covers counter frames [n H - P, n H), at
+ *                  ring positions masked by the capacity: columns are anchored to the counter, not to "now", so column n covers
+ *                  the same frames whenever it is read.  All of this arithmetic is uint32 and wraps with the counter; H and the
+ *                  capacity divide 2^32, so nothing breaks at the wrap.  columns = T = min(64, (ring_cap - P) / H): the oldest
+ *                  column read starts at most (T - 1) H + P + (H - 1) < ring_cap frames back and is always still in the ring.  T
+ *                  depends on the ring alone: 28 for the default ring of 8192 frames, 64 from 32768 up (wf_hip_create's
+ *                  ring_frames).  The entry is indexed by age: db[c][a][b] with a = 0 column `newest` and a < T column
+ *                  newest - a; columns a >= T read -INFINITY.  A host that keeps a waterfall of any length appends the
+ *                  (newest_now - newest_before) mod 2^32 / H new columns of each read, at whatever rate it reads.
+ *   transform      the window is w[i] = 0.5 - 0.5 cos(2 pi i / P), a host-made table.  With two captured channels
+ *                  z[i] = w[i] (l[i] + j r[i]) and Z is its forward DFT with the kernel e^(-j 2 pi i k / P); L[k] and R[k] are
+ *                  separated as WF_HIP_OUT_STEREO does it, L = (Z[k] + conj Z[P - k]) / 2, R = (Z[k] - conj Z[P - k]) / 2j, so
+ *                  that one complex transform serves both channels.  With one captured channel z = w x and X = Z.  Twiddles
+ *                  come from a host-made table.
+ *   bands          the band edges are e[j] = 62.5 * 2^(j / 8) Hz, j = 0 .. 64: eight bands to the octave from 62.5 Hz to 16 kHz;
+ *                  in bins E[j] = e[j] P / sr.  weight(b, k) = max(min(k + 0.5, E[b+1]) - max(k - 0.5, E[b]), 0) for
+ *                  k = 1 .. P/2 - 1, the overlap rule of WF_HIP_OUT_BANDS, and B_c[b] = sum_k weight(b, k) |X_c[k]|^2.  A band
+ *                  narrower than a bin takes its share of that bin: at 48 kHz a bin is 46.9 Hz wide and the bands below about
+ *                  400 Hz are narrower, so the bottom of the picture is blurred by the 21 ms window, not by the grid.
+ *   cell           db = 10 log10(B_c[b] * 32 / (3 P^2)), rounded to float32 once; -INFINITY when the power is 0.  The factor is
+ *                  the periodic Hann's coherent gain 1/2 and its noise bandwidth of exactly 1.5 bins: a sine of amplitude A whose
+ *                  main lobe lies inside the band range reads 20 log10 A, summed over the bands of a column as powers (0.5 at
+ *                  1 kHz and at 5 kHz: -6.0206 dB to 1e-8).  With two channels a band power below WF_HIP_STEREO_DEAD_RATIO times
+ *                  the other channel's in the same band and column counts as 0, the stereo image's rule for a dead channel and
+ *                  for the same reason.  With one captured channel db[1] reads -INFINITY throughout.
+ *   covered        first_covered is the lowest b with E[b] >= 0.5, end_covered the count of bands with E[b+1] <= P/2 - 0.5; both
+ *                  depend on sr alone (0 and 64 at 48000 and 44100, 0 and 47 at 8000, 5 and 64 at 192000).  A band partly inside
+ *                  the spectrum reports what lies inside; a band with no overlap reads -INFINITY.
+ *   determinism    there are no atomics and every sum runs in an order fixed by P and the edges: the same column index reads
+ *                  bit-identically across reads, push paths, slices and shards for as long as its frames are in the ring.
+ * Resolution: a column is 21.3 ms of audio at 48 kHz and columns are 5.3 ms apart; 64 columns span 0.34 s, 28 columns 0.15 s.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one wavefront per column, four columns
+ * to a workgroup, a float64 transform in LDS), into a block the first read allocates together with its tables: a handle that never
+ * reads it allocates and launches nothing new, and no state is kept between reads -- averaging, peak hold and a longer history are
+ * the host's, and `newest` makes them exact.  Cost on an MI355X, 4096 stereo streams at FFT 4096 read into page-locked memory
+ * (134.3 MB back, whatever T): 3.42 ms with the default ring (T = 28) against 4.71 ms for copying the 268.4 MB of both rings that
+ * the columns span to the host, 3.86 ms with ring_frames = 32768 (T = 64) against 10.00 ms for its 570.4 MB; into pageable memory
+ * the read's own copy takes 12 to 13 ms and loses to either (tools/sono_bench.py, profiles/sono_kernel_stats.json;
+ * INTEGRATION.md, "Sonogram").
+ * Spectrum and meter batches with one or two captured channels and any FFT size are served; on waveform batches and on handles
+ * whose ring holds fewer than 2048 frames (T would be below 4) wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.
+ * A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_SONO_WINDOW 1024
+#define WF_HIP_SONO_HOP 256
+#define WF_HIP_SONO_COLUMNS 64
+#define WF_HIP_SONO_BANDS 64
+typedef struct wf_hip_sono {
+    float db[2][WF_HIP_SONO_COLUMNS][WF_HIP_SONO_BANDS]; /* [channel][age][band] */
+    uint32_t columns;        /* T */
+    uint32_t newest;         /* wpos / H: the absolute index of the column of age 0 */
+    uint32_t first_covered, end_covered;
+    uint32_t window, hop;    /* P, H */
+    uint32_t reserved[2];    /* 0 */
+} wf_hip_sono;               /* 32800 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO = range(19)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO = range(20)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -178,6 +178,17 @@ GONIO_MIN_EXP = -24  # WF_HIP_GONIO_MIN_EXP: zoom <= 24
 GONIO_DTYPE = np.dtype([("cell", np.uint16, (GONIO_GRID, GONIO_GRID)), ("window", np.uint32), ("zoom", np.int32), ("peak", np.float32),
                         ("mid_peak", np.float32), ("side_peak", np.float32), ("in_phase", np.uint32), ("out_phase", np.uint32),
                         ("occupied", np.uint32)])
+
+# struct wf_hip_sono (include/wf_hip.h): the sonogram, db[channel][age][band] = the level in band b (SONO_EDGES_HZ[b] to [b + 1]) of
+# the window of SONO_WINDOW frames that ends at counter frame (newest - age) * SONO_HOP, for age < columns; -inf beyond
+SONO_WINDOW = 1024  # WF_HIP_SONO_WINDOW
+SONO_HOP = 256  # WF_HIP_SONO_HOP
+SONO_COLUMNS = 64  # WF_HIP_SONO_COLUMNS
+SONO_BANDS = 64  # WF_HIP_SONO_BANDS
+SONO_EDGES_HZ = 62.5 * np.exp2(np.arange(SONO_BANDS + 1, dtype=np.float64) / 8.0)  # eight bands to the octave, 62.5 Hz to 16 kHz
+SONO_DTYPE = np.dtype([("db", np.float32, (2, SONO_COLUMNS, SONO_BANDS)), ("columns", np.uint32), ("newest", np.uint32),
+                       ("first_covered", np.uint32), ("end_covered", np.uint32), ("window", np.uint32), ("hop", np.uint32),
+                       ("reserved", np.uint32, (2,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -390,6 +401,16 @@ class _MeasureReaders:
         # (not through _read_measure: MEASURES keeps the eight keys tests/test_measure_tables_cpu.py pins; folding this reader
         # into the table is for a change that may touch that test)
         return self._read(OUT_GONIO, first, count, (), GONIO_DTYPE)
+
+    def sono(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_sono (SONO_DTYPE): the sonogram, db[channel][age][band] = the level in dB of band
+        `band` (SONO_EDGES_HZ) in the Hann window of SONO_WINDOW frames that ends at frame (newest - age) * SONO_HOP of the stream's
+        sample counter, for age < columns (which the ring decides: 28 by default, 64 from ring_frames = 32768 up); -inf beyond,
+        for silence, and for channel 1 of a capture of one channel.  Columns are anchored to the counter: the same column reads
+        the same bits whenever it is read, and (newest - newest of the last read) mod 2^24 columns are new.  Transformed in float64
+        on the device when read, from the rings as of the pushes issued so far (batches whose ring holds at least 2048 frames)"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_SONO, first, count, (), SONO_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

@@ -1567,6 +1567,7 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
     case WF_HIP_OUT_CQ:
     case WF_HIP_OUT_SCOPE:
     case WF_HIP_OUT_GONIO:
+    case WF_HIP_OUT_SONO:
         break; // (never asked here: measure_source answers for them)
     }
     *why = "unknown output";

@@ -128,7 +128,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    static constexpr int N_MEASURES = 9;
+    static constexpr int N_MEASURES = 10;
     char *d_measure[N_MEASURES] = {};
     bool measure_ready[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
@@ -157,6 +157,12 @@ struct wf_hip {
         uint32_t max_window = 0;                  // Lmax
         uint32_t end_covered = 0, first_resolved = 0;
     } cq;
+    // what WF_HIP_OUT_SONO derives from the sample rate and the ring (setup_sono, at its first read: wf::host::sono_tables; wf_sono.hpp)
+    struct Sono {
+        double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_SONO_BANDS + 1] band edges in bins of P
+        uint32_t columns = 0;                     // T
+        uint32_t first_covered = 0, end_covered = 0;
+    } sono;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE and _GONIO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO and _SONO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -28,6 +28,7 @@
 #include "wf_cq.hpp"
 #include "wf_scope.hpp"
 #include "wf_gonio.hpp"
+#include "wf_sono.hpp"
 
 namespace {
 
@@ -260,6 +261,50 @@ int launch_gonio(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the sonogram derives from the sample rate and the ring alone (wf::host::sono_tables), in one block
+int setup_sono(wf_hip *h)
+{
+    wf_hip::Sono &s = h->sono;
+    const SonoTables t = sono_tables(h->cfg.sample_rate, h->ring_cap);
+    s.columns = t.columns;
+    s.first_covered = t.first_covered;
+    s.end_covered = t.end_covered;
+    // (64 KB, four columns' transforms: the most a workgroup gets without asking; asked for all the same, so that the limit is
+    // stated here.  Two workgroups to a CU)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::sono_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::WF_SONO_LDS_BYTES));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::sono_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::WF_SONO_LDS_BYTES));
+    return upload(h, &s.d_tab, t.tab); // (pageable memory: staged before the call returns)
+}
+
+// one wavefront per column, four columns to a workgroup, over the newest T columns of every captured channel's ring, behind the
+// pushes issued
+int launch_sono(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Sono &s = h->sono;
+    constexpr uint32_t P = WF_HIP_SONO_WINDOW;
+    wf::SonoArgs a{};
+    a.rings = ring_view(h);
+    a.window = s.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(s.d_tab + P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.edges = s.d_tab + 2 * (size_t)P;
+    a.columns = s.columns; // (>= 4: why_no_sono)
+    a.first_covered = s.first_covered;
+    a.end_covered = s.end_covered;
+    // (streams are indexed by blockIdx.y, at most 65535: larger ranges go out in parts)
+    for(uint32_t off = 0; off < count; off += 65535u) {
+        const dim3 grid((s.columns + wf::WF_SONO_WAVES - 1) / wf::WF_SONO_WAVES, std::min(65535u, count - off));
+        a.out = static_cast<wf_hip_sono *>(d_block) + first + off;
+        a.first = first + off;
+        if(h->cap_ch == 2)
+            hipLaunchKernelGGL(wf::sono_read_kernel<2>, grid, dim3(wf::WF_SONO_THREADS), wf::WF_SONO_LDS_BYTES, h->stream, a);
+        else
+            hipLaunchKernelGGL(wf::sono_read_kernel<1>, grid, dim3(wf::WF_SONO_THREADS), wf::WF_SONO_LDS_BYTES, h->stream, a);
+    }
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -303,6 +348,13 @@ const char *why_no_gonio(const wf_hip *h)
     return h->cap_ch != 2 ? "one captured channel: the vectorscope needs two (capture_channels == 2)" : nullptr;
 }
 
+const char *why_no_sono(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the sonogram belongs to spectrum and meter batches";
+    return h->ring_cap < 2 * WF_HIP_SONO_WINDOW ? "the sonogram needs a ring of at least 2048 frames (wf_hip_create's ring_frames)" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -323,6 +375,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_CQ, sizeof(wf_hip_cq), false, why_no_cq, setup_cq, launch_cq},
     {WF_HIP_OUT_SCOPE, sizeof(wf_hip_scope), false, why_no_scope, setup_scope, launch_scope},
     {WF_HIP_OUT_GONIO, sizeof(wf_hip_gonio), false, why_no_gonio, setup_gonio, launch_gonio},
+    {WF_HIP_OUT_SONO, sizeof(wf_hip_sono), false, why_no_sono, setup_sono, launch_sono},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output

@@ -156,4 +156,33 @@ CqTables cq_tables(uint32_t sample_rate, uint32_t ring_cap)
     return q;
 }
 
+SonoTables sono_tables(uint32_t sample_rate, uint32_t ring_cap)
+{
+    SonoTables s;
+    constexpr uint32_t P = WF_HIP_SONO_WINDOW, H = WF_HIP_SONO_HOP, B = WF_HIP_SONO_BANDS;
+    s.columns = ring_cap > P ? std::min<uint32_t>(WF_HIP_SONO_COLUMNS, (ring_cap - P) / H) : 0u;
+    std::vector<double> &tab = s.tab;
+    tab.resize((size_t)2 * P + B + 1);
+    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
+    for(uint32_t i = 0; i < P; ++i)
+        tab[i] = (double)(0.5L - 0.5L * std::cos(two_pi * (long double)i / (long double)P));
+    for(uint32_t m = 0; m < P / 2; ++m) {
+        const long double x = two_pi * (long double)m / (long double)P;
+        tab[P + 2 * (size_t)m] = (double)std::cos(x);
+        tab[P + 2 * (size_t)m + 1] = (double)-sin_alone(x);
+    }
+    double *edges = tab.data() + 2 * (size_t)P;
+    for(uint32_t j = 0; j <= B; ++j)
+        edges[j] = 62.5 * std::exp2((double)j / 8.0) * (double)P / (double)sample_rate;
+    s.first_covered = B;
+    s.end_covered = 0;
+    for(uint32_t b = 0; b < B; ++b) {
+        if(edges[b] >= 0.5 && s.first_covered == B)
+            s.first_covered = b;
+        if(edges[b + 1] <= (double)(P / 2) - 0.5)
+            ++s.end_covered;
+    }
+    return s;
+}
+
 } // namespace wf::host

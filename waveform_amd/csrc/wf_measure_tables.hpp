@@ -1,4 +1,4 @@
-// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO and _CQ derive from the configuration alone,
+// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ and _SONO derive from the configuration alone,
 // built on the host (wf_measure_tables.cpp) at the output's first read and uploaded by wf_hip_measure.hip.  Plain C++: no HIP
 // and no handle, so the arithmetic also compiles into a program of its own (tests/test_measure_tables_cpu.py).  The sizes of
 // the constant-Q tables are in wf_cq_sizes.hpp, shared with the kernel (wf_cq.hpp).
@@ -47,5 +47,15 @@ struct CqTables {
     std::vector<uint32_t> sched; // [WF_CQ_SCHED_WORDS]
 };
 CqTables cq_tables(uint32_t sample_rate, uint32_t ring_cap);
+
+// WF_HIP_OUT_SONO (wf_sono.hpp), P = WF_HIP_SONO_WINDOW: the periodic Hann window and the twiddles e^(-j 2 pi m / P) in float64,
+// from long double arguments; the edges 62.5 * 2^(j / 8) Hz of the 64 bands in bins of P; how many columns the ring holds
+// (T = min(WF_HIP_SONO_COLUMNS, (ring_cap - P) / H), 0 for a ring that holds no column) and which bands the spectrum covers
+struct SonoTables {
+    uint32_t columns = 0;
+    uint32_t first_covered = 0, end_covered = 0;
+    std::vector<double> tab; // one block [P window][P / 2 twiddles, re im][WF_HIP_SONO_BANDS + 1 edges]
+};
+SonoTables sono_tables(uint32_t sample_rate, uint32_t ring_cap);
 
 } // namespace wf::host
