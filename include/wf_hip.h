@@ -51,6 +51,9 @@
  *   WF_HIP_OUT_SONO      not in the reference: a spectrogram (sonogram) of every stream's newest audio in the rings, up to 64
  *                        columns 256 frames apart by 64 bands of an eighth of an octave, the columns anchored to the stream's
  *                        sample counter, transformed in float64 on the device when read
+ *   WF_HIP_OUT_BITS      not in the reference: a bit meter, per captured channel the sample-value histogram, the activity of each
+ *                        bit, the word length, the over-range count and the longest run of identical samples of every stream's
+ *                        newest window of audio, counted on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -408,10 +411,15 @@ typedef enum wf_hip_output {
                                   min(wf_hip_fft_size(), 8192) frames in the rings, as of the pushes issued so far, fall into each
                                   cell of a 64 x 64 side / mid picture that a power of two magnifies to the peak (spectrum and
                                   meter batches with two captured channels; definition below) */
-    WF_HIP_OUT_SONO            /* wf_hip_sono                                sonogram: the level in 64 bands of an eighth of an
+    WF_HIP_OUT_SONO,           /* wf_hip_sono                                sonogram: the level in 64 bands of an eighth of an
                                   octave of up to 64 windows of 1024 frames, 256 frames apart and anchored to the sample counter,
                                   of the audio in the rings as of the pushes issued so far (spectrum and meter batches with a ring
                                   of at least 2048 frames; definition below) */
+    WF_HIP_OUT_BITS            /* wf_hip_bits                                bit statistics: per captured channel the histogram of
+                                  sample values, how often each bit of the sample on a 32-bit grid is set, the word length, the
+                                  over-range count and the longest run of identical samples of the newest
+                                  min(wf_hip_fft_size(), 8192) frames in the rings as of the pushes issued so far (spectrum and
+                                  meter batches; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -842,6 +850,68 @@ typedef struct wf_hip_sono {
     uint32_t window, hop;    /* P, H */
     uint32_t reserved[2];    /* 0 */
 } wf_hip_sono;               /* 32800 bytes, a multiple of 16 */
+/* ---- bit statistics (WF_HIP_OUT_BITS) ---------------------------------------------------------------------------------------
+ * Per stream and captured channel, the bit meter of a metering suite: how many bits the audio really carries, whether a bit is
+ * stuck, whether the signal is clipped into flat tops, whether a drop-out left a run of identical samples, and whether codes are
+ * missing from the value histogram because the audio was requantised.  W = wf_hip_fft_size().  Every step below is a comparison,
+ * an exact operation or an integer operation: a host that restates it reproduces every field bit for bit (tests/bits_ref.py
+ * does).
+ *   window         P = min(W, WF_HIP_BITS_MAX_WINDOW) frames: the newest P frames of each captured channel's ring, positions
+ *                  (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of WF_HIP_OUT_SIGNAL: every push issued before
+ *                  the read counts whatever its path, the A/V-sync delay is not applied, the zeros of create and wf_hip_reset
+ *                  count as samples.  Hidden and paused streams are read like any other.  x[i], i < P, is the float32 sample
+ *                  and bits[i] its 32-bit pattern.
+ *   code           the sample on a 32-bit two's-complement grid.  y = (double)x * 2^31, which is exact.  over <=> y >= 2^31 or
+ *                  y < -2^31, that is x >= 1 or x < -1: -1.0 fits and +1.0 does not.  v = (int32) min(max(floor(y), -2^31),
+ *                  2^31 - 1).  fine <=> not over and floor(y) != y: only a float32 below 2^-8 in magnitude can be fine, a sample
+ *                  with bits below 2^-31, which no integer PCM format of up to 32 bits produces.  s(v) = v for v >= 0 and ~v for
+ *                  v < 0, and m(v) is the number of significant bits of s(v): 0 for s = 0, else 32 - clz(s); 0 .. 31.  The
+ *                  device derives v from the sign, the exponent and the mantissa with integer shifts, so nothing depends on how
+ *                  the hardware treats denormals.  +-INFINITY follow the rules above (over, clamped); for a NaN nothing is
+ *                  promised except that no index leaves its table.
+ *   hist           hist[(v >> 24) + 128], an arithmetic shift: bin h counts the frames with x in [(h - 128) / 128,
+ *                  (h - 127) / 128), and over-range frames land in bin 0 or 255.  The linear sample-value histogram: clipping
+ *                  shows as spikes at the ends, asymmetry as a lopsided shape, requantised audio as a comb.
+ *   ones           ones[b] = the frames whose v has bit b set; b = 0 is the least significant bit (2^-31), b = 31 the sign.  A
+ *                  bit with ones == 0 or ones == P inside the used range is stuck.
+ *   mag            mag[m(v)]: a level histogram in steps of 6.02 dB; mag[31] is |x| in [0.5, 1), mag[0] is v = 0 or v = -1.
+ *   word_length    0 if every v is 0, else 32 - ctz(the OR of all v): 8 for u8 audio, 16 for s16, 24 for 24-bit audio, and 32
+ *                  for float audio, where fine > 0 says that there is more below the grid.
+ *   magnitude_bits the largest m(v): the headroom is 31 - magnitude_bits bits.
+ *   over, fine     the counts of the frames that are over and fine.
+ *   repeats        the frames i >= 1 with bits[i] == bits[i - 1].  Patterns are compared, so +0 and -0 differ; the frame in
+ *                  front of the window does not count.
+ *   runs           a run is a maximal stretch of equal patterns inside the window.  max_run is the longest run's length (>= 1),
+ *                  max_run_start the window index of the first frame of the first run of that length, and max_run_value its
+ *                  sample.  A long run at 0 is a drop-out, one at the peak a flat top.
+ *   invariants     sum(hist) = sum(mag) = P, and ones[31] = the frames with v < 0.  P <= 8192: no uint16 overflows.
+ *   determinism    the accumulations are integer counts, ORs and a maximum with a fixed tie-break: the same ring contents read
+ *                  bit-identically across push paths, repeated reads, slices and shards.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup per stream, the window of
+ * every captured channel staged in LDS once, ballots and popcounts for the bits, integer LDS atomics that neighbouring lanes of equal
+ * bin share for the histogram), into a block the first read allocates: a handle that never reads it allocates and launches nothing
+ * new, and no state is kept between reads -- averaging and peak hold are the host's.
+ * Cost on an MI355X, 4096 stereo streams, read into page-locked memory (5.57 MB back): 0.53 / 0.52 / 0.50 ms at W = 4096 for
+ * independent noise / a 100 Hz sine / silence against 2.36 ms for copying the 134.2 MB of windows to the host, and 1.28 / 1.29 /
+ * 1.17 ms against 4.71 ms at W = 16384 (P = 8192): the read wins at both shapes and for every kind, 4.5 to 4.8 times at W = 4096
+ * and 3.7 to 4.0 times at the cap.  Into a fresh pageable numpy array (the Python reader) a read takes 0.50 to 1.33 ms and wins as
+ * well.  The kernel's own time without its copy is unmeasured (tools/bits_bench.py, profiles/bits_kernel_stats.json;
+ * INTEGRATION.md, "Bit meter").
+ * Spectrum and meter batches with one or two captured channels are served, and there is no lower limit on W; on waveform batches
+ * wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_BITS_MAX_WINDOW 8192
+typedef struct wf_hip_bits_channel {
+    uint16_t hist[256];      /* [(v >> 24) + 128] */
+    uint16_t ones[32];       /* [bit of v] */
+    uint16_t mag[32];        /* [m(v)] */
+    uint32_t word_length, magnitude_bits, over, fine, repeats, max_run, max_run_start;
+    float max_run_value;
+} wf_hip_bits_channel;       /* 672 bytes */
+typedef struct wf_hip_bits {
+    wf_hip_bits_channel ch[2]; /* captured channels 0 and 1; with one captured channel ch[1] is all zero bytes */
+    uint32_t window;         /* P */
+    uint32_t reserved[3];    /* 0 */
+} wf_hip_bits;               /* 1360 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

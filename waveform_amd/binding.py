@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO = range(20)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS = range(21)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -189,6 +189,16 @@ SONO_EDGES_HZ = 62.5 * np.exp2(np.arange(SONO_BANDS + 1, dtype=np.float64) / 8.0
 SONO_DTYPE = np.dtype([("db", np.float32, (2, SONO_COLUMNS, SONO_BANDS)), ("columns", np.uint32), ("newest", np.uint32),
                        ("first_covered", np.uint32), ("end_covered", np.uint32), ("window", np.uint32), ("hop", np.uint32),
                        ("reserved", np.uint32, (2,))])
+
+# struct wf_hip_bits (include/wf_hip.h): the bit meter, per captured channel the histogram of sample values, how often each bit of the
+# sample on a 32-bit two's-complement grid is set, the level histogram in bits, the word length, the over-range and below-the-grid
+# counts and the longest run of identical samples of the newest P = min(fft_size, BITS_MAX_WINDOW) frames of the ring
+BITS_MAX_WINDOW = 8192  # WF_HIP_BITS_MAX_WINDOW
+BITS_CHANNEL_DTYPE = np.dtype([("hist", np.uint16, (256,)), ("ones", np.uint16, (32,)), ("mag", np.uint16, (32,)),
+                               ("word_length", np.uint32), ("magnitude_bits", np.uint32), ("over", np.uint32), ("fine", np.uint32),
+                               ("repeats", np.uint32), ("max_run", np.uint32), ("max_run_start", np.uint32),
+                               ("max_run_value", np.float32)])
+BITS_DTYPE = np.dtype([("ch", BITS_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("reserved", np.uint32, (3,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -411,6 +421,16 @@ class _MeasureReaders:
         on the device when read, from the rings as of the pushes issued so far (batches whose ring holds at least 2048 frames)"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_SONO, first, count, (), SONO_DTYPE)
+
+    def bits(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_bits (BITS_DTYPE): the bit meter, per captured channel ch[c] the sample-value
+        histogram hist[256], ones[b] = the frames whose code on a 32-bit two's-complement grid has bit b set, the level histogram
+        mag[32], word_length (8 / 16 / 24 for integer PCM, 32 with fine > 0 for float audio), magnitude_bits, the over-range count
+        and the longest run of identical samples (max_run, max_run_start, max_run_value) with the count of repeats, over the
+        newest min(fft_size, BITS_MAX_WINDOW) frames of the ring as of the pushes issued so far; counted on the device when read.
+        With one captured channel ch[1] is all zero"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_BITS, first, count, (), BITS_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO and _SONO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO and _BITS.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -29,6 +29,7 @@
 #include "wf_scope.hpp"
 #include "wf_gonio.hpp"
 #include "wf_sono.hpp"
+#include "wf_bits.hpp"
 
 namespace {
 
@@ -305,6 +306,37 @@ int launch_sono(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// the bit meter's window: the newest min(fft_size, WF_HIP_BITS_MAX_WINDOW) frames (<= ring_cap)
+uint32_t bits_window(const wf_hip *h) { return std::min<uint32_t>(h->N, WF_HIP_BITS_MAX_WINDOW); }
+
+// the bit meter has no tables: its kernels' dynamic LDS is all its first read asks for
+int setup_bits(wf_hip *h)
+{
+    // (about 69 KB at the cap with two channels, the windows and the kernel's working set behind them: more than a workgroup
+    // gets without asking, and two workgroups to a CU)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::bits_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::bits_lds_bytes(1, WF_HIP_BITS_MAX_WINDOW)));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::bits_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::bits_lds_bytes(2, WF_HIP_BITS_MAX_WINDOW)));
+    return WF_HIP_OK;
+}
+
+// one workgroup per stream over its newest P frames of every captured channel, behind the pushes issued
+int launch_bits(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    wf::BitsArgs a{};
+    a.rings = ring_view(h);
+    a.out = static_cast<wf_hip_bits *>(d_block) + first;
+    a.first = first;
+    a.P = bits_window(h);
+    const size_t lds = wf::bits_lds_bytes(h->cap_ch, a.P);
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::bits_read_kernel<2>, dim3(count), dim3(wf::WF_BITS_THREADS), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::bits_read_kernel<1>, dim3(count), dim3(wf::WF_BITS_THREADS), lds, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -355,6 +387,11 @@ const char *why_no_sono(const wf_hip *h)
     return h->ring_cap < 2 * WF_HIP_SONO_WINDOW ? "the sonogram needs a ring of at least 2048 frames (wf_hip_create's ring_frames)" : nullptr;
 }
 
+const char *why_no_bits(const wf_hip *h)
+{
+    return h->wave ? "waveform batch: the bit statistics belong to spectrum and meter batches (a window of fft_size frames)" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -376,6 +413,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_SCOPE, sizeof(wf_hip_scope), false, why_no_scope, setup_scope, launch_scope},
     {WF_HIP_OUT_GONIO, sizeof(wf_hip_gonio), false, why_no_gonio, setup_gonio, launch_gonio},
     {WF_HIP_OUT_SONO, sizeof(wf_hip_sono), false, why_no_sono, setup_sono, launch_sono},
+    {WF_HIP_OUT_BITS, sizeof(wf_hip_bits), false, why_no_bits, setup_bits, launch_bits},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
