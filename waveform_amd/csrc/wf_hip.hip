@@ -2,8 +2,10 @@
 // measurement outputs (wf_hip_measure.hip): audio ingest, the tick, per-stream settings, readbacks, timing -- host side + the
 // launches of the small kernels (rings, level meter, waveform display, RMS, vertex fill).  The fused spectrum kernel is launched through wf_hip::launch
 // with the arguments of tick_args(): the handle's constant wf_hip::tick + the per-tick part
-// (wf_tick_geom.hip, wf_big_dispatch.hip).  gfx950 only.  There is no CPU fallback: every entry point either drives the
-// device or fails.
+// (wf_tick_geom.hip, wf_big_dispatch.hip).  The two pipelines that run beside the compute stream -- the ingest from page-locked
+// memory and wf_hip_read_async -- each keep their per-slot state in one record (wf_hip::IngestSlot, wf_hip::ReadSlot) and have a
+// section here that states the slots' ordering rule once, with the helpers every path goes through ("pipelined ingest",
+// "pipelined readback").  gfx950 only.  There is no CPU fallback: every entry point either drives the device or fails.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -128,7 +130,7 @@ wf::TickArgs tick_args(const wf_hip *h, const wf_hip_tick_params *p)
     a.decibels = h->d_decibels;
     a.delay = p->delay_frames;
     a.delay_stream = h->d_delay;
-    a.stream_flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
+    a.stream_flags = cur_flags(h);
     if(h->split) {
         const uint32_t nxt = (h->flag_cur + 1) % 3, clr = (h->flag_cur + 2) % 3;
         const size_t n_spec = (size_t)h->n_streams * h->cap_ch;
@@ -217,26 +219,13 @@ void launch_input_rms(wf_hip *h, const wf_hip_tick_params *p)
     r.rms_ring = h->d_rms_ring;
     r.bsum = h->d_rms_bsum;
     r.wpos = h->d_wpos;
-    r.flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
+    r.flags = cur_flags(h);
     r.rend = h->d_rend;
     r.delay = p->delay_frames;
     r.delay_stream = h->d_delay;
     r.input_rms = h->d_input_rms;
     r.vol_comp = h->d_vol_comp;
     hipLaunchKernelGGL(wf::input_rms_kernel, dim3(h->n_streams), dim3(64), 0, h->stream, r);
-}
-
-// wf_hip_read_async copies the rows straight out of m_decibels on the readback stream: whatever is about to overwrite rows (a
-// tick of a spectrum or waveform batch, wf_hip_reset) first makes `stream` wait -- on the device -- for copies in flight
-int wait_rows_in_flight(wf_hip *h)
-{
-    for(int i = 0; i < 2; ++i)
-        if(h->rows_in_flight[i]) {
-            WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_read[i], 0));
-            h->rows_in_flight[i] = false;
-            h->main_dirty = true;
-        }
-    return WF_HIP_OK;
 }
 
 } // namespace
@@ -315,14 +304,14 @@ void dev_release(wf_hip *h, void *p)
 // staging blocks grow geometrically and the outgrown block is released once the stream has drained it
 size_t grown(size_t have, size_t need) { return std::max(need, have + have / 2); }
 
-// replaces *d by a block of at least `floats` (the caller has made sure that nothing enqueued still uses the old one)
-int grow_stage(wf_hip *h, float **d, size_t *have, size_t floats)
+// replaces *d by a block of at least `count` elements (the caller has made sure that nothing enqueued still uses the old one)
+template<class T> int grow_stage(wf_hip *h, T **d, size_t *have, size_t count)
 {
     dev_release(h, *d);
     *d = nullptr;
-    const size_t want = grown(*have, floats);
+    const size_t want = grown(*have, count);
     *have = 0;
-    float *p = nullptr;
+    T *p = nullptr;
     WF_TRY_RC(dev_alloc(h, &p, want));
     *d = p;
     *have = want;
@@ -375,8 +364,8 @@ int check_ragged_push(wf_hip *h, uint32_t count, const uint32_t *frames, uint32_
 int finish_push(wf_hip *h, uint32_t first, uint32_t count, uint32_t frames, const uint32_t *d_frames)
 {
     if(d_frames == nullptr)
-        hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos,
-                           h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, frames);
+        hipLaunchKernelGGL(wf::wpos_advance_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_wpos, cur_flags(h),
+                           first, count, frames);
     measure_after_push(h, first, count, frames, d_frames);
     WF_HIP_TRY(h, hipGetLastError());
     if(d_frames == nullptr && frames % 4u)
@@ -492,6 +481,85 @@ int slot_consumed(wf_hip *h, wf_hip::IngestSlot &s)
     return WF_HIP_OK;
 }
 
+// ---- pipelined readback -------------------------------------------------------------------------------------------------
+// wf_hip_read_async goes through one of two slots (wf_hip::ReadSlot): `stream` produces what the slot's copies read -- the ticks'
+// outputs where they lie, the slot's snapshot, its silent bytes --, ev_snap hands it to the readback stream, whose D2H copies no
+// later tick has to wait for, and ev_read, recorded once behind all of them, says that they have landed.  The ordering rule of
+// the slots: the HOST waits for ev_read before anything of the slot is touched again -- its blocks released or overwritten, its
+// events recorded (read_slot_ready; the caller's buffers: wf_hip_readback_done).  What the copies read where it lies (rows, bars,
+// vertices, m_input_rms) has no snapshot: whatever overwrites it next waits for ev_read on the DEVICE (wait_rows_in_flight).
+// Every path reads: validate, read_slot_ready, its launches on `stream`, to_read_stream, its copies (copy_out), copies_issued.
+int ensure_read_stream(wf_hip *h)
+{
+    if(h->read_stream != nullptr)
+        return WF_HIP_OK;
+    WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->read_stream, hipStreamNonBlocking));
+    for(wf_hip::ReadSlot &s : h->read_slot) {
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&s.ev_snap, hipEventDisableTiming));
+        WF_HIP_TRY(h, hipEventCreateWithFlags(&s.ev_read, hipEventDisableTiming));
+    }
+    return WF_HIP_OK;
+}
+
+// Frees the slot -- the host waits for its previous copies, BEFORE any block of it is released or overwritten -- and makes room
+// for a snapshot of `floats` and for `silent` bytes of m_last_silent (0: the path uses no such block)
+int read_slot_ready(wf_hip *h, wf_hip::ReadSlot &s, size_t floats, size_t silent)
+{
+    constexpr size_t FLOOR = 256; // elements: a handful of streams does not regrow its blocks one by one
+    WF_TRY_RC(ensure_read_stream(h));
+    if(s.used)
+        WF_HIP_TRY(h, hipEventSynchronize(s.ev_read));
+    if(s.snap_floats < floats)
+        WF_TRY_RC(grow_stage(h, &s.d_snap, &s.snap_floats, std::max(floats, FLOOR)));
+    if(s.silent_bytes < silent)
+        WF_TRY_RC(grow_stage(h, &s.d_silent, &s.silent_bytes, std::max(silent, FLOOR)));
+    return WF_HIP_OK;
+}
+
+// behind what `stream` holds for the slot (the ticks enqueued so far, the snapshot, the silent bytes): the readback stream waits
+// for it
+int to_read_stream(wf_hip *h, wf_hip::ReadSlot &s)
+{
+    WF_HIP_TRY(h, hipEventRecord(s.ev_snap, h->stream));
+    WF_HIP_TRY(h, hipStreamWaitEvent(h->read_stream, s.ev_snap, 0));
+    return WF_HIP_OK;
+}
+
+// one of the slot's copies
+int copy_out(wf_hip *h, void *pinned, const void *d_src, size_t bytes)
+{
+    WF_HIP_TRY(h, hipMemcpyAsync(pinned, d_src, bytes, hipMemcpyDeviceToHost, h->read_stream));
+    return WF_HIP_OK;
+}
+
+// Behind the slot's copies, whose result is `copies_rc`: ALSO when one of them failed, ev_read is recorded behind whatever went
+// out, so that the next use of the slot, wf_hip_readback_done and -- `in_place`: the copies read the rows where they lie -- the
+// next tick wait for the right thing
+int copies_issued(wf_hip *h, wf_hip::ReadSlot &s, bool in_place, int copies_rc)
+{
+    const hipError_t e = hipEventRecord(s.ev_read, h->read_stream);
+    if(e == hipSuccess) {
+        s.used = true;
+        s.rows_in_flight = s.rows_in_flight || in_place;
+    }
+    WF_TRY_RC(copies_rc);
+    WF_HIP_TRY(h, e);
+    return WF_HIP_OK;
+}
+
+// whatever is about to overwrite rows (a tick of a spectrum or waveform batch, wf_hip_reset) first makes `stream` wait -- on the
+// device -- for the copies that read them where they lie
+int wait_rows_in_flight(wf_hip *h)
+{
+    for(wf_hip::ReadSlot &s : h->read_slot)
+        if(s.rows_in_flight) {
+            WF_HIP_TRY(h, hipStreamWaitEvent(h->stream, s.ev_read, 0));
+            s.rows_in_flight = false;
+            h->main_dirty = true;
+        }
+    return WF_HIP_OK;
+}
+
 // ---- wf_hip_push_pcm ----------------------------------------------------------------------------------------------------
 uint32_t pcm_sample_bytes(uint32_t format)
 {
@@ -573,7 +641,7 @@ int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm,
     wf::PcmPushArgs a{};
     a.ring = h->d_ring;
     a.wpos = h->d_wpos;
-    a.flags = h->d_flags + (size_t)h->flag_cur * h->n_streams;
+    a.flags = cur_flags(h);
     a.ring_cap = h->ring_cap;
     a.ring_stride = h->ring_stride;
     a.cap_ch = h->cap_ch;
@@ -788,9 +856,7 @@ int wf_hip_push_audio_async(wf_hip *h, uint32_t first, uint32_t count, const flo
 int wf_hip_push_audio_ragged_async(wf_hip *h, uint32_t first, uint32_t count, const float *pinned_samples, const uint32_t *frames,
                                    uint32_t max_frames, uint32_t slot)
 {
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
+    WF_TRY_RC(check_range(h, first, count));
     if(pinned_samples == nullptr || frames == nullptr || slot > 1 || max_frames == 0)
         return fail(h, WF_HIP_ERR_INVALID, "samples or frames is NULL, max_frames is 0 or slot is not 0 / 1");
     WF_TRY_RC(check_ragged_push(h, count, frames, max_frames));
@@ -803,8 +869,7 @@ int wf_hip_push_audio_ragged_async(wf_hip *h, uint32_t first, uint32_t count, co
     WF_HIP_TRY(h, hipMemcpyAsync(s.d_stage, pinned_samples, n * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
     WF_TRY_RC(hand_over(h, s, h->ev_copied[slot], count));
     hipLaunchKernelGGL(wf::ring_push_ragged_kernel, dim3(1, count), dim3(256), 0, h->stream, h->d_ring, h->d_wpos,
-                       h->d_flags + (size_t)h->flag_cur * h->n_streams, h->ring_cap, h->ring_stride, h->cap_ch, first, s.d_stage, s.d_frames,
-                       max_frames);
+                       cur_flags(h), h->ring_cap, h->ring_stride, h->cap_ch, first, s.d_stage, s.d_frames, max_frames);
     WF_TRY_RC(finish_push(h, first, count, max_frames, s.d_frames));
     WF_TRY_RC(slot_consumed(h, s));
     if(!c.aligned)
@@ -1063,9 +1128,7 @@ static int wf_hip_tick_impl(wf_hip *h, const wf_hip_tick_params *p)
 
 int wf_hip_set_hidden(wf_hip *h, uint32_t first, uint32_t count, const uint8_t *mask)
 {
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
+    WF_TRY_RC(check_range(h, first, count));
     if(mask == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "mask is NULL");
     if(h->meter || h->wave)
@@ -1074,14 +1137,12 @@ int wf_hip_set_hidden(wf_hip *h, uint32_t first, uint32_t count, const uint8_t *
                 return fail(h, WF_HIP_ERR_INVALID, "WF_HIP_STARVED applies to spectrum batches only");
     WF_HIP_TRY(h, hipSetDevice(h->device));
     if(h->mask_bytes < count) {
-        rc = dev_alloc(h, &h->d_mask, (size_t)count);
-        if(rc)
-            return rc;
+        WF_TRY_RC(dev_alloc(h, &h->d_mask, (size_t)count));
         h->mask_bytes = count;
     }
     WF_HIP_TRY(h, hipMemcpyAsync(h->d_mask, mask, count, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(wf::set_hidden_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream,
-                       h->d_flags + (size_t)h->flag_cur * h->n_streams, first, count, h->d_mask);
+    hipLaunchKernelGGL(wf::set_hidden_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, cur_flags(h), first, count,
+                       h->d_mask);
     WF_HIP_TRY(h, hipGetLastError());
     WF_HIP_TRY(h, hipStreamSynchronize(h->stream)); // `mask` is borrowed for the call only
     return WF_HIP_OK;
@@ -1273,244 +1334,6 @@ const float *wf_hip_vertices_device(wf_hip *h)
     return reinterpret_cast<const float *>(h->d_verts);
 }
 
-static int read_bars_snapshot_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_out, uint32_t slot)
-{
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
-    if(h->d_bars == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "configuration has no bars (cfg.bars == 0)");
-    if(pinned_out == nullptr || slot > 1)
-        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL or slot is not 0 / 1");
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->read_stream == nullptr) {
-        WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->read_stream, hipStreamNonBlocking));
-        for(int i = 0; i < 2; ++i) {
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap[i], hipEventDisableTiming));
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_read[i], hipEventDisableTiming));
-        }
-    }
-    const size_t per = (size_t)h->disp_ch * h->num_bars, n = count * per;
-    if(h->read_used[slot])
-        WF_HIP_TRY(h, hipEventSynchronize(h->ev_read[slot])); // the slot's previous copy must have left its snapshot
-    if(h->snap_floats[slot] < n) { // (the slot's previous copy has left its snapshot: waited for above)
-        dev_release(h, h->d_snap[slot]);
-        h->d_snap[slot] = nullptr;
-        const size_t want = grown(h->snap_floats[slot], n);
-        h->snap_floats[slot] = 0;
-        float *p = nullptr;
-        rc = dev_alloc(h, &p, want);
-        if(rc)
-            return rc;
-        h->d_snap[slot] = p;
-        h->snap_floats[slot] = want;
-    }
-    // compute stream: snapshot behind the ticks enqueued so far (device to device, a few MB at most)
-    WF_HIP_TRY(h, hipMemcpyAsync(h->d_snap[slot], h->d_bars + first * per, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_snap[slot], h->stream));
-    // readback stream: the D2H copy of the snapshot; later ticks do not wait for it
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->read_stream, h->ev_snap[slot], 0));
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_out, h->d_snap[slot], n * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
-    h->read_used[slot] = true;
-    return WF_HIP_OK;
-}
-
-// m_last_silent of streams [first, first+count) as bytes (for the D2H copy of wf_hip_read_async's rows)
-__global__ void silent_bytes_kernel(const uint32_t *flags, uint32_t first, uint32_t count, uint8_t *out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < count)
-        out[i] = (flags[first + i] & wf::WF_STREAM_LAST_SILENT) ? 1 : 0;
-}
-
-static int read_rows_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_rows, uint8_t *pinned_last_silent, uint32_t slot)
-{
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
-    if(h->meter)
-        return fail(h, WF_HIP_ERR_INVALID, "meter batch: there is no m_decibels");
-    if(pinned_rows == nullptr || pinned_last_silent == nullptr || slot > 1)
-        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL or slot is not 0 / 1");
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->read_stream == nullptr) {
-        WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->read_stream, hipStreamNonBlocking));
-        for(int i = 0; i < 2; ++i) {
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap[i], hipEventDisableTiming));
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_read[i], hipEventDisableTiming));
-        }
-    }
-    if(h->read_used[slot])
-        WF_HIP_TRY(h, hipEventSynchronize(h->ev_read[slot])); // the slot's previous copy has landed
-    if(h->silent_bytes_cap[slot] < count) {
-        dev_release(h, h->d_silent_bytes[slot]);
-        h->d_silent_bytes[slot] = nullptr;
-        h->silent_bytes_cap[slot] = 0;
-        const size_t want = std::max<size_t>(count, 256);
-        rc = dev_alloc(h, &h->d_silent_bytes[slot], want);
-        if(rc)
-            return rc;
-        h->silent_bytes_cap[slot] = want;
-    }
-    hipLaunchKernelGGL(silent_bytes_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_flags + (size_t)h->flag_cur * h->n_streams,
-                       first, count, h->d_silent_bytes[slot]);
-    WF_HIP_TRY(h, hipGetLastError());
-    WF_HIP_TRY(h, hipEventRecord(h->ev_snap[slot], h->stream));
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->read_stream, h->ev_snap[slot], 0));
-    const size_t per = (size_t)h->out_ch * h->M;
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_rows, h->d_decibels + first * per, count * per * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_last_silent, h->d_silent_bytes[slot], count, hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
-    h->read_used[slot] = true;
-    h->rows_in_flight[slot] = true;
-    return WF_HIP_OK;
-}
-
-// The riders below copy behind the rows' copy on the readback stream; check_riders has validated them before the rows went out
-static int read_premirror_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_out, uint32_t slot)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_out, h->d_bars_pre + (size_t)first * h->disp_ch, (size_t)count * h->disp_ch * sizeof(float), hipMemcpyDeviceToHost,
-                                 h->read_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
-    return WF_HIP_OK;
-}
-
-static int read_display_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_bars, float *pinned_vertices, uint32_t *pinned_counts,
-                              uint32_t slot)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    // behind the rows' copy on the readback stream (which already waits for the tick, its bars and its vertex fill on every lane);
-    // the next tick waits, on the device, for this slot's event before it overwrites any of them
-    const size_t per = (size_t)h->disp_ch * h->num_bars;
-    if(pinned_bars)
-        WF_HIP_TRY(h, hipMemcpyAsync(pinned_bars, h->d_bars + first * per, count * per * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
-    if(pinned_vertices) {
-        const size_t pv = (size_t)h->disp_ch * h->small->vertex.per_row;
-        WF_HIP_TRY(h, hipMemcpyAsync(pinned_vertices, h->d_verts + first * pv, count * pv * sizeof(wf::f4), hipMemcpyDeviceToHost, h->read_stream));
-    }
-    if(pinned_counts)
-        WF_HIP_TRY(h, hipMemcpyAsync(pinned_counts, h->d_vert_counts + (size_t)first * h->disp_ch, (size_t)count * h->disp_ch * sizeof(uint32_t),
-                                     hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
-    return WF_HIP_OK;
-}
-
-static int read_meter_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_levels, uint8_t *pinned_last_silent, uint32_t slot)
-{
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
-    if(!h->meter)
-        return fail(h, WF_HIP_ERR_INVALID, "not a meter batch (cfg.meter == 0)");
-    if(pinned_levels == nullptr || pinned_last_silent == nullptr || slot > 1)
-        return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL or slot is not 0 / 1");
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    if(h->read_stream == nullptr) {
-        WF_HIP_TRY(h, hipStreamCreateWithFlags(&h->read_stream, hipStreamNonBlocking));
-        for(int i = 0; i < 2; ++i) {
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap[i], hipEventDisableTiming));
-            WF_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_read[i], hipEventDisableTiming));
-        }
-    }
-    const size_t n = (size_t)count * h->cap_ch;
-    if(h->read_used[slot])
-        WF_HIP_TRY(h, hipEventSynchronize(h->ev_read[slot])); // the slot's previous copy has left its snapshot
-    if(h->snap_floats[slot] < n) {
-        dev_release(h, h->d_snap[slot]);
-        h->d_snap[slot] = nullptr;
-        const size_t want = std::max<size_t>(grown(h->snap_floats[slot], n), 64);
-        h->snap_floats[slot] = 0;
-        float *p = nullptr;
-        rc = dev_alloc(h, &p, want);
-        if(rc)
-            return rc;
-        h->d_snap[slot] = p;
-        h->snap_floats[slot] = want;
-    }
-    if(h->silent_bytes_cap[slot] < count) {
-        dev_release(h, h->d_silent_bytes[slot]);
-        h->d_silent_bytes[slot] = nullptr;
-        h->silent_bytes_cap[slot] = 0;
-        const size_t want = std::max<size_t>(count, 256);
-        rc = dev_alloc(h, &h->d_silent_bytes[slot], want);
-        if(rc)
-            return rc;
-        h->silent_bytes_cap[slot] = want;
-    }
-    // compute stream: a snapshot of the few floats behind the ticks enqueued so far (the next tick overwrites m_meter_val)
-    WF_HIP_TRY(h, hipMemcpyAsync(h->d_snap[slot], h->d_meter_val + (size_t)first * h->cap_ch, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    hipLaunchKernelGGL(silent_bytes_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->d_flags, first, count, h->d_silent_bytes[slot]);
-    WF_HIP_TRY(h, hipGetLastError());
-    WF_HIP_TRY(h, hipEventRecord(h->ev_snap[slot], h->stream));
-    WF_HIP_TRY(h, hipStreamWaitEvent(h->read_stream, h->ev_snap[slot], 0));
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_levels, h->d_snap[slot], n * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_last_silent, h->d_silent_bytes[slot], count, hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
-    h->read_used[slot] = true;
-    return WF_HIP_OK;
-}
-
-// m_input_rms behind the rows' copy on the readback stream (which already waits for the tick)
-static int read_input_rms_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_out, uint32_t slot)
-{
-    WF_HIP_TRY(h, hipSetDevice(h->device));
-    WF_HIP_TRY(h, hipMemcpyAsync(pinned_out, h->d_input_rms + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, h->read_stream));
-    WF_HIP_TRY(h, hipEventRecord(h->ev_read[slot], h->read_stream));
-    return WF_HIP_OK;
-}
-
-// the outputs that ride behind the rows of one wf_hip_read_async: each one the batch must have
-static int check_riders(wf_hip *h, const wf_hip_readback *dst)
-{
-    if(h->meter)
-        return fail(h, WF_HIP_ERR_INVALID, "meter batch: there is no m_decibels");
-    if(dst->input_rms && h->d_input_rms == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "the device RMS producer is not enabled (wf_hip_enable_input_rms)");
-    if((dst->bars || dst->vertices || dst->vertex_counts) && h->d_bars == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "the configuration displays neither bars nor a curve (cfg.bars == 0 and cfg.curve == 0)");
-    if((dst->vertices || dst->vertex_counts) && h->d_verts == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "configuration has no vertex fill (cfg.vertices == 0)");
-    if(dst->premirror && h->d_bars_pre == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "the configuration has no mirrored display (cfg.mirror_freq_axis == 0, or no bars / curve)");
-    return WF_HIP_OK;
-}
-
-int wf_hip_read_async(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_readback *dst, uint32_t slot)
-{
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
-    if(dst == nullptr || slot > 1)
-        return fail(h, WF_HIP_ERR_INVALID, "destination set is NULL or slot is not 0 / 1");
-    const bool riders = dst->premirror || dst->vertices || dst->vertex_counts || dst->input_rms;
-    if(dst->meter) { // meter batches: level + m_last_silent, from snapshots
-        if(dst->last_silent == nullptr || dst->rows || dst->bars || riders)
-            return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: meter goes with last_silent and nothing else");
-        return read_meter_async(h, first, count, dst->meter, dst->last_silent, slot);
-    }
-    if(dst->rows == nullptr) { // the bars alone: from a snapshot per slot
-        if(dst->bars == nullptr || dst->last_silent || riders)
-            return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: without rows only the bars can be read (rows + last_silent lead every other combination)");
-        return read_bars_snapshot_async(h, first, count, dst->bars, slot);
-    }
-    if(dst->last_silent == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: rows go with last_silent");
-    // every rider is checked before the rows are enqueued: a refused call leaves no copy in flight and the slot as it was
-    rc = check_riders(h, dst);
-    if(rc)
-        return rc;
-    rc = read_rows_async(h, first, count, dst->rows, dst->last_silent, slot);
-    if(rc == WF_HIP_OK && dst->input_rms)
-        rc = read_input_rms_async(h, first, count, dst->input_rms, slot);
-    if(rc == WF_HIP_OK && (dst->bars || dst->vertices || dst->vertex_counts))
-        rc = read_display_async(h, first, count, dst->bars, dst->vertices, dst->vertex_counts, slot);
-    if(rc == WF_HIP_OK && dst->premirror)
-        rc = read_premirror_async(h, first, count, dst->premirror, slot);
-    return rc;
-}
-
 // where an output other than a measurement lives on the device and how large it is per stream; nullptr + a text when the
 // batch has none
 static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *per_stream, const char **why)
@@ -1588,9 +1411,7 @@ size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what)
 
 int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, void *out)
 {
-    int rc = check_range(h, first, count);
-    if(rc)
-        return rc;
+    WF_TRY_RC(check_range(h, first, count));
     size_t per = 0;
     const char *why = nullptr;
     if(measure_source(h, what, &per, &why))
@@ -1602,9 +1423,7 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
         return fail(h, WF_HIP_ERR_INVALID, "output pointer is NULL");
     if(what == WF_HIP_OUT_LAST_SILENT) { // the flag words of the buffer the newest tick wrote, narrowed to one byte per stream
         std::vector<uint32_t> tmp(count);
-        rc = read_back(h, h->d_flags + (size_t)h->flag_cur * h->n_streams + first, tmp.data(), count * sizeof(uint32_t));
-        if(rc)
-            return rc;
+        WF_TRY_RC(read_back(h, cur_flags(h) + first, tmp.data(), count * sizeof(uint32_t)));
         for(uint32_t i = 0; i < count; ++i)
             static_cast<uint8_t *>(out)[i] = (tmp[i] & wf::WF_STREAM_LAST_SILENT) ? 1 : 0;
         return WF_HIP_OK;
@@ -1612,14 +1431,127 @@ int wf_hip_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, v
     return read_back(h, static_cast<const char *>(src) + (size_t)first * per, out, (size_t)count * per);
 }
 
+// ---- wf_hip_read_async (the slots' helpers: "pipelined readback" above) ---------------------------------------------------
+// every output the caller named is one the batch has, or the call is refused with the text wf_hip_read gives for that output:
+// before anything is enqueued or any state of the slot changes
+static int check_outputs(wf_hip *h, const wf_hip_readback *dst)
+{
+    const std::pair<const void *, wf_hip_output> named[] = {
+        {dst->rows, WF_HIP_OUT_DECIBELS},     {dst->meter, WF_HIP_OUT_METER},       {dst->bars, WF_HIP_OUT_BARS},
+        {dst->premirror, WF_HIP_OUT_PREMIRROR}, {dst->vertices, WF_HIP_OUT_VERTICES}, {dst->vertex_counts, WF_HIP_OUT_VERTEX_COUNTS},
+        {dst->input_rms, WF_HIP_OUT_INPUT_RMS}};
+    for(const auto &o : named) {
+        size_t per = 0;
+        const char *why = nullptr;
+        if(o.first && output_source(h, o.second, &per, &why) == nullptr)
+            return fail(h, WF_HIP_ERR_INVALID, "%s", why);
+    }
+    return WF_HIP_OK;
+}
+
+// m_last_silent of streams [first, first+count) as bytes (for the D2H copy of wf_hip_read_async's rows and meter levels)
+__global__ void silent_bytes_kernel(const uint32_t *flags, uint32_t first, uint32_t count, uint8_t *out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i < count)
+        out[i] = (flags[first + i] & wf::WF_STREAM_LAST_SILENT) ? 1 : 0;
+}
+
+static int silent_bytes(wf_hip *h, uint32_t first, uint32_t count, wf_hip::ReadSlot &s)
+{
+    hipLaunchKernelGGL(silent_bytes_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, cur_flags(h), first, count, s.d_silent);
+    WF_HIP_TRY(h, hipGetLastError());
+    return WF_HIP_OK;
+}
+
+// the bars alone: from a snapshot behind the ticks enqueued so far (device to device, a few MB at most), so that later ticks
+// neither wait for the D2H copy nor disturb it
+static int read_bars_snapshot_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_out, wf_hip::ReadSlot &s)
+{
+    const size_t per = (size_t)h->disp_ch * h->num_bars, n = count * per;
+    WF_TRY_RC(read_slot_ready(h, s, n, 0));
+    WF_HIP_TRY(h, hipMemcpyAsync(s.d_snap, h->d_bars + first * per, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    WF_TRY_RC(to_read_stream(h, s));
+    return copies_issued(h, s, false, copy_out(h, pinned_out, s.d_snap, n * sizeof(float)));
+}
+
+// meter batches: the levels from a snapshot of the few floats (the next tick overwrites m_meter_val) + m_last_silent
+static int read_meter_async(wf_hip *h, uint32_t first, uint32_t count, float *pinned_levels, uint8_t *pinned_last_silent, wf_hip::ReadSlot &s)
+{
+    const size_t n = (size_t)count * h->cap_ch;
+    WF_TRY_RC(read_slot_ready(h, s, n, count));
+    WF_HIP_TRY(h, hipMemcpyAsync(s.d_snap, h->d_meter_val + (size_t)first * h->cap_ch, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    WF_TRY_RC(silent_bytes(h, first, count, s));
+    WF_TRY_RC(to_read_stream(h, s));
+    int rc = copy_out(h, pinned_levels, s.d_snap, n * sizeof(float));
+    if(rc == WF_HIP_OK)
+        rc = copy_out(h, pinned_last_silent, s.d_silent, count);
+    return copies_issued(h, s, false, rc);
+}
+
+// The copies of a rows readback: the rows straight out of m_decibels, m_last_silent, then the riders -- m_input_rms, the bars, the
+// vertices and their counts, the points in front of the mirror -- from where the tick, its vertex fill and the RMS producer left
+// them (the readback stream waits for all of them on every lane; check_outputs has made sure the batch has them)
+static int rows_copies(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_readback *dst, const wf_hip::ReadSlot &s)
+{
+    const size_t per = (size_t)h->out_ch * h->M, bars = (size_t)h->disp_ch * h->num_bars;
+    WF_TRY_RC(copy_out(h, dst->rows, h->d_decibels + first * per, count * per * sizeof(float)));
+    WF_TRY_RC(copy_out(h, dst->last_silent, s.d_silent, count));
+    if(dst->input_rms)
+        WF_TRY_RC(copy_out(h, dst->input_rms, h->d_input_rms + first, (size_t)count * sizeof(float)));
+    if(dst->bars)
+        WF_TRY_RC(copy_out(h, dst->bars, h->d_bars + first * bars, count * bars * sizeof(float)));
+    if(dst->vertices) {
+        const size_t pv = (size_t)h->disp_ch * h->small->vertex.per_row;
+        WF_TRY_RC(copy_out(h, dst->vertices, h->d_verts + first * pv, count * pv * sizeof(wf::f4)));
+    }
+    if(dst->vertex_counts)
+        WF_TRY_RC(copy_out(h, dst->vertex_counts, h->d_vert_counts + (size_t)first * h->disp_ch, (size_t)count * h->disp_ch * sizeof(uint32_t)));
+    if(dst->premirror)
+        WF_TRY_RC(copy_out(h, dst->premirror, h->d_bars_pre + (size_t)first * h->disp_ch, (size_t)count * h->disp_ch * sizeof(float)));
+    return WF_HIP_OK;
+}
+
+static int read_rows_async(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_readback *dst, wf_hip::ReadSlot &s)
+{
+    WF_TRY_RC(read_slot_ready(h, s, 0, count));
+    WF_TRY_RC(silent_bytes(h, first, count, s));
+    WF_TRY_RC(to_read_stream(h, s));
+    return copies_issued(h, s, true, rows_copies(h, first, count, dst, s));
+}
+
+int wf_hip_read_async(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_readback *dst, uint32_t slot)
+{
+    WF_TRY_RC(check_range(h, first, count));
+    if(dst == nullptr || slot > 1)
+        return fail(h, WF_HIP_ERR_INVALID, "destination set is NULL or slot is not 0 / 1");
+    const bool riders = dst->premirror || dst->vertices || dst->vertex_counts || dst->input_rms;
+    if(dst->meter) {
+        if(dst->last_silent == nullptr || dst->rows || dst->bars || riders)
+            return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: meter goes with last_silent and nothing else");
+    } else if(dst->rows == nullptr) {
+        if(dst->bars == nullptr || dst->last_silent || riders)
+            return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: without rows only the bars can be read (rows + last_silent lead every other combination)");
+    } else if(dst->last_silent == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "wf_hip_read_async: rows go with last_silent");
+    WF_TRY_RC(check_outputs(h, dst));
+    WF_HIP_TRY(h, hipSetDevice(h->device));
+    wf_hip::ReadSlot &s = h->read_slot[slot];
+    if(dst->meter)
+        return read_meter_async(h, first, count, dst->meter, dst->last_silent, s);
+    if(dst->rows == nullptr)
+        return read_bars_snapshot_async(h, first, count, dst->bars, s);
+    return read_rows_async(h, first, count, dst, s);
+}
+
 int wf_hip_readback_done(wf_hip *h, uint32_t slot)
 {
     if(h == nullptr || slot > 1)
         return WF_HIP_ERR_INVALID;
-    if(!h->read_used[slot])
+    if(!h->read_slot[slot].used)
         return WF_HIP_OK;
     WF_HIP_TRY(h, hipSetDevice(h->device));
-    WF_HIP_TRY(h, hipEventSynchronize(h->ev_read[slot]));
+    WF_HIP_TRY(h, hipEventSynchronize(h->read_slot[slot].ev_read));
     return WF_HIP_OK;
 }
 
@@ -1630,7 +1562,7 @@ int wf_hip_copy_bars_device_async(wf_hip *h, uint32_t first, uint32_t count, voi
     if(count == 0 || first >= h->n_streams || count > h->n_streams - first)
         return fail(h, WF_HIP_ERR_INVALID, "stream range [%u, %u+%u) outside 0..%u", first, first, count, h->n_streams);
     if(h->d_bars == nullptr)
-        return fail(h, WF_HIP_ERR_INVALID, "configuration has no bars (cfg.bars == 0)");
+        return fail(h, WF_HIP_ERR_INVALID, "configuration has no bars (cfg.bars == 0 and cfg.curve == 0)");
     if(d_out == nullptr || consumer_stream == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "output pointer or consumer stream is NULL");
     const size_t per = (size_t)h->disp_ch * h->num_bars;

@@ -58,15 +58,20 @@ struct wf_hip {
                                                   // buffer free, staging full): wf_hip_ingest_done waits for it
     IngestSlot ingest_slot[2];                    // audio, float or PCM
     IngestSlot sq_slot[2];                        // the squared peaks of wf_hip_push_rms_ragged_async ([count][max_frames])
-    // pipelined readback (wf_hip_read_async): a stream for the D2H copies, a device snapshot and two events per slot
+    // pipelined readback (wf_hip_read_async; wf_hip.hip, "pipelined readback"): a stream for the D2H copies and two slots, used
+    // alternately by the caller
+    struct ReadSlot {
+        float *d_snap = nullptr;          // snapshot of the bars alone or of the meter levels: filled on `stream`, copied out on read_stream
+        size_t snap_floats = 0;
+        uint8_t *d_silent = nullptr;      // m_last_silent as bytes (rows and meter readbacks): filled and copied out the same way
+        size_t silent_bytes = 0;
+        hipEvent_t ev_snap = nullptr;     // `stream` has produced what the slot's copies read
+        hipEvent_t ev_read = nullptr;     // the slot's last D2H copy has landed: wf_hip_readback_done waits for it
+        bool used = false;                // ev_read has been recorded
+        bool rows_in_flight = false;      // the copies read the rows (bars, vertices ...) in place: the next tick waits for ev_read
+    };
     hipStream_t read_stream = nullptr;
-    hipEvent_t ev_snap[2] = {nullptr, nullptr}, ev_read[2] = {nullptr, nullptr};
-    float *d_snap[2] = {nullptr, nullptr};
-    size_t snap_floats[2] = {0, 0};
-    bool read_used[2] = {false, false};
-    bool rows_in_flight[2] = {false, false}; // wf_hip_read_async copies the rows straight from m_decibels: the next tick waits for them
-    uint8_t *d_silent_bytes[2] = {nullptr, nullptr};  // rows readback: m_last_silent as bytes
-    size_t silent_bytes_cap[2] = {0, 0};
+    ReadSlot read_slot[2];
     uint32_t n_streams = 0;
     uint32_t ring_cap = 0;
     uint32_t ring_stride = 0;        // floats between consecutive rings: ring_cap + padding (see wf_hip_create)
@@ -278,6 +283,9 @@ inline int upload(wf_hip *h, const wf::cf **out, const std::vector<wf::cfloat> &
     *out = p;
     return WF_HIP_OK;
 }
+
+// the flag buffer the newest tick wrote: the current m_last_silent / hidden bits of every stream
+inline uint32_t *cur_flags(const wf_hip *h) { return h->d_flags + (size_t)h->flag_cur * h->n_streams; }
 
 inline uint32_t next_pow2(uint32_t v)
 {

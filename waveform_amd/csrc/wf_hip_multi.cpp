@@ -148,7 +148,7 @@ struct Shard {
     hipEvent_t ev_sent[2] = {nullptr, nullptr}; // peer transport: this shard's copies into every device's buffer have run
     hipEvent_t ev_done[2] = {nullptr, nullptr}; // the gathered result of the slot is complete on this device
     bool slot_used[2] = {false, false};
-    // zero-copy gathers (wf_hip_set_bars_mirror): the handle's tick kernel writes its bars into the slot's send buffer itself
+    // zero-copy gathers (wf_hip_set_bars_mirrors): the handle's tick kernel writes its bars into the slot's send buffer itself
     // (LOCAL: into the result), alternating with the ticks -- the slot of a gather is then the buffer the newest tick wrote
     bool mirror = false;
     bool direct = false; // peer transport with peer access everywhere: the tick kernel stores this shard's slice into every device's result itself

@@ -867,9 +867,9 @@ void wf_hip_destroy(wf_hip *h)
     if(h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if(h->read_stream)
         (void)hipStreamSynchronize(h->read_stream);
-    for(int i = 0; i < 2; ++i) {
-        if(h->ev_snap[i]) (void)hipEventDestroy(h->ev_snap[i]);
-        if(h->ev_read[i]) (void)hipEventDestroy(h->ev_read[i]);
+    for(wf_hip::ReadSlot &s : h->read_slot) { // (their device blocks went with h->allocs)
+        if(s.ev_snap) (void)hipEventDestroy(s.ev_snap);
+        if(s.ev_read) (void)hipEventDestroy(s.ev_read);
     }
     if(h->read_stream) (void)hipStreamDestroy(h->read_stream);
     for(auto e : h->ev_bars_lane)

@@ -824,7 +824,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         bar_args.clk = (a.phase_clock && threadIdx.x == 0) ? a.phase_clock + (size_t)blockIdx.x * 16 : nullptr;
         WF_STAMP(12);
 #else
-        // (the Bluestein / mixed-radix instantiations do not serve wf_hip_set_bars_mirror -- the host refuses it for their sizes --:
+        // (the Bluestein / mixed-radix instantiations do not serve wf_hip_set_bars_mirrors -- the host refuses it for their sizes --:
         // with the count a constant 0 the further stores fold away; the 96-register instantiation spilled on them)
         // (and BarArgs::pre_out points at the entry of the row being finished: the stream's only row when the threads of both spectra share it)
         const BarArgs bar_row = [&] {

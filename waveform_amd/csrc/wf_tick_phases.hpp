@@ -117,7 +117,7 @@ struct BarArgs {
     // every output sits on the clamped top position and has the same value: output num_bars / 2 + 1's goes here, one float per
     // displayed row, so that the host finds the reference's miny without drawing the row itself.  nullptr: not kept
     float *pre_out;            // [n_streams][disp_ch]; inside the kernel's display phase: the entry of the row being finished
-    // > 0 (wf_hip_set_bars_mirror / _mirrors): every tick also leaves the batch's bars -- the ones it finishes and, copied over, the
+    // > 0 (wf_hip_set_bars_mirrors): every tick also leaves the batch's bars -- the ones it finishes and, copied over, the
     // ones it does not touch (paused, hidden or silent streams) -- in out2_n more buffers of the same shape, buffer j starting
     // out2_delta[j] floats behind `out`: the send buffer of the all-gather of BASELINE configs[4] (or, with peer access, this shard's
     // slice of every device's gathered result) written by the kernel instead of by copies behind it
