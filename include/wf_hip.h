@@ -1050,8 +1050,12 @@ int wf_hip_multi_create(const wf_config *cfg, const int *devices, uint32_t n_dev
                         wf_hip_multi **out);
 void wf_hip_multi_destroy(wf_hip_multi *m);
 /* text of the last error on this group (or of the last failed wf_hip_multi_create when m == NULL).  Right after a successful
- * wf_hip_multi_create: why the group did not get the transport it would have picked by itself ("ncclCommInitAll failed: ...",
- * "peer access is not enabled between every pair of devices ..."), or "" */
+ * wf_hip_multi_create: why the group did not get the transport it would have picked by itself, or "".  RCCL's reason where it was
+ * wanted and not to be had ("librccl.so not loadable: ...", "librccl.so lacks nccl...", "ncclCommInitAll failed: ..."); otherwise,
+ * on the peer transport, why the tick kernels do not store into every device's result themselves, each ending in ": the bars
+ * travel by hipMemcpyPeerAsync" -- "peer access is not enabled from device I to device J" (the first such ordered pair, HIP device
+ * numbers), "N devices: a tick kernel stores into the results of at most 8 (wf_hip_set_bars_mirrors)", or
+ * "WF_HIP_MULTI_MIRROR=send asks for no direct stores into the other devices' results" (=0 likewise) */
 const char *wf_hip_multi_last_error(const wf_hip_multi *m);
 uint32_t wf_hip_multi_num_devices(const wf_hip_multi *m);
 uint32_t wf_hip_multi_num_streams(const wf_hip_multi *m);

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -36,7 +37,13 @@ hipError_t hipFree(void *p) { std::free(p); return hipSuccess; }
 hipError_t hipMemset(void *p, int v, size_t n) { std::memset(p, v, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { std::memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyPeerAsync(void *d, int, const void *s, int, size_t n, hipStream_t) { std::memcpy(d, s, n); return hipSuccess; }
-hipError_t hipDeviceCanAccessPeer(int *can, int, int) { *can = 1; return hipSuccess; }
+hipError_t hipDeviceCanAccessPeer(int *can, int device, int peer)
+{
+    int i = -1, j = -1; // WF_MOCK_DENY_PEER=i:j: device i may not address device j (that ordered pair alone)
+    const char *deny = getenv("WF_MOCK_DENY_PEER");
+    *can = !(deny && sscanf(deny, "%d:%d", &i, &j) == 2 && i == device && j == peer);
+    return hipSuccess;
+}
 hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char *hipGetErrorString(hipError_t) { return "mock"; }
@@ -122,6 +129,7 @@ int wf_hip_set_bars_mirrors(wf_hip *h, uint32_t n, void *const *a, void *const *
     h->mirror_fresh = false;
     return WF_HIP_OK;
 }
+uint32_t mock_mirror_buffers(const wf_hip *h) { return h->mirrors.empty() ? 0u : (uint32_t)h->mirrors[0].size(); } // per set; 0: no mirrors
 int wf_hip_bars_mirror_ready(wf_hip *h, void *, void **out)
 {
     if(h->mirrors.empty() || h->mirrors[0].empty())

@@ -321,6 +321,83 @@ print("survived")
     assert r.returncode == 0 and "survived" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
+@pytest.mark.parametrize("timed", [False, True])
+def test_a_mirror_handed_over_outside_the_group_fails_the_gather(timed):
+    """wf_hip_bars_mirror_ready on ONE shard handle behind the group's back (the header forbids it): that shard's next hand-over is
+    the other buffer, so the pieces of a gathered result would lie in different buffers.  wf_hip_multi_allgather_bars says so between
+    its halves, a gathering wf_hip_multi_time_ticks once its workers are back (tests/test_multi_mock_cpu.py has both over the mock
+    device); the exchange is then out of service, and ticks, reads, sync and close go on.  Two shards on one device, peer transport,
+    the tick kernels storing into both results themselves (FFT 4096 with bars: the smallest shape whose tick kernel takes the
+    mirror buffers).  An error return on the host, nothing on the device; in a child process like the failure test above."""
+    code = r'''
+import sys, ctypes as C, numpy as np
+sys.path.insert(0, %r)
+import waveform_amd as wf
+from tools import synth
+timed = %d
+cfg = wf.Config.defaults(fft_size=4096, stereo=1, slope=1.0, bars=1, interp_mode=wf.INTERP["lanczos"])
+streams, hop = 6, 800
+ring = 4096 + 12 * hop
+def refused(call, text):
+    try:
+        call()
+    except wf.WfHipError as e:
+        assert text in str(e), str(e)
+        return
+    raise SystemExit("accepted where it had to say: " + text)
+with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as plain, wf.MultiBatch(cfg, streams, [0, 0], ring_frames=ring) as m:
+    assert m.transport == "peer" and m.transport_note == "", (m.transport, m.transport_note)
+    for b in (plain, m):
+        b.push_synth(synth.DEFAULT_SEED, 0, 10 * hop)
+        b.tick(delay_frames=hop * 9)
+    m.allgather_bars()
+    assert np.array_equal(m.gathered(0), plain.bars()) and np.array_equal(m.gathered(1), plain.bars())
+    buf = C.c_void_p()
+    assert m.L.wf_hip_bars_mirror_ready(m.shards[1][0], m.L.wf_hip_multi_gather_stream(m.m, 1), C.byref(buf)) == 0
+    if timed:
+        refused(lambda: m.time_ticks(4, hop, hop * 8, gather=True), "handed over or replaced outside the group")
+    else:
+        m.tick(delay_frames=hop * 8)
+        refused(m.allgather_bars, "handed over or replaced outside the group")
+    refused(m.allgather_bars, "out of service")
+    refused(lambda: m.gathered(0), "out of service")
+    for t in range(4 if timed else 1):
+        plain.tick(delay_frames=hop * (8 - t))
+    for b in (plain, m):
+        b.tick(delay_frames=hop * 3)
+    assert np.array_equal(m.bars(), plain.bars())
+    m.sync()
+print("survived")
+''' % (str(ROOT), int(timed))
+    env = dict(os.environ, WF_HIP_MULTI_TRANSPORT="peer", WF_HIP_MULTI_MIRROR="1")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "survived" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+
+
+@pytest.mark.parametrize("mirror", [None, "send"])
+def test_the_note_names_the_variable_not_peer_access(mirror, monkeypatch):
+    """three shards on one device, peer transport asked for by name: every shard addresses every other, the tick kernels store
+    into every result and there is nothing to note; with WF_HIP_MULTI_MIRROR=send the note names the variable -- the caller asked --
+    and peer access, which is fine, in neither case"""
+    monkeypatch.setenv("WF_HIP_MULTI_TRANSPORT", "peer")
+    if mirror is None:
+        monkeypatch.delenv("WF_HIP_MULTI_MIRROR", raising=False)
+    else:
+        monkeypatch.setenv("WF_HIP_MULTI_MIRROR", mirror)
+    streams, hop = 7, 800
+    with wf.MultiBatch(_cfg(fft_size=2048), streams, [0, 0, 0]) as m:
+        assert m.transport == "peer"
+        assert "peer access" not in m.transport_note
+        if mirror is None:
+            assert m.transport_note == ""
+        else:
+            assert "WF_HIP_MULTI_MIRROR=send" in m.transport_note and "hipMemcpyPeerAsync" in m.transport_note, m.transport_note
+        m.push_synth(SEED, 0, hop)
+        m.tick()
+        m.allgather_bars()
+        assert np.array_equal(m.gathered(2), m.bars())
+
+
 def test_multi_errors_are_reported():
     cfg = _cfg()
     with pytest.raises(wf.WfHipError) as e:

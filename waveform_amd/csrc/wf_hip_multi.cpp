@@ -137,23 +137,34 @@ struct Worker {
 
 enum class Transport { LOCAL, RCCL, PEER };
 
+// The limits of a group.  MAX_DEVICES is what wf_hip_multi_create accepts (validate_devices) and sizes Shard::peer_ok;
+// MAX_MIRRORS is the number of buffers wf_hip_set_bars_mirrors takes per set (include/wf_hip.h: "two sets of n <= 8 buffers"):
+// a larger group cannot have its tick kernels store into every device's result (decide_direct).
+constexpr uint32_t MAX_DEVICES = 64;
+constexpr uint32_t MAX_MIRRORS = 8;
+
+// One of the two slots the gather alternates between: what one exchange reads, writes and signals on this shard's device.
+struct GatherSlot {
+    float *send = nullptr;        // this shard's bars, [largest][disp_ch][num_bars] (padded for ragged RCCL gathers)
+    float *pad = nullptr;         // RCCL with shards of unequal size: [n][largest][...] before compaction
+    float *result = nullptr;      // the gathered bars, [streams_total][disp_ch][num_bars]
+    hipEvent_t ev_sent = nullptr; // peer transport: this shard's copies into every device's buffer have run
+    hipEvent_t ev_done = nullptr; // the gathered result of the slot is complete on this device
+    bool used = false;
+};
+
 struct Shard {
     int device = 0;
     wf_hip *h = nullptr;
     uint32_t first = 0, count = 0;
-    hipStream_t gstream = nullptr;       // the gather's side stream on this device
-    float *send[2] = {nullptr, nullptr}; // this shard's bars, [largest][disp_ch][num_bars] (padded for ragged RCCL gathers)
-    float *recv_pad[2] = {nullptr, nullptr}; // RCCL with shards of unequal size: [n][largest][...] before compaction
-    float *gathered[2] = {nullptr, nullptr}; // [streams_total][disp_ch][num_bars]
-    hipEvent_t ev_sent[2] = {nullptr, nullptr}; // peer transport: this shard's copies into every device's buffer have run
-    hipEvent_t ev_done[2] = {nullptr, nullptr}; // the gathered result of the slot is complete on this device
-    bool slot_used[2] = {false, false};
+    hipStream_t gstream = nullptr; // the gather's side stream on this device
+    GatherSlot slot[2];
     // zero-copy gathers (wf_hip_set_bars_mirrors): the handle's tick kernel writes its bars into the slot's send buffer itself
     // (LOCAL: into the result), alternating with the ticks -- the slot of a gather is then the buffer the newest tick wrote
     bool mirror = false;
     bool direct = false; // peer transport with peer access everywhere: the tick kernel stores this shard's slice into every device's result itself
     uint32_t cur_slot = 0; // the slot of the gather in flight / issued last on this shard
-    bool peer_ok[64] = {}; // [j]: this device may address device j's memory (peer access enabled, or the same device)
+    bool peer_ok[MAX_DEVICES] = {}; // [j]: this device may address device j's memory (peer access enabled, or the same device)
     ncclComm_t comm = nullptr;
     Worker worker;
     std::string err;
@@ -250,6 +261,40 @@ int check_range(wf_hip_multi *m, uint32_t first, uint32_t count)
     return WF_HIP_OK;
 }
 
+// The buffer of slot k that shard s's ticks write (zero-copy gathers: buffer 0 of the set its handle is given, the one
+// wf_hip_bars_mirror_ready hands back) or that its bars are copied into behind the tick: its slice of device 0's result (direct
+// peer stores), its own result (one device) or its send buffer (RCCL, peer copies).  The hand-over at create, the slot
+// gather_fill finds back from the handle's pointer and the copy path all ask here.
+float *tick_target(const wf_hip_multi *m, const Shard &s, uint32_t k)
+{
+    if(s.direct)
+        return m->shard[0]->slot[k].result + (size_t)s.first * m->per;
+    return m->transport == Transport::LOCAL ? s.slot[k].result : s.slot[k].send;
+}
+
+// shard s's bars into slot *k's buffer behind the ticks issued so far, the gather stream waiting for them; zero-copy gathers:
+// *k becomes the slot the handle's newest tick wrote
+int gather_fill(wf_hip_multi *m, Shard &s, uint32_t *k)
+{
+    if(s.mirror) {
+        // the handle's ticks have written the bars into one of the two sets themselves (wf_hip_bars_mirror_ready: the gather stream
+        // waits for the newest tick, the other set becomes the ticks' target; a set no tick has written is filled from the
+        // handle's own bars): nothing is copied here
+        void *buf = nullptr;
+        const int rc = wf_hip_bars_mirror_ready(s.h, s.gstream, &buf);
+        if(rc)
+            return rc;
+        *k = buf == (const void *)tick_target(m, s, 1) ? 1u : 0u;
+        return WF_HIP_OK;
+    }
+    if(s.slot[*k].used) { // the gather that read this send buffer two gathers ago must have run before the buffer is rewritten
+        const int rc = wf_hip_wait_event(s.h, s.slot[*k].ev_done);
+        if(rc)
+            return rc;
+    }
+    return wf_hip_copy_bars_device_async(s.h, 0, s.count, tick_target(m, s, *k), s.gstream);
+}
+
 // The gather of shard i, first half: its bars into the slot's send buffer behind the ticks issued so far, then -- on the
 // device's gather stream, which waits only for that copy -- the collective (RCCL) or this shard's copies into every
 // device's result (peer).  Nothing here waits on the host.
@@ -262,37 +307,17 @@ int gather_issue(wf_hip_multi *m, uint32_t i, uint32_t k)
         return WF_HIP_ERR_RUNTIME;
     }
 #endif
-    int rc;
-    if(s.mirror) {
-        // the handle's ticks have written the bars into one of the two sets themselves (wf_hip_bars_mirror_ready: the gather stream
-        // waits for the newest tick, the other set becomes the ticks' target; a set no tick has written is filled from the
-        // handle's own bars): nothing is copied here
-        void *buf = nullptr;
-        rc = wf_hip_bars_mirror_ready(s.h, s.gstream, &buf);
-        if(rc)
-            return rc;
-        // buffer 0 of a set: the send buffer (RCCL, peer copies), the result itself (one device), or -- direct peer stores -- this
-        // shard's slice of device 0's result
-        const float *b1 = s.direct ? m->shard[0]->gathered[1] + (size_t)s.first * m->per : (m->transport == Transport::LOCAL) ? s.gathered[1] : s.send[1];
-        k = buf == (const void *)b1 ? 1u : 0u;
-    } else {
-        if(s.slot_used[k]) { // the gather that read this send buffer two gathers ago must have run before the buffer is rewritten
-            rc = wf_hip_wait_event(s.h, s.ev_done[k]);
-            if(rc)
-                return rc;
-        }
-        float *dst = (m->transport == Transport::LOCAL) ? s.gathered[k] : s.send[k];
-        rc = wf_hip_copy_bars_device_async(s.h, 0, s.count, dst, s.gstream);
-        if(rc)
-            return rc;
-    }
+    const int rc = gather_fill(m, s, &k);
+    if(rc)
+        return rc;
     s.cur_slot = k;
+    GatherSlot &g = s.slot[k];
     const size_t per = m->per;
     switch(m->transport) {
     case Transport::LOCAL: break;
     case Transport::RCCL: {
-        float *recv = m->ragged ? s.recv_pad[k] : s.gathered[k];
-        const ncclResult_t r = rccl().AllGather(s.send[k], recv, (size_t)m->largest * per, ncclFloat, s.comm, s.gstream);
+        float *recv = m->ragged ? g.pad : g.result;
+        const ncclResult_t r = rccl().AllGather(g.send, recv, (size_t)m->largest * per, ncclFloat, s.comm, s.gstream);
         if(r != ncclSuccess) {
             s.err = std::string("ncclAllGather failed: ") + rccl().GetErrorString(r);
             return WF_HIP_ERR_RUNTIME;
@@ -300,7 +325,7 @@ int gather_issue(wf_hip_multi *m, uint32_t i, uint32_t k)
         if(m->ragged) // rank r's block of `largest` streams holds count_r valid ones: compact into global stream order
             for(uint32_t r2 = 0; r2 < m->n; ++r2) {
                 const Shard &o = *m->shard[r2];
-                WF_MHIP(s, hipMemcpyAsync(s.gathered[k] + (size_t)o.first * per, recv + (size_t)r2 * m->largest * per,
+                WF_MHIP(s, hipMemcpyAsync(g.result + (size_t)o.first * per, recv + (size_t)r2 * m->largest * per,
                                           (size_t)o.count * per * sizeof(float), hipMemcpyDeviceToDevice, s.gstream));
             }
         break;
@@ -308,10 +333,10 @@ int gather_issue(wf_hip_multi *m, uint32_t i, uint32_t k)
     case Transport::PEER:
         for(uint32_t j = 0; j < m->n && !s.direct; ++j) { // (direct: the tick kernel has stored the slice everywhere already)
             Shard &o = *m->shard[j];
-            WF_MHIP(s, hipMemcpyPeerAsync(o.gathered[k] + (size_t)s.first * per, o.device, s.send[k], s.device,
+            WF_MHIP(s, hipMemcpyPeerAsync(o.slot[k].result + (size_t)s.first * per, o.device, g.send, s.device,
                                           (size_t)s.count * per * sizeof(float), s.gstream));
         }
-        WF_MHIP(s, hipEventRecord(s.ev_sent[k], s.gstream));
+        WF_MHIP(s, hipEventRecord(g.ev_sent, s.gstream));
         break;
     }
     return WF_HIP_OK;
@@ -322,21 +347,24 @@ int gather_issue(wf_hip_multi *m, uint32_t i, uint32_t k)
 int gather_complete(wf_hip_multi *m, uint32_t i, uint32_t k)
 {
     Shard &s = *m->shard[i];
+    // Zero-copy gathers: the slot is the one this shard's handle handed over.  The group hands over every shard's set the same
+    // number of times, so it is the same slot on all of them -- which is not checked here, among the workers, but by the API
+    // thread (slots_agree): wf_hip_multi_allgather_bars between the halves, wf_hip_multi_time_ticks once its workers are back.
     if(s.mirror)
-        k = s.cur_slot; // (the group has handed over every shard's set the same number of times: the same slot on all of them -- checked by the callers)
+        k = s.cur_slot;
     if(m->transport == Transport::PEER)
         for(uint32_t j = 0; j < m->n; ++j)
             if(j != i)
-                WF_MHIP(s, hipStreamWaitEvent(s.gstream, m->shard[j]->ev_sent[k], 0));
-    WF_MHIP(s, hipEventRecord(s.ev_done[k], s.gstream));
-    s.slot_used[k] = true;
-    // The ticks issued from here on write the other slot's buffers (the hand-over in gather_issue made them the write set).  Where
+                WF_MHIP(s, hipStreamWaitEvent(s.gstream, m->shard[j]->slot[k].ev_sent, 0));
+    WF_MHIP(s, hipEventRecord(s.slot[k].ev_done, s.gstream));
+    s.slot[k].used = true;
+    // The ticks issued from here on write the other slot's buffers (the hand-over in gather_fill made them the write set).  Where
     // that is a SEND buffer (RCCL; peer copies), the exchange that read it -- a gather old -- must have run: a host wait that returns
     // at once (a device-side wait in front of every tick cost 4 % of the tick rate).  Where the kernels store into the results
     // themselves (local, direct peer stores) nothing inside the group reads the buffer: it is the result of the gather before this
     // one, which the header's contract gives up with the first tick after this gather.
-    if(s.mirror && !s.direct && m->transport != Transport::LOCAL && s.slot_used[k ^ 1u])
-        WF_MHIP(s, hipEventSynchronize(s.ev_done[k ^ 1u]));
+    if(s.mirror && !s.direct && m->transport != Transport::LOCAL && s.slot[k ^ 1u].used)
+        WF_MHIP(s, hipEventSynchronize(s.slot[k ^ 1u].ev_done));
     return WF_HIP_OK;
 }
 
@@ -363,6 +391,15 @@ int gather_check(wf_hip_multi *m)
     return WF_HIP_OK;
 }
 
+// fn on shard s's own thread, where it has one, from the API thread (no job of the group running)
+void on_worker(Shard &s, const std::function<void()> &fn)
+{
+    if(!s.worker.th.joinable())
+        return;
+    s.worker.post([&fn] { return fn(), 0; });
+    (void)s.worker.wait();
+}
+
 // A shard failed inside a gather while others had already enqueued their half of it.  From the API thread, no worker running:
 // the communicators are aborted (every one of them, so that no rank keeps waiting in a kernel for a peer that never launched),
 // the events the handles' streams may be waiting for are recorded afresh on the (now draining) gather streams, and the group
@@ -381,20 +418,14 @@ void gather_fail(wf_hip_multi *m)
             sp->comm = nullptr;
         }
     // whatever a handle's streams were told to wait for (ev_done of a slot whose collective is gone) completes now
-    for(auto &sp : m->shard) {
-        Shard &s = *sp;
-        if(!s.worker.th.joinable() || s.gstream == nullptr)
-            continue;
-        s.worker.post([&s] {
-            for(int k = 0; k < 2; ++k) {
-                if(s.ev_sent[k]) (void)hipEventRecord(s.ev_sent[k], s.gstream);
-                if(s.ev_done[k]) (void)hipEventRecord(s.ev_done[k], s.gstream);
-                s.slot_used[k] = false;
+    for(auto &sp : m->shard)
+        on_worker(*sp, [&s = *sp] {
+            for(GatherSlot &g : s.slot) {
+                if(g.ev_sent) (void)hipEventRecord(g.ev_sent, s.gstream);
+                if(g.ev_done) (void)hipEventRecord(g.ev_done, s.gstream);
+                g.used = false;
             }
-            return 0;
         });
-        (void)s.worker.wait();
-    }
 }
 
 void destroy_impl(wf_hip_multi *m)
@@ -402,19 +433,13 @@ void destroy_impl(wf_hip_multi *m)
     if(m == nullptr)
         return;
     // the workers' last job: drain and free what lives on their device
-    for(auto &sp : m->shard) {
-        Shard &s = *sp;
-        if(!s.worker.th.joinable())
-            continue;
-        s.worker.post([&s] {
+    for(auto &sp : m->shard)
+        on_worker(*sp, [&s = *sp] {
             if(s.gstream)
                 (void)hipStreamSynchronize(s.gstream);
             if(s.h)
                 (void)wf_hip_sync(s.h);
-            return 0;
         });
-        (void)s.worker.wait();
-    }
     for(auto &sp : m->shard) // communicators go first, all of them, from one thread (ncclCommDestroy may synchronise with peers)
         if(sp->comm) {
             (void)hipSetDevice(sp->device);
@@ -422,27 +447,268 @@ void destroy_impl(wf_hip_multi *m)
             sp->comm = nullptr;
         }
     for(auto &sp : m->shard) {
-        Shard &s = *sp;
-        if(s.worker.th.joinable()) {
-            s.worker.post([&s] {
-                for(int k = 0; k < 2; ++k) {
-                    if(s.send[k]) (void)hipFree(s.send[k]);
-                    if(s.recv_pad[k]) (void)hipFree(s.recv_pad[k]);
-                    if(s.gathered[k]) (void)hipFree(s.gathered[k]);
-                    if(s.ev_sent[k]) (void)hipEventDestroy(s.ev_sent[k]);
-                    if(s.ev_done[k]) (void)hipEventDestroy(s.ev_done[k]);
-                }
-                if(s.gstream)
-                    (void)hipStreamDestroy(s.gstream);
-                if(s.h)
-                    wf_hip_destroy(s.h);
-                return 0;
-            });
-            (void)s.worker.wait();
-            s.worker.stop();
-        }
+        on_worker(*sp, [&s = *sp] {
+            for(GatherSlot &g : s.slot) {
+                for(float *p : {g.send, g.pad, g.result})
+                    if(p) (void)hipFree(p);
+                for(hipEvent_t e : {g.ev_sent, g.ev_done})
+                    if(e) (void)hipEventDestroy(e);
+            }
+            if(s.gstream)
+                (void)hipStreamDestroy(s.gstream);
+            if(s.h)
+                wf_hip_destroy(s.h);
+        });
+        sp->worker.stop();
     }
     delete m;
+}
+
+// ---- wf_hip_multi_create, in stages (wf_hip_multi_create itself, below, is their order and the one failure exit) ------------
+
+// What the environment asks of a group: read once per create, on the API thread, before any device is touched.
+struct Overrides {
+    bool transport_named = false, rccl = false, peer = false; // WF_HIP_MULTI_TRANSPORT is set; to rccl; to peer ("local": neither)
+    bool mirrors = false;              // WF_HIP_MULTI_MIRROR is set, and not to 0 (hand_over_mirrors)
+    const char *no_direct = nullptr;   // "send" or "0" where WF_HIP_MULTI_MIRROR rules out the direct peer stores: for the note
+    bool gather_priority_high = false; // WF_HIP_MULTI_GATHER_PRIORITY=high
+};
+
+int read_overrides(Overrides *ov)
+{
+    if(const char *e = std::getenv("WF_HIP_MULTI_TRANSPORT")) {
+        ov->transport_named = true;
+        ov->rccl = std::strcmp(e, "rccl") == 0;
+        ov->peer = std::strcmp(e, "peer") == 0;
+        if(!ov->rccl && !ov->peer && std::strcmp(e, "local") != 0)
+            return mfail(nullptr, WF_HIP_ERR_INVALID, "WF_HIP_MULTI_TRANSPORT=%s: expected rccl or peer", e);
+    }
+    if(const char *e = std::getenv("WF_HIP_MULTI_MIRROR")) {
+        ov->mirrors = e[0] != '0';
+        ov->no_direct = !ov->mirrors ? "0" : std::strcmp(e, "send") == 0 ? "send" : nullptr;
+    }
+    if(const char *e = std::getenv("WF_HIP_MULTI_GATHER_PRIORITY"))
+        ov->gather_priority_high = std::strcmp(e, "high") == 0;
+    return WF_HIP_OK;
+}
+
+// the device list: 1..MAX_DEVICES devices this box has, a stream at least for each; a device may be named more than once
+int validate_devices(const wf_config *cfg, const int *devices, uint32_t n_devices, uint32_t streams_total, bool *duplicates)
+{
+    if(cfg == nullptr || devices == nullptr || n_devices == 0 || n_devices > MAX_DEVICES)
+        return mfail(nullptr, WF_HIP_ERR_INVALID, "cfg / devices NULL, or n_devices %u outside 1..%u", n_devices, MAX_DEVICES);
+    if(streams_total < n_devices)
+        return mfail(nullptr, WF_HIP_ERR_INVALID, "%u streams cannot be spread over %u devices (every shard needs one)", streams_total, n_devices);
+    const int have = wf_hip_device_count();
+    if(have <= 0)
+        return mfail(nullptr, WF_HIP_ERR_NO_DEVICE, "no usable HIP device");
+    *duplicates = false;
+    for(uint32_t i = 0; i < n_devices; ++i) {
+        if(devices[i] < 0 || devices[i] >= have)
+            return mfail(nullptr, WF_HIP_ERR_INVALID, "devices[%u] = %d, the box has %d", i, devices[i], have);
+        for(uint32_t j = 0; j < i; ++j)
+            *duplicates = *duplicates || devices[j] == devices[i];
+    }
+    return WF_HIP_OK;
+}
+
+// the streams in contiguous shards, sizes differing by at most one, the first (streams_total % n) shards holding one more; every
+// shard's host thread starts here.  nullptr: out of host memory.
+wf_hip_multi *split_streams(const wf_config *cfg, const int *devices, uint32_t n_devices, uint32_t streams_total)
+{
+    auto *m = new(std::nothrow) wf_hip_multi;
+    if(m == nullptr)
+        return nullptr;
+    m->cfg = *cfg;
+    m->n = n_devices;
+    m->total = streams_total;
+    const uint32_t base = streams_total / n_devices, extra = streams_total % n_devices;
+    m->largest = base + (extra ? 1u : 0u);
+    m->ragged = extra != 0;
+    for(uint32_t i = 0; i < n_devices; ++i) {
+        auto s = std::make_unique<Shard>();
+        s->device = devices[i];
+        s->count = base + (i < extra ? 1u : 0u);
+        s->first = i * base + std::min(i, extra);
+        s->worker.start(s->device);
+        m->shard.push_back(std::move(s));
+    }
+    return m;
+}
+
+// the shards' handles, every device building its own concurrently
+int build_handles(wf_hip_multi *m, uint32_t ring_frames)
+{
+    const int rc = run_all(m, [m, ring_frames](uint32_t i) {
+        Shard &s = *m->shard[i];
+        const int r = wf_hip_create(&m->cfg, s.device, s.count, ring_frames, &s.h);
+        if(r != WF_HIP_OK)
+            s.err = wf_hip_last_error(nullptr);
+        return r;
+    });
+    if(rc == WF_HIP_OK)
+        m->per = (size_t)wf_hip_display_channels(m->shard[0]->h) * wf_hip_num_bars(m->shard[0]->h);
+    return rc;
+}
+
+// The transport of the gather: RCCL where there is something to gather and the devices are distinct and more than one (or it
+// is asked for by name), peer copies otherwise; one shard gathers by a device copy.  Where RCCL was wanted and is not to be had,
+// m->transport_note says why.
+int choose_transport(wf_hip_multi *m, const Overrides &ov, const int *devices, bool duplicates)
+{
+    const bool want_rccl = ov.transport_named ? ov.rccl : (m->n > 1 && !duplicates);
+    m->transport = (m->n == 1 && !ov.peer) ? Transport::LOCAL : Transport::PEER;
+    if(m->per == 0 || !want_rccl)
+        return WF_HIP_OK;
+    Rccl &r = rccl();
+    if(!r.ok)
+        m->transport_note = r.why;
+    else {
+        std::vector<ncclComm_t> comms(m->n, nullptr);
+        const ncclResult_t e = r.CommInitAll(comms.data(), (int)m->n, devices);
+        if(e == ncclSuccess) {
+            for(uint32_t i = 0; i < m->n; ++i)
+                m->shard[i]->comm = comms[i];
+            m->transport = Transport::RCCL;
+        } else
+            m->transport_note = std::string("ncclCommInitAll failed: ") + r.GetErrorString(e);
+    }
+    if(m->transport != Transport::RCCL && ov.rccl) // asked for by name: do not quietly use something else
+        return mfail(m, WF_HIP_ERR_RUNTIME, "WF_HIP_MULTI_TRANSPORT=rccl: %s", m->transport_note.c_str());
+    return WF_HIP_OK;
+}
+
+// the exchange on shard s's device (its own thread): the gather stream, and both slots' events and buffers
+int alloc_exchange(wf_hip_multi *m, Shard &s, bool gather_priority_high)
+{
+    // HIP multiplexes a process's streams of one priority onto four hardware queues per device, which a handle's lanes fill: a
+    // gather stream that shares an in-order hardware queue with a lane puts that lane's next tick behind whatever the exchange
+    // of the last one enqueued (two shards on one device, peer copies: +36 us per tick), and one with a queue of its own
+    // (another priority) runs its kernels INTO the tick, which fills the CUs in whole rounds (+77 us; both traced:
+    // profiles/r05h_peer_trace*.txt).  The exchange therefore enqueues no kernel where it can avoid it (mirrors below); RCCL's
+    // own kernels remain -- WF_HIP_MULTI_GATHER_PRIORITY=high lets a node check try them on a queue of their own.
+    if(gather_priority_high) {
+        int least = 0, greatest = 0;
+        WF_MHIP(s, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        WF_MHIP(s, hipStreamCreateWithPriority(&s.gstream, hipStreamNonBlocking, greatest));
+    } else
+        WF_MHIP(s, hipStreamCreateWithFlags(&s.gstream, hipStreamNonBlocking));
+    const size_t per = m->per;
+    for(GatherSlot &g : s.slot) {
+        WF_MHIP(s, hipEventCreateWithFlags(&g.ev_sent, hipEventDisableTiming));
+        WF_MHIP(s, hipEventCreateWithFlags(&g.ev_done, hipEventDisableTiming));
+        WF_MHIP(s, hipMalloc((void **)&g.result, (size_t)m->total * per * sizeof(float)));
+        if(m->transport != Transport::LOCAL) {
+            WF_MHIP(s, hipMalloc((void **)&g.send, (size_t)m->largest * per * sizeof(float)));
+            WF_MHIP(s, hipMemset(g.send, 0, (size_t)m->largest * per * sizeof(float)));
+        }
+        if(m->transport == Transport::RCCL && m->ragged)
+            WF_MHIP(s, hipMalloc((void **)&g.pad, (size_t)m->n * m->largest * per * sizeof(float)));
+    }
+    return WF_HIP_OK;
+}
+
+// peer transport: which devices shard s's device may address (on its own thread) -- direct xGMI stores where the link allows;
+// hipMemcpyPeerAsync stages otherwise
+void probe_peer_access(const wf_hip_multi *m, Shard &s)
+{
+    for(uint32_t j = 0; j < m->n; ++j) {
+        const int other = m->shard[j]->device;
+        int can = 0;
+        bool ok = other == s.device;
+        if(!ok && hipDeviceCanAccessPeer(&can, s.device, other) == hipSuccess && can) {
+            // (refused: not fatal for the copies, which are then staged -- but kernel stores to that device's memory would
+            // fault: direct peer stores need the mapping to exist, for every ordered pair)
+            const hipError_t pe = hipDeviceEnablePeerAccess(other, 0);
+            ok = pe == hipSuccess || pe == hipErrorPeerAccessAlreadyEnabled;
+            (void)hipGetLastError();
+        }
+        s.peer_ok[j] = ok;
+    }
+}
+
+// Whether the shards' tick kernels store their slices into EVERY device's result themselves (peer transport only) -- and, where
+// they do not, why: that becomes the group's note unless RCCL has left one already.
+bool decide_direct(wf_hip_multi *m, const Overrides &ov)
+{
+    if(m->transport != Transport::PEER)
+        return false;
+    char why[200] = "";
+    if(ov.no_direct)
+        snprintf(why, sizeof(why), "WF_HIP_MULTI_MIRROR=%s asks for no direct stores into the other devices' results", ov.no_direct);
+    else if(m->n > MAX_MIRRORS)
+        snprintf(why, sizeof(why), "%u devices: a tick kernel stores into the results of at most %u (wf_hip_set_bars_mirrors)", m->n, MAX_MIRRORS);
+    for(uint32_t i = 0; i < m->n && !why[0]; ++i) // hipDeviceEnablePeerAccess succeeded (or had before) on device i for device j
+        for(uint32_t j = 0; j < m->n && !why[0]; ++j)
+            if(!m->shard[i]->peer_ok[j])
+                snprintf(why, sizeof(why), "peer access is not enabled from device %d to device %d", m->shard[i]->device, m->shard[j]->device);
+    if(why[0] && m->transport_note.empty())
+        m->transport_note = std::string(why) + ": the bars travel by hipMemcpyPeerAsync";
+    return !why[0];
+}
+
+// Zero-copy gathers, once every device's buffers exist.  Which shards' tick kernels write the exchange's buffers themselves
+// (wf_hip_set_bars_mirrors) instead of a device copy behind the tick: by default only where that saves the PEER copies -- every
+// device addresses every other, the slices go straight into every device's result: no copy, no kernel on the gather streams at
+// all.  Into a send buffer (RCCL; peer copies) or the one device's own result the kernel-side stores bought nothing once the
+// kernels came in display-specific instantiations: the copy behind the tick 0.651 against 0.618 through this group, 0.649 against
+// 0.650 from a torch process (profiles/r06o_gather_mirror_one_ab.txt).  WF_HIP_MULTI_MIRROR: 1 = the kernels write wherever they
+// can (round 5's default), send = that without the direct peer stores, 0 = the copy for everybody (A/B aids).  The batches whose
+// display comes from a kernel of its own keep the copy behind the tick whatever is asked (WF_HIP_ERR_UNSUPPORTED).
+int hand_over_mirrors(wf_hip_multi *m, const Overrides &ov)
+{
+    const bool direct = decide_direct(m, ov);
+    if(!ov.mirrors && !direct)
+        return WF_HIP_OK;
+    return run_all(m, [m, direct](uint32_t i) {
+        Shard &s = *m->shard[i];
+        s.direct = direct; // (tick_target answers for the set being handed over)
+        void *set[2][MAX_MIRRORS];
+        const uint32_t n_buffers = direct ? m->n : 1u;
+        for(uint32_t k = 0; k < 2; ++k) {
+            set[k][0] = tick_target(m, s, k);
+            for(uint32_t j = 1; j < n_buffers; ++j) // direct: the same slice of every other device's result
+                set[k][j] = m->shard[j]->slot[k].result + (size_t)s.first * m->per;
+        }
+        const int rc = wf_hip_set_bars_mirrors(s.h, n_buffers, set[0], set[1]);
+        s.mirror = rc == WF_HIP_OK;
+        s.direct = s.mirror && direct;
+        if(rc == WF_HIP_OK || rc == WF_HIP_ERR_UNSUPPORTED) // (unsupported: this handle keeps the copy behind the tick)
+            return (int)WF_HIP_OK;
+        s.err = wf_hip_last_error(s.h);
+        return rc;
+    });
+}
+
+// A timed run on shard i (its own thread): the start of the clock, then the ticks, a gather behind each where asked; nothing
+// here waits on the host.  The halves of a peer gather need every device's events recorded in between: a barrier among the
+// workers.  A worker that fails keeps arriving at the barriers (doing nothing) so that the others do not wait for it for ever.
+// Returns the first failure.
+struct TimedRun { // (the call's arguments; k0: the gathers issued before the run)
+    wf_hip_tick_params p;
+    uint32_t ticks, hop, k0;
+    bool gather;
+};
+int timed_ticks(wf_hip_multi *m, uint32_t i, const TimedRun &run, std::barrier<> &sync)
+{
+    const uint32_t period = run.hop ? run.p.delay_frames / run.hop + 1 : run.ticks;
+    int st = wf_hip_time_begin(m->shard[i]->h);
+    wf_hip_tick_params q = run.p;
+    for(uint32_t t = 0; t < run.ticks; ++t) {
+        q.delay_frames = run.p.delay_frames - (t % period) * run.hop;
+        if(st == WF_HIP_OK)
+            st = wf_hip_tick(m->shard[i]->h, &q);
+        if(run.gather) {
+            const uint32_t k = (run.k0 + t) & 1u;
+            if(st == WF_HIP_OK)
+                st = gather_issue(m, i, k);
+            if(m->transport == Transport::PEER)
+                sync.arrive_and_wait();
+            if(st == WF_HIP_OK)
+                st = gather_complete(m, i, k);
+        }
+    }
+    return st;
 }
 
 } // namespace
@@ -464,6 +730,8 @@ int wf::multi::for_each_shard(wf_hip_multi *m, uint32_t first, uint32_t count,
 
 int wf::multi::fail(wf_hip_multi *m, int code, const char *msg) { return mfail(m, code, "%s", msg); }
 
+using wf::multi::for_each_shard;
+
 extern "C" {
 
 const char *wf_hip_multi_last_error(const wf_hip_multi *m) { return m ? m->last_error.c_str() : g_multi_create_error.c_str(); }
@@ -483,179 +751,33 @@ int wf_hip_multi_create(const wf_config *cfg, const int *devices, uint32_t n_dev
     if(out == nullptr)
         return WF_HIP_ERR_INVALID;
     *out = nullptr;
-    if(cfg == nullptr || devices == nullptr || n_devices == 0 || n_devices > 64)
-        return mfail(nullptr, WF_HIP_ERR_INVALID, "cfg / devices NULL, or n_devices %u outside 1..64", n_devices);
-    if(streams_total < n_devices)
-        return mfail(nullptr, WF_HIP_ERR_INVALID, "%u streams cannot be spread over %u devices (every shard needs one)", streams_total, n_devices);
-    const int have = wf_hip_device_count();
-    if(have <= 0)
-        return mfail(nullptr, WF_HIP_ERR_NO_DEVICE, "no usable HIP device");
+    Overrides ov;
     bool duplicates = false;
-    for(uint32_t i = 0; i < n_devices; ++i) {
-        if(devices[i] < 0 || devices[i] >= have)
-            return mfail(nullptr, WF_HIP_ERR_INVALID, "devices[%u] = %d, the box has %d", i, devices[i], have);
-        for(uint32_t j = 0; j < i; ++j)
-            duplicates = duplicates || devices[j] == devices[i];
-    }
-    auto *m = new(std::nothrow) wf_hip_multi;
+    int rc = read_overrides(&ov);
+    if(rc == WF_HIP_OK)
+        rc = validate_devices(cfg, devices, n_devices, streams_total, &duplicates);
+    if(rc)
+        return rc;
+    wf_hip_multi *m = split_streams(cfg, devices, n_devices, streams_total);
     if(m == nullptr)
         return mfail(nullptr, WF_HIP_ERR_NOMEM, "out of host memory");
-    m->cfg = *cfg;
-    m->n = n_devices;
-    m->total = streams_total;
-    const uint32_t base = streams_total / n_devices, extra = streams_total % n_devices;
-    m->largest = base + (extra ? 1u : 0u);
-    m->ragged = extra != 0;
-    for(uint32_t i = 0; i < n_devices; ++i) {
-        auto s = std::make_unique<Shard>();
-        s->device = devices[i];
-        s->count = base + (i < extra ? 1u : 0u);
-        s->first = i * base + std::min(i, extra);
-        s->worker.start(s->device);
-        m->shard.push_back(std::move(s));
+    rc = build_handles(m, ring_frames);
+    if(rc == WF_HIP_OK)
+        rc = choose_transport(m, ov, devices, duplicates);
+    if(rc == WF_HIP_OK && m->per != 0) { // something to gather: the exchange on every device, then the hand-over
+        rc = run_all(m, [m, &ov](uint32_t i) {
+            const int r = alloc_exchange(m, *m->shard[i], ov.gather_priority_high);
+            if(r == WF_HIP_OK && m->transport == Transport::PEER)
+                probe_peer_access(m, *m->shard[i]);
+            return r;
+        });
+        if(rc == WF_HIP_OK)
+            rc = hand_over_mirrors(m, ov);
     }
-    // the shards' handles, every device building its own concurrently
-    int rc = run_all(m, [m, cfg, ring_frames](uint32_t i) {
-        Shard &s = *m->shard[i];
-        const int r = wf_hip_create(cfg, s.device, s.count, ring_frames, &s.h);
-        if(r != WF_HIP_OK)
-            s.err = wf_hip_last_error(nullptr);
-        return r;
-    });
-    if(rc) {
+    if(rc) { // the one failure exit: the text stays for wf_hip_multi_last_error(NULL), what exists is destroyed
         g_multi_create_error = m->last_error;
         destroy_impl(m);
         return rc;
-    }
-    m->per = (size_t)wf_hip_display_channels(m->shard[0]->h) * wf_hip_num_bars(m->shard[0]->h);
-    // transport of the gather
-    const char *force = std::getenv("WF_HIP_MULTI_TRANSPORT");
-    const bool want_rccl = force ? std::strcmp(force, "rccl") == 0 : (n_devices > 1 && !duplicates);
-    const bool want_peer = force ? std::strcmp(force, "peer") == 0 : false;
-    m->transport = n_devices == 1 ? Transport::LOCAL : Transport::PEER;
-    if(force && !want_rccl && !want_peer && std::strcmp(force, "local") != 0) {
-        destroy_impl(m);
-        return mfail(nullptr, WF_HIP_ERR_INVALID, "WF_HIP_MULTI_TRANSPORT=%s: expected rccl or peer", force);
-    }
-    if(want_peer)
-        m->transport = Transport::PEER;
-    if(m->per != 0 && want_rccl) {
-        Rccl &r = rccl();
-        if(!r.ok)
-            m->transport_note = r.why;
-        else {
-            std::vector<ncclComm_t> comms(n_devices, nullptr);
-            const ncclResult_t e = r.CommInitAll(comms.data(), (int)n_devices, devices);
-            if(e == ncclSuccess) {
-                for(uint32_t i = 0; i < n_devices; ++i)
-                    m->shard[i]->comm = comms[i];
-                m->transport = Transport::RCCL;
-            } else
-                m->transport_note = std::string("ncclCommInitAll failed: ") + r.GetErrorString(e);
-        }
-        if(m->transport != Transport::RCCL && force) { // asked for by name: do not quietly use something else
-            const std::string why = m->transport_note;
-            destroy_impl(m);
-            return mfail(nullptr, WF_HIP_ERR_RUNTIME, "WF_HIP_MULTI_TRANSPORT=rccl: %s", why.c_str());
-        }
-    }
-    if(m->per != 0) {
-        rc = run_all(m, [m](uint32_t i) {
-            Shard &s = *m->shard[i];
-            // HIP multiplexes a process's streams of one priority onto four hardware queues per device, which a handle's lanes fill: a
-            // gather stream that shares an in-order hardware queue with a lane puts that lane's next tick behind whatever the exchange
-            // of the last one enqueued (two shards on one device, peer copies: +36 us per tick), and one with a queue of its own
-            // (another priority) runs its kernels INTO the tick, which fills the CUs in whole rounds (+77 us; both traced:
-            // profiles/r05h_peer_trace*.txt).  The exchange therefore enqueues no kernel where it can avoid it (mirrors above); RCCL's
-            // own kernels remain -- WF_HIP_MULTI_GATHER_PRIORITY=high lets a node check try them on a queue of their own.
-            {
-                const char *pe = std::getenv("WF_HIP_MULTI_GATHER_PRIORITY");
-                if(pe && std::strcmp(pe, "high") == 0) {
-                    int least = 0, greatest = 0;
-                    WF_MHIP(s, hipDeviceGetStreamPriorityRange(&least, &greatest));
-                    WF_MHIP(s, hipStreamCreateWithPriority(&s.gstream, hipStreamNonBlocking, greatest));
-                } else
-                    WF_MHIP(s, hipStreamCreateWithFlags(&s.gstream, hipStreamNonBlocking));
-            }
-            const size_t per = m->per;
-            for(int k = 0; k < 2; ++k) {
-                WF_MHIP(s, hipEventCreateWithFlags(&s.ev_sent[k], hipEventDisableTiming));
-                WF_MHIP(s, hipEventCreateWithFlags(&s.ev_done[k], hipEventDisableTiming));
-                WF_MHIP(s, hipMalloc((void **)&s.gathered[k], (size_t)m->total * per * sizeof(float)));
-                if(m->transport != Transport::LOCAL) {
-                    WF_MHIP(s, hipMalloc((void **)&s.send[k], (size_t)m->largest * per * sizeof(float)));
-                    WF_MHIP(s, hipMemset(s.send[k], 0, (size_t)m->largest * per * sizeof(float)));
-                }
-                if(m->transport == Transport::RCCL && m->ragged)
-                    WF_MHIP(s, hipMalloc((void **)&s.recv_pad[k], (size_t)m->n * m->largest * per * sizeof(float)));
-            }
-            if(m->transport == Transport::PEER) // direct xGMI stores where the link allows; hipMemcpyPeerAsync stages otherwise
-                for(uint32_t j = 0; j < m->n; ++j) {
-                    const int other = m->shard[j]->device;
-                    int can = 0;
-                    bool ok = other == s.device;
-                    if(!ok && hipDeviceCanAccessPeer(&can, s.device, other) == hipSuccess && can) {
-                        // (refused: not fatal for the copies, which are then staged -- but kernel stores to that device's memory would
-                        // fault: direct peer stores need the mapping to exist, for every ordered pair)
-                        const hipError_t pe = hipDeviceEnablePeerAccess(other, 0);
-                        ok = pe == hipSuccess || pe == hipErrorPeerAccessAlreadyEnabled;
-                        (void)hipGetLastError();
-                    }
-                    s.peer_ok[j] = ok;
-                }
-            return (int)WF_HIP_OK;
-        });
-        // zero-copy gathers, once every device's buffers exist: the tick kernel writes the slot's send buffer (LOCAL: the result)
-        // itself -- or, peer transport on devices that can all address each other, this shard's slice of EVERY device's result:
-        // no copy, no kernel on the gather streams at all.  The batches whose display comes from a kernel of its own keep the copy
-        // behind the tick (WF_HIP_MULTI_MIRROR=0: the copy for everybody, =send: no direct peer stores; A/B aids)
-        if(rc == WF_HIP_OK) {
-            // Which shards' tick kernels write the exchange's buffers themselves (wf_hip_set_bars_mirrors) instead of a device copy
-            // behind the tick: by default only where that saves the PEER copies -- every device addresses every other, the slices
-            // go straight into every device's result.  Into a send buffer (RCCL; peer copies) or the one device's own result the
-            // kernel-side stores bought nothing once the kernels came in display-specific instantiations: the copy behind the tick
-            // 0.651 against 0.618 through this group, 0.649 against 0.650 from a torch process (profiles/r06o_gather_mirror_one_ab.txt).
-            // WF_HIP_MULTI_MIRROR: 1 = the kernels write wherever they can (round 5's default), send = that without the direct peer
-            // stores, 0 = the copy for everybody (A/B aids).
-            const char *e = std::getenv("WF_HIP_MULTI_MIRROR");
-            bool all_peer = m->transport == Transport::PEER && m->n <= 8 && !(e && std::strcmp(e, "send") == 0);
-            for(uint32_t i = 0; i < m->n && all_peer; ++i) // hipDeviceEnablePeerAccess succeeded (or had before) on device i for device j
-                for(uint32_t j = 0; j < m->n && all_peer; ++j)
-                    all_peer = m->shard[i]->peer_ok[j];
-            if(m->transport == Transport::PEER && !all_peer && m->transport_note.empty())
-                m->transport_note = "peer access is not enabled between every pair of devices: the bars travel by hipMemcpyPeerAsync";
-            rc = run_all(m, [m, e, all_peer](uint32_t i) {
-                Shard &s = *m->shard[i];
-                if(e ? e[0] == '0' : !all_peer)
-                    return (int)WF_HIP_OK;
-                int mrc;
-                if(all_peer) {
-                    void *set0[8], *set1[8];
-                    for(uint32_t j = 0; j < m->n; ++j) {
-                        set0[j] = m->shard[j]->gathered[0] + (size_t)s.first * m->per;
-                        set1[j] = m->shard[j]->gathered[1] + (size_t)s.first * m->per;
-                    }
-                    mrc = wf_hip_set_bars_mirrors(s.h, m->n, set0, set1);
-                } else {
-                    float *const *tgt = (m->transport == Transport::LOCAL) ? s.gathered : s.send;
-                    void *b0 = tgt[0], *b1 = tgt[1];
-                    mrc = wf_hip_set_bars_mirrors(s.h, 1, &b0, &b1);
-                }
-                if(mrc == WF_HIP_OK) {
-                    s.mirror = true;
-                    s.direct = all_peer;
-                } else if(mrc != WF_HIP_ERR_UNSUPPORTED) {
-                    s.err = wf_hip_last_error(s.h);
-                    return mrc;
-                }
-                return (int)WF_HIP_OK;
-            });
-        }
-        if(rc) {
-            g_multi_create_error = m->last_error;
-            destroy_impl(m);
-            return rc;
-        }
     }
     // not an error, but what a node check wants to see: why the group did not get the transport it would have picked
     // (wf_hip_multi_last_error(m) right after create; the next failing call overwrites it)
@@ -679,63 +801,35 @@ wf_hip *wf_hip_multi_shard(wf_hip_multi *m, uint32_t i, int *device, uint32_t *f
 
 int wf_hip_multi_push_audio(wf_hip_multi *m, uint32_t first, uint32_t count, const float *samples, uint32_t frames)
 {
-    int rc = check_range(m, first, count);
-    if(rc)
-        return rc;
+    if(m == nullptr)
+        return WF_HIP_ERR_INVALID;
     if(samples == nullptr)
         return mfail(m, WF_HIP_ERR_INVALID, "samples is NULL");
     const size_t per_stream = (size_t)wf_hip_capture_channels(m->shard[0]->h) * frames;
-    return run_all(m, [=](uint32_t i) {
-        Shard &s = *m->shard[i];
-        uint32_t lf, lc, off;
-        if(!overlap(s, first, count, &lf, &lc, &off))
-            return (int)WF_HIP_OK;
-        return wf_hip_push_audio(s.h, lf, lc, samples + (size_t)off * per_stream, frames);
+    return for_each_shard(m, first, count, [=](wf_hip *h, uint32_t lf, uint32_t lc, uint32_t off) {
+        return wf_hip_push_audio(h, lf, lc, samples + (size_t)off * per_stream, frames);
     });
 }
 
 int wf_hip_multi_push_synth(wf_hip_multi *m, uint32_t first, uint32_t count, uint64_t seed, uint32_t stream_id0, uint64_t index0, uint32_t frames)
 {
-    int rc = check_range(m, first, count);
-    if(rc)
-        return rc;
-    return run_all(m, [=](uint32_t i) {
-        Shard &s = *m->shard[i];
-        uint32_t lf, lc, off;
-        if(!overlap(s, first, count, &lf, &lc, &off))
-            return (int)WF_HIP_OK;
-        return wf_hip_push_synth(s.h, lf, lc, seed, stream_id0 + off, index0, frames);
+    return for_each_shard(m, first, count, [=](wf_hip *h, uint32_t lf, uint32_t lc, uint32_t off) {
+        return wf_hip_push_synth(h, lf, lc, seed, stream_id0 + off, index0, frames);
     });
 }
 
 int wf_hip_multi_set_hidden(wf_hip_multi *m, uint32_t first, uint32_t count, const uint8_t *mask)
 {
-    int rc = check_range(m, first, count);
-    if(rc)
-        return rc;
+    if(m == nullptr)
+        return WF_HIP_ERR_INVALID;
     if(mask == nullptr)
         return mfail(m, WF_HIP_ERR_INVALID, "mask is NULL");
-    return run_all(m, [=](uint32_t i) {
-        Shard &s = *m->shard[i];
-        uint32_t lf, lc, off;
-        if(!overlap(s, first, count, &lf, &lc, &off))
-            return (int)WF_HIP_OK;
-        return wf_hip_set_hidden(s.h, lf, lc, mask + off);
-    });
+    return for_each_shard(m, first, count, [=](wf_hip *h, uint32_t lf, uint32_t lc, uint32_t off) { return wf_hip_set_hidden(h, lf, lc, mask + off); });
 }
 
 int wf_hip_multi_reset(wf_hip_multi *m, uint32_t first, uint32_t count)
 {
-    int rc = check_range(m, first, count);
-    if(rc)
-        return rc;
-    return run_all(m, [=](uint32_t i) {
-        Shard &s = *m->shard[i];
-        uint32_t lf, lc, off;
-        if(!overlap(s, first, count, &lf, &lc, &off))
-            return (int)WF_HIP_OK;
-        return wf_hip_reset(s.h, lf, lc);
-    });
+    return for_each_shard(m, first, count, [](wf_hip *h, uint32_t lf, uint32_t lc, uint32_t) { return wf_hip_reset(h, lf, lc); });
 }
 
 int wf_hip_multi_tick(wf_hip_multi *m, const wf_hip_tick_params *p)
@@ -763,20 +857,16 @@ int wf_hip_multi_sync(wf_hip_multi *m)
 
 int wf_hip_multi_read(wf_hip_multi *m, wf_hip_output what, uint32_t first, uint32_t count, void *out)
 {
-    int rc = check_range(m, first, count);
+    int rc = check_range(m, first, count); // (here too: the special case below asks shard 0, whatever the range)
     if(rc)
         return rc;
     if(out == nullptr)
         return mfail(m, WF_HIP_ERR_INVALID, "out is NULL");
     const size_t per_stream = wf_hip_output_bytes(m->shard[0]->h, what);
-    if(per_stream == 0) // (the shard's own error text: why the batch has no such output)
-        return run_all(m, [=](uint32_t i) { return i == 0 ? wf_hip_read(m->shard[0]->h, what, 0, 1, out) : (int)WF_HIP_OK; });
-    return run_all(m, [=](uint32_t i) {
-        Shard &s = *m->shard[i];
-        uint32_t lf, lc, off;
-        if(!overlap(s, first, count, &lf, &lc, &off))
-            return (int)WF_HIP_OK;
-        return wf_hip_read(s.h, what, lf, lc, static_cast<char *>(out) + (size_t)off * per_stream);
+    if(per_stream == 0) // an output the batch does not have is asked of shard 0 alone: its own text says why there is none
+        return for_each_shard(m, 0, 1, [=](wf_hip *h, uint32_t, uint32_t, uint32_t) { return wf_hip_read(h, what, 0, 1, out); });
+    return for_each_shard(m, first, count, [=](wf_hip *h, uint32_t lf, uint32_t lc, uint32_t off) {
+        return wf_hip_read(h, what, lf, lc, static_cast<char *>(out) + (size_t)off * per_stream);
     });
 }
 
@@ -805,7 +895,7 @@ const float *wf_hip_multi_gathered_device(wf_hip_multi *m, uint32_t i)
 {
     if(m == nullptr || i >= m->n || m->last_slot < 0)
         return nullptr;
-    return m->shard[i]->gathered[m->last_slot];
+    return m->shard[i]->slot[m->last_slot].result;
 }
 
 #ifdef WF_DEV_BUILD
@@ -831,10 +921,10 @@ int wf_hip_multi_read_gathered(wf_hip_multi *m, uint32_t i, float *out)
         return mfail(m, WF_HIP_ERR_INVALID, "device index %u outside 0..%u, or out is NULL", i, m->n);
     if(m->last_slot < 0)
         return mfail(m, WF_HIP_ERR_INVALID, "no complete gather to read (none issued yet, or the last timed run failed half way)");
-    const uint32_t k = (uint32_t)m->last_slot;
     Shard &s = *m->shard[i];
-    s.worker.post([m, &s, k, out] {
-        WF_MHIP(s, hipMemcpyAsync(out, s.gathered[k], (size_t)m->total * m->per * sizeof(float), hipMemcpyDeviceToHost, s.gstream));
+    const float *result = s.slot[m->last_slot].result;
+    s.worker.post([m, &s, result, out] {
+        WF_MHIP(s, hipMemcpyAsync(out, result, (size_t)m->total * m->per * sizeof(float), hipMemcpyDeviceToHost, s.gstream));
         WF_MHIP(s, hipStreamSynchronize(s.gstream));
         return (int)WF_HIP_OK;
     });
@@ -856,40 +946,19 @@ int wf_hip_multi_time_ticks(wf_hip_multi *m, const wf_hip_tick_params *p, uint32
         if(rc)
             return rc;
     }
-    const uint32_t period = hop ? p->delay_frames / hop + 1 : ticks;
-    const wf_hip_tick_params p0 = *p;
+    const TimedRun run{*p, ticks, hop, m->gathers, gather != 0};
     std::vector<float> ms(m->n, 0.0f);
-    std::vector<int> status(m->n, WF_HIP_OK);
-    // the halves of a peer gather need every device's events recorded in between: a barrier among the workers.  A worker that
-    // fails keeps arriving at the barriers (doing nothing) so that the others do not wait for it for ever.
     std::barrier sync((std::ptrdiff_t)m->n);
     std::atomic<bool> any_failed{false};
-    const uint32_t k0 = m->gathers;
     int rc = run_all(m, [&, m](uint32_t i) {
         Shard &s = *m->shard[i];
-        int &st = status[i];
-        st = wf_hip_time_begin(s.h);
-        wf_hip_tick_params q = p0;
-        for(uint32_t t = 0; t < ticks; ++t) {
-            q.delay_frames = p0.delay_frames - (t % period) * hop;
-            if(st == WF_HIP_OK)
-                st = wf_hip_tick(s.h, &q);
-            if(gather) {
-                const uint32_t k = (k0 + t) & 1u;
-                if(st == WF_HIP_OK)
-                    st = gather_issue(m, i, k);
-                if(m->transport == Transport::PEER)
-                    sync.arrive_and_wait();
-                if(st == WF_HIP_OK)
-                    st = gather_complete(m, i, k);
-            }
-            if(st != WF_HIP_OK)
-                any_failed.store(true, std::memory_order_relaxed);
-        }
+        int st = timed_ticks(m, i, run, sync);
         // Nothing above waits on the host.  Below it does -- for streams that, after a failure anywhere, may be waiting for a
         // collective one rank never joined: every worker first learns whether all of them got through (gather_fail, called by
         // the API thread once the workers are back, is what releases those streams).
         if(gather) {
+            if(st != WF_HIP_OK)
+                any_failed.store(true, std::memory_order_relaxed);
             sync.arrive_and_wait();
             if(any_failed.load(std::memory_order_relaxed))
                 return st; // (a bystander returns OK: the failing shard's own status and text are the call's)
@@ -900,24 +969,26 @@ int wf_hip_multi_time_ticks(wf_hip_multi *m, const wf_hip_tick_params *p, uint32
             st = WF_HIP_ERR_RUNTIME;
         return st;
     });
-    if(gather) {
-        if(rc == WF_HIP_OK && !any_failed.load()) {
-            m->gathers = k0 + ticks;
-            m->last_slot = (int)m->shard[0]->cur_slot;
-        } else {
-            // some gathers of the run completed on some shards and overwrote the slots: no slot holds a result every device agrees
-            // on -- wf_hip_multi_gathered_device / _read_gathered say so until the next complete gather
-            m->last_slot = -1;
-        }
-    }
-    if(rc) {
-        // A shard that stopped in a tick (nothing to do with the exchange) left the others with a collective it never joined as
-        // well -- from that tick on; the communicators are aborted in both cases, but only because peers are stuck, and the text
-        // kept is the failing call's
-        if(gather && any_failed.load())
+    // A shard that stopped in a tick (nothing to do with the exchange) left the others with a collective it never joined as
+    // well -- from that tick on; the communicators are aborted in both cases, but only because peers are stuck, and the text
+    // kept is the failing call's
+    bool stuck = gather && any_failed.load();
+    // The shards' slots, as wf_hip_multi_allgather_bars checks them between its halves: here once the workers are back, outside
+    // the timed region (a check per tick costs).  A run whose pieces lie in different buffers is a failed gather.
+    if(gather && rc == WF_HIP_OK && (rc = slots_agree(m)) != WF_HIP_OK)
+        stuck = true;
+    if(gather && rc == WF_HIP_OK) {
+        m->gathers = run.k0 + ticks;
+        m->last_slot = (int)m->shard[0]->cur_slot;
+    } else if(gather) {
+        // some gathers of the run completed on some shards and overwrote the slots: no slot holds a result every device agrees
+        // on -- wf_hip_multi_gathered_device / _read_gathered say so until the next complete gather
+        m->last_slot = -1;
+        if(stuck)
             gather_fail(m);
-        return rc;
     }
+    if(rc)
+        return rc;
     float worst = 0.0f;
     for(uint32_t i = 0; i < m->n; ++i) {
         ms[i] /= (float)ticks;
