@@ -54,6 +54,9 @@
  *   WF_HIP_OUT_BITS      not in the reference: a bit meter, per captured channel the sample-value histogram, the activity of each
  *                        bit, the word length, the over-range count and the longest run of identical samples of every stream's
  *                        newest window of audio, counted on the device when read
+ *   WF_HIP_OUT_THD       not in the reference: a distortion analyser, per captured channel the fundamental of a test tone, its
+ *                        harmonics, THD, THD+N, SNR, SFDR and the noise floor, from a float64 transform of every stream's newest
+ *                        window through a -180 dB taper on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -415,11 +418,15 @@ typedef enum wf_hip_output {
                                   octave of up to 64 windows of 1024 frames, 256 frames apart and anchored to the sample counter,
                                   of the audio in the rings as of the pushes issued so far (spectrum and meter batches with a ring
                                   of at least 2048 frames; definition below) */
-    WF_HIP_OUT_BITS            /* wf_hip_bits                                bit statistics: per captured channel the histogram of
+    WF_HIP_OUT_BITS,           /* wf_hip_bits                                bit statistics: per captured channel the histogram of
                                   sample values, how often each bit of the sample on a 32-bit grid is set, the word length, the
                                   over-range count and the longest run of identical samples of the newest
                                   min(wf_hip_fft_size(), 8192) frames in the rings as of the pushes issued so far (spectrum and
                                   meter batches; definition below) */
+    WF_HIP_OUT_THD             /* wf_hip_thd                                 distortion: per captured channel the fundamental, the
+                                  harmonics 2 .. 10, THD, THD+N, SNR, SFDR and the noise floor of the newest P frames in the
+                                  rings as of the pushes issued so far, P the largest power of two <= min(wf_hip_fft_size(),
+                                  8192) (spectrum and meter batches of at least 512 frames; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -912,6 +919,79 @@ typedef struct wf_hip_bits {
     uint32_t window;         /* P */
     uint32_t reserved[3];    /* 0 */
 } wf_hip_bits;               /* 1360 bytes, a multiple of 16 */
+/* ---- distortion (WF_HIP_OUT_THD) --------------------------------------------------------------------------------------------
+ * Per stream and captured channel, the distortion analyser of a metering suite: the level and frequency of a test tone, the level
+ * of its harmonics 2 .. 10, THD, THD+N (SINAD is its negative), SNR, SFDR, the noise floor and the effective number of bits.  No
+ * other output can stand in for it: the tick's rows are float32 and Hann-class windowed, with a leakage floor far above a -100 dB
+ * harmonic.  W = wf_hip_fft_size(), sr = cfg.sample_rate; everything is float64 unless it says otherwise.
+ *   window         P = the largest power of two <= min(W, WF_HIP_THD_MAX_WINDOW = 8192): the newest P frames of each captured
+ *                  channel's ring, positions (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of WF_HIP_OUT_SIGNAL:
+ *                  every push issued before the read counts whatever its path, the A/V-sync delay is not applied, the zeros of
+ *                  create and wf_hip_reset count as samples.  Hidden and paused streams are read like any other.
+ *   taper          w[i] = sum_{m = 0 .. 6} (-1)^m a_m cos(2 pi m i / P), the periodic 7-term Blackman-Harris window, a host-made
+ *                  table, with a = 0.27105140069342, 0.43329793923448, 0.21812299954311, 0.06592544638803, 0.01081174209837,
+ *                  0.00077658482522, 0.00001388721735.  Its side lobes are about -180 dB and its main lobe is +-7 bins;
+ *                  H = WF_HIP_THD_LOBE = 8 is the half-width of every region below.
+ *   spectrum       per captured channel c, X_c = DFT_P(w x_c) with the kernel e^(-j 2 pi i k / P) and p[k] = |X_c[k]|^2 for
+ *                  1 <= k < M = P / 2.  With two captured channels both come out of one complex transform of w (x_0 + j x_1),
+ *                  separated as WF_HIP_OUT_STEREO does it; with one the imaginary part is 0 and ch[1] is all zero bytes.  A
+ *                  channel whose P frames are all +-0 has p = 0 exactly, whatever the other channel holds (the device sets it
+ *                  so: the shared transform's rounding would otherwise leave it some 1e-32 of the other channel's power), and a
+ *                  NaN or an infinity in either channel's window spoils the shared transform: both channels then read valid = 0.
+ *                  S = P sum w[i]^2 / 4: a sine of amplitude A well inside the band has a lobe power of A^2 S.
+ *   fundamental    k0 = the argmax of p over k in [2H + 1, M - H - 1]: the search starts from (k = 2H + 1, best = 0) and only a
+ *                  strictly greater value wins, so the lowest index wins a tie and a NaN never wins.  F = the sum of p[k] over
+ *                  |k - k0| <= H and f0 = (sum k p[k]) / F over the same bins, in bins of P.  If F is not a finite number > 0
+ *                  (silence; a NaN or an infinity in the window) valid = 0 and every other field of the channel is 0.
+ *   harmonics      for h = 2 .. 10 (WF_HIP_THD_HARMONICS = 9) k_h = floor(h f0 + 0.5).  Harmonic h is in band iff
+ *                  k_h + H <= M - 1; then H_h = the sum of p[k] over |k - k_h| <= H and bit h - 2 of `harmonics` is set.
+ *                  Harmonics beyond the band are not folded back.
+ *   residue        D = the sum of p[k] over H < k < M with |k - k0| > H, summed directly and never as a difference.  N = the sum
+ *                  over those of these bins that lie in no in-band harmonic region, n their count, and
+ *                  N_s = N (M - 3H - 2) / n fills the removed bins back in.  k_s = the argmax, lowest index on ties, of p over
+ *                  the bins of D: the strongest spur, a harmonic included.
+ *   levels         dB(x, y) = 10 log10(x / y); -INFINITY where x is 0, else +INFINITY where y is 0.  Each float32 field is
+ *                  rounded once from float64.
+ *                    fundamental_hz (double) f0 sr / P          fundamental_db   dB(F, S): a sine of amplitude A reads 20 log10 A
+ *                    harmonic_db[h - 2]      dB(H_h, F), dBc; -INFINITY when harmonic h is not in band
+ *                    thd_db                  dB(sum H_h, F); -INFINITY when no harmonic is in band
+ *                    thdn_db                 dB(D, F)           snr_db           dB(F, N_s)
+ *                    noise_db                dB(N_s, 2S): white noise of variance s^2 reads 10 log10 s^2
+ *                    sfdr_db                 dB(p[k0], p[k_s])  spur_hz          k_s sr / P
+ *                    enob                    (-thdn_db - 1.76) / 6.02, from the float64 thdn_db
+ *                    fundamental_bin k0, spur_bin k_s, harmonics, valid (uint32)
+ *                  Nothing reads NaN while valid is 1.
+ *   determinism    the order of every sum follows from P, k0 and the k_h alone and there are no atomics: the same ring contents
+ *                  read bit-identically across push paths, repeated reads, slices and shards.
+ * Resolution: a bin is 5.9 Hz wide at P = 8192 and 48 kHz, and the fundamental must lie at least 17 bins up, about 100 Hz.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 512 threads per stream,
+ * a float64 transform of P points in up to 128 KB of LDS, so one workgroup to a CU at the cap), into a block the first read
+ * allocates together with its tables: a handle that never reads it allocates and launches nothing new, and no state is kept between
+ * reads -- averaging is the host's.
+ * Cost on an MI355X, 4096 stereo streams, read into page-locked memory (0.85 MB back): 0.29 ms at W = 4096 against 2.37 ms for
+ * copying the 134.2 MB of windows to the host, and 0.63 ms against 5.62 ms at W = 16384 (P = 8192): 8.1 and 8.9 times.  Into a fresh
+ * pageable numpy array (the Python reader) a read takes 0.32 and 0.66 ms.  The kernel's own time without its copy is unmeasured
+ * (tools/thd_bench.py, profiles/thd_kernel_stats.json; INTEGRATION.md, "Distortion").
+ * Spectrum and meter batches with one or two captured channels and W >= 512 are served (the analysis needs 17 bins below the
+ * fundamental and room for the regions above it); on waveform batches and below 512 frames wf_hip_read returns WF_HIP_ERR_INVALID
+ * and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_THD_MAX_WINDOW 8192
+#define WF_HIP_THD_LOBE 8
+#define WF_HIP_THD_HARMONICS 9
+typedef struct wf_hip_thd_channel {
+    double fundamental_hz;
+    float fundamental_db, thd_db, thdn_db, snr_db, noise_db, sfdr_db, spur_hz, enob;
+    float harmonic_db[WF_HIP_THD_HARMONICS]; /* [h - 2], dBc */
+    uint32_t fundamental_bin, spur_bin;
+    uint32_t harmonics;      /* bit h - 2: harmonic h is in band */
+    uint32_t valid;
+    uint32_t reserved;       /* 0 */
+} wf_hip_thd_channel;        /* 96 bytes */
+typedef struct wf_hip_thd {
+    wf_hip_thd_channel ch[2]; /* captured channels 0 and 1; with one captured channel ch[1] is all zero bytes */
+    uint32_t window;         /* P */
+    uint32_t reserved[3];    /* 0 */
+} wf_hip_thd;                /* 208 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS = range(21)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD = range(22)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -199,6 +199,19 @@ BITS_CHANNEL_DTYPE = np.dtype([("hist", np.uint16, (256,)), ("ones", np.uint16, 
                                ("repeats", np.uint32), ("max_run", np.uint32), ("max_run_start", np.uint32),
                                ("max_run_value", np.float32)])
 BITS_DTYPE = np.dtype([("ch", BITS_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("reserved", np.uint32, (3,))])
+
+# struct wf_hip_thd (include/wf_hip.h): the distortion analyser, per captured channel the fundamental of a test tone, its harmonics
+# 2 .. 10 in dBc, THD, THD+N, SNR, SFDR, the noise floor and the strongest spur of the newest P frames of the ring through a 7-term
+# Blackman-Harris taper, P the largest power of two <= min(fft_size, THD_MAX_WINDOW)
+THD_MAX_WINDOW = 8192  # WF_HIP_THD_MAX_WINDOW
+THD_LOBE = 8  # WF_HIP_THD_LOBE
+THD_HARMONICS = 9  # WF_HIP_THD_HARMONICS
+THD_CHANNEL_DTYPE = np.dtype([("fundamental_hz", np.float64), ("fundamental_db", np.float32), ("thd_db", np.float32),
+                              ("thdn_db", np.float32), ("snr_db", np.float32), ("noise_db", np.float32), ("sfdr_db", np.float32),
+                              ("spur_hz", np.float32), ("enob", np.float32), ("harmonic_db", np.float32, (THD_HARMONICS,)),
+                              ("fundamental_bin", np.uint32), ("spur_bin", np.uint32), ("harmonics", np.uint32), ("valid", np.uint32),
+                              ("reserved", np.uint32)])
+THD_DTYPE = np.dtype([("ch", THD_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("reserved", np.uint32, (3,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -431,6 +444,17 @@ class _MeasureReaders:
         With one captured channel ch[1] is all zero"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_BITS, first, count, (), BITS_DTYPE)
+
+    def thd(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_thd (THD_DTYPE): the distortion analyser, per captured channel ch[c] the fundamental
+        of a test tone (fundamental_hz, fundamental_db, fundamental_bin), harmonic_db[h - 2] of the harmonics 2 .. 10 in dBc with
+        the mask `harmonics` of those in band, thd_db, thdn_db (SINAD is its negative), snr_db, noise_db, sfdr_db with the strongest
+        spur (spur_hz, spur_bin), enob and valid (0 for silence or a window holding a NaN: every field 0), over the newest P frames
+        of the ring as of the pushes issued so far, P = `window` the largest power of two <= min(fft_size, THD_MAX_WINDOW);
+        transformed in float64 through a 7-term Blackman-Harris taper on the device when read (batches of at least 512 frames).
+        With one captured channel ch[1] is all zero"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_THD, first, count, (), THD_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

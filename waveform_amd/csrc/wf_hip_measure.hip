@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO and _BITS.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS and _THD.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -30,6 +30,7 @@
 #include "wf_gonio.hpp"
 #include "wf_sono.hpp"
 #include "wf_bits.hpp"
+#include "wf_thd.hpp"
 
 namespace {
 
@@ -337,6 +338,43 @@ int launch_bits(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the distortion analyser derives from the configuration alone (wf::host::thd_tables), in one block
+int setup_thd(wf_hip *h)
+{
+    wf_hip::Thd &d = h->thd;
+    const ThdTables t = thd_tables(h->cfg.sample_rate, h->N);
+    d.P = t.P;
+    d.log2p = t.log2p;
+    d.S = t.S;
+    // (128 KB at P = 8192: twice what a workgroup gets without asking, and one workgroup to a CU)
+    const int lds = (int)(WF_HIP_THD_MAX_WINDOW * sizeof(double2));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::thd_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::thd_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return upload(h, &d.d_tab, t.tab); // (pageable memory: staged before the call returns)
+}
+
+// one workgroup per stream over its newest P frames of every captured channel, behind the pushes issued
+int launch_thd(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Thd &d = h->thd;
+    wf::ThdArgs a{};
+    a.rings = ring_view(h);
+    a.out = static_cast<wf_hip_thd *>(d_block) + first;
+    a.window = d.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(d.d_tab + d.P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.S = d.S;
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.P = d.P; // (<= fft_size <= ring_cap)
+    a.log2p = d.log2p;
+    const size_t lds = (size_t)d.P * sizeof(double2);
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::thd_read_kernel<2>, dim3(count), dim3(wf::WF_THD_THREADS), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::thd_read_kernel<1>, dim3(count), dim3(wf::WF_THD_THREADS), lds, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -392,6 +430,13 @@ const char *why_no_bits(const wf_hip *h)
     return h->wave ? "waveform batch: the bit statistics belong to spectrum and meter batches (a window of fft_size frames)" : nullptr;
 }
 
+const char *why_no_thd(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the distortion analyser belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->N < 512 ? "the distortion analyser needs a window of at least 512 frames" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -414,6 +459,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_GONIO, sizeof(wf_hip_gonio), false, why_no_gonio, setup_gonio, launch_gonio},
     {WF_HIP_OUT_SONO, sizeof(wf_hip_sono), false, why_no_sono, setup_sono, launch_sono},
     {WF_HIP_OUT_BITS, sizeof(wf_hip_bits), false, why_no_bits, setup_bits, launch_bits},
+    {WF_HIP_OUT_THD, sizeof(wf_hip_thd), false, why_no_thd, setup_thd, launch_thd},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output

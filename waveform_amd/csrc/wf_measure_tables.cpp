@@ -11,6 +11,19 @@ namespace {
 // sincos does not give its sin in every last bit (2 pi 1955 / 4096 is one argument where it does not); the device's results
 // depend on every bit of these tables, so the two stay the two calls they are written as, whichever compiler builds this.
 template<class T> [[gnu::noinline]] T sin_alone(T x) { return std::sin(x); }
+
+constexpr long double TWO_PI_L = 2.0L * 3.14159265358979323846264338327950288L;
+
+// e^(-j 2 pi m / p), m < p / 2, as [re im] pairs of float64 rounded from long double arguments (the sonogram's and the
+// distortion analyser's transforms)
+void twiddles_from_long_double(double *tw, uint32_t p)
+{
+    for(uint32_t m = 0; m < p / 2; ++m) {
+        const long double x = TWO_PI_L * (long double)m / (long double)p;
+        tw[2 * (size_t)m] = (double)std::cos(x);
+        tw[2 * (size_t)m + 1] = (double)-sin_alone(x);
+    }
+}
 } // namespace
 
 uint32_t third_octave_edges(uint32_t sample_rate, uint32_t n, uint32_t m, double edges[WF_HIP_NUM_BANDS + 1])
@@ -166,11 +179,7 @@ SonoTables sono_tables(uint32_t sample_rate, uint32_t ring_cap)
     const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
     for(uint32_t i = 0; i < P; ++i)
         tab[i] = (double)(0.5L - 0.5L * std::cos(two_pi * (long double)i / (long double)P));
-    for(uint32_t m = 0; m < P / 2; ++m) {
-        const long double x = two_pi * (long double)m / (long double)P;
-        tab[P + 2 * (size_t)m] = (double)std::cos(x);
-        tab[P + 2 * (size_t)m + 1] = (double)-sin_alone(x);
-    }
+    twiddles_from_long_double(tab.data() + P, P);
     double *edges = tab.data() + 2 * (size_t)P;
     for(uint32_t j = 0; j <= B; ++j)
         edges[j] = 62.5 * std::exp2((double)j / 8.0) * (double)P / (double)sample_rate;
@@ -183,6 +192,43 @@ SonoTables sono_tables(uint32_t sample_rate, uint32_t ring_cap)
             ++s.end_covered;
     }
     return s;
+}
+
+uint32_t thd_window(uint32_t fft_size)
+{
+    uint32_t p = 1;
+    while(2 * p <= std::min<uint32_t>(fft_size, WF_HIP_THD_MAX_WINDOW))
+        p *= 2;
+    return p;
+}
+
+ThdTables thd_tables(uint32_t /*sample_rate*/, uint32_t N)
+{
+    ThdTables t;
+    const uint32_t P = thd_window(N);
+    static const long double a[7] = {0.27105140069342L, 0.43329793923448L, 0.21812299954311L, 0.06592544638803L,
+                                     0.01081174209837L, 0.00077658482522L, 0.00001388721735L};
+    std::vector<double> &tab = t.tab;
+    tab.resize((size_t)2 * P);
+    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
+    // (the terms cancel down to 6e-8 at the ends: summed in long double, m ascending, the argument reduced as an integer first)
+    long double s2 = 0.0L;
+    for(uint32_t i = 0; i < P; ++i) {
+        long double w = a[0];
+        for(uint32_t m = 1; m < 7; ++m) {
+            const long double c = a[m] * std::cos(two_pi * (long double)((m * i) % P) / (long double)P);
+            w = (m & 1u) ? w - c : w + c;
+        }
+        tab[i] = (double)w;
+        s2 += (long double)tab[i] * (long double)tab[i];
+    }
+    twiddles_from_long_double(tab.data() + P, P);
+    t.S = (double)((long double)P * s2 / 4.0L);
+    t.P = P;
+    t.log2p = 0;
+    while((1u << t.log2p) < P)
+        ++t.log2p;
+    return t;
 }
 
 } // namespace wf::host
