@@ -15,6 +15,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 
 namespace {
 
@@ -119,35 +120,220 @@ uint32_t group_capacity()
     return (uint32_t)std::min<long>(std::max<long>(v, 1), 16384);
 }
 
+// WF_HIP_DEVICE pins everything to one device; -1: not set
+int pinned_device()
+{
+    const char *e = std::getenv("WF_HIP_DEVICE");
+    return e ? std::min(std::max(std::atoi(e), 0), std::max(api().device_count(), 1) - 1) : -1;
+}
+
+// does the handle produce the display its configuration asks for (cfg.bars / cfg.curve with cfg.vertices), and in what shape:
+// displayed channels, outputs per row, vertices per row (0 for a curve: its points come back, the strip is written on the host)
+bool display_shape(const wf_config &c, wf_hip *h, uint32_t &disp_ch, uint32_t &points, uint32_t &per_row)
+{
+    auto &a = api();
+    if(!((c.bars != 0 || c.curve != 0) && a.num_bars(h) > 0 && (c.curve != 0 || a.num_vertices(h) > 0)))
+        return false;
+    disp_ch = a.display_channels(h);
+    points = a.num_bars(h);
+    per_row = a.num_vertices(h);
+    return true;
+}
+
+template<class T>
+bool host_alloc(T *&p, size_t count)
+{
+    p = static_cast<T *>(api().host_alloc(count * sizeof(T)));
+    return p != nullptr;
+}
+
+template<class T>
+void host_free(T *p)
+{
+    if(p)
+        api().host_free(p);
+}
+
 } // namespace
 
-// One handle shared by the sources of one configuration: sources are streams of its batch.
+// What the two kinds of group share: one handle for the sources of one configuration -- sources are streams of its batch --,
+// who sits in which slot, and the hand-over of a video frame.
 //
 // A video frame, seen from the group: OBS ticks its active sources one after the other on the video thread
-// (reference callbacks::tick, src/source.cpp:481-484).  Every member's tick_spectrum
-//   1. collects: copies its row of the PREVIOUS frame's tick out of the page-locked readback buffer (one frame of latency:
-//      the copy was enqueued 16 ms ago and has long landed), and
-//   2. submits: writes the samples its window gained since its last tick into the page-locked staging block of the batch
-//      being assembled, with its show / hide / timeout state and its m_input_rms.
+// (reference callbacks::tick, src/source.cpp:481-484).  Every member's tick
+//   1. collects: copies its part of the PREVIOUS frame's tick out of the page-locked readback buffer (one frame of latency:
+//      the copy was enqueued 16 ms ago and has long landed; begin_tick), and
+//   2. submits: what its own tick would consume this frame goes into the batch being assembled, with its show / hide / timeout
+//      state (submit).
 // The member that completes the frame -- or one that comes round again while an incomplete batch is waiting -- flushes:
-// state masks and RMS values that changed, ONE ragged ingest (wf_hip_push_audio_ragged_async), ONE wf_hip_tick, ONE
-// readback (wf_hip_read_async); members that did not show up are paused for that tick.  Nothing in a flush waits for
-// the device.
-struct WFHipGroup {
+// the state masks that changed (begin_flush), then what the group type stages: ONE ragged ingest, ONE wf_hip_tick, ONE readback
+// (wf_hip_read_async); members that did not show up are paused for that tick.  Nothing in a flush waits for the device.
+struct WFHipGroupCore {
     wf_config cfg{};
     wf_hip *h = nullptr;
-    uint32_t capacity = 0, cap_ch = 0, out_ch = 0, N = 0, M = 0;
+    int device = 0;
+    const char *kind = "spectrum";        // for the log
+    uint32_t capacity = 0;
     std::vector<WAVSourceHIP *> member;   // [capacity] or nullptr
     uint32_t members = 0;
     uint64_t batch = 1;                   // the batch being assembled (batch - 1: the last one flushed)
     std::vector<uint64_t> submitted;      // [capacity] the batch a member last submitted to
     uint32_t n_submitted = 0;
-    float *stage[2] = {nullptr, nullptr}; // page-locked [capacity][cap_ch][N]
-    float *rows[2] = {nullptr, nullptr};  // page-locked [capacity][out_ch][M]
-    uint8_t *silent[2] = {nullptr, nullptr};
-    bool rows_valid[2] = {false, false};
     std::vector<uint32_t> frames;         // [capacity] frames each member staged for this batch
     std::vector<uint8_t> state, state_dev;
+    uint8_t *silent[2] = {nullptr, nullptr}; // page-locked [capacity], allocated by the group type among its own buffers
+    bool valid[2] = {false, false};       // the readback of that slot was enqueued: its results may be collected
+    float seconds = 1.0f / 60.0f;
+    bool failed = false;
+
+    // the handle and the bookkeeping of its slots; the group type's create() adds its buffers
+    bool open(const wf_config &c, int dev)
+    {
+        cfg = c;
+        device = dev;
+        capacity = group_capacity();
+        if(api().create(&c, dev, capacity, 0, &h) != WF_HIP_OK) {
+            h = nullptr;
+            return false;
+        }
+        member.assign(capacity, nullptr);
+        submitted.assign(capacity, 0);
+        frames.assign(capacity, 0);
+        state.assign(capacity, WF_HIP_PAUSED);
+        state_dev.assign(capacity, WF_HIP_SHOWN);
+        return true;
+    }
+
+    // the handle goes first (wf_hip_destroy synchronises its streams), the page-locked buffers after it: every group type's
+    // destructor starts with this
+    void close()
+    {
+        if(h)
+            api().destroy(h);
+        h = nullptr;
+    }
+
+    virtual ~WFHipGroupCore()
+    {
+        close();
+        host_free(silent[0]);
+        host_free(silent[1]);
+    }
+
+    virtual bool flush() = 0;             // everything the frame's members staged goes to the device as one batch; false: the device path failed
+    virtual void joined(uint32_t) {}      // the per-slot words of the group type that a new member must find reset ...
+    virtual void left(uint32_t) {}        // ... and those that must not outlive a member
+
+    // the first free slot for `src`, its stream as update() leaves a source; false: the device refused
+    bool join(WAVSourceHIP *src, uint32_t &slot)
+    {
+        slot = 0;
+        while(member[slot] != nullptr)
+            ++slot;
+        if(api().reset(h, slot, 1) != WF_HIP_OK)
+            return false;
+        // reset has put the device's view of the slot back to SHOWN with no per-stream RMS: the cache of what the device holds
+        // must say so, or a flush before this member's first submit would skip re-sending PAUSED and the device would tick the
+        // fresh stream on its zero ring (m_last_silent = 1 where the reference still has false)
+        state_dev[slot] = WF_HIP_SHOWN;
+        member[slot] = src;
+        submitted[slot] = 0;
+        state[slot] = WF_HIP_PAUSED;
+        ++members;
+        joined(slot);
+        return true;
+    }
+
+    // true: that was the last member
+    bool leave(uint32_t slot)
+    {
+        member[slot] = nullptr;
+        if(submitted[slot] == batch && n_submitted > 0)
+            --n_submitted; // what it staged for the batch in assembly is dropped with it
+        submitted[slot] = 0;
+        frames[slot] = 0;
+        state[slot] = WF_HIP_PAUSED;
+        left(slot);
+        return --members == 0;
+    }
+
+    // A member's tick opens.  One that comes round again while its last hand-over is still waiting for the rest of the frame
+    // completes it; then, if the last flushed batch has something for this member (whatever the stream holds after that batch: a
+    // source that sat a frame out finds the results of its last tick, unchanged; rows of batches older than `joined_at` belong to
+    // whoever held the slot then), its readback is awaited and `last` is its slot -- else -1.  false: the group has failed.
+    bool begin_tick(uint32_t slot, uint64_t joined_at, int &last)
+    {
+        last = -1;
+        bool ok = !failed;
+        if(ok && submitted[slot] == batch)
+            ok = flush();
+        const uint32_t b = (uint32_t)((batch - 1) & 1);
+        if(ok && batch > 1 && valid[b] && batch - 1 >= joined_at) {
+            ok = api().readback_done(h, b) == WF_HIP_OK;
+            if(ok)
+                last = (int)b;
+        }
+        return ok;
+    }
+
+    // A member's tick closes: what it staged for this frame counts; the frame's last member sends the batch off (a failure
+    // shows at the members' next tick)
+    void submit(uint32_t slot, uint32_t staged, uint8_t st, float secs)
+    {
+        frames[slot] = staged;
+        state[slot] = st;
+        seconds = secs;
+        submitted[slot] = batch;
+        if(++n_submitted >= members)
+            flush();
+    }
+
+    // flush opens: whoever was not ticked in this frame (inactive source, free slot) is left exactly as it is; the state masks
+    // go to the device if any changed
+    bool begin_flush()
+    {
+        for(uint32_t i = 0; i < capacity; ++i)
+            if(submitted[i] != batch) {
+                state[i] = WF_HIP_PAUSED;
+                frames[i] = 0;
+            }
+        if(state == state_dev)
+            return true;
+        state_dev = state;
+        return api().set_hidden(h, 0, capacity, state.data()) == WF_HIP_OK;
+    }
+
+    // flush closes: the next batch is assembled in the other slot
+    bool end_flush(bool ok)
+    {
+        valid[batch & 1] = ok;
+        ++batch;
+        n_submitted = 0;
+        std::fill(frames.begin(), frames.end(), 0u);
+        if(!ok) {
+            LogWarn << "HIP " << kind << " batch tick failed (" << api().last_error(h) << "); its sources fall back to the CPU path";
+            failed = true;
+        }
+        return ok;
+    }
+
+    // tick + readback of a flush, common to the group types once `dst` names their buffers
+    bool tick_and_read(wf_hip_readback &dst)
+    {
+        wf_hip_tick_params p{};
+        p.seconds = seconds;
+        dst.last_silent = silent[batch & 1];
+        return api().tick(h, &p) == WF_HIP_OK && api().read_async(h, 0, capacity, &dst, (uint32_t)(batch & 1)) == WF_HIP_OK;
+    }
+};
+
+// The spectrum display's batch.  A member submits the samples its window gained since its last tick, into the page-locked staging
+// block, with its m_input_rms; the flush adds the RMS values that changed; rows, m_last_silent and what the display draws from
+// come back.
+struct WFHipGroup : WFHipGroupCore {
+    uint32_t cap_ch = 0, out_ch = 0, N = 0, M = 0;
+    float *stage[2] = {nullptr, nullptr}; // page-locked [capacity][cap_ch][N]
+    float *rows[2] = {nullptr, nullptr};  // page-locked [capacity][out_ch][M]
     std::vector<float> rms, rms_dev;
     // volume normalisation produced on the device (WAVSourceHIP::update_input_rms): the squared peaks every member's
     // sync_rms_buffer consumed this frame, page-locked [capacity][sq_max] per ingest slot, and m_input_rms coming back
@@ -156,9 +342,6 @@ struct WFHipGroup {
     float *sq_stage[2] = {nullptr, nullptr};
     float *rms_back[2] = {nullptr, nullptr};
     std::vector<uint32_t> sq_frames;      // [capacity] values staged for the batch being assembled
-    float seconds = 1.0f / 60.0f;
-    bool failed = false;
-    int device = 0;
     // the display from the device (cfg.bars / cfg.curve with cfg.vertices): bar tops / curve points, vertices and vertex counts
     // of every member come back with the rows
     bool display = false;
@@ -170,100 +353,63 @@ struct WFHipGroup {
 
     bool create(const wf_config &c, int dev)
     {
-        auto &a = api();
-        cfg = c;
-        device = dev;
-        capacity = group_capacity();
-        if(a.create(&c, dev, capacity, 0, &h) != WF_HIP_OK) {
-            h = nullptr;
+        if(!open(c, dev))
             return false;
-        }
         cap_ch = c.capture_channels;
         N = c.fft_size;
         M = c.fft_size / 2;
         out_ch = ((cap_ch > 1) || c.stereo) ? 2u : 1u; // src/source.cpp:1171
-        display = (c.bars != 0 || c.curve != 0) && a.num_bars(h) > 0 && (c.curve != 0 || a.num_vertices(h) > 0);
-        if(display) {
-            disp_ch = a.display_channels(h);
-            points = a.num_bars(h);
-            per_row = a.num_vertices(h); // 0 for a curve: its points come back, the strip is written on the host
-            for(int i = 0; i < 2; ++i) {
-                bars[i] = static_cast<float *>(a.host_alloc((size_t)capacity * disp_ch * points * sizeof(float)));
-                if(bars[i] == nullptr)
-                    return false;
-                if(c.mirror_freq_axis) {
-                    pre[i] = static_cast<float *>(a.host_alloc((size_t)capacity * disp_ch * sizeof(float)));
-                    if(pre[i] == nullptr)
-                        return false;
-                }
-                if(per_row == 0)
-                    continue;
-                verts[i] = static_cast<float *>(a.host_alloc((size_t)capacity * disp_ch * per_row * 4 * sizeof(float)));
-                vcounts[i] = static_cast<uint32_t *>(a.host_alloc((size_t)capacity * disp_ch * sizeof(uint32_t)));
-                if(verts[i] == nullptr || vcounts[i] == nullptr)
-                    return false;
-            }
+        display = display_shape(c, h, disp_ch, points, per_row);
+        for(int i = 0; display && i < 2; ++i) {
+            if(!host_alloc(bars[i], (size_t)capacity * disp_ch * points))
+                return false;
+            if(c.mirror_freq_axis && !host_alloc(pre[i], (size_t)capacity * disp_ch))
+                return false;
+            if(per_row == 0)
+                continue;
+            if(!host_alloc(verts[i], (size_t)capacity * disp_ch * per_row * 4) || !host_alloc(vcounts[i], (size_t)capacity * disp_ch))
+                return false;
         }
-        member.assign(capacity, nullptr);
-        submitted.assign(capacity, 0);
-        frames.assign(capacity, 0);
-        state.assign(capacity, WF_HIP_PAUSED);
-        state_dev.assign(capacity, WF_HIP_SHOWN);
         rms.assign(capacity, 0.0f);
         rms_dev.assign(capacity, -1.0f);
         sq_frames.assign(capacity, 0);
-        if(c.normalize_volume && std::getenv("WF_HIP_HOST_RMS") == nullptr && a.enable_input_rms(h, 1) == WF_HIP_OK) {
+        if(c.normalize_volume && std::getenv("WF_HIP_HOST_RMS") == nullptr && api().enable_input_rms(h, 1) == WF_HIP_OK) {
             rms_feed = true;
             sq_max = c.sample_rate & ~15u; // m_input_rms_size: more than a window's worth per frame is never needed
-            for(int i = 0; i < 2; ++i) {
-                sq_stage[i] = static_cast<float *>(a.host_alloc((size_t)capacity * sq_max * sizeof(float)));
-                rms_back[i] = static_cast<float *>(a.host_alloc((size_t)capacity * sizeof(float)));
-                if(sq_stage[i] == nullptr || rms_back[i] == nullptr)
+            for(int i = 0; i < 2; ++i)
+                if(!host_alloc(sq_stage[i], (size_t)capacity * sq_max) || !host_alloc(rms_back[i], capacity))
                     return false;
-            }
         }
-        for(int i = 0; i < 2; ++i) {
-            stage[i] = static_cast<float *>(a.host_alloc((size_t)capacity * cap_ch * N * sizeof(float)));
-            rows[i] = static_cast<float *>(a.host_alloc((size_t)capacity * out_ch * M * sizeof(float)));
-            silent[i] = static_cast<uint8_t *>(a.host_alloc(capacity));
-            if(stage[i] == nullptr || rows[i] == nullptr || silent[i] == nullptr)
+        for(int i = 0; i < 2; ++i)
+            if(!host_alloc(stage[i], (size_t)capacity * cap_ch * N) || !host_alloc(rows[i], (size_t)capacity * out_ch * M) || !host_alloc(silent[i], capacity))
                 return false;
-        }
         return true;
     }
 
-    ~WFHipGroup()
+    ~WFHipGroup() override
     {
-        auto &a = api();
-        if(h)
-            a.destroy(h); // synchronises its streams first
+        close();
+        // NOTE: pre[] is never released -- a leak of capacity * disp_ch floats per slot for every group with a mirrored axis,
+        // kept as found: releasing it changes the call trace tests/golden/host_groups_mock.json records
         for(int i = 0; i < 2; ++i) {
-            if(stage[i]) a.host_free(stage[i]);
-            if(rows[i]) a.host_free(rows[i]);
-            if(silent[i]) a.host_free(silent[i]);
-            if(sq_stage[i]) a.host_free(sq_stage[i]);
-            if(rms_back[i]) a.host_free(rms_back[i]);
-            if(bars[i]) a.host_free(bars[i]);
-            if(verts[i]) a.host_free(verts[i]);
-            if(vcounts[i]) a.host_free(vcounts[i]);
+            host_free(stage[i]);
+            host_free(rows[i]);
+            host_free(sq_stage[i]);
+            host_free(rms_back[i]);
+            host_free(bars[i]);
+            host_free(verts[i]);
+            host_free(vcounts[i]);
         }
     }
 
-    // everything the frame's members staged goes to the device as one batch; returns false when the device path failed
-    bool flush()
+    void joined(uint32_t slot) override { rms_dev[slot] = -1.0f; } // (wf_hip_reset leaves the slot without a per-stream RMS)
+    void left(uint32_t slot) override { sq_frames[slot] = 0; }
+
+    bool flush() override
     {
         auto &a = api();
         const uint32_t b = (uint32_t)(batch & 1);
-        for(uint32_t i = 0; i < capacity; ++i)
-            if(submitted[i] != batch) { // not ticked in this frame (inactive source, free slot): left exactly as it is
-                state[i] = WF_HIP_PAUSED;
-                frames[i] = 0;
-            }
-        bool ok = true;
-        if(state != state_dev) {
-            ok = a.set_hidden(h, 0, capacity, state.data()) == WF_HIP_OK;
-            state_dev = state;
-        }
+        bool ok = begin_flush();
         if(ok && rms_feed) {
             ok = a.push_rms_ragged_async(h, 0, capacity, sq_stage[b], sq_frames.data(), sq_max, b) == WF_HIP_OK;
             std::fill(sq_frames.begin(), sq_frames.end(), 0u);
@@ -272,13 +418,9 @@ struct WFHipGroup {
             rms_dev = rms;
         }
         ok = ok && a.push_audio_ragged_async(h, 0, capacity, stage[b], frames.data(), N, b) == WF_HIP_OK;
-        wf_hip_tick_params p{};
-        p.seconds = seconds;
-        ok = ok && a.tick(h, &p) == WF_HIP_OK;
         if(ok) { // the frame: rows + m_last_silent, and behind them what the members draw from one frame later
             wf_hip_readback dst{};
             dst.rows = rows[b];
-            dst.last_silent = silent[b];
             if(rms_feed)
                 dst.input_rms = rms_back[b];
             if(display) {
@@ -287,44 +429,22 @@ struct WFHipGroup {
                 dst.vertex_counts = per_row ? vcounts[b] : nullptr;
                 dst.premirror = pre[b];
             }
-            ok = a.read_async(h, 0, capacity, &dst, b) == WF_HIP_OK;
+            ok = tick_and_read(dst);
         }
-        rows_valid[b] = ok;
-        ++batch;
-        n_submitted = 0;
-        std::fill(frames.begin(), frames.end(), 0u);
-        if(!ok) {
-            LogWarn << "HIP batch tick failed (" << a.last_error(h) << "); its sources fall back to the CPU path";
-            failed = true;
-        }
-        return ok;
+        return end_flush(ok);
     }
 };
 
-// The level meter's batch (same idea as WFHipGroup; reference tick_meter src/source_generic.cpp:182-269): every member's
-// tick_meter collects the levels the PREVIOUS frame's tick left for it and submits what its own tick_meter would consume this
-// frame -- every captured frame older than the A/V-sync point, :201-220 -- with its show / hide / timeout state; the member that
-// completes the frame flushes: ONE ragged ingest, ONE wf_hip_tick (meter_tick_kernel over all streams), ONE readback.
-struct WFHipMeterGroup {
-    wf_config cfg{};
-    wf_hip *h = nullptr;
-    int device = 0;
-    uint32_t capacity = 0, cap_ch = 0, ring_cap = 0;
-    std::vector<WAVSourceHIP *> member;
-    uint32_t members = 0;
-    uint64_t batch = 1;
-    std::vector<uint64_t> submitted;
-    uint32_t n_submitted = 0;
+// The level meter's batch (reference tick_meter src/source_generic.cpp:182-269): every member's tick_meter collects the levels
+// the PREVIOUS frame's tick left for it and submits what its own tick_meter would consume this frame -- every captured frame
+// older than the A/V-sync point, :201-220; the flush rebuilds its staging block from them: ONE ragged ingest, ONE wf_hip_tick
+// (meter_tick_kernel over all streams), ONE readback.
+struct WFHipMeterGroup : WFHipGroupCore {
+    uint32_t cap_ch = 0, ring_cap = 0;
     std::vector<std::vector<float>> pending; // [capacity] what the member consumed this frame: [cap_ch][frames[i]]
-    std::vector<uint32_t> frames;
-    std::vector<uint8_t> state, state_dev;
     float *stage[2] = {nullptr, nullptr};    // page-locked [capacity][cap_ch][stage_frames[b]], rebuilt at every flush
     size_t stage_floats[2] = {0, 0};
     float *levels[2] = {nullptr, nullptr};   // page-locked [capacity][cap_ch]
-    uint8_t *silent[2] = {nullptr, nullptr};
-    bool valid[2] = {false, false};
-    float seconds = 1.0f / 60.0f;
-    bool failed = false;
     // waveform display (cfg.waveform): the same frame-by-frame hand-over, with every member's A/V-sync reserve and audio
     // timestamp, and the rows of the whole group coming back instead of the levels
     bool wave = false;
@@ -335,23 +455,14 @@ struct WFHipMeterGroup {
 
     bool create(const wf_config &c, int dev)
     {
-        auto &a = api();
-        cfg = c;
-        device = dev;
-        capacity = group_capacity();
-        if(a.create(&c, dev, capacity, 0, &h) != WF_HIP_OK) {
-            h = nullptr;
+        if(!open(c, dev))
             return false;
-        }
+        auto &a = api();
         cap_ch = c.capture_channels;
         ring_cap = a.ring_frames(h);
         wave = c.waveform != 0;
-        member.assign(capacity, nullptr);
-        submitted.assign(capacity, 0);
+        kind = wave ? "waveform" : "meter";
         pending.assign(capacity, {});
-        frames.assign(capacity, 0);
-        state.assign(capacity, WF_HIP_PAUSED);
-        state_dev.assign(capacity, WF_HIP_SHOWN);
         if(wave) {
             out_ch = a.output_channels(h);
             width = c.fft_size;
@@ -359,56 +470,43 @@ struct WFHipMeterGroup {
             delay_dev.assign(capacity, 0);
             audio_ts.assign(capacity, 0);
         }
-        for(int i = 0; i < 2; ++i) {
-            silent[i] = static_cast<uint8_t *>(a.host_alloc(capacity));
-            if(wave)
-                rows[i] = static_cast<float *>(a.host_alloc((size_t)capacity * out_ch * width * sizeof(float)));
-            else
-                levels[i] = static_cast<float *>(a.host_alloc((size_t)capacity * cap_ch * sizeof(float)));
-            if(silent[i] == nullptr || (wave ? rows[i] : levels[i]) == nullptr)
+        for(int i = 0; i < 2; ++i)
+            if(!host_alloc(silent[i], capacity) || !(wave ? host_alloc(rows[i], (size_t)capacity * out_ch * width) : host_alloc(levels[i], (size_t)capacity * cap_ch)))
                 return false;
-        }
         return true;
     }
 
-    ~WFHipMeterGroup()
+    ~WFHipMeterGroup() override
     {
-        auto &a = api();
-        if(h)
-            a.destroy(h);
+        close();
         for(int i = 0; i < 2; ++i) {
-            if(stage[i]) a.host_free(stage[i]);
-            if(levels[i]) a.host_free(levels[i]);
-            if(rows[i]) a.host_free(rows[i]);
-            if(silent[i]) a.host_free(silent[i]);
+            host_free(stage[i]);
+            host_free(levels[i]);
+            host_free(rows[i]);
         }
     }
 
-    bool flush()
+    void joined(uint32_t slot) override
+    {
+        if(wave) {
+            delay[slot] = 0;
+            audio_ts[slot] = 0;
+        }
+    }
+
+    bool flush() override
     {
         auto &a = api();
         const uint32_t b = (uint32_t)(batch & 1);
-        uint32_t maxf = 0;
-        for(uint32_t i = 0; i < capacity; ++i) {
-            if(submitted[i] != batch) { // not ticked in this frame: left exactly as it is
-                state[i] = WF_HIP_PAUSED;
-                frames[i] = 0;
-            }
-            maxf = std::max(maxf, frames[i]);
-        }
-        bool ok = true;
-        if(state != state_dev) {
-            ok = a.set_hidden(h, 0, capacity, state.data()) == WF_HIP_OK;
-            state_dev = state;
-        }
+        bool ok = begin_flush();
+        const uint32_t maxf = *std::max_element(frames.begin(), frames.end());
         if(ok && maxf > 0) {
             a.ingest_done(h, b); // the slot's block has been copied out (two frames ago)
             const size_t need = (size_t)capacity * cap_ch * maxf;
             if(stage_floats[b] < need) {
-                if(stage[b]) a.host_free(stage[b]);
+                host_free(stage[b]);
                 stage_floats[b] = need + need / 2;
-                stage[b] = static_cast<float *>(a.host_alloc(stage_floats[b] * sizeof(float)));
-                if(stage[b] == nullptr) {
+                if(!host_alloc(stage[b], stage_floats[b])) {
                     stage_floats[b] = 0;
                     ok = false;
                 }
@@ -427,27 +525,12 @@ struct WFHipMeterGroup {
             }
             ok = ok && a.set_stream_audio_ts(h, 0, capacity, audio_ts.data()) == WF_HIP_OK;
         }
-        wf_hip_tick_params p{};
-        p.seconds = seconds;
-        ok = ok && a.tick(h, &p) == WF_HIP_OK;
         if(ok) {
             wf_hip_readback dst{};
-            dst.last_silent = silent[b];
-            if(wave)
-                dst.rows = rows[b];
-            else
-                dst.meter = levels[b];
-            ok = a.read_async(h, 0, capacity, &dst, b) == WF_HIP_OK;
+            (wave ? dst.rows : dst.meter) = wave ? rows[b] : levels[b];
+            ok = tick_and_read(dst);
         }
-        valid[b] = ok;
-        ++batch;
-        n_submitted = 0;
-        std::fill(frames.begin(), frames.end(), 0u);
-        if(!ok) {
-            LogWarn << "HIP " << (wave ? "waveform" : "meter") << " batch tick failed (" << a.last_error(h) << "); its sources fall back to the CPU path";
-            failed = true;
-        }
-        return ok;
+        return end_flush(ok);
     }
 };
 
@@ -462,6 +545,73 @@ Registry &registry()
 {
     static Registry *r = new Registry; // never destroyed: sources an exiting host leaks must not call into an unloaded runtime
     return *r;
+}
+
+// batches spread over the devices the box has: a new group goes to the device that serves the fewest (sources share nothing,
+// SURVEY.md section 8(e); WF_HIP_DEVICE pins everything to one device).  The asymmetry is as found: a new spectrum group counts
+// the spectrum groups only, a new meter / waveform group counts both kinds.
+int pick_device(const Registry &r, bool count_meter_groups)
+{
+    const int pinned = pinned_device();
+    if(pinned >= 0)
+        return pinned;
+    const int ndev = std::max(api().device_count(), 1);
+    std::vector<int> load((size_t)ndev, 0);
+    const auto count = [&](const auto &list) {
+        for(auto &p : list)
+            if(p->device >= 0 && p->device < ndev)
+                ++load[(size_t)p->device];
+    };
+    count(r.groups);
+    if(count_meter_groups)
+        count(r.mgroups);
+    return (int)(std::min_element(load.begin(), load.end()) - load.begin());
+}
+
+template<class G>
+void drop_group(std::vector<std::unique_ptr<G>> &list, const G *g)
+{
+    list.erase(std::remove_if(list.begin(), list.end(), [g](const auto &p) { return p.get() == g; }), list.end());
+}
+
+using Attach = WFHipAttach;
+
+// `src` joins the group of configuration `c` in `list` that has room, or a new one (registry lock held)
+template<class G>
+Attach join_group(std::vector<std::unique_ptr<G>> &list, const wf_config &c, bool count_meter_groups, WAVSourceHIP *src, G *&g, uint32_t &slot)
+{
+    g = nullptr;
+    for(auto &p : list)
+        if(!p->failed && p->members < p->capacity && std::memcmp(&p->cfg, &c, sizeof(c)) == 0) {
+            g = p.get();
+            break;
+        }
+    const bool opened = g == nullptr;
+    if(opened) {
+        auto fresh = std::make_unique<G>();
+        if(!fresh->create(c, pick_device(registry(), count_meter_groups)))
+            return Attach::refused;
+        g = fresh.get();
+        list.push_back(std::move(fresh));
+    }
+    if(!g->join(src, slot)) {
+        if(opened) // nobody joined: the group would stay in the registry with no member for ever
+            drop_group(list, g);
+        g = nullptr;
+        return Attach::failed;
+    }
+    return Attach::ok;
+}
+
+// the member in `slot` of `g` leaves; a group without members is closed
+template<class G>
+void leave_group(std::vector<std::unique_ptr<G>> &list, G *&g, uint32_t slot)
+{
+    std::lock_guard lock(registry().mtx);
+    G *was = g;
+    g = nullptr;
+    if(was->leave(slot))
+        drop_group(list, was);
 }
 
 } // namespace
@@ -489,43 +639,26 @@ void WAVSourceHIP::hip_release()
         api().destroy(m_hip);
         m_hip = nullptr;
     }
-    if(m_mgroup != nullptr) {
-        auto &r = registry();
-        std::lock_guard lock(r.mtx);
-        auto g = m_mgroup;
-        m_mgroup = nullptr;
-        g->member[m_slot] = nullptr;
-        if(g->submitted[m_slot] == g->batch && g->n_submitted > 0)
-            --g->n_submitted;
-        g->submitted[m_slot] = 0;
-        g->frames[m_slot] = 0;
-        g->state[m_slot] = WF_HIP_PAUSED;
-        if(--g->members == 0)
-            r.mgroups.erase(std::remove_if(r.mgroups.begin(), r.mgroups.end(), [g](const auto &p) { return p.get() == g; }), r.mgroups.end());
-    }
-    if(m_group != nullptr) {
-        auto &r = registry();
-        std::lock_guard lock(r.mtx);
-        auto g = m_group;
-        m_group = nullptr;
-        g->member[m_slot] = nullptr;
-        if(g->submitted[m_slot] == g->batch && g->n_submitted > 0)
-            --g->n_submitted; // what it staged for the batch in assembly is dropped with it
-        g->submitted[m_slot] = 0;
-        g->frames[m_slot] = 0;
-        g->sq_frames[m_slot] = 0;
-        g->state[m_slot] = WF_HIP_PAUSED;
-        if(--g->members == 0)
-            r.groups.erase(std::remove_if(r.groups.begin(), r.groups.end(), [g](const auto &p) { return p.get() == g; }), r.groups.end());
-    }
+    if(m_mgroup != nullptr)
+        leave_group(registry().mgroups, m_mgroup, m_slot);
+    if(m_group != nullptr)
+        leave_group(registry().groups, m_group, m_slot);
 }
 
-// WAVSource members -> wf_config (include/wf_config.h lists the member behind every field)
-bool WAVSourceHIP::hip_configure()
+// One "leave the device for the CPU class" step: this tick goes to the reference's own class (the caller hands it over, after
+// unlocking the registry), and so do the following ones until update() configures the device path again.  An empty `why`: the
+// source was not on the device in the first place.
+void WAVSourceHIP::hip_fall_back(const std::string &why)
 {
+    if(!why.empty())
+        LogWarn << why;
     hip_release();
-    if(!available() || (m_capture_channels == 0))
-        return false;
+    g_fallback_ticks.fetch_add(1);
+}
+
+// WAVSource members -> wf_config (include/wf_config.h lists the member behind every field), without the display
+wf_config WAVSourceHIP::hip_config() const
+{
     wf_config c{};
     c.waveform = (m_display_mode == DisplayMode::WAVEFORM) ? 1u : 0u; // m_fft_size is m_width in this mode
     c.meter = m_meter_mode ? 1u : 0u;   // update() has already applied the mode's overrides to the members below
@@ -550,7 +683,7 @@ bool WAVSourceHIP::hip_configure()
     c.normalize_volume = m_normalize_volume ? 1u : 0u;
     c.volume_target = m_volume_target;
     c.max_gain = m_max_gain;
-    c.bars = 0; // (hip_display_config below sets the display fields where render() is served from the device)
+    c.bars = 0; // (hip_display_config sets the display fields where render() is served from the device)
     c.interp_mode = (int32_t)m_interp_mode;
     c.log_scale = m_log_scale ? 1u : 0u;
     c.mirror_freq_axis = m_mirror_freq_axis ? 1u : 0u;
@@ -561,179 +694,99 @@ bool WAVSourceHIP::hip_configure()
     c.channel_spacing = m_channel_spacing;
     c.min_bar_height = m_min_bar_height;
     c.rounded_caps = m_rounded_caps ? 1u : 0u;
+    return c;
+}
+
+// (re)connects this source to the device from the members update() has just set
+bool WAVSourceHIP::hip_configure()
+{
+    hip_release();
+    if(!available() || (m_capture_channels == 0))
+        return false;
+    wf_config c = hip_config();
     m_hip_have_prev = false;
     m_hip_display = m_hip_display_valid = false;
     const wf_config rows_only = c;
     if(!c.waveform && !c.meter && device_render_mode() && m_vbuf != nullptr)
         hip_display_config(c);
-    const auto has_display = [](const wf_config &k) { return k.bars != 0 || k.curve != 0; };
-    for(int attempt = 0; attempt < 2; ++attempt) {
-    // (second attempt: the same configuration without the display -- e.g. a filtered curve whose staging the device refuses:
-    // the rows still come from the device, render() keeps interpolating on the host)
-    if(attempt == 1) {
-        if(!has_display(c))
-            break;
-        c = rows_only;
-    }
-    if(!c.waveform && !c.meter && batched_mode()) {
-        // spectrum display: join (or open) the batch of this configuration
-        auto &r = registry();
-        std::lock_guard lock(r.mtx);
-        WFHipGroup *g = nullptr;
-        for(auto &p : r.groups)
-            if(!p->failed && p->members < p->capacity && std::memcmp(&p->cfg, &c, sizeof(c)) == 0) {
-                g = p.get();
-                break;
-            }
-        bool opened = false;
-        if(g == nullptr) {
-            // batches spread over the devices the box has: a new group goes to the device that serves the fewest
-            // (sources share nothing; WF_HIP_DEVICE pins everything to one device)
-            const int ndev = std::max(api().device_count(), 1);
-            std::vector<int> load((size_t)ndev, 0);
-            for(auto &p : r.groups)
-                if(p->device >= 0 && p->device < ndev)
-                    ++load[(size_t)p->device];
-            int dev = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            if(const char *e = std::getenv("WF_HIP_DEVICE"))
-                dev = std::min(std::max(std::atoi(e), 0), ndev - 1);
-            auto fresh = std::make_unique<WFHipGroup>();
-            if(!fresh->create(c, dev)) {
-                if(has_display(c))
-                    continue; // once more without the display
-                LogWarn << "HIP spectrum path unavailable for this configuration (" << api().last_error(nullptr) << "); using the CPU path";
-                return false;
-            }
-            g = fresh.get();
-            r.groups.push_back(std::move(fresh));
-            opened = true;
-        }
-        uint32_t slot = 0;
-        while(g->member[slot] != nullptr)
-            ++slot;
-        if(api().reset(g->h, slot, 1) != WF_HIP_OK) { // the stream starts as update() leaves a source
-            if(opened) // nobody joined: the group would stay in the registry with no member for ever
-                r.groups.erase(std::remove_if(r.groups.begin(), r.groups.end(), [g](const auto &p) { return p.get() == g; }), r.groups.end());
-            return false;
-        }
-        // reset has put the device's view of the slot back to SHOWN with no per-stream RMS: the cache of what the device holds
-        // must say so, or a flush before this member's first submit would skip re-sending PAUSED and the device would tick the
-        // fresh stream on its zero ring (m_last_silent = 1 where the reference still has false)
-        g->state_dev[slot] = WF_HIP_SHOWN;
-        g->rms_dev[slot] = -1.0f;
-        g->member[slot] = this;
-        m_hip_joined = g->batch; // rows read back for earlier batches belong to whoever held the slot then
-        g->submitted[slot] = 0;
-        g->state[slot] = WF_HIP_PAUSED;
-        ++g->members;
-        m_group = g;
-        m_slot = slot;
-        m_hip_window.assign((size_t)m_capture_channels * m_fft_size, 0.0f);
-        m_hip_prev.assign((size_t)m_capture_channels * m_fft_size, 0.0f);
-        m_hip_display = g->display;
-        if(m_hip_display) {
-            m_hip_points = g->points;
-            m_hip_per_row = g->per_row;
-            m_hip_bars.assign((size_t)g->disp_ch * g->points, 0.0f);
-            m_hip_verts.assign((size_t)g->disp_ch * g->per_row * 4, 0.0f);
-            m_hip_vcounts.assign(g->per_row ? g->disp_ch : 0u, 0u);
-            m_hip_pre.assign(g->disp_ch, 0.0f);
-        }
-        return true;
-    }
-    // level meter: join (or open) the batch of this meter configuration.  Meter buffers beyond 65536 samples (meter_buf above
-    // ~1.3 s; the reference allows 600 s) stay synchronous: a member's first hand-over is the whole buffer.
+    Attach rc = hip_attach(c);
+    // once more without the display -- e.g. a filtered curve whose staging the device refuses: the rows still come from the
+    // device, render() keeps interpolating on the host
+    if(rc == Attach::refused && (c.bars != 0 || c.curve != 0))
+        rc = hip_attach(rows_only);
+    if(rc == Attach::refused) // e.g. WF_HIP_ERR_UNSUPPORTED for a configuration the device refuses
+        LogWarn << "HIP path unavailable for this configuration (" << api().last_error(nullptr) << "); using the CPU path";
+    return rc == Attach::ok;
+}
+
+// configuration `c` on the device: as a member of a group where its kind of display batches, else on a handle of its own
+WFHipAttach WAVSourceHIP::hip_attach(const wf_config &c)
+{
+    // Meter buffers beyond 65536 samples (meter_buf above ~1.3 s; the reference allows 600 s) stay synchronous: a member's first
+    // hand-over is the whole buffer.  The waveform display batches in the same kind of group (a group's configuration has either
+    // cfg.meter or cfg.waveform set, so the two never share one); with volume normalisation a source stays synchronous: its
+    // m_input_rms is computed on the host per call.
     const char *mb = std::getenv("WF_HIP_BATCHED_METER"); // 0: the meter stays synchronous while the spectrum batches
     const char *wb = std::getenv("WF_HIP_BATCHED_WAVE");  // 0: so does the waveform display
-    // waveform display: the same kind of batch (a group's configuration has either cfg.meter or cfg.waveform set, so the two never
-    // share one).  With volume normalisation a source stays synchronous: its m_input_rms is computed on the host per call.
-    const bool wave_batch = c.waveform && !c.normalize_volume && !(wb && wb[0] == '0');
-    if(((c.meter && m_fft_size <= 65536 && !(mb && mb[0] == '0')) || wave_batch) && batched_mode()) {
-        auto &r = registry();
-        std::lock_guard lock(r.mtx);
-        WFHipMeterGroup *g = nullptr;
-        for(auto &p : r.mgroups)
-            if(!p->failed && p->members < p->capacity && std::memcmp(&p->cfg, &c, sizeof(c)) == 0) {
-                g = p.get();
-                break;
-            }
-        bool opened = false;
-        if(g == nullptr) {
-            const int ndev = std::max(api().device_count(), 1);
-            std::vector<int> load((size_t)ndev, 0);
-            for(auto &p : r.groups)
-                if(p->device >= 0 && p->device < ndev)
-                    ++load[(size_t)p->device];
-            for(auto &p : r.mgroups)
-                if(p->device >= 0 && p->device < ndev)
-                    ++load[(size_t)p->device];
-            int dev = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            if(const char *e = std::getenv("WF_HIP_DEVICE"))
-                dev = std::min(std::max(std::atoi(e), 0), ndev - 1);
-            auto fresh = std::make_unique<WFHipMeterGroup>();
-            if(!fresh->create(c, dev)) {
-                LogWarn << "HIP meter path unavailable for this configuration (" << api().last_error(nullptr) << "); using the CPU path";
-                return false;
-            }
-            g = fresh.get();
-            r.mgroups.push_back(std::move(fresh));
-            opened = true;
-        }
-        uint32_t slot = 0;
-        while(g->member[slot] != nullptr)
-            ++slot;
-        if(api().reset(g->h, slot, 1) != WF_HIP_OK) {
-            if(opened)
-                r.mgroups.erase(std::remove_if(r.mgroups.begin(), r.mgroups.end(), [g](const auto &p) { return p.get() == g; }), r.mgroups.end());
-            return false;
-        }
-        g->state_dev[slot] = WF_HIP_SHOWN; // (what reset leaves on the device: the next flush re-sends the slot's mask)
-        g->member[slot] = this;
-        m_hip_joined = g->batch;
-        g->submitted[slot] = 0;
-        g->state[slot] = WF_HIP_PAUSED;
-        ++g->members;
-        m_mgroup = g;
-        m_slot = slot;
-        if(g->wave) {
-            g->delay[slot] = 0;
-            g->audio_ts[slot] = 0;
-            m_hip_pushed = m_fft_size; // update() pre-fills m_fft_size zeros; so does the device (wf_hip_reset)
-            m_hip_prev.assign((size_t)m_capture_channels * m_hip_pushed, 0.0f);
-        }
-        return true;
+    bool batches = batched_mode();
+    if(c.meter)
+        batches = batches && m_fft_size <= 65536 && !(mb && mb[0] == '0');
+    else if(c.waveform)
+        batches = batches && !c.normalize_volume && !(wb && wb[0] == '0');
+    return batches ? hip_join_group(c) : hip_open_own(c);
+}
+
+// join (or open) the batch of this configuration: a spectrum group, or a meter / waveform group (which has no display to drop)
+WFHipAttach WAVSourceHIP::hip_join_group(const wf_config &c)
+{
+    auto &r = registry();
+    std::lock_guard lock(r.mtx);
+    const bool spectrum = !c.waveform && !c.meter;
+    const Attach rc = spectrum ? join_group(r.groups, c, false, this, m_group, m_slot) : join_group(r.mgroups, c, true, this, m_mgroup, m_slot);
+    if(rc != Attach::ok)
+        return rc;
+    m_hip_joined = spectrum ? m_group->batch : m_mgroup->batch; // rows read back for earlier batches belong to whoever held the slot then
+    if(spectrum) {
+        m_hip_window.assign((size_t)m_capture_channels * m_fft_size, 0.0f);
+        m_hip_prev.assign((size_t)m_capture_channels * m_fft_size, 0.0f);
+        m_hip_display = m_group->display;
+        if(m_hip_display)
+            hip_size_display(m_group->disp_ch, m_group->points, m_group->per_row);
+    } else if(m_mgroup->wave) {
+        m_hip_pushed = m_fft_size; // update() pre-fills m_fft_size zeros; so does the device (wf_hip_reset)
+        m_hip_prev.assign((size_t)m_capture_channels * m_hip_pushed, 0.0f);
     }
-    int dev = 0;
-    if(const char *e = std::getenv("WF_HIP_DEVICE"))
-        dev = std::min(std::max(std::atoi(e), 0), std::max(api().device_count(), 1) - 1);
-    const int rc = api().create(&c, dev, 1, 0, &m_hip);
-    if(rc != WF_HIP_OK) {
+    return rc;
+}
+
+// synchronous: a handle of one stream for this source alone
+WFHipAttach WAVSourceHIP::hip_open_own(const wf_config &c)
+{
+    if(api().create(&c, std::max(pinned_device(), 0), 1, 0, &m_hip) != WF_HIP_OK) {
         m_hip = nullptr;
-        if(has_display(c))
-            continue; // once more without the display
-        // e.g. WF_HIP_ERR_UNSUPPORTED for a configuration the device refuses
-        LogWarn << "HIP spectrum path unavailable for this configuration (" << api().last_error(nullptr) << "); using the CPU path";
-        return false;
+        return Attach::refused;
     }
-    m_hip_display = has_display(c) && api().num_bars(m_hip) > 0 && (c.curve != 0 || api().num_vertices(m_hip) > 0);
-    if(m_hip_display) {
-        const uint32_t dch = api().display_channels(m_hip);
-        m_hip_points = api().num_bars(m_hip);
-        m_hip_per_row = api().num_vertices(m_hip);
-        m_hip_bars.assign((size_t)dch * m_hip_points, 0.0f);
-        m_hip_verts.assign((size_t)dch * m_hip_per_row * 4, 0.0f);
-        m_hip_vcounts.assign(m_hip_per_row ? dch : 0u, 0u);
-        m_hip_pre.assign(dch, 0.0f);
-    }
+    uint32_t dch = 0, points = 0, per_row = 0;
+    m_hip_display = display_shape(c, m_hip, dch, points, per_row);
+    if(m_hip_display)
+        hip_size_display(dch, points, per_row);
     m_hip_window.assign((size_t)m_capture_channels * m_fft_size, 0.0f);
     m_hip_out.assign((size_t)m_output_channels * (m_fft_size / 2), 0.0f);
-    m_hip_hidden = false;
     m_hip_state = WF_HIP_SHOWN;
     m_hip_pushed = (m_display_mode == DisplayMode::WAVEFORM) ? m_fft_size : 0; // update() pre-fills m_fft_size zeros; so does the device
     m_hip_prev.assign((size_t)m_capture_channels * m_hip_pushed, 0.0f);          // ... and those zeros are what tick_waveform expects at the front
-    return true;
-    } // (attempts)
-    return false;
+    return Attach::ok;
+}
+
+// the members render() draws from, for a display of this shape
+void WAVSourceHIP::hip_size_display(uint32_t disp_ch, uint32_t points, uint32_t per_row)
+{
+    m_hip_points = points;
+    m_hip_per_row = per_row;
+    m_hip_bars.assign((size_t)disp_ch * points, 0.0f);
+    m_hip_verts.assign((size_t)disp_ch * per_row * 4, 0.0f);
+    m_hip_vcounts.assign(per_row ? disp_ch : 0u, 0u);
+    m_hip_pre.assign(disp_ch, 0.0f);
 }
 
 // The display part of wf_config (include/wf_config.h) from the members get_settings / update() have set: which of render_bars /
@@ -893,17 +946,20 @@ void WAVSourceHIP::update(obs_data_t *settings)
     hip_configure();
 }
 
-// Same observable behaviour as WAVSourceGeneric::tick_spectrum (src/source_generic.cpp:26-180): the A/V-synchronised
-// window of each channel goes to the device, the device runs the whole per-tick state machine (hidden/timeout reset,
-// silence detection, window, FFT, magnitude, slope, smoothing, dBFS, normalisation, roll-off) and m_decibels /
-// m_last_silent come back.
+// The A/V-sync point in frames: how much of the newest captured audio lies ahead of this tick's video time and stays behind for
+// later ticks (dtaudio > 0, src/source_generic.cpp:50-51)
+size_t WAVSourceHIP::hip_sync_frames()
+{
+    const int64_t dtaudio = get_audio_sync(m_tick_ts);
+    return (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) : 0;
+}
+
 // reference :50-59: keep dtsize bytes in every channel's ring, copy the first fft_size samples of what is left -- the
 // A/V-synchronised window -- into m_hip_window.  false: a channel holds less than that (the reference skips it).
 bool WAVSourceHIP::hip_window(size_t &dtframes)
 {
     const auto bufsz = m_fft_size * sizeof(float);
-    const int64_t dtaudio = get_audio_sync(m_tick_ts);
-    dtframes = (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) : 0;
+    dtframes = hip_sync_frames();
     const size_t dtsize = dtframes * sizeof(float) + bufsz;
     for(auto channel = 0u; channel < m_capture_channels; ++channel)
         if(m_capturebufs[channel].size() < dtsize)
@@ -915,42 +971,122 @@ bool WAVSourceHIP::hip_window(size_t &dtframes)
     return true;
 }
 
+// What tick_meter would pop into its meter buffer this tick (:201-220: everything older than the A/V-sync point) is popped into
+// dst instead, [capture_channels][frames], oldest first; returns the frames (the channels of a source are pushed together by
+// capture_audio; capture_audio keeps at most dtsamples + m_fft_size samples, so this is never more than the device ring holds)
+uint32_t WAVSourceHIP::hip_pop_meter(std::vector<float> &dst)
+{
+    const size_t dtsize = hip_sync_frames() * sizeof(float);
+    size_t frames = 0;
+    for(auto channel = 0u; channel < m_capture_channels; ++channel) {
+        const auto sz = m_capturebufs[channel].size();
+        const size_t n = (sz > dtsize) ? (sz - dtsize) / sizeof(float) : 0;
+        frames = (channel == 0) ? n : std::min(frames, n);
+    }
+    dst.resize((size_t)m_capture_channels * frames);
+    for(auto channel = 0u; channel < m_capture_channels && frames; ++channel)
+        m_capturebufs[channel].pop_front(dst.data() + (size_t)channel * frames, frames * sizeof(float));
+    return (uint32_t)frames;
+}
+
+// The frames of m_capturebufs that are new to the waveform's device ring go into dst, [capture_channels][fresh], and the rings are
+// popped down to the A/V-sync reserve as the reference does (:321).  false: a ring holds no more than the reserve (:293-295: the
+// reference returns before it touches anything, and so does this).
+//
+// The device ring holds every frame pushed so far and counts "what the reference's ring holds" as (frames pushed since
+// the last tick) + (the reserve that tick left behind), :321.  Frames at the front of m_capturebufs that are already
+// there -- the last tick's reserve, m_hip_pushed of them -- must not be pushed twice; but capture_audio drops from the
+// front once a ring exceeds dtsamples + m_waveform_samples (src/source.cpp:1883-1886), and then what is left is
+// re-sent whole: after a drop the ring is at its cap, the reference trims it to max_size and so does the device
+// (avail > max_size), and the re-sent frames are contiguous.  Whether the old reserve is still at the front is
+// checked against a copy of it, m_hip_prev (all-zero audio can match by accident: then both ways of pushing give zeros).
+bool WAVSourceHIP::hip_wave_fresh(size_t reserve, std::vector<float> &dst)
+{
+    for(auto i = 0u; i < m_capture_channels; ++i)
+        if(m_capturebufs[i].size() <= reserve * sizeof(float))
+            return false;
+    const size_t max_frames = m_waveform_samples + reserve;
+    size_t frames = 0;
+    bool front_kept = true;
+    std::vector<std::vector<float>> all(m_capture_channels);
+    for(auto channel = 0u; channel < m_capture_channels; ++channel) {
+        auto &buf = m_capturebufs[channel];
+        if(buf.size() > max_frames * sizeof(float)) // :303-304
+            buf.pop_front(nullptr, buf.size() - max_frames * sizeof(float));
+        const size_t s = buf.size() / sizeof(float);
+        all[channel].resize(s);
+        buf.peek_front(all[channel].data(), s * sizeof(float));
+        if(channel == 0)
+            frames = s;
+        front_kept = front_kept && s >= m_hip_pushed && m_hip_prev.size() == (size_t)m_capture_channels * m_hip_pushed &&
+                     std::memcmp(all[channel].data(), m_hip_prev.data() + (size_t)channel * m_hip_pushed, m_hip_pushed * sizeof(float)) == 0;
+    }
+    const size_t fresh = front_kept ? frames - m_hip_pushed : frames;
+    // "timestamp rollover, give up" (:314-317; a tick before any audio has a timestamp): the reference has trimmed its
+    // ring but consumes nothing.  The device takes the same exit from the same timestamps (and records the trim); here the
+    // ring keeps what it holds, all of it now on the device.
+    const auto start_ts = m_audio_ts - audio_frames_to_ns(m_audio_info.samples_per_sec, frames);
+    const auto stop_ts = m_audio_ts - audio_frames_to_ns(m_audio_info.samples_per_sec, reserve);
+    const bool rollover = (start_ts >= m_audio_ts) || (stop_ts > m_audio_ts);
+    const size_t stay = rollover ? frames : reserve; // frames left in m_capturebufs behind this tick
+    dst.resize((size_t)m_capture_channels * fresh);
+    m_hip_prev.assign((size_t)m_capture_channels * stay, 0.0f);
+    for(auto channel = 0u; channel < m_capture_channels; ++channel) {
+        const size_t s = all[channel].size();
+        std::memcpy(dst.data() + (size_t)channel * fresh, all[channel].data() + (s - fresh), fresh * sizeof(float));
+        std::memcpy(m_hip_prev.data() + (size_t)channel * stay, all[channel].data() + (s - stay), stay * sizeof(float));
+        m_capturebufs[channel].pop_front(nullptr, (s - stay) * sizeof(float)); // :321: only the reserve stays
+    }
+    m_hip_pushed = stay;
+    return true;
+}
+
+// synchronous: the handle's one stream is told its state when it changes
+bool WAVSourceHIP::hip_send_state(int state)
+{
+    if(state == m_hip_state)
+        return true;
+    const uint8_t mask = (uint8_t)state;
+    m_hip_state = state;
+    return api().set_hidden(m_hip, 0, 1, &mask) == WF_HIP_OK;
+}
+
+// rows ([output_channels][outsz]) and the silence verdict of a tick -> m_decibels / m_last_silent
+void WAVSourceHIP::hip_take_rows(const float *rows, size_t outsz, bool silent)
+{
+    for(auto channel = 0u; channel < m_output_channels; ++channel)
+        std::memcpy(m_decibels[channel].get(), rows + (size_t)channel * outsz, outsz * sizeof(float));
+    m_last_silent = silent;
+}
+
+// synchronous: the tick, and its rows and m_last_silent inside the call
+bool WAVSourceHIP::hip_tick_and_take_rows(const wf_hip_tick_params &p, size_t outsz)
+{
+    auto &a = api();
+    m_hip_out.resize((size_t)m_output_channels * outsz);
+    uint8_t silent = 0;
+    if(a.tick(m_hip, &p) != WF_HIP_OK || a.read(m_hip, WF_HIP_OUT_DECIBELS, 0, 1, m_hip_out.data()) != WF_HIP_OK ||
+       a.read(m_hip, WF_HIP_OUT_LAST_SILENT, 0, 1, &silent) != WF_HIP_OK)
+        return false;
+    hip_take_rows(m_hip_out.data(), outsz, silent != 0);
+    return true;
+}
+
+// Same observable behaviour as WAVSourceGeneric::tick_spectrum (src/source_generic.cpp:26-180): the A/V-synchronised
+// window of each channel goes to the device, the device runs the whole per-tick state machine (hidden/timeout reset,
+// silence detection, window, FFT, magnitude, slope, smoothing, dBFS, normalisation, roll-off) and m_decibels /
+// m_last_silent come back.
 // The batched path (struct WFHipGroup).  m_decibels / m_last_silent are the device's results for the previous video frame.
 void WAVSourceHIP::tick_spectrum_batched(float seconds)
 {
-    auto &a = api();
     auto &r = registry();
     std::unique_lock lock(r.mtx);
     WFHipGroup *g = m_group;
     const uint32_t slot = m_slot;
-    const size_t N = m_fft_size, outsz = m_fft_size / 2;
-    bool ok = !g->failed;
-    // a member that comes round again while its last hand-over is still waiting for the rest of the frame completes it
-    if(ok && g->submitted[slot] == g->batch)
-        ok = g->flush();
-    // 1. collect the row the last flushed batch left for this source
-    const uint32_t last = (uint32_t)((g->batch - 1) & 1);
-    // (whatever the stream holds after that batch: a source that sat a frame out finds the row of its last tick, unchanged)
-    if(ok && g->batch > 1 && g->rows_valid[last] && g->batch - 1 >= m_hip_joined) {
-        ok = a.readback_done(g->h, last) == WF_HIP_OK;
-        if(ok) {
-            const float *row = g->rows[last] + (size_t)slot * g->out_ch * g->M;
-            for(auto channel = 0u; channel < m_output_channels; ++channel)
-                std::memcpy(m_decibels[channel].get(), row + (size_t)channel * outsz, outsz * sizeof(float));
-            m_last_silent = g->silent[last][slot] != 0;
-            if(g->rms_feed)
-                m_input_rms = g->rms_back[last][slot]; // as of that batch's tick (for observers; the device uses its own)
-            if(g->display && m_hip_display && g->pre[last])
-                m_hip_pre.assign(g->pre[last] + (size_t)slot * g->disp_ch, g->pre[last] + (size_t)(slot + 1) * g->disp_ch);
-            if(g->display && m_hip_display)
-                hip_collect_display(g->bars[last] + (size_t)slot * g->disp_ch * g->points,
-                                    g->per_row ? g->verts[last] + (size_t)slot * g->disp_ch * g->per_row * 4 : nullptr,
-                                    g->per_row ? g->vcounts[last] + (size_t)slot * g->disp_ch : nullptr);
-        }
-    }
-    if(!ok) {
+    const size_t N = m_fft_size;
+    int last = -1;
+    if(!g->begin_tick(slot, m_hip_joined, last)) {
         lock.unlock();
-        LogWarn << "HIP batch unavailable; this source continues on the CPU path";
         if(g->rms_feed && m_input_rms_buf && m_input_rms_size > 0) {
             // the device kept the one-second window of squared peaks; the host's ring was never advanced.  Seed it so that its
             // sum reproduces the last m_input_rms that came back (every entry = the mean square), instead of a window of zeros
@@ -960,17 +1096,27 @@ void WAVSourceHIP::tick_spectrum_batched(float seconds)
                 m_input_rms_buf[i] = ms;
             m_input_rms_pos = 0;
         }
-        hip_release();
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back("HIP batch unavailable; this source continues on the CPU path");
         WAVSourceGeneric::tick_spectrum(seconds);
         return;
+    }
+    // 1. collect the row the last flushed batch left for this source
+    if(last >= 0) {
+        hip_take_rows(g->rows[last] + (size_t)slot * g->out_ch * g->M, N / 2, g->silent[last][slot] != 0);
+        if(g->rms_feed)
+            m_input_rms = g->rms_back[last][slot]; // as of that batch's tick (for observers; the device uses its own)
+        if(g->display && m_hip_display && g->pre[last])
+            m_hip_pre.assign(g->pre[last] + (size_t)slot * g->disp_ch, g->pre[last] + (size_t)(slot + 1) * g->disp_ch);
+        if(g->display && m_hip_display)
+            hip_collect_display(g->bars[last] + (size_t)slot * g->disp_ch * g->points,
+                                g->per_row ? g->verts[last] + (size_t)slot * g->disp_ch * g->per_row * 4 : nullptr,
+                                g->per_row ? g->vcounts[last] + (size_t)slot * g->disp_ch : nullptr);
     }
     // 2. submit this frame
     const uint32_t b = (uint32_t)(g->batch & 1);
     if(g->n_submitted == 0)
-        a.ingest_done(g->h, b); // the staging block of this slot has been copied out (two frames ago)
-    const auto dtcapture = m_tick_ts - m_capture_ts;
-    const bool timed_out = dtcapture > CAPTURE_TIMEOUT;
+        api().ingest_done(g->h, b); // the staging block of this slot has been copied out (two frames ago)
+    const bool timed_out = hip_timed_out();
     const bool hidden = !m_show || timed_out; // reference :34
     uint32_t fresh = 0;
     uint8_t st = hidden ? (timed_out ? WF_HIP_HIDDEN_TIMEOUT : WF_HIP_HIDDEN) : WF_HIP_SHOWN;
@@ -1015,15 +1161,8 @@ void WAVSourceHIP::tick_spectrum_batched(float seconds)
             m_hip_prev_sync = (int64_t)dtframes;
         }
     }
-    g->frames[slot] = fresh;
-    g->state[slot] = st;
     g->rms[slot] = m_input_rms;
-    g->seconds = seconds;
-    g->submitted[slot] = g->batch;
-    ++g->n_submitted;
-    // 3. the frame's last member sends the batch off
-    if(g->n_submitted >= g->members)
-        g->flush(); // (a failure shows at the members' next tick)
+    g->submit(slot, fresh, st, seconds);
 }
 
 // WAVSourceGeneric::update_input_rms (src/source_generic.cpp:392-403) = sync_rms_buffer (src/source.cpp:810-835: everything
@@ -1046,8 +1185,7 @@ void WAVSourceHIP::update_input_rms()
     // a member that comes round again while its last hand-over is still waiting for the rest of the frame completes it
     if(g->submitted[m_slot] == g->batch)
         g->flush();
-    const int64_t dtaudio = get_audio_sync(m_tick_ts);
-    const size_t dtsize = (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) * sizeof(float) : 0;
+    const size_t dtsize = hip_sync_frames() * sizeof(float);
     if(m_rms_sync_buf.size() <= dtsize)
         return; // sync_rms_buffer returns false: m_input_rms stays
     const uint32_t b = (uint32_t)(g->batch & 1);
@@ -1072,27 +1210,19 @@ void WAVSourceHIP::tick_spectrum(float seconds)
         return;
     }
     if(m_hip == nullptr) {
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back({});
         WAVSourceGeneric::tick_spectrum(seconds);
         return;
     }
     auto &a = api();
-    const auto outsz = m_fft_size / 2;
-
-    const auto dtcapture = m_tick_ts - m_capture_ts;
-    const bool hidden = !m_show || (dtcapture > CAPTURE_TIMEOUT); // reference :34
-    bool ok = true;
+    const bool hidden = !m_show || hip_timed_out(); // reference :34
     size_t dtframes = 0;
     // Underflow (fewer samples than window + A/V-sync delay, :55-61): every channel is skipped, but unless m_last_silent the
     // reference's end-of-tick pass still runs over the rows as they are -- dbfs of a stale dB value is DB_MIN, and the volume
     // normalisation gain goes on top (:138-179).  The device does the same for a stream marked WF_HIP_STARVED.
     const bool starved = !hidden && !hip_window(dtframes);
     const int state = hidden ? WF_HIP_HIDDEN : (starved ? WF_HIP_STARVED : WF_HIP_SHOWN);
-    if(state != m_hip_state) {
-        const uint8_t mask = (uint8_t)state;
-        ok = a.set_hidden(m_hip, 0, 1, &mask) == WF_HIP_OK;
-        m_hip_state = state;
-    }
+    bool ok = hip_send_state(state);
     if(ok && state == WF_HIP_SHOWN) // the whole window replaces the device ring's newest fft_size samples
         ok = a.push_audio(m_hip, 0, 1, m_hip_window.data(), (uint32_t)m_fft_size) == WF_HIP_OK;
     wf_hip_tick_params p{};
@@ -1100,18 +1230,11 @@ void WAVSourceHIP::tick_spectrum(float seconds)
     p.delay_frames = 0;
     p.input_rms = m_input_rms;
     p.flags = 0;
-    uint8_t silent = 0;
-    if(!ok || a.tick(m_hip, &p) != WF_HIP_OK || a.read(m_hip, WF_HIP_OUT_DECIBELS, 0, 1, m_hip_out.data()) != WF_HIP_OK ||
-       a.read(m_hip, WF_HIP_OUT_LAST_SILENT, 0, 1, &silent) != WF_HIP_OK) {
-        LogWarn << "HIP tick failed (" << a.last_error(m_hip) << "); falling back to the CPU path";
-        hip_release();
-        g_fallback_ticks.fetch_add(1);
+    if(!ok || !hip_tick_and_take_rows(p, m_fft_size / 2)) {
+        hip_fall_back(std::string("HIP tick failed (") + a.last_error(m_hip) + "); falling back to the CPU path");
         WAVSourceGeneric::tick_spectrum(seconds);
         return;
     }
-    for(auto channel = 0u; channel < m_output_channels; ++channel)
-        std::memcpy(m_decibels[channel].get(), m_hip_out.data() + (size_t)channel * outsz, outsz * sizeof(float));
-    m_last_silent = silent != 0;
     if(m_hip_display) {
         // straight into the members render() draws from (no per-tick allocations, no staging copy)
         if(a.read(m_hip, WF_HIP_OUT_BARS, 0, 1, m_hip_bars.data()) == WF_HIP_OK &&
@@ -1131,58 +1254,27 @@ void WAVSourceHIP::tick_spectrum(float seconds)
 // The batched meter path (struct WFHipMeterGroup): m_meter_val / m_last_silent are the device's results for the previous frame.
 void WAVSourceHIP::tick_meter_batched(float seconds)
 {
-    auto &a = api();
     auto &r = registry();
     std::unique_lock lock(r.mtx);
     WFHipMeterGroup *g = m_mgroup;
     const uint32_t slot = m_slot;
-    bool ok = !g->failed;
-    if(ok && g->submitted[slot] == g->batch) // came round again while the frame was still being assembled: complete it
-        ok = g->flush();
-    // 1. collect the levels the last flushed batch left for this source
-    const uint32_t last = (uint32_t)((g->batch - 1) & 1);
-    if(ok && g->batch > 1 && g->valid[last] && g->batch - 1 >= m_hip_joined) {
-        ok = a.readback_done(g->h, last) == WF_HIP_OK;
-        if(ok) {
-            for(auto channel = 0u; channel < m_capture_channels; ++channel)
-                m_meter_val[channel] = g->levels[last][(size_t)slot * g->cap_ch + channel];
-            m_last_silent = g->silent[last][slot] != 0;
-        }
-    }
-    if(!ok) {
+    int last = -1;
+    if(!g->begin_tick(slot, m_hip_joined, last)) {
         lock.unlock();
-        LogWarn << "HIP meter batch unavailable; this source continues on the CPU path";
-        hip_release();
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back("HIP meter batch unavailable; this source continues on the CPU path");
         WAVSourceGeneric::tick_meter(seconds);
         return;
     }
-    // 2. submit this frame: state, and what tick_meter would pop into its meter buffer (:201-220)
-    const auto dtcapture = m_tick_ts - m_capture_ts;
-    const bool timed_out = dtcapture > CAPTURE_TIMEOUT; // :184
-    uint32_t frames = 0;
-    if(!timed_out) {
-        const int64_t dtaudio = get_audio_sync(m_tick_ts);
-        const size_t dtsize = (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) * sizeof(float) : 0;
-        size_t n_min = 0;
-        for(auto channel = 0u; channel < m_capture_channels; ++channel) {
-            const auto sz = m_capturebufs[channel].size();
-            const size_t n = (sz > dtsize) ? (sz - dtsize) / sizeof(float) : 0;
-            n_min = (channel == 0) ? n : std::min(n_min, n);
-        }
-        frames = (uint32_t)n_min;
-        auto &dst = g->pending[slot];
-        dst.resize((size_t)m_capture_channels * frames);
-        for(auto channel = 0u; channel < m_capture_channels && frames; ++channel)
-            m_capturebufs[channel].pop_front(dst.data() + (size_t)channel * frames, (size_t)frames * sizeof(float));
+    // 1. collect the levels the last flushed batch left for this source
+    if(last >= 0) {
+        for(auto channel = 0u; channel < m_capture_channels; ++channel)
+            m_meter_val[channel] = g->levels[last][(size_t)slot * g->cap_ch + channel];
+        m_last_silent = g->silent[last][slot] != 0;
     }
-    g->frames[slot] = frames;
-    g->state[slot] = timed_out ? WF_HIP_HIDDEN_TIMEOUT : (m_show ? WF_HIP_SHOWN : WF_HIP_HIDDEN);
-    g->seconds = seconds;
-    g->submitted[slot] = g->batch;
-    ++g->n_submitted;
-    if(g->n_submitted >= g->members)
-        g->flush();
+    // 2. submit this frame: state, and what tick_meter would pop into its meter buffer
+    const bool timed_out = hip_timed_out(); // :184
+    const uint32_t frames = timed_out ? 0u : hip_pop_meter(g->pending[slot]);
+    g->submit(slot, frames, timed_out ? WF_HIP_HIDDEN_TIMEOUT : (m_show ? WF_HIP_SHOWN : WF_HIP_HIDDEN), seconds);
 }
 
 void WAVSourceHIP::tick_meter(float seconds)
@@ -1192,37 +1284,17 @@ void WAVSourceHIP::tick_meter(float seconds)
         return;
     }
     if(m_hip == nullptr) {
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back({});
         WAVSourceGeneric::tick_meter(seconds);
         return;
     }
     auto &a = api();
-    const auto dtcapture = m_tick_ts - m_capture_ts;
-    const bool timed_out = dtcapture > CAPTURE_TIMEOUT; // :184
-    const int state = timed_out ? WF_HIP_HIDDEN_TIMEOUT : (m_show ? WF_HIP_SHOWN : WF_HIP_HIDDEN);
-    bool ok = true;
-    if(state != m_hip_state) {
-        const uint8_t mask = (uint8_t)state;
-        ok = a.set_hidden(m_hip, 0, 1, &mask) == WF_HIP_OK;
-        m_hip_state = state;
-    }
+    const bool timed_out = hip_timed_out(); // :184
+    bool ok = hip_send_state(timed_out ? WF_HIP_HIDDEN_TIMEOUT : (m_show ? WF_HIP_SHOWN : WF_HIP_HIDDEN));
     if(ok && !timed_out) {
-        // :201-220: everything beyond dtsize bytes is consumed -- here: moved to the device ring, oldest first
-        const int64_t dtaudio = get_audio_sync(m_tick_ts);
-        const size_t dtsize = (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) * sizeof(float) : 0;
-        size_t frames = 0;
-        for(auto channel = 0u; channel < m_capture_channels; ++channel) {
-            const auto sz = m_capturebufs[channel].size();
-            const size_t n = (sz > dtsize) ? (sz - dtsize) / sizeof(float) : 0;
-            frames = (channel == 0) ? n : std::min(frames, n); // the channels of a source are pushed together by capture_audio
-        }
-        if(frames > 0) {
-            m_hip_window.resize((size_t)m_capture_channels * frames);
-            for(auto channel = 0u; channel < m_capture_channels; ++channel)
-                m_capturebufs[channel].pop_front(m_hip_window.data() + (size_t)channel * frames, frames * sizeof(float));
-            // capture_audio keeps at most dtsamples + m_fft_size samples, so this is never more than the ring holds
-            ok = a.push_audio(m_hip, 0, 1, m_hip_window.data(), (uint32_t)frames) == WF_HIP_OK;
-        }
+        const uint32_t frames = hip_pop_meter(m_hip_window); // moved to the device ring, oldest first
+        if(frames > 0)
+            ok = a.push_audio(m_hip, 0, 1, m_hip_window.data(), frames) == WF_HIP_OK;
     }
     wf_hip_tick_params p{};
     p.seconds = seconds;
@@ -1230,9 +1302,7 @@ void WAVSourceHIP::tick_meter(float seconds)
     uint8_t silent = 0;
     if(!ok || a.tick(m_hip, &p) != WF_HIP_OK || a.read(m_hip, WF_HIP_OUT_METER, 0, 1, levels) != WF_HIP_OK ||
        a.read(m_hip, WF_HIP_OUT_LAST_SILENT, 0, 1, &silent) != WF_HIP_OK) {
-        LogWarn << "HIP meter tick failed (" << a.last_error(m_hip) << "); falling back to the CPU path";
-        hip_release();
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back(std::string("HIP meter tick failed (") + a.last_error(m_hip) + "); falling back to the CPU path");
         WAVSourceGeneric::tick_meter(seconds);
         return;
     }
@@ -1245,115 +1315,56 @@ void WAVSourceHIP::tick_meter(float seconds)
 // the previous video frame.  What this frame hands over is exactly what the synchronous path below pushes inside the call.
 void WAVSourceHIP::tick_waveform_batched(float seconds)
 {
-    auto &a = api();
     auto &r = registry();
     std::unique_lock lock(r.mtx);
     WFHipMeterGroup *g = m_mgroup;
     const uint32_t slot = m_slot;
-    const size_t outsz = m_fft_size;
-    bool ok = !g->failed;
-    if(ok && g->submitted[slot] == g->batch) // came round again while the frame was still being assembled: complete it
-        ok = g->flush();
-    // 1. collect the rows the last flushed batch left for this source
-    const uint32_t last = (uint32_t)((g->batch - 1) & 1);
-    if(ok && g->batch > 1 && g->valid[last] && g->batch - 1 >= m_hip_joined) {
-        ok = a.readback_done(g->h, last) == WF_HIP_OK;
-        if(ok) {
-            const float *row = g->rows[last] + (size_t)slot * g->out_ch * g->width;
-            for(auto channel = 0u; channel < m_output_channels; ++channel)
-                std::memcpy(m_decibels[channel].get(), row + (size_t)channel * outsz, outsz * sizeof(float));
-            m_last_silent = g->silent[last][slot] != 0;
-        }
-    }
-    if(!ok) {
+    int last = -1;
+    if(!g->begin_tick(slot, m_hip_joined, last)) {
         lock.unlock();
-        LogWarn << "HIP waveform batch unavailable; this source continues on the CPU path";
-        hip_release();
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back("HIP waveform batch unavailable; this source continues on the CPU path");
         WAVSourceGeneric::tick_waveform(seconds);
         return;
     }
+    // 1. collect the rows the last flushed batch left for this source
+    if(last >= 0)
+        hip_take_rows(g->rows[last] + (size_t)slot * g->out_ch * g->width, m_fft_size, g->silent[last][slot] != 0);
     // 2. submit this frame
-    const auto dtcapture = m_tick_ts - m_capture_ts;
-    const bool hidden = !m_show || (dtcapture > CAPTURE_TIMEOUT); // :279
+    const bool hidden = !m_show || hip_timed_out(); // :279
     uint8_t st = hidden ? WF_HIP_HIDDEN : WF_HIP_SHOWN;
-    size_t fresh = 0;
+    uint32_t fresh = 0;
     if(!hidden) {
-        const int64_t dtaudio = get_audio_sync(m_tick_ts);
-        const size_t reserve = (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) : 0; // frames
-        const size_t max_frames = m_waveform_samples + reserve;
-        if(max_frames > g->ring_cap) {
+        const size_t reserve = hip_sync_frames();
+        if(m_waveform_samples + reserve > g->ring_cap) {
             // wf_hip_set_stream_delay would reject the whole batch for this one stream (an A/V-sync reserve beyond what the
             // device rings were sized for): only THIS source leaves -- nothing of it has been staged or popped yet, so the
             // reference's tick_waveform takes the frame over from m_capturebufs as they are, with m_decibels as step 1 left
             // them (the previous frame's rows) and the sweep position the device kept for it (one 8-byte read that waits for
             // the last batch: this happens once) -- and the group's other members never notice
             uint64_t wts = 0;
-            if(a.read(g->h, WF_HIP_OUT_WAVEFORM_TS, slot, 1, &wts) == WF_HIP_OK)
+            if(api().read(g->h, WF_HIP_OUT_WAVEFORM_TS, slot, 1, &wts) == WF_HIP_OK)
                 m_waveform_ts = (size_t)wts; // (else 0: the reference catches up by itself, src/source_generic.cpp:318-321)
+            const uint32_t ring_cap = g->ring_cap;
             lock.unlock();
-            LogWarn << "HIP waveform batch: this source's A/V-sync reserve (" << reserve << " frames) does not fit the device ring ("
-                    << g->ring_cap << "); it continues on the CPU path";
-            hip_release();
-            g_fallback_ticks.fetch_add(1);
+            hip_fall_back("HIP waveform batch: this source's A/V-sync reserve (" + std::to_string(reserve) + " frames) does not fit the device ring (" +
+                          std::to_string(ring_cap) + "); it continues on the CPU path");
             WAVSourceGeneric::tick_waveform(seconds);
             return;
         }
-        bool enough = true;
-        for(auto i = 0u; i < m_capture_channels; ++i)
-            if(m_capturebufs[i].size() <= reserve * sizeof(float)) // :293-295: the reference returns before it touches anything
-                enough = false;
-        if(!enough) {
+        if(!hip_wave_fresh(reserve, g->pending[slot])) {
             st = WF_HIP_PAUSED;
         } else {
-            // (see the synchronous path below for what is pushed and why)
-            size_t frames = 0;
-            bool front_kept = true;
-            std::vector<std::vector<float>> all(m_capture_channels);
-            for(auto channel = 0u; channel < m_capture_channels; ++channel) {
-                auto &buf = m_capturebufs[channel];
-                if(buf.size() > max_frames * sizeof(float)) // :303-304
-                    buf.pop_front(nullptr, buf.size() - max_frames * sizeof(float));
-                const size_t s = buf.size() / sizeof(float);
-                all[channel].resize(s);
-                buf.peek_front(all[channel].data(), s * sizeof(float));
-                if(channel == 0)
-                    frames = s;
-                front_kept = front_kept && s >= m_hip_pushed && m_hip_prev.size() == (size_t)m_capture_channels * m_hip_pushed &&
-                             std::memcmp(all[channel].data(), m_hip_prev.data() + (size_t)channel * m_hip_pushed, m_hip_pushed * sizeof(float)) == 0;
-            }
-            fresh = front_kept ? frames - m_hip_pushed : frames;
-            const auto start_ts = m_audio_ts - audio_frames_to_ns(m_audio_info.samples_per_sec, frames);
-            const auto stop_ts = m_audio_ts - audio_frames_to_ns(m_audio_info.samples_per_sec, reserve);
-            const bool rollover = (start_ts >= m_audio_ts) || (stop_ts > m_audio_ts); // :314-317
-            const size_t stay = rollover ? frames : reserve; // frames left in m_capturebufs behind this tick
-            auto &dst = g->pending[slot];
-            dst.resize((size_t)m_capture_channels * fresh);
-            m_hip_prev.assign((size_t)m_capture_channels * stay, 0.0f);
-            for(auto channel = 0u; channel < m_capture_channels; ++channel) {
-                auto &buf = m_capturebufs[channel];
-                const size_t s = all[channel].size();
-                std::memcpy(dst.data() + (size_t)channel * fresh, all[channel].data() + (s - fresh), fresh * sizeof(float));
-                std::memcpy(m_hip_prev.data() + (size_t)channel * stay, all[channel].data() + (s - stay), stay * sizeof(float));
-                buf.pop_front(nullptr, (s - stay) * sizeof(float)); // :321: only the reserve stays
-            }
-            m_hip_pushed = stay;
+            fresh = (uint32_t)(g->pending[slot].size() / m_capture_channels);
             g->delay[slot] = (uint32_t)reserve;
             g->audio_ts[slot] = m_audio_ts;
         }
     }
-    g->frames[slot] = (uint32_t)fresh;
-    g->state[slot] = st;
-    g->seconds = seconds;
-    g->submitted[slot] = g->batch;
-    ++g->n_submitted;
-    if(g->n_submitted >= g->members)
-        g->flush();
+    g->submit(slot, fresh, st, seconds);
 }
 
 // Same observable behaviour as WAVSourceGeneric::tick_waveform (src/source_generic.cpp:271-390).  The device ring mirrors
-// m_capturebufs: every tick the frames captured since the last one are appended to it, the device picks the new points
-// from its ring exactly where the reference picks them from its scratch copy (both count back from the newest sample),
+// m_capturebufs: every tick the frames captured since the last one are appended to it (hip_wave_fresh), the device picks the new
+// points from its ring exactly where the reference picks them from its scratch copy (both count back from the newest sample),
 // and m_capturebufs is popped down to the A/V-sync reserve as the reference does (:321).  m_waveform_ts lives on the device.
 void WAVSourceHIP::tick_waveform(float seconds)
 {
@@ -1362,85 +1373,28 @@ void WAVSourceHIP::tick_waveform(float seconds)
         return;
     }
     if(m_hip == nullptr) {
-        g_fallback_ticks.fetch_add(1);
+        hip_fall_back({});
         WAVSourceGeneric::tick_waveform(seconds);
         return;
     }
     auto &a = api();
-    const auto outsz = m_fft_size;
-    const auto dtcapture = m_tick_ts - m_capture_ts;
-    const bool hidden = !m_show || (dtcapture > CAPTURE_TIMEOUT); // :279
-    bool ok = true;
-    if(hidden != m_hip_hidden) {
-        const uint8_t mask = hidden ? 1 : 0;
-        ok = a.set_hidden(m_hip, 0, 1, &mask) == WF_HIP_OK;
-        m_hip_hidden = hidden;
-    }
+    const bool hidden = !m_show || hip_timed_out(); // :279
+    bool ok = hip_send_state(hidden ? WF_HIP_HIDDEN : WF_HIP_SHOWN);
     wf_hip_tick_params p{};
     p.seconds = seconds;
     p.input_rms = m_input_rms;
     p.audio_ts_ns = m_audio_ts;
     if(ok && !hidden) {
-        const int64_t dtaudio = get_audio_sync(m_tick_ts);
-        const size_t reserve = (dtaudio > 0) ? size_t(ns_to_audio_frames(m_audio_info.samples_per_sec, (uint64_t)dtaudio)) : 0; // frames
-        const size_t max_frames = m_waveform_samples + reserve;
-        for(auto i = 0u; i < m_capture_channels; ++i)
-            if(m_capturebufs[i].size() <= reserve * sizeof(float)) // :293-295
-                return;
-        // The device ring holds every frame pushed so far and counts "what the reference's ring holds" as (frames pushed since
-        // the last tick) + (the reserve that tick left behind), :321.  Frames at the front of m_capturebufs that are already
-        // there -- the last tick's reserve, m_hip_pushed of them -- must not be pushed twice; but capture_audio drops from the
-        // front once a ring exceeds dtsamples + m_waveform_samples (src/source.cpp:1883-1886), and then what is left is
-        // re-sent whole: after a drop the ring is at its cap, the reference trims it to max_size and so does the device
-        // (avail > max_size), and the re-sent frames are contiguous.  Whether the old reserve is still at the front is
-        // checked against a copy of it (all-zero audio can match by accident: then both ways of pushing give zeros).
-        size_t frames = 0, fresh = 0;
-        bool front_kept = true;
-        std::vector<std::vector<float>> all(m_capture_channels);
-        for(auto channel = 0u; channel < m_capture_channels; ++channel) {
-            auto &buf = m_capturebufs[channel];
-            if(buf.size() > max_frames * sizeof(float)) // :303-304
-                buf.pop_front(nullptr, buf.size() - max_frames * sizeof(float));
-            const size_t s = buf.size() / sizeof(float);
-            all[channel].resize(s);
-            buf.peek_front(all[channel].data(), s * sizeof(float));
-            if(channel == 0)
-                frames = s;
-            front_kept = front_kept && s >= m_hip_pushed && m_hip_prev.size() == (size_t)m_capture_channels * m_hip_pushed &&
-                         std::memcmp(all[channel].data(), m_hip_prev.data() + (size_t)channel * m_hip_pushed, m_hip_pushed * sizeof(float)) == 0;
-        }
-        fresh = front_kept ? frames - m_hip_pushed : frames;
-        // "timestamp rollover, give up" (:314-317; a tick before any audio has a timestamp): the reference has trimmed its
-        // ring but consumes nothing.  The device takes the same exit from the same timestamps (and records the trim); here the
-        // ring keeps what it holds, all of it now on the device.
-        const auto start_ts = m_audio_ts - audio_frames_to_ns(m_audio_info.samples_per_sec, frames);
-        const auto stop_ts = m_audio_ts - audio_frames_to_ns(m_audio_info.samples_per_sec, reserve);
-        const bool rollover = (start_ts >= m_audio_ts) || (stop_ts > m_audio_ts);
-        const size_t stay = rollover ? frames : reserve; // frames left in m_capturebufs behind this tick
-        m_hip_window.resize((size_t)m_capture_channels * fresh);
-        m_hip_prev.assign((size_t)m_capture_channels * stay, 0.0f);
-        for(auto channel = 0u; channel < m_capture_channels; ++channel) {
-            auto &buf = m_capturebufs[channel];
-            const size_t s = all[channel].size();
-            std::memcpy(m_hip_window.data() + (size_t)channel * fresh, all[channel].data() + (s - fresh), fresh * sizeof(float));
-            std::memcpy(m_hip_prev.data() + (size_t)channel * stay, all[channel].data() + (s - stay), stay * sizeof(float));
-            buf.pop_front(nullptr, (s - stay) * sizeof(float)); // :321: only the reserve stays
-        }
-        if(fresh > 0)
-            ok = a.push_audio(m_hip, 0, 1, m_hip_window.data(), (uint32_t)fresh) == WF_HIP_OK;
-        m_hip_pushed = stay;
+        const size_t reserve = hip_sync_frames();
+        if(!hip_wave_fresh(reserve, m_hip_window))
+            return;
+        if(!m_hip_window.empty())
+            ok = a.push_audio(m_hip, 0, 1, m_hip_window.data(), (uint32_t)(m_hip_window.size() / m_capture_channels)) == WF_HIP_OK;
         p.delay_frames = (uint32_t)reserve;
     }
-    m_hip_out.resize((size_t)m_output_channels * outsz);
-    uint8_t silent = 0;
-    if(!ok || a.tick(m_hip, &p) != WF_HIP_OK || a.read(m_hip, WF_HIP_OUT_DECIBELS, 0, 1, m_hip_out.data()) != WF_HIP_OK ||
-       a.read(m_hip, WF_HIP_OUT_LAST_SILENT, 0, 1, &silent) != WF_HIP_OK) {
-        LogWarn << "HIP waveform tick failed (" << a.last_error(m_hip) << "); falling back to the CPU path";
-        hip_release();
-        g_fallback_ticks.fetch_add(1);
+    if(!ok || !hip_tick_and_take_rows(p, m_fft_size)) {
+        hip_fall_back(std::string("HIP waveform tick failed (") + a.last_error(m_hip) + "); falling back to the CPU path");
         return; // the audio of this tick has been consumed; the CPU path takes over at the next one
     }
-    for(auto channel = 0u; channel < m_output_channels; ++channel)
-        std::memcpy(m_decibels[channel].get(), m_hip_out.data() + (size_t)channel * outsz, outsz * sizeof(float));
-    m_last_silent = silent != 0; // (no device display here: hip_configure builds one for spectrum displays only, the waveform's points are the rows)
+    // (no device display here: hip_configure builds one for spectrum displays only, the waveform's points are the rows)
 }

@@ -18,6 +18,10 @@
 #pragma once
 #include "source.hpp"   // the reference's
 #include "wf_hip.h"
+#include <string>
+
+// how an attempt to put a configuration on the device ended; refused: wf_hip_create does not take this configuration
+enum class WFHipAttach { ok, refused, failed };
 
 class WAVSourceHIP : public WAVSourceGeneric
 {
@@ -40,8 +44,11 @@ protected:
     //    with volume normalisation stay synchronous);
     //  * synchronous (WF_HIP_BATCHED=0): a handle of one stream per source,
     //    push -> tick -> read inside the call, zero latency (m_hip).
+    // The two group types add their buffers and the middle of their flush to one core (struct WFHipGroupCore): the handle, the
+    // slots, join / leave, and the frame's hand-over (begin_tick: collect gate; submit: flush when the frame is complete).  What
+    // a tick hands over is decided by the hip_* rules below, each shared by the batched and the synchronous form.
     struct WFHipGroup *m_group = nullptr;
-    struct WFHipMeterGroup *m_mgroup = nullptr; // level meter, batched: the sources of one meter configuration share a handle too
+    struct WFHipMeterGroup *m_mgroup = nullptr; // level meter / waveform display, batched: the sources of one configuration share a handle too
     uint32_t m_slot = 0;
     uint64_t m_hip_joined = 0;         // the group's batch counter when this source took its slot
     bool m_hip_have_prev = false;      // m_hip_prev holds the window handed over at the previous tick
@@ -49,11 +56,10 @@ protected:
     uint64_t m_hip_prev_audio_ts = 0;  // m_audio_ts / A/V-sync frames of that window: where the next one is expected to start
     int64_t m_hip_prev_sync = 0;
     wf_hip *m_hip = nullptr;
-    bool m_hip_hidden = false;
     std::vector<float> m_hip_window;   // [capture_channels][fft_size] staging for the H2D copy
     std::vector<float> m_hip_out;      // [output_channels][fft_size/2]
     size_t m_hip_pushed = 0;           // waveform: frames at the front of m_capturebufs that are already in the device ring
-    int m_hip_state = 0;               // what the device was last told: WF_HIP_SHOWN / WF_HIP_HIDDEN / WF_HIP_HIDDEN_TIMEOUT
+    int m_hip_state = 0;               // synchronous: what the device was last told (WF_HIP_SHOWN / WF_HIP_HIDDEN / WF_HIP_HIDDEN_TIMEOUT / WF_HIP_STARVED)
 
     // The display from the device (render() override): what render_bars / render_curve would compute from m_decibels -- bar tops
     // or curve points in pixels, and the vertices they write into the vertex buffer -- comes back with the rows (one frame late
@@ -68,8 +74,16 @@ protected:
     std::vector<float> m_hip_pre;        // [display channels] mirrored axis: the value the outputs above the middle had before the mirror
 
     void hip_release();
-    bool hip_configure();              // (re)creates m_hip from the members update() has just set
+    // update() -> the device, in stages: the members as a wf_config (hip_config) with its display fields (hip_display_config);
+    // hip_attach: a slot in the group of that configuration (hip_join_group) or a handle of its own
+    // (hip_open_own), once more without the display where the device refuses it; hip_size_display for either
+    bool hip_configure();
+    wf_config hip_config() const;
     void hip_display_config(struct wf_config &c) const; // the display fields of wf_config from the members update() has set
+    WFHipAttach hip_attach(const wf_config &c);
+    WFHipAttach hip_join_group(const wf_config &c);
+    WFHipAttach hip_open_own(const wf_config &c);
+    void hip_size_display(uint32_t disp_ch, uint32_t points, uint32_t per_row);
     void hip_collect_display(const float *bars, const float *verts, const uint32_t *counts);
     void hip_publish_display();
 
@@ -100,7 +114,14 @@ private:
     void tick_spectrum_batched(float seconds);
     void tick_meter_batched(float seconds);
     void tick_waveform_batched(float seconds);
+    // what a tick hands over and how it ends, each rule once for the batched and the synchronous form
+    bool hip_timed_out() const { return m_tick_ts - m_capture_ts > CAPTURE_TIMEOUT; } // no packet for that long: the reference's capture timeout
+    size_t hip_sync_frames();           // the A/V-sync point: frames of captured audio ahead of this tick
     bool hip_window(size_t &dtframes);  // the A/V-synchronised window of every channel -> m_hip_window; false on underflow
-    friend struct WFHipGroup;
-    friend struct WFHipMeterGroup;
+    uint32_t hip_pop_meter(std::vector<float> &dst);                  // what tick_meter would consume -> dst; frames
+    bool hip_wave_fresh(size_t reserve, std::vector<float> &dst);     // the frames new to the waveform's device ring -> dst; false: nothing beyond the reserve
+    bool hip_send_state(int state);     // synchronous: the state mask when it changes
+    void hip_take_rows(const float *rows, size_t outsz, bool silent); // -> m_decibels / m_last_silent
+    bool hip_tick_and_take_rows(const wf_hip_tick_params &p, size_t outsz); // synchronous: tick + rows + m_last_silent inside the call
+    void hip_fall_back(const std::string &why); // leave the device for the CPU class ("": was not on it), counted
 };
