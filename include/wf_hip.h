@@ -57,6 +57,9 @@
  *   WF_HIP_OUT_THD       not in the reference: a distortion analyser, per captured channel the fundamental of a test tone, its
  *                        harmonics, THD, THD+N, SNR, SFDR and the noise floor, from a float64 transform of every stream's newest
  *                        window through a -180 dB taper on the device when read
+ *   WF_HIP_OUT_DELAY     not in the reference: a delay finder, by how many frames one captured channel lags the other and whether
+ *                        one of them is inverted, from the floored-PHAT cross-correlation of every stream's newest window, in
+ *                        float64 on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -423,10 +426,15 @@ typedef enum wf_hip_output {
                                   over-range count and the longest run of identical samples of the newest
                                   min(wf_hip_fft_size(), 8192) frames in the rings as of the pushes issued so far (spectrum and
                                   meter batches; definition below) */
-    WF_HIP_OUT_THD             /* wf_hip_thd                                 distortion: per captured channel the fundamental, the
+    WF_HIP_OUT_THD,            /* wf_hip_thd                                 distortion: per captured channel the fundamental, the
                                   harmonics 2 .. 10, THD, THD+N, SNR, SFDR and the noise floor of the newest P frames in the
                                   rings as of the pushes issued so far, P the largest power of two <= min(wf_hip_fft_size(),
                                   8192) (spectrum and meter batches of at least 512 frames; definition below) */
+    WF_HIP_OUT_DELAY           /* wf_hip_delay                               inter-channel delay: the lag in frames and the
+                                  polarity of captured channel 0 against channel 1, with the correlation curve around the peak, of
+                                  the newest P frames in the rings as of the pushes issued so far, P the largest power of two <=
+                                  min(wf_hip_fft_size(), 4096) (spectrum and meter batches with two captured channels; definition
+                                  below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -992,6 +1000,78 @@ typedef struct wf_hip_thd {
     uint32_t window;         /* P */
     uint32_t reserved[3];    /* 0 */
 } wf_hip_thd;                /* 208 bytes, a multiple of 16 */
+/* ---- inter-channel delay (WF_HIP_OUT_DELAY) -------------------------------------------------------------------------------------
+ * Per stream, the delay finder of a metering suite: by how many frames one captured channel lags the other, and whether one of
+ * them is inverted -- two microphones on one voice, a desktop capture behind a microphone, a lead wired out of phase.  No other
+ * output can stand in for it: WF_HIP_OUT_SIGNAL and WF_HIP_OUT_STEREO report the correlation at lag 0 only, where a negative
+ * reading cannot tell a polarity flip from a 0.3 ms offset.  W = wf_hip_fft_size(), sr = cfg.sample_rate; everything is float64
+ * unless it says otherwise.
+ *   window         P = the largest power of two <= min(W, WF_HIP_DELAY_MAX_WINDOW = 4096): the newest P frames of both captured
+ *                  channels' rings, positions (wpos - P .. wpos - 1) mod the ring's capacity, with the rules of WF_HIP_OUT_SIGNAL:
+ *                  every push issued before the read counts whatever its path, the A/V-sync delay is not applied, the zeros of
+ *                  create and wf_hip_reset count as samples.  Hidden and paused streams are read like any other.  M = P / 2 and
+ *                  L = P / 4, the range of lags.
+ *   taper          w[i] = 0.5 - 0.5 cos(2 pi i / P), the periodic Hann window, a host-made table.
+ *   spectra        X_c = DFT_P(w x_c) with the kernel e^(-j 2 pi i k / P); on the device both come out of one complex transform
+ *                  of w (x_0 + j x_1), separated as WF_HIP_OUT_STEREO does it.  Only the bins 1 <= k < M are used: DC and Nyquist
+ *                  are not.
+ *   cross spectrum G[k] = X_0[k] conj X_1[k], g = max_k |G[k]|, E_c = sum_k |X_c[k]|^2.
+ *   weighting      PHAT with a floor: u[k] = |G[k]| / max(|G[k]|, b g) and A[k] = G[k] / max(|G[k]|, b g) with b = 1e-3.  A bin
+ *                  more than 60 dB under the strongest cross-power fades out in proportion instead of entering with unit weight
+ *                  and a phase made of rounding noise, which is what plain PHAT gives it.
+ *   correlations   for integer n, circular over P:
+ *                    R[n] = (1 / (M - 1)) sum_k Re(A[k] e^(j 2 pi k n / P))    a pure broadband delay reads close to 1
+ *                    C[n] = sum_k Re(G[k] e^(j 2 pi k n / P)) / sqrt(E_0 E_1)  the ordinary normalised cross-correlation of the
+ *                                                                              tapered windows, in [-1, 1]
+ *   lag            n0 = the argmax of |R[n]| over -L <= n <= L: the scan runs from n = -L upwards and only a strictly greater
+ *                  value wins.  polarity = +1 if R[n0] > 0, else -1.  A positive lag means that channel 0 is the later one:
+ *                  x_0(t) = x_1(t - d).
+ *   fraction       from the slope of the phase, not by interpolating the peak (parabolic interpolation of a sinc-shaped peak is
+ *                  biased: it reads 5.07 to 5.18 for a true 5.3): B[k] = polarity A[k] e^(j 2 pi ((k n0) mod P) / P),
+ *                  phi[k] = atan2(Im B[k], Re B[k]), f = -(P / 2 pi) sum_k u[k] k phi[k] / sum_k u[k] k^2, clamped to [-0.5, 0.5]
+ *                  and 0 where the denominator is 0.  With the integer lag taken out |phi| stays under pi / 2 for coherent bins,
+ *                  so nothing is unwrapped.
+ *   fields         each float32 field is rounded once from float64.
+ *                    delay_frames (double)  n0 + f              delay_ms     1000 delay_frames / sr
+ *                    peak                   R[n0], signed       corr         C[n0]           corr_zero   C[0]
+ *                    ambiguity              the largest |R[n]| over -L <= n <= L with |n - n0| > 2, over |R[n0]| (0 where
+ *                                           R[n0] is 0): near 0 one clear arrival, near 1 a tone or unrelated channels -- the
+ *                                           delay is not to be trusted
+ *                    lag (int32) n0, polarity (int32), valid, window = P (uint32)
+ *                    curve[i]               R[n0 - 32 + i], i < WF_HIP_DELAY_CURVE = 65: the picture a delay finder draws around
+ *                                           its peak.  The index is circular and may leave +-L.
+ *   validity       valid = 0, and every other field but `window` 0, when either channel's window is all +-0, when either holds a
+ *                  NaN or an infinity, or when g is not a finite number > 0.  valid = 1 says "computed", not "reliable":
+ *                  reliability is `peak` against `ambiguity`, for the host to judge.
+ *   determinism    no atomics, and every sum and every max runs in an order that follows from P alone: the same ring contents
+ *                  read bit-identically across push paths, repeated reads, slices and shards.
+ * Limits: the correlation is circular over tapered windows, so the peak shrinks as |d| approaches L (to about 0.55 at |d| = L), and
+ * delays beyond L read as noise with a high `ambiguity`.  At 48 kHz and P = 4096 L is 21 ms, a path of 7 m.  At P = 128 a delay
+ * of a few frames is found to about 0.03 frame and one beyond P / 8 to about 0.16; from P = 1024 up to 0.01.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 256 threads per
+ * stream, two float64 transforms of P points in two LDS regions, 128 KB at the cap, so one workgroup to a CU there), into a block
+ * the first read allocates together with its tables: a handle that never reads it allocates and launches nothing new, and no state
+ * is kept between reads -- smoothing over reads is the host's.
+ * Cost on an MI355X, 4096 stereo streams, read into page-locked memory (1.31 MB back): 0.44 ms at W = 4096 and at W = 16384 (P =
+ * 4096 at both) against 2.36 ms for copying the 134.2 MB of windows to the host: 5.4 times.  Into a fresh pageable numpy array (the
+ * Python reader) a read takes 0.44 ms as well.  The kernel's own time without its copy is unmeasured (tools/delay_bench.py,
+ * profiles/delay_kernel_stats.json; INTEGRATION.md, "Inter-channel delay").
+ * Spectrum and meter batches with two captured channels are served, at every legal W; with one captured channel and on waveform
+ * batches wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through
+ * wf_hip_multi_read. */
+#define WF_HIP_DELAY_MAX_WINDOW 4096
+#define WF_HIP_DELAY_CURVE 65
+typedef struct wf_hip_delay {
+    double delay_frames;     /* n0 + f: positive when channel 0 is the later one */
+    float delay_ms, peak, corr, corr_zero, ambiguity;
+    int32_t lag;             /* n0 */
+    int32_t polarity;        /* +1, or -1: one channel is inverted */
+    uint32_t valid;
+    uint32_t window;         /* P */
+    uint32_t reserved;       /* 0 */
+    float curve[WF_HIP_DELAY_CURVE]; /* R[n0 - 32 + i] */
+    uint32_t reserved2[3];   /* 0 */
+} wf_hip_delay;              /* 320 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

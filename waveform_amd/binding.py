@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD = range(22)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY = range(23)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -212,6 +212,16 @@ THD_CHANNEL_DTYPE = np.dtype([("fundamental_hz", np.float64), ("fundamental_db",
                               ("fundamental_bin", np.uint32), ("spur_bin", np.uint32), ("harmonics", np.uint32), ("valid", np.uint32),
                               ("reserved", np.uint32)])
 THD_DTYPE = np.dtype([("ch", THD_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("reserved", np.uint32, (3,))])
+
+# struct wf_hip_delay (include/wf_hip.h): the delay finder, by how many frames captured channel 0 lags channel 1 (positive: channel 0
+# is the later one) and whether one of them is inverted, from the floored-PHAT cross-correlation of the newest P frames of both
+# rings, P the largest power of two <= min(fft_size, DELAY_MAX_WINDOW), with the correlation curve around the peak
+DELAY_MAX_WINDOW = 4096  # WF_HIP_DELAY_MAX_WINDOW
+DELAY_CURVE = 65  # WF_HIP_DELAY_CURVE
+DELAY_DTYPE = np.dtype([("delay_frames", np.float64), ("delay_ms", np.float32), ("peak", np.float32), ("corr", np.float32),
+                        ("corr_zero", np.float32), ("ambiguity", np.float32), ("lag", np.int32), ("polarity", np.int32),
+                        ("valid", np.uint32), ("window", np.uint32), ("reserved", np.uint32), ("curve", np.float32, (DELAY_CURVE,)),
+                        ("reserved2", np.uint32, (3,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -455,6 +465,18 @@ class _MeasureReaders:
         With one captured channel ch[1] is all zero"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_THD, first, count, (), THD_DTYPE)
+
+    def delay(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_delay (DELAY_DTYPE): the delay finder, delay_frames / delay_ms by which captured
+        channel 0 lags channel 1 (positive: channel 0 is the later one; lag is its integer part, found within +-window / 4), polarity
+        (-1: one channel is inverted), peak (the floored-PHAT correlation at the lag, signed; close to +-1 for one broadband
+        arrival) against ambiguity (the second peak over the first: near 1 for a tone or unrelated channels, the delay is not to
+        be trusted), corr and corr_zero (the ordinary normalised cross-correlation at the lag and at lag 0), curve (the PHAT
+        correlation at lag - 32 .. lag + 32) and valid (0 for silence in either channel or a window holding a NaN: every field 0),
+        over the newest P frames of both rings as of the pushes issued so far, P = `window` the largest power of two <=
+        min(fft_size, DELAY_MAX_WINDOW); in float64 on the device when read (batches with two captured channels)"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_DELAY, first, count, (), DELAY_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

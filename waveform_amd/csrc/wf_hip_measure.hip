@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS and _THD.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD and _DELAY.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -31,6 +31,7 @@
 #include "wf_sono.hpp"
 #include "wf_bits.hpp"
 #include "wf_thd.hpp"
+#include "wf_delay.hpp"
 
 namespace {
 
@@ -375,6 +376,36 @@ int launch_thd(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the delay finder derives from the configuration alone (wf::host::delay_tables), in one block
+int setup_delay(wf_hip *h)
+{
+    wf_hip::Delay &d = h->delay;
+    const DelayTables t = delay_tables(h->N);
+    d.P = t.P;
+    d.log2p = t.log2p;
+    // (two regions, 128 KB at P = 4096: twice what a workgroup gets without asking, and one workgroup to a CU)
+    const int lds = (int)(2 * WF_HIP_DELAY_MAX_WINDOW * sizeof(double2));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::delay_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return upload(h, &d.d_tab, t.tab); // (pageable memory: staged before the call returns)
+}
+
+// one workgroup per stream over the newest P frames of both captured channels, behind the pushes issued
+int launch_delay(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Delay &d = h->delay;
+    wf::DelayArgs a{};
+    a.rings = ring_view(h); // (two captured channels: why_no_delay)
+    a.out = static_cast<wf_hip_delay *>(d_block) + first;
+    a.window = d.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(d.d_tab + d.P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.P = d.P; // (<= fft_size <= ring_cap)
+    a.log2p = d.log2p;
+    hipLaunchKernelGGL(wf::delay_read_kernel, dim3(count), dim3(wf::WF_DELAY_THREADS), 2 * (size_t)d.P * sizeof(double2), h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -437,6 +468,13 @@ const char *why_no_thd(const wf_hip *h)
     return h->N < 512 ? "the distortion analyser needs a window of at least 512 frames" : nullptr;
 }
 
+const char *why_no_delay(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the inter-channel delay belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->cap_ch != 2 ? "the inter-channel delay needs two captured channels" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -460,6 +498,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_SONO, sizeof(wf_hip_sono), false, why_no_sono, setup_sono, launch_sono},
     {WF_HIP_OUT_BITS, sizeof(wf_hip_bits), false, why_no_bits, setup_bits, launch_bits},
     {WF_HIP_OUT_THD, sizeof(wf_hip_thd), false, why_no_thd, setup_thd, launch_thd},
+    {WF_HIP_OUT_DELAY, sizeof(wf_hip_delay), false, why_no_delay, setup_delay, launch_delay},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output

@@ -231,4 +231,25 @@ ThdTables thd_tables(uint32_t /*sample_rate*/, uint32_t N)
     return t;
 }
 
+// (WF_HIP_DELAY_MAX_WINDOW is a power of two, so the largest one <= min(fft_size, it) is the distortion analyser's, capped)
+static_assert(WF_HIP_DELAY_MAX_WINDOW <= WF_HIP_THD_MAX_WINDOW && (WF_HIP_DELAY_MAX_WINDOW & (WF_HIP_DELAY_MAX_WINDOW - 1)) == 0);
+uint32_t delay_window(uint32_t fft_size) { return std::min<uint32_t>(thd_window(fft_size), WF_HIP_DELAY_MAX_WINDOW); }
+
+DelayTables delay_tables(uint32_t N)
+{
+    DelayTables t;
+    const uint32_t P = delay_window(N);
+    std::vector<double> &tab = t.tab;
+    tab.resize((size_t)2 * P);
+    // (in long double, the argument reduced as an integer first, as thd_tables builds its taper)
+    for(uint32_t i = 0; i < P; ++i)
+        tab[i] = (double)(0.5L - 0.5L * std::cos(TWO_PI_L * (long double)(i % P) / (long double)P));
+    twiddles_from_long_double(tab.data() + P, P);
+    t.P = P;
+    t.log2p = 0;
+    while((1u << t.log2p) < P)
+        ++t.log2p;
+    return t;
+}
+
 } // namespace wf::host

@@ -1,4 +1,4 @@
-// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO and _THD derive from the configuration alone,
+// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD and _DELAY derive from the configuration alone,
 // built on the host (wf_measure_tables.cpp) at the output's first read and uploaded by wf_hip_measure.hip.  Plain C++: no HIP
 // and no handle, so the arithmetic also compiles into a program of its own (tests/test_measure_tables_cpu.py).  The sizes of
 // the constant-Q tables are in wf_cq_sizes.hpp, shared with the kernel (wf_cq.hpp).
@@ -69,5 +69,16 @@ struct ThdTables {
     std::vector<double> tab; // one block [P taper][P / 2 twiddles, re im]
 };
 ThdTables thd_tables(uint32_t sample_rate, uint32_t N);
+
+// the delay finder's window: the largest power of two <= min(fft_size, WF_HIP_DELAY_MAX_WINDOW) (<= ring_cap)
+uint32_t delay_window(uint32_t fft_size);
+
+// WF_HIP_OUT_DELAY (wf_delay.hpp): the periodic Hann taper and the twiddles e^(-j 2 pi m / P) in float64, from long double
+// arguments
+struct DelayTables {
+    uint32_t P = 0, log2p = 0;
+    std::vector<double> tab; // one block [P taper][P / 2 twiddles, re im]
+};
+DelayTables delay_tables(uint32_t N);
 
 } // namespace wf::host
