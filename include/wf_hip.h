@@ -60,6 +60,9 @@
  *   WF_HIP_OUT_DELAY     not in the reference: a delay finder, by how many frames one captured channel lags the other and whether
  *                        one of them is inverted, from the floored-PHAT cross-correlation of every stream's newest window, in
  *                        float64 on the device when read
+ *   WF_HIP_OUT_ONSET     not in the reference: an onset detector, the onset strength of every stream's newest audio in the rings
+ *                        in columns of 256 frames, in total and in three frequency groups, with the onsets picked from it by a
+ *                        fixed rule, anchored to the sample counter, in float64 on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -430,11 +433,15 @@ typedef enum wf_hip_output {
                                   harmonics 2 .. 10, THD, THD+N, SNR, SFDR and the noise floor of the newest P frames in the
                                   rings as of the pushes issued so far, P the largest power of two <= min(wf_hip_fft_size(),
                                   8192) (spectrum and meter batches of at least 512 frames; definition below) */
-    WF_HIP_OUT_DELAY           /* wf_hip_delay                               inter-channel delay: the lag in frames and the
+    WF_HIP_OUT_DELAY,          /* wf_hip_delay                               inter-channel delay: the lag in frames and the
                                   polarity of captured channel 0 against channel 1, with the correlation curve around the peak, of
                                   the newest P frames in the rings as of the pushes issued so far, P the largest power of two <=
                                   min(wf_hip_fft_size(), 4096) (spectrum and meter batches with two captured channels; definition
                                   below) */
+    WF_HIP_OUT_ONSET           /* wf_hip_onset                               onsets: the onset strength of the newest up to 128
+                                  columns of 256 frames in the rings as of the pushes issued so far, in total and in three
+                                  frequency groups, and the onsets picked from them (spectrum and meter batches whose ring holds at
+                                  least 8192 frames; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -1072,6 +1079,84 @@ typedef struct wf_hip_delay {
     float curve[WF_HIP_DELAY_CURVE]; /* R[n0 - 32 + i] */
     uint32_t reserved2[3];   /* 0 */
 } wf_hip_delay;              /* 320 bytes, a multiple of 16 */
+/* ---- onsets (WF_HIP_OUT_ONSET) -----------------------------------------------------------------------------------------------
+ * Per stream, when something starts: a kick, a note, a consonant, a cut.  No other output says so -- the levels say how loud it
+ * is, and the tick's time step (a video frame, about 800 frames of audio, under an 85 ms window) is too coarse to tell.  This
+ * output is the positive change of a compressed band level from one sonogram column to the next (spectral flux), in total and in
+ * three frequency groups, and the onsets picked from each of the four curves by one fixed rule.  sr = cfg.sample_rate; everything is
+ * float64 unless it says otherwise.
+ *   constants      P = WF_HIP_ONSET_WINDOW = 1024 frames, H = WF_HIP_ONSET_HOP = 256 frames, WF_HIP_ONSET_COLUMNS = 128,
+ *                  WF_HIP_ONSET_BANDS = 64, the sonogram's filterbank, in three groups: low = bands 0 .. 15 (62.5 to 250 Hz),
+ *                  mid = 16 .. 39 (250 Hz to 2 kHz), high = 40 .. 63 (2 to 16 kHz).
+ *   columns        the sonogram's: wpos is the stream's uint32 write counter as of the pushes issued so far, with the rules of
+ *                  WF_HIP_OUT_SIGNAL (every push counts whatever its path, the A/V-sync delay is not applied, the zeros of create
+ *                  and wf_hip_reset count as samples, hidden and paused streams are read like any other); newest = wpos / H, and
+ *                  spectral column n covers counter frames [n H - P, n H) at ring positions masked by the capacity.  The
+ *                  arithmetic is uint32 and wraps with the counter.  Ts = min(129, (ring_cap - P) / H) spectral columns are
+ *                  always in the ring and give T = Ts - 1 strength columns: 27 for a ring of 8192 frames, 59 for 16384, 123 for
+ *                  32768, 128 from 65536 up (wf_hip_create's ring_frames).  Every array is indexed by age: age a is column
+ *                  newest - a; ages >= T read 0 with flags 0.
+ *   transform      exactly the sonogram's: the periodic Hann window, both captured channels through one complex transform and
+ *                  separated from Z[k] and conj Z[P - k], the 64 eighth-octave bands from 62.5 Hz with the same overlap weights.
+ *                  The band power is B[n][b] = B_0[n][b] + B_1[n][b], the sum over the captured channels; there is no
+ *                  dead-channel rule here.
+ *   level          a[n][b] = sqrt(B[n][b] * 32 / (3 P^2 capture_channels)), the rms amplitude a sine would need, and
+ *                  S[n][b] = log1p(100 a[n][b]) / ln 10: linear below the knee at -40 dBFS, logarithmic above it, so that neither
+ *                  the noise floor's flutter nor level alone decides.  A column of zeros gives S = 0 exactly.
+ *   strength       d[n][b] = max(S[n][b] - S[n-1][b], 0); low, mid and high are the sums of d over the group's bands, each in
+ *                  ascending band order, and strength[n] = (low + mid) + high.  Each of the four is rounded to float32 once.
+ *   picking        on the float32 values alone, by comparisons, float64 additions and one division -- no product, so that no
+ *                  compiler can contract anything -- and with the same constants for the total and for each group.  Column n is
+ *                  decided when the columns n - 16 .. n + 3 are all among the T returned: ages 3 .. T - 17.  A decided column
+ *                  of the curve o is an onset if and only if
+ *                    o[n] >  o[m] for m = n - 6 .. n - 1,
+ *                    o[n] >= o[m] for m = n + 1 .. n + 3, and
+ *                    o[n] >= mean + 2.0 with mean = (o[n - 16] + ... + o[n + 3]) / 20, summed oldest first in float64.
+ *                  A decision depends on 20 columns anchored to the counter: once decided, a column's flags never change, and
+ *                  read the same bits at any later read while the column is in view.  With the smallest ring ages 3 .. 10 are
+ *                  decided, 2048 frames: a reader at 24 Hz or faster sees every column decided.  The latency is 3 hops, 16 ms at
+ *                  48 kHz.
+ *   flags          bit 0: onset of the total; bits 1, 2, 3: onset of low, mid, high; bit 7: decided.
+ *   summary        columns = T, newest, decided_first = 3, decided_end = T - 16 (0 if no column is decided), window = P,
+ *                  hop = H; onsets = the decided columns in view with bit 0; last_age = the age of the newest of them (0xFFFFFFFF
+ *                  if there is none, and last_frame and last_strength are then 0), last_frame = n H - 384 of that column (uint32,
+ *                  wraps with the counter): the column's end less 3 P / 8, where the start of the event lies to within about a
+ *                  hop; last_strength = its strength.
+ *   determinism    no atomics, and every sum runs in a fixed order: the same column reads bit-identically across reads, push
+ *                  paths, slices and shards for as long as its frames and its predecessor's are in the ring.
+ * The constants -- the knee 100, the margin 2.0, the windows 6 / 3 / 16 -- were chosen with a numpy prototype on synthetic audio:
+ * over 4 s each they find every event of 60 Hz kicks over noise at -40 dB, of noise bursts over noise at -30 dB and of legato note
+ * changes at equal level, and flag nothing on stationary noise at -20 and -60 dBFS or on a steady sine.  They are definitional, as
+ * a library's defaults are, and have not been tuned on recorded music.  Tempo, smoothing and any longer history are the host's:
+ * `newest` makes appending exact.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 256 threads per
+ * stream, one wavefront per spectral column, float64 transforms in LDS), into a block the first read allocates together with its
+ * tables: a handle that never reads it allocates and launches nothing new, nothing is added to the tick, and no state is kept
+ * between reads.  Cost on an MI355X, 4096 stereo streams at FFT 4096 read into page-locked memory (9.18 MB back): 0.86 ms with the
+ * default ring (T = 27) against 4.72 ms for copying the 268.4 MB of both rings that the columns span to the host, 3.29 ms with
+ * ring_frames = 65536 (T = 128) against 19.64 ms for its 1115.7 MB.  The kernel's own time without its copy is unmeasured
+ * (tools/onset_bench.py, profiles/onset_kernel_stats.json; INTEGRATION.md, "Onsets").
+ * Spectrum and meter batches with one or two captured channels and any FFT size are served; on waveform batches and on handles
+ * whose ring holds fewer than 8192 frames (no column would be decided) wf_hip_read returns WF_HIP_ERR_INVALID and
+ * wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_ONSET_WINDOW 1024
+#define WF_HIP_ONSET_HOP 256
+#define WF_HIP_ONSET_COLUMNS 128
+#define WF_HIP_ONSET_BANDS 64
+typedef struct wf_hip_onset {
+    float strength[WF_HIP_ONSET_COLUMNS];  /* [age] (low + mid) + high */
+    float group[3][WF_HIP_ONSET_COLUMNS];  /* [low, mid, high][age] */
+    uint8_t flags[WF_HIP_ONSET_COLUMNS];   /* [age] */
+    uint32_t columns;        /* T */
+    uint32_t newest;         /* wpos / H: the absolute index of the column of age 0 */
+    uint32_t decided_first, decided_end; /* the ages [3, T - 16) carry bit 7 */
+    uint32_t window, hop;    /* P, H */
+    uint32_t onsets;         /* decided columns in view with bit 0 */
+    uint32_t last_age;       /* of the newest of them; 0xFFFFFFFF: none */
+    uint32_t last_frame;     /* its counter position, (newest - last_age) H - 384 */
+    float last_strength;
+    uint32_t reserved[6];    /* 0 */
+} wf_hip_onset;              /* 2240 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -59,7 +59,7 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY = range(23)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET = range(24)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -222,6 +222,22 @@ DELAY_DTYPE = np.dtype([("delay_frames", np.float64), ("delay_ms", np.float32), 
                         ("corr_zero", np.float32), ("ambiguity", np.float32), ("lag", np.int32), ("polarity", np.int32),
                         ("valid", np.uint32), ("window", np.uint32), ("reserved", np.uint32), ("curve", np.float32, (DELAY_CURVE,)),
                         ("reserved2", np.uint32, (3,))])
+
+# struct wf_hip_onset (include/wf_hip.h): the onset detector, strength[age] and group[low, mid, high][age] = the positive change of
+# the compressed level in the sonogram's 64 bands between the columns that end at counter frames (newest - age - 1) and
+# (newest - age) * ONSET_HOP, for age < columns; flags[age] (ONSET_FLAG_*) say which of the four curves has an onset there and
+# whether the column is decided; 0 beyond
+ONSET_WINDOW = 1024  # WF_HIP_ONSET_WINDOW
+ONSET_HOP = 256  # WF_HIP_ONSET_HOP
+ONSET_COLUMNS = 128  # WF_HIP_ONSET_COLUMNS
+ONSET_BANDS = 64  # WF_HIP_ONSET_BANDS
+ONSET_FLAG_TOTAL, ONSET_FLAG_LOW, ONSET_FLAG_MID, ONSET_FLAG_HIGH, ONSET_FLAG_DECIDED = 1, 2, 4, 8, 0x80
+ONSET_NONE = 0xFFFFFFFF  # last_age when no decided column in view is an onset
+ONSET_DTYPE = np.dtype([("strength", np.float32, (ONSET_COLUMNS,)), ("group", np.float32, (3, ONSET_COLUMNS)),
+                        ("flags", np.uint8, (ONSET_COLUMNS,)), ("columns", np.uint32), ("newest", np.uint32),
+                        ("decided_first", np.uint32), ("decided_end", np.uint32), ("window", np.uint32), ("hop", np.uint32),
+                        ("onsets", np.uint32), ("last_age", np.uint32), ("last_frame", np.uint32), ("last_strength", np.float32),
+                        ("reserved", np.uint32, (6,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -477,6 +493,21 @@ class _MeasureReaders:
         min(fft_size, DELAY_MAX_WINDOW); in float64 on the device when read (batches with two captured channels)"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_DELAY, first, count, (), DELAY_DTYPE)
+
+    def onset(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_onset (ONSET_DTYPE): the onset detector.  strength[age] and group[g][age] (g = low,
+        mid, high: 62.5 to 250 Hz, to 2 kHz, to 16 kHz) are the onset strength -- the positive change of the compressed level in
+        the sonogram's bands from one column to the next -- of the column that ends at frame (newest - age) * ONSET_HOP of the
+        stream's sample counter, for age < columns (which the ring decides: 27 by default, 128 from ring_frames = 65536 up); 0
+        beyond.  flags[age]: ONSET_FLAG_TOTAL / _LOW / _MID / _HIGH = an onset of that curve (a strict maximum of the 6 columns
+        before, no less than the 3 after, and 2.0 above the mean of the 20 around it), ONSET_FLAG_DECIDED = the column's 20 columns
+        are all in view (ages decided_first .. decided_end - 1); once decided a column's flags never change.  onsets counts the
+        decided onsets of the total in view; last_age (ONSET_NONE: none), last_frame (the counter position where it started, to
+        about a hop) and last_strength describe the newest.  Columns are anchored to the counter: (newest - newest of the last
+        read) mod 2^24 columns are new.  In float64 on the device when read, from the rings as of the pushes issued so far
+        (batches whose ring holds at least 8192 frames)"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_ONSET, first, count, (), ONSET_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

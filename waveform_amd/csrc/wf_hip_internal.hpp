@@ -133,7 +133,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    static constexpr int N_MEASURES = 13;
+    static constexpr int N_MEASURES = 14;
     char *d_measure[N_MEASURES] = {};
     bool measure_ready[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
@@ -179,6 +179,11 @@ struct wf_hip {
         double *d_tab = nullptr;                  // [P] taper, [P / 2][2] twiddles
         uint32_t P = 0, log2p = 0;                // the window: a power of two
     } delay;
+    // what WF_HIP_OUT_ONSET derives from the sample rate and the ring (setup_onset, at its first read: wf::host::sono_tables; wf_onset.hpp)
+    struct Onset {
+        double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_ONSET_BANDS + 1] band edges in bins of P
+        uint32_t spectral = 0;                    // Ts = T + 1 spectral columns
+    } onset;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

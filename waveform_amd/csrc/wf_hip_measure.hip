@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD and _DELAY.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY and _ONSET.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -32,6 +32,7 @@
 #include "wf_bits.hpp"
 #include "wf_thd.hpp"
 #include "wf_delay.hpp"
+#include "wf_onset.hpp"
 
 namespace {
 
@@ -406,6 +407,43 @@ int launch_delay(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the onset detector derives from the sample rate and the ring alone: the sonogram's tables (wf::host::sono_tables), in one block
+int setup_onset(wf_hip *h)
+{
+    wf_hip::Onset &o = h->onset;
+    const SonoTables t = sono_tables(h->cfg.sample_rate, h->ring_cap);
+    // Ts spectral columns, T = Ts - 1 strengths: Ts H + P <= ring_cap, so the oldest is in the ring wherever in a hop the counter stands
+    o.spectral = std::min<uint32_t>(WF_HIP_ONSET_COLUMNS + 1, (h->ring_cap - WF_HIP_ONSET_WINDOW) / WF_HIP_ONSET_HOP); // (>= 28: why_no_onset)
+    // (about 69 KB, four columns' transforms, the round's levels and the entry's strengths: more than a workgroup gets without
+    // asking, and two workgroups to a CU)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::onset_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::WF_ONSET_LDS_BYTES));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::onset_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::WF_ONSET_LDS_BYTES));
+    return upload(h, &o.d_tab, t.tab); // (pageable memory: staged before the call returns)
+}
+
+// one workgroup per stream, one wavefront per spectral column in rounds of four, over the newest Ts columns of every captured
+// channel's ring, behind the pushes issued
+int launch_onset(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Onset &o = h->onset;
+    constexpr uint32_t P = WF_HIP_ONSET_WINDOW;
+    wf::OnsetArgs a{};
+    a.rings = ring_view(h);
+    a.out = static_cast<wf_hip_onset *>(d_block) + first;
+    a.window = o.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(o.d_tab + P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.edges = o.d_tab + 2 * (size_t)P;
+    a.first = first;
+    a.spectral = o.spectral;
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::onset_read_kernel<2>, dim3(count), dim3(wf::WF_ONSET_THREADS), wf::WF_ONSET_LDS_BYTES, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::onset_read_kernel<1>, dim3(count), dim3(wf::WF_ONSET_THREADS), wf::WF_ONSET_LDS_BYTES, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -475,6 +513,13 @@ const char *why_no_delay(const wf_hip *h)
     return h->cap_ch != 2 ? "the inter-channel delay needs two captured channels" : nullptr;
 }
 
+const char *why_no_onset(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the onset detector belongs to spectrum and meter batches";
+    return h->ring_cap < 8192 ? "the onset detector needs a ring of at least 8192 frames (wf_hip_create's ring_frames)" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -499,6 +544,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_BITS, sizeof(wf_hip_bits), false, why_no_bits, setup_bits, launch_bits},
     {WF_HIP_OUT_THD, sizeof(wf_hip_thd), false, why_no_thd, setup_thd, launch_thd},
     {WF_HIP_OUT_DELAY, sizeof(wf_hip_delay), false, why_no_delay, setup_delay, launch_delay},
+    {WF_HIP_OUT_ONSET, sizeof(wf_hip_onset), false, why_no_onset, setup_onset, launch_onset},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output

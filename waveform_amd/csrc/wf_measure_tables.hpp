@@ -50,7 +50,8 @@ CqTables cq_tables(uint32_t sample_rate, uint32_t ring_cap);
 
 // WF_HIP_OUT_SONO (wf_sono.hpp), P = WF_HIP_SONO_WINDOW: the periodic Hann window and the twiddles e^(-j 2 pi m / P) in float64,
 // from long double arguments; the edges 62.5 * 2^(j / 8) Hz of the 64 bands in bins of P; how many columns the ring holds
-// (T = min(WF_HIP_SONO_COLUMNS, (ring_cap - P) / H), 0 for a ring that holds no column) and which bands the spectrum covers
+// (T = min(WF_HIP_SONO_COLUMNS, (ring_cap - P) / H), 0 for a ring that holds no column) and which bands the spectrum covers.
+// WF_HIP_OUT_ONSET (wf_onset.hpp) runs on the same columns and takes `tab` as it is; it counts its own columns (setup_onset)
 struct SonoTables {
     uint32_t columns = 0;
     uint32_t first_covered = 0, end_covered = 0;
