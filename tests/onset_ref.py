@@ -62,7 +62,11 @@ def flux(s):
 
 def strengths(hist, wpos, sr, ring_cap):
     """hist: float32 [streams, channels, L], the frames of counter positions [wpos - L, wpos), the newest last (what came before
-    reads as the zeros of create).  float32 [streams, 4, T], age 0 first"""
+    reads as the zeros of create).  float32 [streams, 4, T], age 0 first.  wpos: one counter for the whole batch, or [streams] of
+    them, each stream's history ending at its own"""
+    if np.ndim(wpos):
+        assert len(wpos) == len(hist)
+        return np.concatenate([strengths(hist[s:s + 1], int(w), sr, ring_cap) for s, w in enumerate(wpos)])
     hist = np.asarray(hist, np.float32).astype(np.float64)
     streams, ch, length = hist.shape
     ts = spectral(ring_cap)
@@ -131,14 +135,14 @@ def margins(o):
 
 
 def entries(o, wpos):
-    """[streams] of wf_hip_onset from the float32 strengths o [streams, 4, T] by age"""
+    """[streams] of wf_hip_onset from the float32 strengths o [streams, 4, T] by age (wpos: a scalar or [streams])"""
     o = np.asarray(o, np.float32)
     streams, _, t = o.shape
     out = np.zeros(streams, ONSET_DTYPE)
     out["strength"][:, :t] = o[:, 0]
     out["group"][:, :, :t] = o[:, 1:]
     out["flags"][:, :t] = pick(o)
-    newest = (int(wpos) % (1 << 32)) // H
+    newest = np.broadcast_to((np.asarray(wpos).astype(np.int64) % (1 << 32)) // H, (streams,))
     out["columns"], out["newest"], out["window"], out["hop"] = t, newest, P, H
     out["decided_first"], out["decided_end"] = decided(t)
     out["last_age"] = NONE
@@ -147,7 +151,7 @@ def entries(o, wpos):
         out["onsets"][s] = len(hit)
         if len(hit):
             out["last_age"][s] = hit[0]
-            out["last_frame"][s] = ((newest - int(hit[0])) * H - 3 * P // 8) % (1 << 32)
+            out["last_frame"][s] = ((int(newest[s]) - int(hit[0])) * H - 3 * P // 8) % (1 << 32)
             out["last_strength"][s] = o[s, 0, hit[0]]
     return out
 

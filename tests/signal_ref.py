@@ -65,3 +65,33 @@ def signal(window):
         out["mid_db"] = _db((((l + r) / 2) ** 2).sum(axis=1) / W, 10.0)
         out["side_db"] = _db((((l - r) / 2) ** 2).sum(axis=1) / W, 10.0)
     return out
+
+
+DB_TOL = 1e-4  # dB, of rms_db, balance_db, mid_db and side_db
+
+
+def mismatches(got, want):
+    """(field, stream index, got, want) of everything in `got` ([streams] of wf_hip_signal) beyond the bound of `want` (signal()'s
+    dict): rms_db, balance_db, mid_db and side_db within 1e-4 dB, infinities equal; peak_db (the maximum is one of the samples) and
+    clipped exact; dc within 1e-7 + 1e-6 |want|; correlation within 1e-6"""
+    bad = []
+
+    def note(name, ok, g, w):
+        bad.extend((name, tuple(i), np.asarray(g)[tuple(i)].item(), np.asarray(w)[tuple(i)].item()) for i in np.argwhere(~np.asarray(ok))[:5])
+
+    def db_close(g, w):
+        g, w = np.asarray(g, np.float64), np.asarray(w, np.float64)
+        with np.errstate(invalid="ignore"):
+            return np.where(np.isinf(w), g == w, np.abs(g - w) <= DB_TOL)
+
+    ch = got["ch"]
+    note("ch.rms_db", db_close(ch["rms_db"], want["rms_db"]), ch["rms_db"], want["rms_db"])
+    note("ch.peak_db", ch["peak_db"] == want["peak_db"].astype(np.float32), ch["peak_db"], want["peak_db"])
+    note("ch.clipped", ch["clipped"] == want["clipped"], ch["clipped"], want["clipped"])
+    d, w = ch["dc"].astype(np.float64), want["dc"]
+    note("ch.dc", np.abs(d - w) <= 1e-7 + 1e-6 * np.abs(w), d, w)
+    c = got["correlation"].astype(np.float64)
+    note("correlation", np.abs(c - want["correlation"]) <= 1e-6, c, want["correlation"])
+    for f in ("balance_db", "mid_db", "side_db"):
+        note(f, db_close(got[f], want[f]), got[f], want[f])
+    return bad

@@ -47,7 +47,10 @@ def hann():
 def band_powers(hist, wpos, sr, ring_cap):
     """hist: float32 [streams, channels, L], the frames of counter positions [wpos - L, wpos), the newest last (what came before
     reads as the zeros of create).  B: float64 [streams, 2, T, 64], age 0 first, the dead-channel rule applied, channel 1 of a
-    capture of one channel 0"""
+    capture of one channel 0.  wpos: one counter for the whole batch, or [streams] of them, each stream's history ending at its own"""
+    if np.ndim(wpos):
+        assert len(wpos) == len(hist)
+        return np.concatenate([band_powers(hist[s:s + 1], int(w), sr, ring_cap) for s, w in enumerate(wpos)])
     hist = np.asarray(hist, np.float32).astype(np.float64)
     streams, ch, length = hist.shape
     t = columns(ring_cap)
@@ -82,7 +85,7 @@ def sono(hist, wpos, sr, ring_cap):
     out["db"] = -np.inf
     out["db"][:, :, :b.shape[2]] = to_db(b)
     out["columns"] = b.shape[2]
-    out["newest"] = (int(wpos) % (1 << 32)) // H
+    out["newest"] = (np.asarray(wpos).astype(np.int64) % (1 << 32)) // H  # (a scalar or [streams])
     out["first_covered"], out["end_covered"] = covered(sr)
     out["window"], out["hop"] = P, H
     return out

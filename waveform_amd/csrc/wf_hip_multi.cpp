@@ -660,6 +660,10 @@ int hand_over_mirrors(wf_hip_multi *m, const Overrides &ov)
     const bool direct = decide_direct(m, ov);
     if(!ov.mirrors && !direct)
         return WF_HIP_OK;
+    // a level-meter or waveform batch has a bar per channel to gather, but its tick kernel writes no further buffers
+    // (wf_hip_set_bars_mirrors: WF_HIP_ERR_INVALID, not UNSUPPORTED): such a group keeps the copy behind the tick as well
+    if(m->cfg.meter || m->cfg.waveform)
+        return WF_HIP_OK;
     return run_all(m, [m, direct](uint32_t i) {
         Shard &s = *m->shard[i];
         s.direct = direct; // (tick_target answers for the set being handed over)
