@@ -63,6 +63,10 @@
  *   WF_HIP_OUT_ONSET     not in the reference: an onset detector, the onset strength of every stream's newest audio in the rings
  *                        in columns of 256 frames, in total and in three frequency groups, with the onsets picked from it by a
  *                        fixed rule, anchored to the sample counter, in float64 on the device when read
+ *   WF_HIP_OUT_XFER      not in the reference: a dual-channel analyser's transfer function, the gain, phase and coherence against
+ *                        frequency of one captured channel against the other with the programme as the stimulus, averaged over the
+ *                        13 to 32 half-overlapped segments in every stream's rings, anchored to the sample counter, in float64 on
+ *                        the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -438,10 +442,15 @@ typedef enum wf_hip_output {
                                   the newest P frames in the rings as of the pushes issued so far, P the largest power of two <=
                                   min(wf_hip_fft_size(), 4096) (spectrum and meter batches with two captured channels; definition
                                   below) */
-    WF_HIP_OUT_ONSET           /* wf_hip_onset                               onsets: the onset strength of the newest up to 128
+    WF_HIP_OUT_ONSET,          /* wf_hip_onset                               onsets: the onset strength of the newest up to 128
                                   columns of 256 frames in the rings as of the pushes issued so far, in total and in three
                                   frequency groups, and the onsets picked from them (spectrum and meter batches whose ring holds at
                                   least 8192 frames; definition below) */
+    WF_HIP_OUT_XFER            /* wf_hip_xfer                                transfer function: gain, phase and coherence per bin
+                                  of captured channel 0 (measured) against channel 1 (reference), averaged over K segments of P
+                                  frames in the rings as of the pushes issued so far, with the integer delay between them found
+                                  and taken out (spectrum and meter batches of at least 256 frames with two captured channels;
+                                  definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -1157,6 +1166,97 @@ typedef struct wf_hip_onset {
     float last_strength;
     uint32_t reserved[6];    /* 0 */
 } wf_hip_onset;              /* 2240 bytes, a multiple of 16 */
+/* ---- transfer function (WF_HIP_OUT_XFER) ---------------------------------------------------------------------------------------
+ * Per stream, the third instrument of a dual-channel analyser: the frequency response between the two captured channels with the
+ * programme itself as the stimulus -- magnitude, phase and coherence against frequency, what Smaart, REW and ARTA call the transfer
+ * function: a microphone chain against its dry feed, a return against its send.  No other output can stand in for it:
+ * WF_HIP_OUT_STEREO reads one window, so its coherence means something only across a band, and it reports no gain and no phase of a
+ * system; WF_HIP_OUT_DELAY reads one window and reports one number.  A transfer function needs an average over several segments, and
+ * the ring holds them, so nothing is kept between reads.  W = wf_hip_fft_size(), R = wf_hip_ring_frames(), sr = cfg.sample_rate;
+ * everything is float64 unless it says otherwise.
+ *   roles          captured channel 1 is the reference (what went in), channel 0 the measured signal (what came out): the
+ *                  convention of WF_HIP_OUT_DELAY, where a positive lag means that channel 0 is the later one, x_0(t) = x_1(t - d),
+ *                  a causal system.  The other direction costs the host nothing: H_01[k] = coherence[k] / H_10[k].
+ *   segments       P = the largest power of two <= min(W, WF_HIP_XFER_MAX_WINDOW = 2048, R / 8); M = P / 2 bins, the hop H = P / 2
+ *                  (50 % overlap) and L = P / 4, the range of lags.  K = min(WF_HIP_XFER_MAX_SEGMENTS = 32, 2 R / P - 3) segments,
+ *                  at least 13.  They are anchored to the stream's uint32 write counter wpos as the sonogram's columns are:
+ *                  E = wpos - (wpos mod H) - L, and segment a (its age, 0 the newest) of channel 0 covers the counter frames
+ *                  E - a H - P .. E - a H - 1, in uint32 arithmetic that wraps with the counter, at ring positions masked by the
+ *                  capacity.  The span is the frames E - (K - 1) H - P - L .. E + L - 1 of both channels, the segments with the L
+ *                  frames on either side that the alignment may reach into: (K - 1) H + P + 2 L frames, and with the up to H - 1
+ *                  frames behind the anchor at most R - 1, so it is in the ring wherever in a hop the counter stands.  The rules
+ *                  are WF_HIP_OUT_SIGNAL's: every push issued before the read counts whatever its path, the A/V-sync delay is not
+ *                  applied, the zeros of create and wf_hip_reset count as samples, hidden and paused streams are read like any
+ *                  other.
+ *   taper          w[i] = 0.5 - 0.5 cos(2 pi i / P), the periodic Hann window, the host-made table of WF_HIP_OUT_DELAY at this P.
+ *   spectra        for segment a and a shift n, X_0,a = DFT_P(w x_0) over the segment's frames and X_1,a^(n) = DFT_P(w x_1(. - n)):
+ *                  channel 1 is read n frames earlier.  The kernel is e^(-j 2 pi i k / P); on the device both come out of one
+ *                  complex transform of w (x_0 + j x_1^(n)), separated as WF_HIP_OUT_STEREO does it.  Only the bins 1 <= k < M are
+ *                  used.  Two properties of separate transforms are kept to the bit: a segment of a channel that is all +-0 has the
+ *                  spectrum 0, and a segment whose two channels are the same bits has X_0 = X_1 (the device takes such a
+ *                  segment's spectra from Z[k] alone instead of separating them).  A muted measured channel therefore reads
+ *                  Syy = 0, and dual mono reads gain_db 0, phase 0 and coherence 1, exactly.  With Sxx[k] = sum_a |X_1,a^(n)[k]|^2, Syy[k] = sum_a |X_0,a[k]|^2 and
+ *                  Sxy[k] = sum_a conj(X_1,a^(n)[k]) X_0,a[k], every sum over the segments oldest first:
+ *   pass 1         n = 0.  G[k] = Sxy[k] (which is sum_a X_0,a conj X_1,a), g = max_k |G[k]|, and the floored PHAT weighting of
+ *                  WF_HIP_OUT_DELAY, A[k] = G[k] / max(|G[k]|, b g) with b = 1e-3; r[n] = (1 / (M - 1)) sum_k Re(A[k] e^(j 2 pi k n
+ *                  / P)).  n0 = the argmax of |r[n]| over -L <= n <= L: the scan runs from n = -L upwards and only a strictly
+ *                  greater value wins.  lag_peak = r[n0].  Where g is 0 -- no cross power in any bin -- n0 = 0 and lag_peak = 0.
+ *   pass 2         n = n0 (where n0 is 0 the sums of pass 1 are the result, bit for bit).  Hk = Sxy[k] / Sxx[k] and
+ *                  coherence[k] = min(|Sxy[k]|^2 / (Sxx[k] Syy[k]), 1).
+ *   fields         each float32 field is rounded once from float64.
+ *                    gain_db[k]     10 log10(|Sxy[k]|^2 / Sxx[k]^2)
+ *                    phase[k]       atan2(Im Hk, Re Hk): the system's phase with `lag` frames of delay taken out; a host that
+ *                                   wants the raw one adds -2 pi k lag / P
+ *                    coherence[k]
+ *                    valid, window = P, hop = H, segments = K, lag = n0 (int32), newest = (E + L) / H = wpos / H, lag_peak,
+ *                    mean_coherence = sum_k Sxx[k] coherence[k] / sum_k Sxx[k] over the live bins (0 where there is none); the
+ *                    reserved words are 0.  Bin k lies at k sr / P Hz.
+ *   dead bins      a bin with Sxx[k] <= WF_HIP_STEREO_DEAD_RATIO max_k Sxx is dead: the reference has nothing there, and what is
+ *                  left is the transform's rounding.  It reads gain_db = 0, phase = 0, coherence = 0.  A live bin with Syy[k] == 0
+ *                  reads gain_db = -INFINITY, phase = 0, coherence = 0.  Index 0 and the indices M .. WF_HIP_XFER_BINS - 1 are
+ *                  written as zeros on every read.
+ *   validity       valid = 0, and everything but window, hop and segments 0, when the span of either channel is all +-0 or when
+ *                  the span of either channel holds a NaN or an infinity.  valid = 1 says "computed", not "reliable": reliability
+ *                  is `coherence`.
+ *   determinism    no atomics, and every sum and every max runs in an order that follows from P and K alone: the same ring
+ *                  contents read bit-identically across push paths, repeated reads, slices and shards -- and, because of the
+ *                  anchor, so do any two reads within one hop.
+ * Limits: a delay beyond L is not found and biases the coherence down by about (1 - |d| / P)^2; a fractional delay stays in `phase`
+ * as a linear slope; with K = 13 segments two independent channels read a coherence near 1 / K and not 0 -- the half overlap makes
+ * it somewhat more: the numpy restatement reads a mean of 0.081 at K = 13 and 0.033 at K = 32 on white noise (tests/test_xfer_cpu.py).
+ * The impulse response, smoothing to fractional octaves and averaging across reads are the host's; `newest` says when a read
+ * brings new segments.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 256 threads per
+ * stream; K float64 transforms of P points per pass, one behind the other in one LDS region, every thread keeping the running sums
+ * of its own bins in registers; the lag search as one more transform of the weighted cross spectrum held in half a region beside
+ * it: 48 KB at the cap, two workgroups to a CU; a second pass of K transforms only where the lag is not 0), into a block the first read allocates together
+ * with its tables: a handle that never reads it allocates and launches nothing new, nothing is added to the tick, and no state is
+ * kept between reads.
+ * Cost on an MI355X, 4096 stereo streams at FFT 4096 read into page-locked memory (50.53 MB back): 1.88 ms with the default ring
+ * (P = 1024, K = 13) where the lag is not 0 and both passes run, 1.50 ms where it is 0, against 4.71 ms for copying the 268.4 MB of
+ * both rings that the segments span to the host; 4.85 and 3.28 ms with ring_frames = 65536 (P = 2048, K = 32) against 22.9 and 20.6
+ * ms for its 1174.4 MB.  Into a fresh pageable numpy array (the Python reader) a read takes 5.14 and 8.42 ms, most of it the copy of
+ * the 12 KB entries.  The kernel's own time without its copy is unmeasured (tools/xfer_bench.py, profiles/xfer_kernel_stats.json;
+ * INTEGRATION.md, "Transfer function").
+ * Spectrum and meter batches with two captured channels and W >= 256 are served; with one captured channel, with W < 256, with a
+ * ring under 512 frames (W = 256 and ring_frames <= 256: P would fall under the transform's 64 points) and on waveform batches
+ * wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_XFER_MAX_WINDOW 2048
+#define WF_HIP_XFER_MAX_SEGMENTS 32
+#define WF_HIP_XFER_BINS 1024
+typedef struct wf_hip_xfer {
+    uint32_t valid;
+    uint32_t window, hop;    /* P, H */
+    uint32_t segments;       /* K */
+    int32_t lag;             /* n0: by how many frames channel 0 is the later one, taken out of `phase` */
+    uint32_t newest;         /* wpos / H: the absolute index of the newest segment's anchor */
+    float lag_peak;          /* r[n0], signed */
+    float mean_coherence;
+    uint32_t reserved[4];    /* 0 */
+    float gain_db[WF_HIP_XFER_BINS];   /* [k], 1 <= k < P / 2; 0 elsewhere */
+    float phase[WF_HIP_XFER_BINS];     /* radians */
+    float coherence[WF_HIP_XFER_BINS];
+} wf_hip_xfer;               /* 12336 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

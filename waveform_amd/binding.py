@@ -59,7 +59,8 @@ TICK_NO_DECIBELS = 1
 
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
-    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET = range(24)
+    OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET, \
+    OUT_XFER = range(25)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -238,6 +239,17 @@ ONSET_DTYPE = np.dtype([("strength", np.float32, (ONSET_COLUMNS,)), ("group", np
                         ("decided_first", np.uint32), ("decided_end", np.uint32), ("window", np.uint32), ("hop", np.uint32),
                         ("onsets", np.uint32), ("last_age", np.uint32), ("last_frame", np.uint32), ("last_strength", np.float32),
                         ("reserved", np.uint32, (6,))])
+
+# struct wf_hip_xfer (include/wf_hip.h): the transfer function of captured channel 0 (measured) against channel 1 (reference),
+# gain_db[k], phase[k] and coherence[k] at bin k (k sample_rate / window Hz, 1 <= k < window / 2; 0 elsewhere), averaged over
+# `segments` half-overlapped segments of `window` frames anchored to the sample counter, with `lag` frames of delay taken out
+XFER_MAX_WINDOW = 2048  # WF_HIP_XFER_MAX_WINDOW
+XFER_MAX_SEGMENTS = 32  # WF_HIP_XFER_MAX_SEGMENTS
+XFER_BINS = 1024  # WF_HIP_XFER_BINS
+XFER_DTYPE = np.dtype([("valid", np.uint32), ("window", np.uint32), ("hop", np.uint32), ("segments", np.uint32), ("lag", np.int32),
+                       ("newest", np.uint32), ("lag_peak", np.float32), ("mean_coherence", np.float32), ("reserved", np.uint32, (4,)),
+                       ("gain_db", np.float32, (XFER_BINS,)), ("phase", np.float32, (XFER_BINS,)),
+                       ("coherence", np.float32, (XFER_BINS,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -508,6 +520,22 @@ class _MeasureReaders:
         (batches whose ring holds at least 8192 frames)"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_ONSET, first, count, (), ONSET_DTYPE)
+
+    def xfer(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_xfer (XFER_DTYPE): the transfer function of a dual-channel analyser with the programme
+        as the stimulus, captured channel 0 (measured, what came out) against channel 1 (reference, what went in).  gain_db[k],
+        phase[k] (radians, with `lag` frames of delay taken out: add -2 pi k lag / window for the raw one) and coherence[k] (0 .. 1:
+        how far the reading at that bin is to be trusted) at bin k = k sample_rate / window Hz for 1 <= k < window / 2, 0 elsewhere;
+        averaged over `segments` (13 .. 32, the ring decides) segments of `window` frames (the largest power of two <=
+        min(fft_size, XFER_MAX_WINDOW, ring_frames / 8)) `hop` = window / 2 frames apart and anchored to the stream's sample counter:
+        reads within one hop are bit-identical, and `newest` = the counter / hop says when a read brings a new segment.  lag is the
+        delay of channel 0 behind channel 1 in whole frames, found within +-window / 4 by the floored PHAT of the averaged cross
+        spectrum, lag_peak its correlation there; mean_coherence is weighted by the reference's power.  A bin where the reference
+        has nothing reads 0 / 0 / 0; valid = 0 (silence in either channel or a NaN in the span) leaves everything but window, hop
+        and segments 0.  In float64 on the device when read, from the rings as of the pushes issued so far (batches with two
+        captured channels and fft_size >= 256)"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_XFER, first, count, (), XFER_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

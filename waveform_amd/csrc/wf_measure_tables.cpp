@@ -252,4 +252,12 @@ DelayTables delay_tables(uint32_t N)
     return t;
 }
 
+static_assert(WF_HIP_XFER_MAX_WINDOW <= WF_HIP_DELAY_MAX_WINDOW && (WF_HIP_XFER_MAX_WINDOW & (WF_HIP_XFER_MAX_WINDOW - 1)) == 0);
+uint32_t xfer_window(uint32_t fft_size, uint32_t ring_cap)
+{
+    return delay_window(std::min<uint32_t>(std::min<uint32_t>(fft_size, WF_HIP_XFER_MAX_WINDOW), ring_cap / 8));
+}
+
+uint32_t xfer_segments(uint32_t P, uint32_t ring_cap) { return std::min<uint32_t>(WF_HIP_XFER_MAX_SEGMENTS, 2 * ring_cap / P - 3); }
+
 } // namespace wf::host
