@@ -67,6 +67,10 @@
  *                        frequency of one captured channel against the other with the programme as the stimulus, averaged over the
  *                        13 to 32 half-overlapped segments in every stream's rings, anchored to the sample counter, in float64 on
  *                        the device when read
+ *   WF_HIP_OUT_IMPULSE   not in the reference: the same analyser's response against time, the impulse response of one captured
+ *                        channel against the other from the regularised average of the same segments, its energy-time curve and
+ *                        the up to eight strongest arrivals with their delay, level and polarity, in float64 on the device when
+ *                        read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -446,10 +450,15 @@ typedef enum wf_hip_output {
                                   columns of 256 frames in the rings as of the pushes issued so far, in total and in three
                                   frequency groups, and the onsets picked from them (spectrum and meter batches whose ring holds at
                                   least 8192 frames; definition below) */
-    WF_HIP_OUT_XFER            /* wf_hip_xfer                                transfer function: gain, phase and coherence per bin
+    WF_HIP_OUT_XFER,           /* wf_hip_xfer                                transfer function: gain, phase and coherence per bin
                                   of captured channel 0 (measured) against channel 1 (reference), averaged over K segments of P
                                   frames in the rings as of the pushes issued so far, with the integer delay between them found
                                   and taken out (spectrum and meter batches of at least 256 frames with two captured channels;
+                                  definition below) */
+    WF_HIP_OUT_IMPULSE         /* wf_hip_impulse                             impulse response: the response over time of captured
+                                  channel 0 (measured) against channel 1 (reference) from the same K segments of P frames, L = P / 4
+                                  frames before the delay taken out and 3 L behind it, its envelope in dB and the up to 8 strongest
+                                  arrivals (spectrum and meter batches of at least 256 frames with two captured channels;
                                   definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
@@ -1224,8 +1233,8 @@ typedef struct wf_hip_onset {
  * Limits: a delay beyond L is not found and biases the coherence down by about (1 - |d| / P)^2; a fractional delay stays in `phase`
  * as a linear slope; with K = 13 segments two independent channels read a coherence near 1 / K and not 0 -- the half overlap makes
  * it somewhat more: the numpy restatement reads a mean of 0.081 at K = 13 and 0.033 at K = 32 on white noise (tests/test_xfer_cpu.py).
- * The impulse response, smoothing to fractional octaves and averaging across reads are the host's; `newest` says when a read
- * brings new segments.
+ * The response against time is WF_HIP_OUT_IMPULSE (below); smoothing to fractional octaves and averaging across reads are the
+ * host's; `newest` says when a read brings new segments.
  * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 256 threads per
  * stream; K float64 transforms of P points per pass, one behind the other in one LDS region, every thread keeping the running sums
  * of its own bins in registers; the lag search as one more transform of the weighted cross spectrum held in half a region beside
@@ -1257,6 +1266,103 @@ typedef struct wf_hip_xfer {
     float phase[WF_HIP_XFER_BINS];     /* radians */
     float coherence[WF_HIP_XFER_BINS];
 } wf_hip_xfer;               /* 12336 bytes, a multiple of 16 */
+/* ---- impulse response (WF_HIP_OUT_IMPULSE) ----------------------------------------------------------------------------------------
+ * Per stream, the fourth view of the dual-channel analyser: the response of the measured channel against the reference over *time*,
+ * what such analysers show beside the transfer function as the "live IR" with its energy-time curve.  It answers what the others
+ * cannot: is there an echo, how late and how loud is it, is it inverted -- a monitor bleeding into a microphone, a doubled route
+ * through a mixer, a room reflection.  A host cannot make it from WF_HIP_OUT_XFER: that output's curves are float32, its dead bins
+ * are forced to 0 and ring in the time domain, and at 4096 streams the host would pull 50.5 MB per read and run 4096 inverse
+ * transforms.  Everything is float64 unless it says otherwise.
+ *   sums           roles, P, M = H = P / 2, L = P / 4, K, the anchor E, the span, the taper, the spectra, pass 1, the lag n0 and
+ *                  pass 2 are WF_HIP_OUT_XFER's (above), taken by the same code: Sxx[k], Syy[k] and Sxy[k] = sum_a conj(X_1) X_0 for
+ *                  1 <= k < M are the bits that output holds, and so are valid, window, hop, segments, lag, newest, lag_peak and
+ *                  mean_coherence.  The validity rule and everything a zero record carries (window, hop, segments; all else 0) are
+ *                  that output's too.
+ *   response       lambda = WF_HIP_IMPULSE_REG (1e-6) max_k Sxx[k]; Hr[k] = Sxy[k] / (Sxx[k] + lambda) for 1 <= k < M, the real and
+ *                  the imaginary part each divided by the real sum, and Hr[0] = Hr[M] = 0.  There are no dead bins: the
+ *                  regulariser takes their place smoothly, so the response does not ring.  (Where Sxx[k] + lambda is 0 -- a
+ *                  reference whose only samples lie in the slack beside the segments -- Hr[k] = 0.)
+ *   ir             h[n] = (1 / P) sum_{k < P} Hext[k] e^(+j 2 pi k n / P) with Hext the Hermitian extension of Hr, Hext[P - k] =
+ *                  conj Hr[k]: one forward transform read at (-n) mod P, as the lag search reads its own.  ir[i] = (float) h[i - L]
+ *                  for 0 <= i < P, negative n taken mod P: L frames before the arrival that was taken out and 3 L behind it.  Index i
+ *                  lies lag + i - L frames behind the reference.  The indices P .. WF_HIP_IMPULSE_FRAMES - 1 read 0.
+ *   envelope       the energy-time curve: a[n] = (1 / P) sum_{1 <= k < M} 2 T[k] Hr[k] e^(+j 2 pi k n / P), the analytic signal of
+ *                  the response under the taper T[k] = 1 - cos(2 pi k / M) = 2 w[2 k], a Hann window across frequency with the mean
+ *                  1 (without it the Hilbert part of a single tap decays only as 1 / n, and every odd index would be a local
+ *                  maximum).  env[i] = |a[i - L]| and etc_db[i] = (float)(20 log10 env[i]), -INFINITY where env[i] == 0; the indices
+ *                  from P up read 0.  A unit tap reads about 0 dB; the taper's side lobes lie 5 frames to either side of a tap, 31 to
+ *                  33 dB under it.
+ *   arrivals       the peak is the argmax of env over 0 <= i < P: the larger value, the lower index of equal ones.  Candidates are
+ *                  the interior local maxima, env[i] > env[i - 1] && env[i] >= env[i + 1], 1 <= i <= P - 2.  arrivals[0] is the
+ *                  peak; then, up to WF_HIP_IMPULSE_ARRIVALS = 8 in all, the strongest candidate (the lower index of equal ones)
+ *                  that lies more than WF_HIP_IMPULSE_GUARD = 8 indices from every arrival taken so far and has env[i] >=
+ *                  WF_HIP_IMPULSE_ARRIVAL_RATIO env[peak] (-30 dB), until there is none.  Of the arrival at index i:
+ *                    frames     (float)(lag + i - L + frac): frac = 0.5 (l - r) / ((l - c) + (r - c)) with l, c, r = env[i - 1],
+ *                               env[i], env[i + 1], the vertex of the parabola through them, clamped to +-0.5; 0 where the divisor
+ *                               is not negative and at i == 0 and i == P - 1
+ *                    level_db   (float)(20 log10(env[i] / env[peak])): the peak reads 0
+ *                    polarity   +1 where Re a[i - L] >= 0, else -1
+ *                  The slots not used are zeros, and so is every `reserved`.
+ *   scalars        count, the number of arrivals; peak_index; peak_db = 20 log10 env[peak]; delay_ms, the peak's float64 `frames`
+ *                  times 1000 / sr; energy_db = 10 log10 sum_{i < P} h[i - L]^2 and direct_db, the same sum over |i - peak_index| <=
+ *                  WF_HIP_IMPULSE_DIRECT = 16 (the host subtracts the two for direct-to-rest); -INFINITY where a sum is 0.  Each
+ *                  float32 field is rounded once from float64.
+ *   no response    env[peak] == 0 -- a measured channel that is +-0 under every segment while the span is not silent: valid = 1,
+ *                  count = 0, ir all +0, etc_db all -INFINITY up to P, and the peak fields, energy_db and direct_db 0.
+ *   determinism    as WF_HIP_OUT_XFER's: no atomics, every sum and every max in an order that follows from P and K alone, so the
+ *                  same ring contents read bit-identically across push paths, repeated reads, slices, shards and any two reads
+ *                  within one hop.
+ * Limits: an arrival d frames behind the one taken out is scaled by the overlap of the Hann segments, rho(d) = sum_n w[n] w[n + d] /
+ * sum_n w[n]^2 -- -0.22 dB at P / 16, -3.62 dB at P / 4 and -3.9 dB at P / 4 + 11 frames of P = 1024 --, so later arrivals read low, and one beyond the view (more than
+ * 3 L behind or L before the lag) is noise.  Around rho the estimate scatters with the K segments: over eight seeds of white noise
+ * through taps of +1, -0.5 and +0.25 the numpy restatement stayed within 0.016 of the first tap in ir, 0.54 dB in level and 0.062 frames
+ * in place of g rho(d) at P = 256, K = 13, and within 0.003, 0.05 dB and 0.01 frames at P = 2048, K = 32 (tests/test_impulse_cpu.py).  DC
+ * and Nyquist are not part of the response.  With K = 13 and noise as strong as the signal in the measured channel, the floor's
+ * maxima stand 22.9 to 26.2 dB under the peak on the restatement (29.3 to 32.4 dB with K = 32): they can pass the -30 dB rule, and mean_coherence says when they do.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 256 threads per
+ * stream: the transfer function's passes, then two more of the shared float64 transforms in the same LDS, 48 KB at the cap), into
+ * a block the first read allocates together with its tables: a handle that never reads it allocates and launches nothing new,
+ * nothing is added to the tick, and no state is kept between reads.
+ * Cost on an MI355X, 4096 stereo streams at FFT 4096 read into page-locked memory (67.9 MB back): 2.39 ms with the default ring
+ * (P = 1024, K = 13) where the lag is not 0 and both passes run, 1.95 ms where it is 0, against 4.71 ms for copying the 268.4 MB of
+ * both rings that the segments span to the host; 5.43 and 3.79 ms with ring_frames = 65536 (P = 2048, K = 32) against 20.6 ms for
+ * its 1174.4 MB.  Into a fresh pageable numpy array (the Python reader) a read takes 7.52 and 10.35 ms, most of it the copy of the
+ * 16 KB entries.
+ * The kernel's own time without its copy is unmeasured (tools/impulse_bench.py, profiles/impulse_kernel_stats.json; INTEGRATION.md,
+ * "Impulse response").
+ * The refusals are WF_HIP_OUT_XFER's: with one captured channel, with W < 256, with a ring under 512 frames and on waveform batches
+ * wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_IMPULSE_FRAMES 2048
+#define WF_HIP_IMPULSE_ARRIVALS 8
+#define WF_HIP_IMPULSE_GUARD 8
+#define WF_HIP_IMPULSE_DIRECT 16
+#define WF_HIP_IMPULSE_REG 1e-6
+#define WF_HIP_IMPULSE_ARRIVAL_RATIO 0.031622776601683794 /* 10^(-30 / 20) */
+typedef struct wf_hip_impulse_arrival {
+    float frames;            /* behind the reference; lag + i - L + frac */
+    float level_db;          /* against the peak: 0 for arrivals[0] */
+    int32_t polarity;        /* +1 or -1 */
+    uint32_t reserved;       /* 0 */
+} wf_hip_impulse_arrival;
+typedef struct wf_hip_impulse {
+    uint32_t valid;
+    uint32_t window, hop;    /* P, H */
+    uint32_t segments;       /* K */
+    int32_t lag;             /* n0, as wf_hip_xfer's */
+    uint32_t newest;         /* wpos / H */
+    float lag_peak;
+    float mean_coherence;
+    uint32_t count;          /* arrivals listed */
+    uint32_t peak_index;     /* into ir and etc_db */
+    float peak_db;           /* 20 log10 env[peak] */
+    float delay_ms;          /* arrivals[0].frames in milliseconds */
+    float energy_db;         /* 10 log10 sum h^2 */
+    float direct_db;         /* the same within WF_HIP_IMPULSE_DIRECT indices of the peak */
+    uint32_t reserved[2];    /* 0 */
+    wf_hip_impulse_arrival arrivals[WF_HIP_IMPULSE_ARRIVALS]; /* the peak, then by falling level */
+    float ir[WF_HIP_IMPULSE_FRAMES];     /* [i], 0 <= i < P: h[i - L]; 0 elsewhere */
+    float etc_db[WF_HIP_IMPULSE_FRAMES]; /* [i], 0 <= i < P: 20 log10 |a[i - L]|; 0 elsewhere */
+} wf_hip_impulse;            /* 16576 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

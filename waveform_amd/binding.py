@@ -60,7 +60,7 @@ TICK_NO_DECIBELS = 1
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
     OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET, \
-    OUT_XFER = range(25)
+    OUT_XFER, OUT_IMPULSE = range(26)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -250,6 +250,22 @@ XFER_DTYPE = np.dtype([("valid", np.uint32), ("window", np.uint32), ("hop", np.u
                        ("newest", np.uint32), ("lag_peak", np.float32), ("mean_coherence", np.float32), ("reserved", np.uint32, (4,)),
                        ("gain_db", np.float32, (XFER_BINS,)), ("phase", np.float32, (XFER_BINS,)),
                        ("coherence", np.float32, (XFER_BINS,))])
+
+# struct wf_hip_impulse (include/wf_hip.h): the impulse response of captured channel 0 (measured) against channel 1 (reference), ir[i]
+# and its envelope etc_db[i] at lag + i - window / 4 frames behind the reference (0 <= i < window; 0 elsewhere), from the transfer
+# function's segments, and the up to IMPULSE_ARRIVALS strongest arrivals, the peak first
+IMPULSE_FRAMES = 2048  # WF_HIP_IMPULSE_FRAMES
+IMPULSE_ARRIVALS = 8  # WF_HIP_IMPULSE_ARRIVALS
+IMPULSE_GUARD = 8  # WF_HIP_IMPULSE_GUARD
+IMPULSE_DIRECT = 16  # WF_HIP_IMPULSE_DIRECT
+IMPULSE_REG = 1e-6  # WF_HIP_IMPULSE_REG
+IMPULSE_ARRIVAL_RATIO = 0.031622776601683794  # WF_HIP_IMPULSE_ARRIVAL_RATIO: -30 dB
+IMPULSE_ARRIVAL_DTYPE = np.dtype([("frames", np.float32), ("level_db", np.float32), ("polarity", np.int32), ("reserved", np.uint32)])
+IMPULSE_DTYPE = np.dtype([("valid", np.uint32), ("window", np.uint32), ("hop", np.uint32), ("segments", np.uint32), ("lag", np.int32),
+                          ("newest", np.uint32), ("lag_peak", np.float32), ("mean_coherence", np.float32), ("count", np.uint32),
+                          ("peak_index", np.uint32), ("peak_db", np.float32), ("delay_ms", np.float32), ("energy_db", np.float32),
+                          ("direct_db", np.float32), ("reserved", np.uint32, (2,)), ("arrivals", IMPULSE_ARRIVAL_DTYPE, (IMPULSE_ARRIVALS,)),
+                          ("ir", np.float32, (IMPULSE_FRAMES,)), ("etc_db", np.float32, (IMPULSE_FRAMES,))])
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -536,6 +552,22 @@ class _MeasureReaders:
         captured channels and fft_size >= 256)"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_XFER, first, count, (), XFER_DTYPE)
+
+    def impulse(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_impulse (IMPULSE_DTYPE): the impulse response of a dual-channel analyser with the
+        programme as the stimulus, captured channel 0 (measured) against channel 1 (reference), from the segments xfer() averages
+        (window, hop, segments, lag, newest, lag_peak, mean_coherence and valid are its fields, bit for bit).  ir[i] is the response
+        and etc_db[i] its envelope in dB (the energy-time curve; -inf where it is 0) lag + i - window / 4 frames behind the
+        reference, 0 <= i < window: window / 4 frames before the delay that was taken out and 3 window / 4 behind it; 0 elsewhere.
+        arrivals[:count] are the strongest local maxima of the envelope, the peak first and then by falling level, at least
+        IMPULSE_GUARD + 1 indices apart and no more than 30 dB under the peak: frames (behind the reference, to a fraction),
+        level_db (against the peak) and polarity (+1 / -1).  peak_index, peak_db and delay_ms describe the peak; energy_db is the
+        power of the whole response and direct_db that within IMPULSE_DIRECT indices of the peak.  A later arrival reads low by the
+        overlap of the segments (-3.9 dB at window / 4).  valid = 0 as xfer(); valid = 1 with count = 0 where the measured channel
+        is silent under every segment.  In float64 on the device when read, from the rings as of the pushes issued so far (batches
+        with two captured channels and fft_size >= 256)"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_IMPULSE, first, count, (), IMPULSE_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

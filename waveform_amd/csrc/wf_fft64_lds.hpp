@@ -1,8 +1,9 @@
 // wf_fft64_lds.hpp -- the complex float64 transform in LDS that the read kernels of WF_HIP_OUT_STEREO (wf_stereo.hpp: one
 // transform per workgroup of 256 threads), WF_HIP_OUT_SONO (wf_sono.hpp: one per wavefront), WF_HIP_OUT_THD (wf_thd.hpp: one
 // per workgroup of 512 threads, up to P = 8192), WF_HIP_OUT_DELAY (wf_delay.hpp: two per workgroup of 256 threads, one behind
-// the other in two regions), WF_HIP_OUT_ONSET (wf_onset.hpp: one per wavefront and round, as the sonogram's) and WF_HIP_OUT_XFER
-// (wf_xfer.hpp: up to 65 per workgroup of 256 threads, one behind the other in one region) share (device code only; hipcc).
+// the other in two regions), WF_HIP_OUT_ONSET (wf_onset.hpp: one per wavefront and round, as the sonogram's), WF_HIP_OUT_XFER
+// (wf_xfer.hpp by wf_xfer_sums.hpp: up to 65 per workgroup of 256 threads, one behind the other in one region) and
+// WF_HIP_OUT_IMPULSE (wf_impulse.hpp: the same and two more) share (device code only; hipcc).
 //
 // P complex float64 (16 B each), P a power of two >= 64, decimation in time, natural order out:
 //   load    thread c' < P / 16 takes the 16 elements c' + m P/16, m = 0 .. 15 (consecutive lanes on consecutive elements) from

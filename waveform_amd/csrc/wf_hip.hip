@@ -1396,6 +1396,7 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
     case WF_HIP_OUT_DELAY:
     case WF_HIP_OUT_ONSET:
     case WF_HIP_OUT_XFER:
+    case WF_HIP_OUT_IMPULSE:
         break; // (never asked here: measure_source answers for them)
     }
     *why = "unknown output";

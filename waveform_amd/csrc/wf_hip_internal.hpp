@@ -133,7 +133,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    static constexpr int N_MEASURES = 15;
+    static constexpr int N_MEASURES = 16;
     char *d_measure[N_MEASURES] = {};
     bool measure_ready[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
@@ -191,6 +191,14 @@ struct wf_hip {
         uint32_t P = 0, log2p = 0;                // the segment: a power of two
         uint32_t K = 0;                           // segments
     } xfer;
+    // what WF_HIP_OUT_IMPULSE derives from the configuration and the ring (setup_impulse, at its first read: the transfer
+    // function's geometry and wf::host::delay_tables at that P, a block of its own so that neither output needs the other read
+    // first; wf_impulse.hpp)
+    struct Impulse {
+        double *d_tab = nullptr;                  // [P] taper, [P / 2][2] twiddles
+        uint32_t P = 0, log2p = 0;                // the segment: a power of two
+        uint32_t K = 0;                           // segments
+    } impulse;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

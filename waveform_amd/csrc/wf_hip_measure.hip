@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET and _XFER.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER and _IMPULSE.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -34,6 +34,7 @@
 #include "wf_delay.hpp"
 #include "wf_onset.hpp"
 #include "wf_xfer.hpp"
+#include "wf_impulse.hpp"
 
 namespace {
 
@@ -475,6 +476,37 @@ int launch_xfer(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the impulse response derives from the configuration and the ring: the transfer function's P and K and the same tables
+int setup_impulse(wf_hip *h)
+{
+    wf_hip::Impulse &x = h->impulse;
+    const uint32_t P = xfer_window(h->N, h->ring_cap); // (>= 64: why_no_impulse)
+    const DelayTables t = delay_tables(P);
+    x.P = t.P;
+    x.log2p = t.log2p;
+    x.K = xfer_segments(P, h->ring_cap);
+    // (48 KB of dynamic LDS at the cap: what a workgroup gets without asking)
+    return upload(h, &x.d_tab, t.tab); // (pageable memory: staged before the call returns)
+}
+
+// one workgroup per stream over the K newest anchored segments of both captured channels, behind the pushes issued
+int launch_impulse(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Impulse &x = h->impulse;
+    wf::ImpulseArgs a{};
+    a.rings = ring_view(h); // (two captured channels: why_no_impulse)
+    a.out = static_cast<wf_hip_impulse *>(d_block) + first;
+    a.window = x.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(x.d_tab + x.P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.P = x.P; // (<= ring_cap / 8)
+    a.log2p = x.log2p;
+    a.K = x.K;
+    hipLaunchKernelGGL(wf::impulse_read_kernel, dim3(count), dim3(wf::WF_XFER_THREADS), (size_t)(x.P + x.P / 2 + 1) * sizeof(double2), h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -562,6 +594,17 @@ const char *why_no_xfer(const wf_hip *h)
     return h->ring_cap < 512 ? "the transfer function needs a ring of at least 512 frames (wf_hip_create's ring_frames)" : nullptr;
 }
 
+const char *why_no_impulse(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the impulse response belongs to spectrum and meter batches (a window of fft_size frames)";
+    if(h->cap_ch != 2)
+        return "the impulse response needs two captured channels";
+    if(h->N < 256)
+        return "the impulse response needs a window of at least 256 frames";
+    return h->ring_cap < 512 ? "the impulse response needs a ring of at least 512 frames (wf_hip_create's ring_frames)" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -588,6 +631,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_DELAY, sizeof(wf_hip_delay), false, why_no_delay, setup_delay, launch_delay},
     {WF_HIP_OUT_ONSET, sizeof(wf_hip_onset), false, why_no_onset, setup_onset, launch_onset},
     {WF_HIP_OUT_XFER, sizeof(wf_hip_xfer), false, why_no_xfer, setup_xfer, launch_xfer},
+    {WF_HIP_OUT_IMPULSE, sizeof(wf_hip_impulse), false, why_no_impulse, setup_impulse, launch_impulse},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output

@@ -1,4 +1,4 @@
-// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD, _DELAY and _XFER derive from the configuration alone,
+// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD, _DELAY, _XFER and _IMPULSE derive from the configuration alone,
 // built on the host (wf_measure_tables.cpp) at the output's first read and uploaded by wf_hip_measure.hip.  Plain C++: no HIP
 // and no handle, so the arithmetic also compiles into a program of its own (tests/test_measure_tables_cpu.py).  The sizes of
 // the constant-Q tables are in wf_cq_sizes.hpp, shared with the kernel (wf_cq.hpp).
@@ -82,7 +82,7 @@ struct DelayTables {
 };
 DelayTables delay_tables(uint32_t N);
 
-// WF_HIP_OUT_XFER (wf_xfer.hpp): the segment length P, the largest power of two <= min(fft_size, WF_HIP_XFER_MAX_WINDOW,
+// WF_HIP_OUT_XFER (wf_xfer.hpp) and WF_HIP_OUT_IMPULSE (wf_impulse.hpp): the segment length P, the largest power of two <= min(fft_size, WF_HIP_XFER_MAX_WINDOW,
 // ring_cap / 8), and the number of half-overlapped segments K = min(WF_HIP_XFER_MAX_SEGMENTS, 2 ring_cap / P - 3), at least 13: with
 // the P / 4 frames of slack on either side and the up to P / 2 - 1 frames behind the anchor they span at most ring_cap - 1 frames.
 // Its tables are delay_tables(P)
