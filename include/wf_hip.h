@@ -71,6 +71,9 @@
  *                        channel against the other from the regularised average of the same segments, its energy-time curve and
  *                        the up to eight strongest arrivals with their delay, level and polarity, in float64 on the device when
  *                        read
+ *   WF_HIP_OUT_CLICK     not in the reference: a click detector, per captured channel the clicks, pops and splices of every
+ *                        stream's newest window of audio -- the frames that a linear predictor fitted to the window cannot account
+ *                        for -- as a count, a rate and the up to eight strongest events, in float64 on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -455,11 +458,16 @@ typedef enum wf_hip_output {
                                   frames in the rings as of the pushes issued so far, with the integer delay between them found
                                   and taken out (spectrum and meter batches of at least 256 frames with two captured channels;
                                   definition below) */
-    WF_HIP_OUT_IMPULSE         /* wf_hip_impulse                             impulse response: the response over time of captured
+    WF_HIP_OUT_IMPULSE,        /* wf_hip_impulse                             impulse response: the response over time of captured
                                   channel 0 (measured) against channel 1 (reference) from the same K segments of P frames, L = P / 4
                                   frames before the delay taken out and 3 L behind it, its envelope in dB and the up to 8 strongest
                                   arrivals (spectrum and meter batches of at least 256 frames with two captured channels;
                                   definition below) */
+    WF_HIP_OUT_CLICK           /* wf_hip_click                               clicks: per captured channel the clicks, pops and
+                                  splices of the newest min(wf_hip_fft_size(), 8192) frames in the rings as of the pushes issued so
+                                  far, the frames a linear predictor fitted to the window cannot account for, as a count, a rate
+                                  and the up to 8 strongest events (spectrum and meter batches of at least 256 frames; definition
+                                  below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -1363,6 +1371,83 @@ typedef struct wf_hip_impulse {
     float ir[WF_HIP_IMPULSE_FRAMES];     /* [i], 0 <= i < P: h[i - L]; 0 elsewhere */
     float etc_db[WF_HIP_IMPULSE_FRAMES]; /* [i], 0 <= i < P: 20 log10 |a[i - L]|; 0 elsewhere */
 } wf_hip_impulse;            /* 16576 bytes, a multiple of 16 */
+/* ---- clicks (WF_HIP_OUT_CLICK) -----------------------------------------------------------------------------------------------------
+ * Per stream and captured channel, the click detector of a QC monitor: the clicks of an interface that drops buffers, the splice
+ * where a block was skipped or repeated, the pop of a bad cable.  The programme is predictable from its own recent past and a click
+ * is not: a linear predictor is fitted to the window, and the frames whose residual stands far above the residual's own robust level
+ * are the clicks.  Let W = wf_hip_fft_size() and sr = cfg.sample_rate.  Everything is float64 unless it says otherwise, and every
+ * product and every sum is rounded on its own (no fused multiply-add, except where it is named).
+ *   window         P = min(W, WF_HIP_CLICK_MAX_WINDOW) frames: the newest P frames of the channel's ring.  WF_HIP_OUT_SIGNAL's rules:
+ *                  every push issued before the read counts, the A/V-sync delay is not applied, the zeros of create and reset count,
+ *                  hidden and paused streams are read like any other.  x[n], 0 <= n < P, is the float32 sample widened exactly;
+ *                  A = the largest |x[n]|.
+ *   predictor      of order p = WF_HIP_CLICK_ORDER = 16.  r[k] = sum_{n=k}^{P-1} x[n] x[n-k] for k = 0 .. p, the biased
+ *                  autocorrelation, which keeps Levinson stable.  The order of the sum is fixed: partial t, 0 <= t < 256, is the
+ *                  fused sum over n = t, t + 256, ... in ascending n (a product of two float32 values is exact in float64: the fused
+ *                  sum is the plain one); then, within each 64 consecutive partials, six rounds v[t] += v[t ^ 32], ^ 16, ^ 8, ^ 4,
+ *                  ^ 2, ^ 1; then ((s_0 + s_1) + s_2) + s_3 of the four groups.  The same frames therefore give the same bits, and
+ *                  a host that restates the order reproduces them (tests/click_ref.py does).  Levinson-Durbin on r'[0] = r[0] (1 +
+ *                  1e-9), r'[k] = r[k]: E = r'[0]; for i = 1 .. p: acc = r[i], acc = acc - a[j] r[i-j] for j = 1 .. i-1 ascending,
+ *                  k = acc / E, a'[j] = a[j] - k a[i-j] for j < i, a'[i] = k, E = E (1 - k k).  It gives a[1..p] and the error power
+ *                  E.  e[n] = x[n] - acc for p <= n < P, acc = 0, acc = acc + a[k] x[n-k] for k = 1 .. p ascending; the frames n < p
+ *                  are not judged.  d[n] = (float) |e[n]|.
+ *   scale          blocks of B = 256 judged frames: nb = max(1, (P - p) / B); block b covers [p + b B, p + (b+1) B), the last one
+ *                  runs to P (up to 511 frames).  m_b = the element of rank len_b / 2 (0-based, ascending) of the block's d;
+ *                  g = the element of rank (P - p) / 2 of all judged d: exact order statistics of float32 values.
+ *                  s_b = 1.4826 max(m_{b-1}, m_b, m_{b+1}, 0.25 g, 2^-24 A) over the neighbours that exist.  The neighbours keep a
+ *                  signal that starts inside the window from reading as clicks; the last term lets a lone click in digital silence
+ *                  read as one (141 dB) instead of 0 / 0.  A window of one block (nb = 1: P - p < 512) has no neighbours, and half
+ *                  the medians of its two halves stand in for them: h = p + (P - p) / 2, m_lo and m_hi the elements of rank len / 2
+ *                  of d over [p, h) and [h, P), s_0 = 1.4826 max(m_0, 0.5 m_lo, 0.5 m_hi, 0.25 g, 2^-24 A).  Without them zeros
+ *                  followed by noise at P = 256 read 1 to 3 events on 18 of 24 seeds of the restatement; with them none does, and a
+ *                  block of one kind reads the same bits as without, half a half's median lying under the block's own.
+ *   hits           frame n of block b is a hit when d[n] / s_b > WF_HIP_CLICK_THRESHOLD = 16 (24.1 dB).  A Laplacian residual exceeds
+ *                  it with probability exp(-1.028 * 16) = 7e-8 per frame, 6e-4 per window.
+ *   events         hits whose gaps are at most WF_HIP_CLICK_GAP = 32 frames form one event: start (its first hit), length (last
+ *                  hit - first + 1), peak (the hit of the largest ratio, the lower index of equal ones), strength_db = 20 log10 of
+ *                  that ratio, amplitude = (float) e[peak], signed.
+ *   list           the up to WF_HIP_CLICK_MAX_EVENTS = 8 strongest events, strength_db (the float32) descending, then start
+ *                  ascending; the slots behind them are zero bytes.
+ *   validity       valid = 0 when r[0] == 0 or the window holds a NaN or an infinity; every other field of that channel is then 0
+ *                  and peak_db, floor_db and prediction_gain_db are -INFINITY.
+ * Limits.  Hard clipping reads as long events: the flat tops are unpredictable, and WF_HIP_OUT_SIGNAL's clip count says why.  A
+ * source that is an impulse train through a resonator with no noise under it (a synthetic voice) reads its own pulses.  A window of
+ * 800 frames or fewer leaves a pure sine too much residual for a 0.01 click on a 0.5 sine to be found; at 4096 and 8192 it reads 36
+ * and 43 dB.  A signal that starts in the last quarter of a window of one block, or in the last 128 frames of a longer one, has no later
+ * block or half to lean on and reads as events until the next read.  The constants were chosen on synthetic noise, tones, notes and splices, not on recorded programme.  The host can raise
+ * the threshold on strength_db; it cannot lower it.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 256 threads per stream
+ * and captured channel, the window and the residual in LDS, about 73 KB at the cap), into a block the first read allocates: a handle
+ * that never reads it allocates and launches nothing new, nothing is added to the tick, and no state is kept between reads (a host
+ * that polls tells an event it has seen by `frame`).
+ * Cost on an MI355X, 4096 stereo streams read into page-locked memory (1.9 MB back): 980 us on noise, 1002 us on a sine with a click
+ * and 272 us on silence at FFT 4096, against 2361 us for copying the windows to the host; 2277, 2307 and 597 us at FFT 16384 (P =
+ * 8192) against 4890 us.  The kernel's own time without its copy is unmeasured (tools/click_bench.py,
+ * profiles/click_kernel_stats.json; INTEGRATION.md, "Clicks").
+ * On waveform batches and with W < 256 wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads
+ * it through wf_hip_multi_read; the pipelined readback (wf_hip_read_async) carries the tick's outputs only. */
+#define WF_HIP_CLICK_MAX_WINDOW 8192
+#define WF_HIP_CLICK_ORDER 16
+#define WF_HIP_CLICK_GAP 32
+#define WF_HIP_CLICK_MAX_EVENTS 8
+#define WF_HIP_CLICK_THRESHOLD 16.0
+typedef struct wf_hip_click_event {
+    uint32_t start, length, peak;   /* indices into the window */
+    uint32_t frame;                 /* counter position of `start`: wpos - P + start (mod 2^32), as WF_HIP_OUT_ONSET's last_frame */
+    float strength_db, amplitude;
+} wf_hip_click_event;               /* 24 bytes */
+typedef struct wf_hip_click_channel {
+    uint32_t valid, events, hit_frames, listed;   /* events in the window; frames that are hits; min(events, 8) */
+    float rate;              /* events * sr / (P - p): clicks per second */
+    float peak_db;           /* 20 log10 of the largest d[n] / s_b over all judged frames, hit or not: the "crackle meter" */
+    float floor_db;          /* 20 log10(1.4826 g): the residual's robust level, dBFS */
+    float prediction_gain_db;/* 10 log10(r[0] / E) */
+    wf_hip_click_event ev[WF_HIP_CLICK_MAX_EVENTS];
+} wf_hip_click_channel;      /* 224 bytes */
+typedef struct wf_hip_click {
+    wf_hip_click_channel ch[2];   /* captured channels 0 and 1; with one captured channel ch[1] is all zero bytes */
+    uint32_t window, order, reserved[2];   /* P, p, 0 */
+} wf_hip_click;              /* 464 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

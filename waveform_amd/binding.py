@@ -60,7 +60,7 @@ TICK_NO_DECIBELS = 1
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
     OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET, \
-    OUT_XFER, OUT_IMPULSE = range(26)
+    OUT_XFER, OUT_IMPULSE, OUT_CLICK = range(27)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -266,6 +266,22 @@ IMPULSE_DTYPE = np.dtype([("valid", np.uint32), ("window", np.uint32), ("hop", n
                           ("peak_index", np.uint32), ("peak_db", np.float32), ("delay_ms", np.float32), ("energy_db", np.float32),
                           ("direct_db", np.float32), ("reserved", np.uint32, (2,)), ("arrivals", IMPULSE_ARRIVAL_DTYPE, (IMPULSE_ARRIVALS,)),
                           ("ir", np.float32, (IMPULSE_FRAMES,)), ("etc_db", np.float32, (IMPULSE_FRAMES,))])
+
+# struct wf_hip_click (include/wf_hip.h): the click detector, per captured channel the clicks, pops and splices of the newest
+# P = min(fft_size, CLICK_MAX_WINDOW) frames of the ring -- the frames a linear predictor of order CLICK_ORDER fitted to the window
+# cannot account for -- as a count, a rate and the up to CLICK_MAX_EVENTS strongest events
+CLICK_MAX_WINDOW = 8192  # WF_HIP_CLICK_MAX_WINDOW
+CLICK_ORDER = 16  # WF_HIP_CLICK_ORDER
+CLICK_GAP = 32  # WF_HIP_CLICK_GAP
+CLICK_MAX_EVENTS = 8  # WF_HIP_CLICK_MAX_EVENTS
+CLICK_THRESHOLD = 16.0  # WF_HIP_CLICK_THRESHOLD
+CLICK_EVENT_DTYPE = np.dtype([("start", np.uint32), ("length", np.uint32), ("peak", np.uint32), ("frame", np.uint32),
+                              ("strength_db", np.float32), ("amplitude", np.float32)])
+CLICK_CHANNEL_DTYPE = np.dtype([("valid", np.uint32), ("events", np.uint32), ("hit_frames", np.uint32), ("listed", np.uint32),
+                                ("rate", np.float32), ("peak_db", np.float32), ("floor_db", np.float32), ("prediction_gain_db", np.float32),
+                                ("ev", CLICK_EVENT_DTYPE, (CLICK_MAX_EVENTS,))])
+CLICK_DTYPE = np.dtype([("ch", CLICK_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("order", np.uint32), ("reserved", np.uint32, (2,))])
+
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -568,6 +584,18 @@ class _MeasureReaders:
         with two captured channels and fft_size >= 256)"""
         # (not through _read_measure, as gonio() above)
         return self._read(OUT_IMPULSE, first, count, (), IMPULSE_DTYPE)
+
+    def click(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_click (CLICK_DTYPE): the click detector, per captured channel ch[c] the clicks, pops
+        and splices of the newest min(fft_size, CLICK_MAX_WINDOW) frames of the ring as of the pushes issued so far -- the frames
+        whose residual under a linear predictor of order CLICK_ORDER, fitted to the window, stands more than CLICK_THRESHOLD times
+        above the residual's robust level around them -- as events (hits at most CLICK_GAP frames apart), hit_frames, rate in
+        clicks per second, peak_db (the largest ratio, hit or not), floor_db, prediction_gain_db and ev[:listed], the up to
+        CLICK_MAX_EVENTS strongest events with start, length, peak, frame (the counter position of start: what a polling host tells
+        an event it has seen by), strength_db and amplitude; valid = 0 for digital silence, a NaN or an infinity.  Fitted in float64
+        on the device when read (batches of at least 256 frames).  With one captured channel ch[1] is all zero"""
+        # (not through _read_measure, as gonio() above)
+        return self._read(OUT_CLICK, first, count, (), CLICK_DTYPE)
 
 
 class SpectrumBatch(_MeasureReaders):

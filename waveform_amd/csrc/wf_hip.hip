@@ -1397,6 +1397,7 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
     case WF_HIP_OUT_ONSET:
     case WF_HIP_OUT_XFER:
     case WF_HIP_OUT_IMPULSE:
+    case WF_HIP_OUT_CLICK:
         break; // (never asked here: measure_source answers for them)
     }
     *why = "unknown output";

@@ -133,7 +133,7 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    static constexpr int N_MEASURES = 16;
+    static constexpr int N_MEASURES = 17;
     char *d_measure[N_MEASURES] = {};
     bool measure_ready[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off

@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER and _IMPULSE.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE and _CLICK.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
@@ -35,6 +35,7 @@
 #include "wf_onset.hpp"
 #include "wf_xfer.hpp"
 #include "wf_impulse.hpp"
+#include "wf_click.hpp"
 
 namespace {
 
@@ -507,6 +508,38 @@ int launch_impulse(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// the click detector's window: the newest min(fft_size, WF_HIP_CLICK_MAX_WINDOW) frames (<= ring_cap)
+uint32_t click_window(const wf_hip *h) { return std::min<uint32_t>(h->N, WF_HIP_CLICK_MAX_WINDOW); }
+
+// the click detector has no tables: its kernels' dynamic LDS is all its first read asks for
+int setup_click(wf_hip *h)
+{
+    // (about 73 KB at the cap, the window, the residual and the kernel's working set behind them: more than a workgroup gets
+    // without asking, and two workgroups to a CU)
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::click_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::click_lds_bytes(WF_HIP_CLICK_MAX_WINDOW)));
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::click_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)wf::click_lds_bytes(WF_HIP_CLICK_MAX_WINDOW)));
+    return WF_HIP_OK;
+}
+
+// one workgroup per stream and captured channel over its newest P frames, behind the pushes issued
+int launch_click(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    wf::ClickArgs a{};
+    a.rings = ring_view(h);
+    a.out = static_cast<wf_hip_click *>(d_block) + first;
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.P = click_window(h); // (>= 256: why_no_click)
+    const size_t lds = wf::click_lds_bytes(a.P);
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(wf::click_read_kernel<2>, dim3(count * 2u), dim3(wf::WF_CLICK_THREADS), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(wf::click_read_kernel<1>, dim3(count), dim3(wf::WF_CLICK_THREADS), lds, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -605,6 +638,13 @@ const char *why_no_impulse(const wf_hip *h)
     return h->ring_cap < 512 ? "the impulse response needs a ring of at least 512 frames (wf_hip_create's ring_frames)" : nullptr;
 }
 
+const char *why_no_click(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the click detector belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->N < 256 ? "the click detector needs a window of at least 256 frames" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -632,6 +672,7 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_ONSET, sizeof(wf_hip_onset), false, why_no_onset, setup_onset, launch_onset},
     {WF_HIP_OUT_XFER, sizeof(wf_hip_xfer), false, why_no_xfer, setup_xfer, launch_xfer},
     {WF_HIP_OUT_IMPULSE, sizeof(wf_hip_impulse), false, why_no_impulse, setup_impulse, launch_impulse},
+    {WF_HIP_OUT_CLICK, sizeof(wf_hip_click), false, why_no_click, setup_click, launch_click},
 };
 
 int measure_row(wf_hip_output what) // -1: not a measurement output
