@@ -54,7 +54,7 @@ def test_both_batch_classes_share_the_reader():
     reader = binding.SpectrumBatch.bits
     assert reader is binding.MultiBatch.bits is binding._MeasureReaders.bits
     assert reader.__doc__ and "bits" not in vars(binding.SpectrumBatch) and "bits" not in vars(binding.MultiBatch)
-    assert "bits" not in binding.MEASURES and len(binding.MEASURES) == 8  # read the way gonio() is
+    assert binding.MEASURES["bits"] == (binding.OUT_BITS, binding.BITS_DTYPE, False)
 
 
 def _one(kind, p, seed=1):

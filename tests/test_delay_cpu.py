@@ -56,7 +56,7 @@ def test_both_batch_classes_share_the_reader():
     reader = binding.SpectrumBatch.delay
     assert reader is binding.MultiBatch.delay is binding._MeasureReaders.delay
     assert reader.__doc__ and "delay" not in vars(binding.SpectrumBatch) and "delay" not in vars(binding.MultiBatch)
-    assert "delay" not in binding.MEASURES and len(binding.MEASURES) == 8  # read the way gonio() is
+    assert binding.MEASURES["delay"] == (binding.OUT_DELAY, binding.DELAY_DTYPE, False)
 
 
 # ---- the host tables ----------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ classes being the same functions.
 Bound of the float64 comparisons: rtol 1e-12 (atol 1e-300 for exact zeros), the figure test_loudness_cpu.py uses for the filter
 design: four orders of magnitude above what a handful of correctly rounded double operations and two libm calls can differ by,
 eight below the float32 resolution of any output.  Integers and masks are compared exactly."""
+import re
 import subprocess
 from pathlib import Path
 
@@ -203,9 +204,24 @@ def test_the_program_is_clean_under_the_sanitizers(tables, tmp_path):
     assert text == tables["text"]
 
 
+NAMES = ["loudness", "peaks", "signal", "pitch", "bands", "stereo", "cq", "scope", "gonio", "sono", "bits", "thd", "delay", "onset", "xfer",
+         "impulse", "click"]
+
+
 def test_both_batch_classes_share_the_readers():
-    assert sorted(binding.MEASURES) == sorted(["loudness", "peaks", "signal", "pitch", "bands", "stereo", "cq", "scope"])
+    """all seventeen readers: one function on both batch classes, documented, and the Python table the C table's twin"""
+    assert list(binding.MEASURES) == NAMES
     for name in binding.MEASURES:
         reader = getattr(binding.SpectrumBatch, name)
         assert reader is getattr(binding.MultiBatch, name) is getattr(binding._MeasureReaders, name), name
         assert reader.__doc__ and name not in vars(binding.SpectrumBatch) and name not in vars(binding.MultiBatch)
+    # the rows of MEASURES in wf_hip_measure.hip, from the source text: {WF_HIP_OUT_X, sizeof(wf_hip_x), per_row, ...}
+    text = (CSRC / "wf_hip_measure.hip").read_text()
+    table = text[text.index("constexpr Measure MEASURES["):]
+    table = table[:table.index("};")]
+    rows = re.findall(r"\{WF_HIP_OUT_(\w+), sizeof\(wf_hip_(\w+)\), (true|false),", table)
+    assert len(rows) == len(NAMES) == 17 and table.count("{WF_HIP_OUT_") == 17
+    for (out, struct, per_row), (name, (what, dtype, py_per_row)) in zip(rows, binding.MEASURES.items()):
+        assert out.lower() == struct == name, (out, struct, name)
+        assert what == getattr(binding, "OUT_" + out) and dtype is getattr(binding, out + "_DTYPE"), name
+        assert py_per_row is (per_row == "true"), name

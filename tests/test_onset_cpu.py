@@ -64,7 +64,7 @@ def test_both_batch_classes_share_the_reader():
     reader = binding.SpectrumBatch.onset
     assert reader is binding.MultiBatch.onset is binding._MeasureReaders.onset
     assert reader.__doc__ and "onset" not in vars(binding.SpectrumBatch) and "onset" not in vars(binding.MultiBatch)
-    assert "onset" not in binding.MEASURES and len(binding.MEASURES) == 8  # read the way gonio() is
+    assert binding.MEASURES["onset"] == (binding.OUT_ONSET, binding.ONSET_DTYPE, False)
 
 
 def test_columns_and_the_decided_range_per_ring():

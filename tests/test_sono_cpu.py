@@ -57,7 +57,7 @@ def test_both_batch_classes_share_the_reader():
     reader = binding.SpectrumBatch.sono
     assert reader is binding.MultiBatch.sono is binding._MeasureReaders.sono
     assert reader.__doc__ and "sono" not in vars(binding.SpectrumBatch) and "sono" not in vars(binding.MultiBatch)
-    assert "sono" not in binding.MEASURES  # read the way gonio() is
+    assert binding.MEASURES["sono"] == (binding.OUT_SONO, binding.SONO_DTYPE, False)
 
 
 def _tone(freq, amp, frames, sr=SR):

@@ -60,7 +60,7 @@ def test_both_batch_classes_share_the_reader():
     reader = binding.SpectrumBatch.thd
     assert reader is binding.MultiBatch.thd is binding._MeasureReaders.thd
     assert reader.__doc__ and "thd" not in vars(binding.SpectrumBatch) and "thd" not in vars(binding.MultiBatch)
-    assert "thd" not in binding.MEASURES and len(binding.MEASURES) == 8  # read the way gonio() is
+    assert binding.MEASURES["thd"] == (binding.OUT_THD, binding.THD_DTYPE, False)
 
 
 # ---- the host tables ----------------------------------------------------------------------------------------------------------------

@@ -65,7 +65,7 @@ def test_both_batch_classes_share_the_reader():
     reader = binding.SpectrumBatch.xfer
     assert reader is binding.MultiBatch.xfer is binding._MeasureReaders.xfer
     assert reader.__doc__ and "xfer" not in vars(binding.SpectrumBatch) and "xfer" not in vars(binding.MultiBatch)
-    assert "xfer" not in binding.MEASURES and len(binding.MEASURES) == 8  # read the way gonio() is
+    assert binding.MEASURES["xfer"] == (binding.OUT_XFER, binding.XFER_DTYPE, False)
 
 
 # ---- P and K of every ring the library makes ----------------------------------------------------------------------------------------

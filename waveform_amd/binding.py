@@ -294,6 +294,15 @@ MEASURES = {
     "stereo": (OUT_STEREO, STEREO_DTYPE, False),
     "cq": (OUT_CQ, CQ_DTYPE, False),
     "scope": (OUT_SCOPE, SCOPE_DTYPE, False),
+    "gonio": (OUT_GONIO, GONIO_DTYPE, False),
+    "sono": (OUT_SONO, SONO_DTYPE, False),
+    "bits": (OUT_BITS, BITS_DTYPE, False),
+    "thd": (OUT_THD, THD_DTYPE, False),
+    "delay": (OUT_DELAY, DELAY_DTYPE, False),
+    "onset": (OUT_ONSET, ONSET_DTYPE, False),
+    "xfer": (OUT_XFER, XFER_DTYPE, False),
+    "impulse": (OUT_IMPULSE, IMPULSE_DTYPE, False),
+    "click": (OUT_CLICK, CLICK_DTYPE, False),
 }
 
 
@@ -491,9 +500,7 @@ class _MeasureReaders:
         min(fft_size, GONIO_MAX_WINDOW) frames of captured channels 0 and 1, as of the pushes issued so far, fall into each cell
         of the side (x) / mid (y) picture magnified by 2^zoom, with the peaks, the phase counts and the number of occupied cells;
         counted on the device when read (batches with two captured channels)"""
-        # (not through _read_measure: MEASURES keeps the eight keys tests/test_measure_tables_cpu.py pins; folding this reader
-        # into the table is for a change that may touch that test)
-        return self._read(OUT_GONIO, first, count, (), GONIO_DTYPE)
+        return _read_measure(self, "gonio", first, count)
 
     def sono(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_sono (SONO_DTYPE): the sonogram, db[channel][age][band] = the level in dB of band
@@ -502,8 +509,7 @@ class _MeasureReaders:
         for silence, and for channel 1 of a capture of one channel.  Columns are anchored to the counter: the same column reads
         the same bits whenever it is read, and (newest - newest of the last read) mod 2^24 columns are new.  Transformed in float64
         on the device when read, from the rings as of the pushes issued so far (batches whose ring holds at least 2048 frames)"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_SONO, first, count, (), SONO_DTYPE)
+        return _read_measure(self, "sono", first, count)
 
     def bits(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_bits (BITS_DTYPE): the bit meter, per captured channel ch[c] the sample-value
@@ -512,8 +518,7 @@ class _MeasureReaders:
         and the longest run of identical samples (max_run, max_run_start, max_run_value) with the count of repeats, over the
         newest min(fft_size, BITS_MAX_WINDOW) frames of the ring as of the pushes issued so far; counted on the device when read.
         With one captured channel ch[1] is all zero"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_BITS, first, count, (), BITS_DTYPE)
+        return _read_measure(self, "bits", first, count)
 
     def thd(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_thd (THD_DTYPE): the distortion analyser, per captured channel ch[c] the fundamental
@@ -523,8 +528,7 @@ class _MeasureReaders:
         of the ring as of the pushes issued so far, P = `window` the largest power of two <= min(fft_size, THD_MAX_WINDOW);
         transformed in float64 through a 7-term Blackman-Harris taper on the device when read (batches of at least 512 frames).
         With one captured channel ch[1] is all zero"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_THD, first, count, (), THD_DTYPE)
+        return _read_measure(self, "thd", first, count)
 
     def delay(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_delay (DELAY_DTYPE): the delay finder, delay_frames / delay_ms by which captured
@@ -535,8 +539,7 @@ class _MeasureReaders:
         correlation at lag - 32 .. lag + 32) and valid (0 for silence in either channel or a window holding a NaN: every field 0),
         over the newest P frames of both rings as of the pushes issued so far, P = `window` the largest power of two <=
         min(fft_size, DELAY_MAX_WINDOW); in float64 on the device when read (batches with two captured channels)"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_DELAY, first, count, (), DELAY_DTYPE)
+        return _read_measure(self, "delay", first, count)
 
     def onset(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_onset (ONSET_DTYPE): the onset detector.  strength[age] and group[g][age] (g = low,
@@ -550,8 +553,7 @@ class _MeasureReaders:
         about a hop) and last_strength describe the newest.  Columns are anchored to the counter: (newest - newest of the last
         read) mod 2^24 columns are new.  In float64 on the device when read, from the rings as of the pushes issued so far
         (batches whose ring holds at least 8192 frames)"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_ONSET, first, count, (), ONSET_DTYPE)
+        return _read_measure(self, "onset", first, count)
 
     def xfer(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_xfer (XFER_DTYPE): the transfer function of a dual-channel analyser with the programme
@@ -566,8 +568,7 @@ class _MeasureReaders:
         has nothing reads 0 / 0 / 0; valid = 0 (silence in either channel or a NaN in the span) leaves everything but window, hop
         and segments 0.  In float64 on the device when read, from the rings as of the pushes issued so far (batches with two
         captured channels and fft_size >= 256)"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_XFER, first, count, (), XFER_DTYPE)
+        return _read_measure(self, "xfer", first, count)
 
     def impulse(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_impulse (IMPULSE_DTYPE): the impulse response of a dual-channel analyser with the
@@ -582,8 +583,7 @@ class _MeasureReaders:
         overlap of the segments (-3.9 dB at window / 4).  valid = 0 as xfer(); valid = 1 with count = 0 where the measured channel
         is silent under every segment.  In float64 on the device when read, from the rings as of the pushes issued so far (batches
         with two captured channels and fft_size >= 256)"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_IMPULSE, first, count, (), IMPULSE_DTYPE)
+        return _read_measure(self, "impulse", first, count)
 
     def click(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count] structured array of wf_hip_click (CLICK_DTYPE): the click detector, per captured channel ch[c] the clicks, pops
@@ -594,8 +594,7 @@ class _MeasureReaders:
         CLICK_MAX_EVENTS strongest events with start, length, peak, frame (the counter position of start: what a polling host tells
         an event it has seen by), strength_db and amplitude; valid = 0 for digital silence, a NaN or an infinity.  Fitted in float64
         on the device when read (batches of at least 256 frames).  With one captured channel ch[1] is all zero"""
-        # (not through _read_measure, as gonio() above)
-        return self._read(OUT_CLICK, first, count, (), CLICK_DTYPE)
+        return _read_measure(self, "click", first, count)
 
 
 class SpectrumBatch(_MeasureReaders):

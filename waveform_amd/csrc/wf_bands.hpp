@@ -48,14 +48,6 @@ __device__ __forceinline__ double bands_tenth(double x)
     return fma(fma(-10.0, q, x), 0.1, q);
 }
 
-// a value every lane holds, moved to scalar registers: what is decided from it branches for the whole wavefront
-__device__ __forceinline__ double bands_uniform(double v)
-{
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
 __global__ __launch_bounds__(64 * WF_BANDS_WAVES, WF_BANDS_OCC) void bands_read_kernel(const BandsArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(64 * WF_BANDS_WAVES, WF_BANDS_OCC) void bands_read_
     double acc = 0.0;  // this lane's share of band `band`
     double mine = 0.0; // lane b: the sum of band b once it has ended
     uint32_t band = 0; // the band in progress (wave-uniform); the bands below it have ended
-    double lo = bands_uniform(a.edges[0]), hi = bands_uniform(a.edges[1]);
+    double lo = wave_uniform(a.edges[0]), hi = wave_uniform(a.edges[1]);
 
     float4 cur[WF_BANDS_GROUP], nxt[WF_BANDS_GROUP];
 #pragma unroll
@@ -127,7 +119,7 @@ __global__ __launch_bounds__(64 * WF_BANDS_WAVES, WF_BANDS_OCC) void bands_read_
                 ++band;
                 lo = hi;
                 if(band < WF_HIP_NUM_BANDS)
-                    hi = bands_uniform(a.edges[band + 1u]);
+                    hi = wave_uniform(a.edges[band + 1u]);
             }
         }
 #pragma unroll

@@ -7,7 +7,7 @@
 // far, and copies the result back; nothing runs while the output is not read.
 //
 // One workgroup of WF_BITS_THREADS per stream; the ring is read once.
-//   stage    wf_scope.hpp's scope_stage<CH>: the at most two contiguous runs of the window into dynamic LDS; frame i of channel c at
+//   stage    wf_ring_stage.hpp's ring_stage_window<CH>: the at most two contiguous runs of the window into dynamic LDS; frame i of channel c at
 //            x[c][o + i].  The BitsWork follows the windows; its image, the entry as it leaves, is zeroed meanwhile.
 //   count    a wavefront per 64 consecutive frames, lane j the j-th of them.  The code v comes from the sample's sign, exponent and
 //            mantissa by integer shifts (bits_code): no float operation sees the sample, so nothing depends on how the hardware
@@ -40,7 +40,8 @@
 #include <stdint.h>
 #include "wf_hip.h"
 #include "wf_ring_view.hpp"
-#include "wf_scope.hpp" // scope_stage, scope_lds_stride
+#include "wf_ring_stage.hpp"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -51,8 +52,9 @@ struct BitsArgs {
     uint32_t P;              // window <= min(ring_cap, WF_HIP_BITS_MAX_WINDOW), >= 1
 };
 
-constexpr uint32_t WF_BITS_THREADS = WF_SCOPE_THREADS; // (scope_stage strides by it)
+constexpr uint32_t WF_BITS_THREADS = 256;
 constexpr uint32_t WF_BITS_WAVES = WF_BITS_THREADS / 64;
+constexpr uint32_t WF_BITS_UNROLL = 4;                 // float4 loads per channel in flight per lane
 constexpr int WF_BITS_OCC = 4;                         // waves per SIMD the registers allow; the LDS allows two workgroups per CU at the cap
 constexpr uint32_t WF_BITS_MAX_CHUNKS = WF_HIP_BITS_MAX_WINDOW / 64;
 constexpr uint32_t WF_BITS_CH_WORDS = sizeof(wf_hip_bits_channel) / 4; // words of a channel in the image
@@ -61,7 +63,6 @@ static_assert(offsetof(wf_hip_bits_channel, ones) == 512 && offsetof(wf_hip_bits
 static_assert(offsetof(wf_hip_bits_channel, word_length) == 640 && offsetof(wf_hip_bits_channel, max_run_value) == 668);
 static_assert(offsetof(wf_hip_bits, window) == 2 * sizeof(wf_hip_bits_channel));
 static_assert(WF_HIP_BITS_MAX_WINDOW <= 8192, "the run key holds 13 bits of start, and a uint16 count must not overflow");
-static_assert(WF_HIP_BITS_MAX_WINDOW <= WF_HIP_SCOPE_MAX_WINDOW); // (scope_lds_stride and scope_stage are sized by the latter)
 
 // what follows the staged windows in dynamic LDS
 struct BitsWork {
@@ -72,10 +73,11 @@ struct BitsWork {
 };
 static_assert(offsetof(BitsWork, heads) % 8 == 0);
 
-__host__ __device__ inline size_t bits_lds_bytes(uint32_t channels, uint32_t P)
+__host__ __device__ constexpr size_t bits_lds_bytes(uint32_t channels, uint32_t P)
 {
-    return (size_t)channels * scope_lds_stride(P) * sizeof(float) + sizeof(BitsWork);
+    return (size_t)channels * ring_stage_stride(P) * sizeof(float) + sizeof(BitsWork);
 }
+static_assert(2 * bits_lds_bytes(2, WF_HIP_BITS_MAX_WINDOW) <= WF_LDS_PER_CU, "two workgroups to a CU at the cap");
 
 // The code of a float32 pattern u: v = clamp(floor(x 2^31)) on the int32 grid, whether x 2^31 lies outside the grid and whether
 // it has bits below it.  |x| = M 2^(e - 150) with M the 24-bit significand (no hidden bit and e = 1 for a denormal), so
@@ -105,21 +107,6 @@ __device__ __forceinline__ int32_t bits_code(uint32_t u, bool &over, bool &fine)
     return neg ? -(int32_t)I - (frac ? 1 : 0) : (int32_t)I;
 }
 
-__device__ __forceinline__ uint32_t bits_wave_or(uint32_t v)
-{
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1)
-        v |= __shfl_xor(v, off, 64);
-    return v;
-}
-
-// a 64-bit word that every lane read from the same address, as the wave-uniform value it is
-__device__ __forceinline__ unsigned long long bits_uniform(unsigned long long v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // grid: one workgroup per stream of [first, first + gridDim.x); dynamic LDS: bits_lds_bytes(CH, P)
 template<int CH>
 __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel(const BitsArgs a)
@@ -129,7 +116,7 @@ __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel
     const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const uint32_t stream = a.first + blockIdx.x;
     const uint32_t P = a.P;
-    const uint32_t S = scope_lds_stride(P);
+    const uint32_t S = ring_stage_stride(P);
     BitsWork &w = *reinterpret_cast<BitsWork *>(bits_x + (size_t)CH * S);
     const uint32_t ring_cap = a.rings.ring_cap;
     const uint32_t s = window_start(a.rings, stream, P) & (ring_cap - 1u);
@@ -139,10 +126,7 @@ __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel
     const uint32_t *x0 = reinterpret_cast<const uint32_t *>(bits_x) + o; // x_c[i] = x0[c S + i], as patterns
     const uint32_t chunks = (P + 63u) / 64u;
 
-    const uint32_t end = s + P; // <= 2 ring_cap
-    scope_stage<CH>(bits_x, S, r0, r1, s, end < ring_cap ? end : ring_cap, o - s);
-    if(end > ring_cap)
-        scope_stage<CH>(bits_x, S, r0, r1, 0u, end - ring_cap, o + (ring_cap - s));
+    ring_stage_window<CH, WF_BITS_THREADS, WF_BITS_UNROLL>(bits_x, S, r0, r1, s, P, ring_cap);
     for(uint32_t i = t; i < sizeof(wf_hip_bits) / 4u; i += WF_BITS_THREADS)
         w.image[i] = 0u;
     __syncthreads();
@@ -195,8 +179,8 @@ __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel
                 __hip_atomic_fetch_add(&img[bin >> 1], (next - lane) << (16u * (bin & 1u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
-        or_v = bits_wave_or(or_v);
-        or_s = bits_wave_or(or_s);
+        or_v = wave_or(or_v);
+        or_s = wave_or(or_s);
         if(lane < 32u) { // (zeros from a wave that had no chunk)
             const uint32_t sh = 16u * (lane & 1u);
             __hip_atomic_fetch_add(&img[offsetof(wf_hip_bits_channel, ones) / 4u + lane / 2u], ones << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel
     for(int c = 0; c < CH; ++c) {
         uint32_t key = 0u; // (length << 13) | (8191 - start): every run's is different, and every window has a run
         for(uint32_t g = wave; g < chunks; g += WF_BITS_WAVES) {
-            const unsigned long long H = bits_uniform(w.heads[c][g]);
+            const unsigned long long H = wave_uniform(w.heads[c][g]);
             if(H == 0)
                 continue;
             // where the run of the chunk's last head ends: the first head of the first later chunk that has one
@@ -228,7 +212,7 @@ __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel
                 const unsigned long long some = __ballot(Hk != 0);
                 if(some != 0) {
                     const uint32_t kk = k0 + (uint32_t)__builtin_ctzll(some);
-                    far = 64u * kk + (uint32_t)__builtin_ctzll(bits_uniform(w.heads[c][kk]));
+                    far = 64u * kk + (uint32_t)__builtin_ctzll(wave_uniform(w.heads[c][kk]));
                     break;
                 }
             }
@@ -240,11 +224,7 @@ __global__ __launch_bounds__(WF_BITS_THREADS, WF_BITS_OCC) void bits_read_kernel
                 key = key > k ? key : k;
             }
         }
-#pragma unroll
-        for(int off = 32; off > 0; off >>= 1) {
-            const uint32_t k = __shfl_xor(key, off, 64);
-            key = key > k ? key : k;
-        }
+        key = wave_max(key);
         if(lane == 0u)
             w.key[c][wave] = key;
     }

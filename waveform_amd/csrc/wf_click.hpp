@@ -25,8 +25,8 @@
 //              wave, then of the four.  A hit starts an event if the 32 bits below it are clear (a thread per word); an event's
 //              number is the count of starts up to its hit.  Per event, integer LDS atomics: the largest ratio as the pattern of
 //              a positive double, the last hit, then the first hit whose ratio is that largest.  Words without a hit are skipped.
-//   list       a thread per event (at most 248: starts lie more than 32 frames apart); eight rounds of thd_wave_argmax /
-//              thd_better over ((double) strength_db, start), the winner writes its slot and leaves.
+//   list       a thread per event (at most 248: starts lie more than 32 frames apart); eight rounds of wave_argmax /
+//              argmax_better over ((double) strength_db, start), the winner writes its slot and leaves.
 //   leave      the channel's 224 bytes from an image in LDS; channel 0's workgroup writes the tail, and with CH == 1 the zero ch[1].
 // No float atomics: every float sum has the order above, every other accumulation is an integer count, a maximum or a minimum.
 // Measured on an MI355X (tools/click_bench.py, profiles/click_kernel_stats.json; 4096 stereo streams, the read's 1.9 MB copy into
@@ -42,7 +42,6 @@
 #include "wf_hip.h"
 #include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
-#include "wf_thd.hpp" // thd_better, thd_wave_argmax
 
 namespace wf {
 
@@ -188,11 +187,7 @@ __global__ __launch_bounds__(WF_CLICK_THREADS) void click_read_kernel(const Clic
     }
     if(t < WF_CLICK_CH_WORDS)
         w.image[t] = 0u;
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = __shfl_xor(amax, off, 64);
-        amax = amax > o ? amax : o;
-    }
+    amax = wave_max(amax);
     const bool wave_bad = __ballot(bad) != 0ull;
     if(lane == 0u) {
         w.amax[wave] = amax;
@@ -345,9 +340,7 @@ __global__ __launch_bounds__(WF_CLICK_THREADS) void click_read_kernel(const Clic
             nhit += (uint32_t)__popcll(H);
             pk = __builtin_fmax(pk, ratio);
         }
-#pragma unroll
-        for(int off = 32; off > 0; off >>= 1)
-            pk = __builtin_fmax(pk, __shfl_xor(pk, off, 64));
+        pk = wave_max(pk);
         if(lane == 0u) {
             w.pk[wave] = pk;
             w.nhit[wave] = nhit;
@@ -412,7 +405,7 @@ __global__ __launch_bounds__(WF_CLICK_THREADS) void click_read_kernel(const Clic
     for(uint32_t round = 0; round < listed; ++round) {
         double best = mine;
         uint32_t kbest = my_start;
-        thd_wave_argmax(best, kbest);
+        wave_argmax(best, kbest);
         if(lane == 0u) {
             w.arg_v[round & 1u][wave] = best;
             w.arg_k[round & 1u][wave] = kbest;
@@ -422,7 +415,7 @@ __global__ __launch_bounds__(WF_CLICK_THREADS) void click_read_kernel(const Clic
         kbest = w.arg_k[round & 1u][0];
 #pragma unroll
         for(uint32_t k = 1; k < WF_CLICK_WAVES; ++k)
-            thd_better(best, kbest, w.arg_v[round & 1u][k], w.arg_k[round & 1u][k]);
+            argmax_better(best, kbest, w.arg_v[round & 1u][k], w.arg_k[round & 1u][k]);
         if(t < events && my_start == kbest && mine == best) { // (starts differ: one thread)
             const uint32_t peak = w.ev_peak[t];
             uint32_t *ev = w.image + offsetof(wf_hip_click_channel, ev) / 4u + round * (uint32_t)(sizeof(wf_hip_click_event) / 4u);

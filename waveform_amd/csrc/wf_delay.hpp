@@ -19,7 +19,7 @@
 //   transform  fft64_load16 fetches from zb and stores its rows into za (G is spent by then): the fetch reads one region and the
 //              row stores fall into the other, so they cannot race.  za = y, and R[n] = Re y[-n] / (2 (M - 1)),
 //              C[n] = g Im y[-n] / (2 sqrt(E_0 E_1)).
-//   argmax     threads stride over the 2 L + 1 lags from -L up; thd_better with the index n + L: the larger |R| wins and the lower
+//   argmax     threads stride over the 2 L + 1 lags from -L up; argmax_better with the index n + L: the larger |R| wins and the lower
 //              lag a tie.  Then the largest |R| more than two lags away from it.
 //   fraction   zb still holds Y, which the transform only read: A[k] = (Y[k] + conj Y[P - k]) / 2 comes back from it to one
 //              rounding of a value <= 1 (this is the choice "keep A in the second region"), u[k] = |A[k]|, and the rotation
@@ -34,7 +34,7 @@
 #include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
 #include "wf_fft64_lds.hpp"
-#include "wf_thd.hpp" // thd_better, thd_wave_argmax
+#include "wf_phat.hpp"
 
 namespace wf {
 
@@ -51,17 +51,8 @@ struct DelayArgs {
 
 constexpr uint32_t WF_DELAY_THREADS = 256;
 constexpr uint32_t WF_DELAY_WAVES = WF_DELAY_THREADS / 64;
-constexpr double WF_DELAY_BETA = 1e-3; // the floor of the PHAT weighting: 60 dB under the strongest cross-power
 static_assert(WF_DELAY_THREADS * 16 == WF_HIP_DELAY_MAX_WINDOW, "one thread per 16 frames of the largest window");
 static_assert(WF_HIP_DELAY_CURVE <= WF_DELAY_THREADS && (WF_HIP_DELAY_CURVE & 1) == 1, "a lane per curve entry, the peak in the middle");
-
-__device__ __forceinline__ double delay_wave_max(double v)
-{
-#pragma unroll
-    for(int i = 0; i < 6; ++i)
-        v = fmax(v, __shfl_xor(v, 32 >> i, 64));
-    return v;
-}
 
 // grid: one workgroup per stream of [first, first + gridDim.x); dynamic LDS: 2 * P * sizeof(double2)
 __global__ __launch_bounds__(WF_DELAY_THREADS) void delay_read_kernel(const DelayArgs a)
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(WF_DELAY_THREADS) void delay_read_kernel(const Dela
         e1 += rr * rr + ri * ri;
         za[ia] = make_double2(gr, gi);
     }
-    g = delay_wave_max(g);
+    g = wave_max(g);
     e0 = wave_sum(e0);
     e1 = wave_sum(e1);
     if(lane == 0u) {
@@ -185,7 +176,7 @@ __global__ __launch_bounds__(WF_DELAY_THREADS) void delay_read_kernel(const Dela
             kbest = i;
         }
     }
-    thd_wave_argmax(best, kbest);
+    wave_argmax(best, kbest);
     if(lane == 0u) {
         arg_v[wave] = best;
         arg_k[wave] = kbest;
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(WF_DELAY_THREADS) void delay_read_kernel(const Dela
     kbest = arg_k[0];
 #pragma unroll
     for(uint32_t w = 1; w < WF_DELAY_WAVES; ++w)
-        thd_better(best, kbest, arg_v[w], arg_k[w]);
+        argmax_better(best, kbest, arg_v[w], arg_k[w]);
     const int32_t n0 = (int32_t)kbest - (int32_t)L;
 
     // the second peak: the largest |R| more than two lags from n0
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(WF_DELAY_THREADS) void delay_read_kernel(const Dela
         if(dist > 2u)
             second = fmax(second, fabs(R((int32_t)i - (int32_t)L)));
     }
-    second = delay_wave_max(second);
+    second = wave_max(second);
     if(lane == 0u)
         second_v[wave] = second;
 

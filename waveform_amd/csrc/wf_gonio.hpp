@@ -6,7 +6,7 @@
 // handle's stream, behind every push issued so far, and copies the result back; nothing runs while the output is not read.
 //
 // One workgroup of WF_GONIO_THREADS per stream; the ring is read once.
-//   stage    wf_scope.hpp's scope_stage<2>: the at most two contiguous runs of the window into dynamic LDS, 16-B words over the
+//   stage    wf_ring_stage.hpp's ring_stage_window<2>: the at most two contiguous runs of the window into dynamic LDS, 16-B words over the
 //            aligned body, element by element over the at most 3 frames around it; frame i of channel c at x[c][o + i].
 //   pass one the largest |sample| as an integer maximum over the samples' bits less their sign (the order of non-negative floats
 //            is the order of their bits: nothing depends on how the hardware treats denormals), max |mid| and max |side| in
@@ -39,7 +39,8 @@
 #include <stdint.h>
 #include "wf_hip.h"
 #include "wf_ring_view.hpp"
-#include "wf_scope.hpp" // scope_stage, scope_lds_stride
+#include "wf_ring_stage.hpp"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -50,13 +51,13 @@ struct GonioArgs {
     uint32_t P;              // window <= min(ring_cap, WF_HIP_GONIO_MAX_WINDOW), >= 1
 };
 
-constexpr uint32_t WF_GONIO_THREADS = WF_SCOPE_THREADS; // (scope_stage strides by it)
+constexpr uint32_t WF_GONIO_THREADS = 256;
 constexpr uint32_t WF_GONIO_WAVES = WF_GONIO_THREADS / 64;
+constexpr uint32_t WF_GONIO_UNROLL = 4;                  // float4 loads per channel in flight per lane
 constexpr int WF_GONIO_OCC = 4;                         // waves per SIMD the registers allow; the LDS allows two workgroups per CU at the cap
 constexpr uint32_t WF_GONIO_CELLS = WF_HIP_GONIO_GRID * WF_HIP_GONIO_GRID;
 static_assert(WF_GONIO_THREADS == 256 && sizeof(wf_hip_gonio) % 16 == 0 && offsetof(wf_hip_gonio, window) == WF_GONIO_CELLS * 2);
 static_assert(sizeof(wf_hip_gonio) - offsetof(wf_hip_gonio, window) == 32 && WF_HIP_GONIO_MAX_WINDOW < 65536);
-static_assert(WF_HIP_GONIO_MAX_WINDOW <= WF_HIP_SCOPE_MAX_WINDOW); // (scope_lds_stride and scope_stage are sized by the latter)
 
 // what follows the staged windows in dynamic LDS
 struct GonioWork {
@@ -66,15 +67,8 @@ struct GonioWork {
 };
 static_assert(offsetof(GonioWork, mid) % 8 == 0);
 
-__host__ __device__ inline size_t gonio_lds_bytes(uint32_t P) { return (size_t)2 * scope_lds_stride(P) * sizeof(float) + sizeof(GonioWork); }
-
-__device__ __forceinline__ uint32_t gonio_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
+__host__ __device__ constexpr size_t gonio_lds_bytes(uint32_t P) { return (size_t)2 * ring_stage_stride(P) * sizeof(float) + sizeof(GonioWork); }
+static_assert(2 * gonio_lds_bytes(WF_HIP_GONIO_MAX_WINDOW) <= WF_LDS_PER_CU, "two workgroups to a CU at the cap");
 
 // the cell index of a coordinate: min and max in floating point before the conversion, so no index leaves the grid
 __device__ __forceinline__ uint32_t gonio_index(double u)
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(WF_GONIO_THREADS, WF_GONIO_OCC) void gonio_read_ker
     const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const uint32_t stream = a.first + blockIdx.x;
     const uint32_t P = a.P;
-    const uint32_t S = scope_lds_stride(P);
+    const uint32_t S = ring_stage_stride(P);
     GonioWork &w = *reinterpret_cast<GonioWork *>(gonio_x + (size_t)2 * S);
     const uint32_t ring_cap = a.rings.ring_cap;
     const uint32_t s = window_start(a.rings, stream, P) & (ring_cap - 1u);
@@ -100,10 +94,7 @@ __global__ __launch_bounds__(WF_GONIO_THREADS, WF_GONIO_OCC) void gonio_read_ker
     const float *r1 = channel_ring(a.rings, stream, 1, 2);
     const float *x0 = gonio_x + o, *x1 = x0 + S; // x_c[i]
 
-    const uint32_t end = s + P; // <= 2 ring_cap
-    scope_stage<2>(gonio_x, S, r0, r1, s, end < ring_cap ? end : ring_cap, o - s);
-    if(end > ring_cap)
-        scope_stage<2>(gonio_x, S, r0, r1, 0u, end - ring_cap, o + (ring_cap - s));
+    ring_stage_window<2, WF_GONIO_THREADS, WF_GONIO_UNROLL>(gonio_x, S, r0, r1, s, P, ring_cap);
     for(uint32_t i = t; i < sizeof(wf_hip_gonio) / 4u; i += WF_GONIO_THREADS)
         w.image[i] = 0u;
     __syncthreads();
@@ -125,15 +116,14 @@ __global__ __launch_bounds__(WF_GONIO_THREADS, WF_GONIO_OCC) void gonio_read_ker
         in_phase += both && same ? 1u : 0u;
         out_phase += both && !same ? 1u : 0u;
     }
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1) {
-        const uint32_t p = __shfl_xor(peak, off, 64);
+    wave_butterfly([&](auto other) {
+        const uint32_t p = other(peak);
         peak = peak > p ? peak : p;
-        mid = __builtin_fmax(mid, __shfl_xor(mid, off, 64));
-        side = __builtin_fmax(side, __shfl_xor(side, off, 64));
-    }
-    in_phase = gonio_wave_sum(in_phase);
-    out_phase = gonio_wave_sum(out_phase);
+        mid = __builtin_fmax(mid, other(mid));
+        side = __builtin_fmax(side, other(side));
+    });
+    in_phase = wave_sum(in_phase);
+    out_phase = wave_sum(out_phase);
     if(lane == 0) {
         w.peak[wave] = peak;
         w.mid[wave] = mid;
@@ -193,7 +183,7 @@ __global__ __launch_bounds__(WF_GONIO_THREADS, WF_GONIO_OCC) void gonio_read_ker
         const uint32_t c = w.image[i];
         occupied += ((c & 0xffffu) != 0u ? 1u : 0u) + ((c >> 16) != 0u ? 1u : 0u);
     }
-    occupied = gonio_wave_sum(occupied);
+    occupied = wave_sum(occupied);
     if(lane == 0)
         w.occupied[wave] = occupied;
     __syncthreads();

@@ -184,21 +184,14 @@ struct wf_hip {
         double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_ONSET_BANDS + 1] band edges in bins of P
         uint32_t spectral = 0;                    // Ts = T + 1 spectral columns
     } onset;
-    // what WF_HIP_OUT_XFER derives from the configuration and the ring (setup_xfer, at its first read: wf::host::delay_tables at its
-    // own P; wf_xfer.hpp)
-    struct Xfer {
+    // what WF_HIP_OUT_XFER and WF_HIP_OUT_IMPULSE derive from the configuration and the ring (setup_xfer_plan, at each output's first
+    // read: wf::host::delay_tables at their own P; wf_xfer.hpp, wf_impulse.hpp).  A plan and a block each, so that neither output
+    // needs the other read first
+    struct XferPlan {
         double *d_tab = nullptr;                  // [P] taper, [P / 2][2] twiddles
         uint32_t P = 0, log2p = 0;                // the segment: a power of two
         uint32_t K = 0;                           // segments
-    } xfer;
-    // what WF_HIP_OUT_IMPULSE derives from the configuration and the ring (setup_impulse, at its first read: the transfer
-    // function's geometry and wf::host::delay_tables at that P, a block of its own so that neither output needs the other read
-    // first; wf_impulse.hpp)
-    struct Impulse {
-        double *d_tab = nullptr;                  // [P] taper, [P / 2][2] twiddles
-        uint32_t P = 0, log2p = 0;                // the segment: a power of two
-        uint32_t K = 0;                           // segments
-    } impulse;
+    } xfer, impulse;
     uint32_t rms_cap = 0, rms_size = 0;
     // waveform batches (cfg.waveform): N = M = width (points per row), there is no FFT state
     bool wave = false;

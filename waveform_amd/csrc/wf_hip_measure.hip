@@ -7,9 +7,12 @@
 // and is switched on by wf_hip_enable_loudness.  gfx950 only.
 //
 // A new measurement output: its kernel in a header of its own, included here and nowhere else, with a wf::RingView in its
-// arguments if it reads the rings; if it needs tables, a builder in wf_measure_tables.cpp that sees no handle and no HIP, and a
-// setup function here that calls it, keeps the scalars on the handle and uploads; a launch function, a refusal function and a
-// row of MEASURES below; a row of MEASURES and a reader on _MeasureReaders in waveform_amd/binding.py.
+// arguments if it reads the rings.  What kernels share lies in headers that hold no kernel (wf_wave_reduce.hpp, wf_ring_stage.hpp,
+// wf_fft64_lds.hpp, wf_phat.hpp): no kernel header includes another output's, but for wf_xfer.hpp and wf_impulse.hpp over
+// wf_xfer_sums.hpp, the head they share.  If it needs tables, a builder in wf_measure_tables.cpp that sees no handle and no HIP, and a
+// setup function here that calls it, keeps the scalars on the handle, states its kernels' dynamic LDS (allow_lds) and uploads; a
+// launch function (launch_by_channels where the kernel is instantiated per captured channels), a refusal function and a row of
+// MEASURES below; a row of MEASURES and a reader on _MeasureReaders in waveform_amd/binding.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,6 +56,29 @@ int clear_loudness(wf_hip *h, uint32_t first, uint32_t count)
 // how the kernels that read the rings see them
 wf::RingView ring_view(const wf_hip *h) { return wf::RingView{h->d_ring, h->d_wpos, h->ring_cap, h->ring_stride}; }
 
+// The <1> or <2> instantiation of a kernel by the batch's captured channels, each on its own grid
+template<class Args>
+void launch_by_channels(const wf_hip *h, void (*one)(Args), void (*two)(Args), dim3 grid_one, dim3 grid_two, uint32_t threads, size_t lds, const Args &a)
+{
+    if(h->cap_ch == 2)
+        hipLaunchKernelGGL(two, grid_two, dim3(threads), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(one, grid_one, dim3(threads), lds, h->stream, a);
+}
+// ... and on the same grid
+template<class Args>
+void launch_by_channels(const wf_hip *h, void (*one)(Args), void (*two)(Args), dim3 grid, uint32_t threads, size_t lds, const Args &a)
+{
+    launch_by_channels(h, one, two, grid, grid, threads, lds, a);
+}
+
+// what a kernel may ask for as dynamic LDS: a setup function states the most its launches will
+template<class Kernel> int allow_lds(wf_hip *h, Kernel *kernel, size_t bytes)
+{
+    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return WF_HIP_OK;
+}
+
 // One launch function per output: the entries of streams [first, first+count) into d_block, the output's whole block.
 // Loudness: the readings are made from the state when asked for, behind the pushes issued so far
 int launch_loudness(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
@@ -85,10 +111,7 @@ int launch_signal(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.out = static_cast<wf_hip_signal *>(d_block) + first;
     a.first = first;
     a.W = h->N; // (<= ring_cap: wf_hip_create sizes the ring from it)
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::signal_read_kernel<2>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::signal_read_kernel<1>, dim3(count), dim3(wf::WF_SIGNAL_THREADS), 0, h->stream, a);
+    launch_by_channels(h, wf::signal_read_kernel<1>, wf::signal_read_kernel<2>, dim3(count), wf::WF_SIGNAL_THREADS, 0, a);
     return WF_HIP_OK;
 }
 
@@ -101,10 +124,7 @@ int launch_pitch(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.sample_rate = (double)h->cfg.sample_rate;
     a.first = first;
     a.P = std::min<uint32_t>(h->N, WF_HIP_PITCH_MAX_WINDOW); // (a multiple of 16 on spectrum and meter batches; <= ring_cap)
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::pitch_read_kernel<2>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::pitch_read_kernel<1>, dim3(count), dim3(wf::WF_PITCH_THREADS), 0, h->stream, a);
+    launch_by_channels(h, wf::pitch_read_kernel<1>, wf::pitch_read_kernel<2>, dim3(count), wf::WF_PITCH_THREADS, 0, a);
     return WF_HIP_OK;
 }
 
@@ -148,8 +168,7 @@ int setup_stereo(wf_hip *h)
     s.log2p = t.log2p;
     s.covered = t.covered;
     // (64 KB at P = 4096: the most a workgroup gets without asking; asked for all the same, so that the limit is stated here)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::stereo_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(WF_HIP_STEREO_MAX_WINDOW * sizeof(double2))));
+    WF_TRY_RC(allow_lds(h, wf::stereo_read_kernel, WF_HIP_STEREO_MAX_WINDOW * sizeof(double2)));
     return upload(h, &s.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
 
@@ -181,8 +200,8 @@ int setup_cq(wf_hip *h)
     q.first_resolved = t.first_resolved;
     // (128 KB at the cap with two channels: more than a workgroup gets without asking)
     const int lds = (int)(WF_HIP_CQ_MAX_WINDOW * 2 * sizeof(float));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::cq_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds / 2));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::cq_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    WF_TRY_RC(allow_lds(h, wf::cq_read_kernel<1>, lds / 2));
+    WF_TRY_RC(allow_lds(h, wf::cq_read_kernel<2>, lds));
     // (pageable memory: staged before the call returns, so `t` may go.  A retry after a failed second upload keeps the first)
     if(q.d_sched == nullptr)
         WF_TRY_RC(upload(h, &q.d_sched, t.sched));
@@ -203,10 +222,7 @@ int launch_cq(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.end_covered = q.end_covered;
     a.first_resolved = q.first_resolved;
     const size_t lds = (size_t)h->cap_ch * q.max_window * sizeof(float);
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::cq_read_kernel<2>, dim3(count), dim3(wf::WF_CQ_THREADS), lds, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::cq_read_kernel<1>, dim3(count), dim3(wf::WF_CQ_THREADS), lds, h->stream, a);
+    launch_by_channels(h, wf::cq_read_kernel<1>, wf::cq_read_kernel<2>, dim3(count), wf::WF_CQ_THREADS, lds, a);
     return WF_HIP_OK;
 }
 
@@ -218,10 +234,8 @@ int setup_scope(wf_hip *h)
 {
     // (about 71 KB at the cap with two channels, the windows and the kernel's working set behind them: more than a workgroup
     // gets without asking, and two workgroups to a CU)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::scope_lds_bytes(1, WF_HIP_SCOPE_MAX_WINDOW)));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::scope_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::scope_lds_bytes(2, WF_HIP_SCOPE_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::scope_read_kernel<1>, wf::scope_lds_bytes(1, WF_HIP_SCOPE_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::scope_read_kernel<2>, wf::scope_lds_bytes(2, WF_HIP_SCOPE_MAX_WINDOW)));
     return WF_HIP_OK;
 }
 
@@ -236,10 +250,7 @@ int launch_scope(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.V = a.P / 2;
     a.K = std::min<uint32_t>(WF_HIP_SCOPE_COLUMNS, a.V);
     const size_t lds = wf::scope_lds_bytes(h->cap_ch, a.P);
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::scope_read_kernel<2>, dim3(count), dim3(wf::WF_SCOPE_THREADS), lds, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::scope_read_kernel<1>, dim3(count), dim3(wf::WF_SCOPE_THREADS), lds, h->stream, a);
+    launch_by_channels(h, wf::scope_read_kernel<1>, wf::scope_read_kernel<2>, dim3(count), wf::WF_SCOPE_THREADS, lds, a);
     return WF_HIP_OK;
 }
 
@@ -251,8 +262,7 @@ int setup_gonio(wf_hip *h)
 {
     // (about 74 KB at the cap, both windows and the entry's image behind them: more than a workgroup gets without asking, and two
     // workgroups to a CU)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::gonio_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::gonio_lds_bytes(WF_HIP_GONIO_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::gonio_read_kernel, wf::gonio_lds_bytes(WF_HIP_GONIO_MAX_WINDOW)));
     return WF_HIP_OK;
 }
 
@@ -278,10 +288,8 @@ int setup_sono(wf_hip *h)
     s.end_covered = t.end_covered;
     // (64 KB, four columns' transforms: the most a workgroup gets without asking; asked for all the same, so that the limit is
     // stated here.  Two workgroups to a CU)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::sono_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::WF_SONO_LDS_BYTES));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::sono_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::WF_SONO_LDS_BYTES));
+    WF_TRY_RC(allow_lds(h, wf::sono_read_kernel<1>, wf::WF_SONO_LDS_BYTES));
+    WF_TRY_RC(allow_lds(h, wf::sono_read_kernel<2>, wf::WF_SONO_LDS_BYTES));
     return upload(h, &s.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
 
@@ -304,10 +312,7 @@ int launch_sono(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
         const dim3 grid((s.columns + wf::WF_SONO_WAVES - 1) / wf::WF_SONO_WAVES, std::min(65535u, count - off));
         a.out = static_cast<wf_hip_sono *>(d_block) + first + off;
         a.first = first + off;
-        if(h->cap_ch == 2)
-            hipLaunchKernelGGL(wf::sono_read_kernel<2>, grid, dim3(wf::WF_SONO_THREADS), wf::WF_SONO_LDS_BYTES, h->stream, a);
-        else
-            hipLaunchKernelGGL(wf::sono_read_kernel<1>, grid, dim3(wf::WF_SONO_THREADS), wf::WF_SONO_LDS_BYTES, h->stream, a);
+        launch_by_channels(h, wf::sono_read_kernel<1>, wf::sono_read_kernel<2>, grid, wf::WF_SONO_THREADS, wf::WF_SONO_LDS_BYTES, a);
     }
     return WF_HIP_OK;
 }
@@ -320,10 +325,8 @@ int setup_bits(wf_hip *h)
 {
     // (about 69 KB at the cap with two channels, the windows and the kernel's working set behind them: more than a workgroup
     // gets without asking, and two workgroups to a CU)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::bits_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::bits_lds_bytes(1, WF_HIP_BITS_MAX_WINDOW)));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::bits_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::bits_lds_bytes(2, WF_HIP_BITS_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::bits_read_kernel<1>, wf::bits_lds_bytes(1, WF_HIP_BITS_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::bits_read_kernel<2>, wf::bits_lds_bytes(2, WF_HIP_BITS_MAX_WINDOW)));
     return WF_HIP_OK;
 }
 
@@ -336,10 +339,7 @@ int launch_bits(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.first = first;
     a.P = bits_window(h);
     const size_t lds = wf::bits_lds_bytes(h->cap_ch, a.P);
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::bits_read_kernel<2>, dim3(count), dim3(wf::WF_BITS_THREADS), lds, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::bits_read_kernel<1>, dim3(count), dim3(wf::WF_BITS_THREADS), lds, h->stream, a);
+    launch_by_channels(h, wf::bits_read_kernel<1>, wf::bits_read_kernel<2>, dim3(count), wf::WF_BITS_THREADS, lds, a);
     return WF_HIP_OK;
 }
 
@@ -353,8 +353,8 @@ int setup_thd(wf_hip *h)
     d.S = t.S;
     // (128 KB at P = 8192: twice what a workgroup gets without asking, and one workgroup to a CU)
     const int lds = (int)(WF_HIP_THD_MAX_WINDOW * sizeof(double2));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::thd_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::thd_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    WF_TRY_RC(allow_lds(h, wf::thd_read_kernel<1>, lds));
+    WF_TRY_RC(allow_lds(h, wf::thd_read_kernel<2>, lds));
     return upload(h, &d.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
 
@@ -373,10 +373,7 @@ int launch_thd(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.P = d.P; // (<= fft_size <= ring_cap)
     a.log2p = d.log2p;
     const size_t lds = (size_t)d.P * sizeof(double2);
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::thd_read_kernel<2>, dim3(count), dim3(wf::WF_THD_THREADS), lds, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::thd_read_kernel<1>, dim3(count), dim3(wf::WF_THD_THREADS), lds, h->stream, a);
+    launch_by_channels(h, wf::thd_read_kernel<1>, wf::thd_read_kernel<2>, dim3(count), wf::WF_THD_THREADS, lds, a);
     return WF_HIP_OK;
 }
 
@@ -389,7 +386,7 @@ int setup_delay(wf_hip *h)
     d.log2p = t.log2p;
     // (two regions, 128 KB at P = 4096: twice what a workgroup gets without asking, and one workgroup to a CU)
     const int lds = (int)(2 * WF_HIP_DELAY_MAX_WINDOW * sizeof(double2));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::delay_read_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    WF_TRY_RC(allow_lds(h, wf::delay_read_kernel, lds));
     return upload(h, &d.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
 
@@ -419,10 +416,8 @@ int setup_onset(wf_hip *h)
     o.spectral = std::min<uint32_t>(WF_HIP_ONSET_COLUMNS + 1, (h->ring_cap - WF_HIP_ONSET_WINDOW) / WF_HIP_ONSET_HOP); // (>= 28: why_no_onset)
     // (about 69 KB, four columns' transforms, the round's levels and the entry's strengths: more than a workgroup gets without
     // asking, and two workgroups to a CU)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::onset_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::WF_ONSET_LDS_BYTES));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::onset_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::WF_ONSET_LDS_BYTES));
+    WF_TRY_RC(allow_lds(h, wf::onset_read_kernel<1>, wf::WF_ONSET_LDS_BYTES));
+    WF_TRY_RC(allow_lds(h, wf::onset_read_kernel<2>, wf::WF_ONSET_LDS_BYTES));
     return upload(h, &o.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
 
@@ -440,18 +435,15 @@ int launch_onset(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.edges = o.d_tab + 2 * (size_t)P;
     a.first = first;
     a.spectral = o.spectral;
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::onset_read_kernel<2>, dim3(count), dim3(wf::WF_ONSET_THREADS), wf::WF_ONSET_LDS_BYTES, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::onset_read_kernel<1>, dim3(count), dim3(wf::WF_ONSET_THREADS), wf::WF_ONSET_LDS_BYTES, h->stream, a);
+    launch_by_channels(h, wf::onset_read_kernel<1>, wf::onset_read_kernel<2>, dim3(count), wf::WF_ONSET_THREADS, wf::WF_ONSET_LDS_BYTES, a);
     return WF_HIP_OK;
 }
 
-// what the transfer function derives from the configuration and the ring: P and K, and the delay finder's tables at that P
-int setup_xfer(wf_hip *h)
+// what the transfer function and the impulse response derive from the configuration and the ring: P and K, and the delay finder's
+// tables at that P.  Each output's first read makes a plan of its own, so neither needs the other read first
+int setup_xfer_plan(wf_hip *h, wf_hip::XferPlan &x)
 {
-    wf_hip::Xfer &x = h->xfer;
-    const uint32_t P = xfer_window(h->N, h->ring_cap); // (>= 64: why_no_xfer)
+    const uint32_t P = xfer_window(h->N, h->ring_cap); // (>= 64: why_no_xfer, why_no_impulse)
     const DelayTables t = delay_tables(P);             // (a power of two <= WF_HIP_DELAY_MAX_WINDOW: its own window)
     x.P = t.P;
     x.log2p = t.log2p;
@@ -459,11 +451,13 @@ int setup_xfer(wf_hip *h)
     // (48 KB of dynamic LDS at the cap: what a workgroup gets without asking)
     return upload(h, &x.d_tab, t.tab); // (pageable memory: staged before the call returns)
 }
+int setup_xfer(wf_hip *h) { return setup_xfer_plan(h, h->xfer); }
+int setup_impulse(wf_hip *h) { return setup_xfer_plan(h, h->impulse); }
 
 // one workgroup per stream over the K newest anchored segments of both captured channels, behind the pushes issued
 int launch_xfer(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
-    const wf_hip::Xfer &x = h->xfer;
+    const wf_hip::XferPlan &x = h->xfer;
     wf::XferArgs a{};
     a.rings = ring_view(h); // (two captured channels: why_no_xfer)
     a.out = static_cast<wf_hip_xfer *>(d_block) + first;
@@ -477,23 +471,10 @@ int launch_xfer(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
-// what the impulse response derives from the configuration and the ring: the transfer function's P and K and the same tables
-int setup_impulse(wf_hip *h)
-{
-    wf_hip::Impulse &x = h->impulse;
-    const uint32_t P = xfer_window(h->N, h->ring_cap); // (>= 64: why_no_impulse)
-    const DelayTables t = delay_tables(P);
-    x.P = t.P;
-    x.log2p = t.log2p;
-    x.K = xfer_segments(P, h->ring_cap);
-    // (48 KB of dynamic LDS at the cap: what a workgroup gets without asking)
-    return upload(h, &x.d_tab, t.tab); // (pageable memory: staged before the call returns)
-}
-
 // one workgroup per stream over the K newest anchored segments of both captured channels, behind the pushes issued
 int launch_impulse(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
 {
-    const wf_hip::Impulse &x = h->impulse;
+    const wf_hip::XferPlan &x = h->impulse;
     wf::ImpulseArgs a{};
     a.rings = ring_view(h); // (two captured channels: why_no_impulse)
     a.out = static_cast<wf_hip_impulse *>(d_block) + first;
@@ -516,10 +497,8 @@ int setup_click(wf_hip *h)
 {
     // (about 73 KB at the cap, the window, the residual and the kernel's working set behind them: more than a workgroup gets
     // without asking, and two workgroups to a CU)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::click_read_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::click_lds_bytes(WF_HIP_CLICK_MAX_WINDOW)));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::click_read_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::click_lds_bytes(WF_HIP_CLICK_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::click_read_kernel<1>, wf::click_lds_bytes(WF_HIP_CLICK_MAX_WINDOW)));
+    WF_TRY_RC(allow_lds(h, wf::click_read_kernel<2>, wf::click_lds_bytes(WF_HIP_CLICK_MAX_WINDOW)));
     return WF_HIP_OK;
 }
 
@@ -533,10 +512,7 @@ int launch_click(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     a.first = first;
     a.P = click_window(h); // (>= 256: why_no_click)
     const size_t lds = wf::click_lds_bytes(a.P);
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::click_read_kernel<2>, dim3(count * 2u), dim3(wf::WF_CLICK_THREADS), lds, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::click_read_kernel<1>, dim3(count), dim3(wf::WF_CLICK_THREADS), lds, h->stream, a);
+    launch_by_channels(h, wf::click_read_kernel<1>, wf::click_read_kernel<2>, dim3(count), dim3(count * 2u), wf::WF_CLICK_THREADS, lds, a);
     return WF_HIP_OK;
 }
 
@@ -709,10 +685,8 @@ void wf::host::measure_after_push(wf_hip *h, uint32_t first, uint32_t count, uin
     a.first = first;
     a.frames = frames;
     a.k = h->loud.k;
-    if(h->cap_ch == 2)
-        hipLaunchKernelGGL(wf::loudness_push_kernel<2>, dim3(count), dim3(128), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(wf::loudness_push_kernel<1>, dim3(count), dim3(64), 0, h->stream, a);
+    // (a wavefront per captured channel)
+    launch_by_channels(h, wf::loudness_push_kernel<1>, wf::loudness_push_kernel<2>, dim3(count), 64u * h->cap_ch, 0, a);
 }
 
 bool wf::host::measure_source(const wf_hip *h, wf_hip_output what, size_t *per_stream, const char **why)

@@ -16,7 +16,7 @@
 //              the eight float64 values in registers for direct_db and adds their squares up.
 //   envelope   a barrier, then one transform of the one-sided spectrum 4 w[2 k] ya[k] -- T[k] = 1 - cos(2 pi k / M) is twice the Hann
 //              table's entry 2 k --, 0 outside 1 <= k < M.  Behind it ya is free and holds exactly P doubles and two: env[i], which
-//              the candidates' neighbours are read from.  etc_db[i]; the peak by thd_wave_argmax and thd_better.
+//              the candidates' neighbours are read from.  etc_db[i]; the peak by wave_argmax and argmax_better.
 //   arrivals   every thread holds env of its own indices that are candidates at or above the -30 dB rule, -1 otherwise; a round
 //              strikes those within the guard of the arrival just taken and takes the block's argmax, up to seven times, one
 //              barrier and one hand-over slot a round; thread 0 writes each arrival as it is taken.
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(WF_XFER_THREADS, 2) void impulse_read_kernel(const 
 #pragma unroll
     for(uint32_t u = 0; u < WF_XFER_OWN; ++u)
         mx = fmax(mx, sxx[u]);
-    mx = delay_wave_max(mx);
+    mx = wave_max(mx);
     if(lane == 0u)
         max_x[wave] = mx;
     __syncthreads();
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(WF_XFER_THREADS, 2) void impulse_read_kernel(const 
         }
         out->etc_db[i] = db;
     }
-    thd_wave_argmax(best, kbest);
+    wave_argmax(best, kbest);
     if(lane == 0u) {
         arg_v[0][wave] = best;
         arg_k[0][wave] = kbest;
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(WF_XFER_THREADS, 2) void impulse_read_kernel(const 
     kbest = arg_k[0][0];
 #pragma unroll
     for(uint32_t w = 1; w < WF_XFER_WAVES; ++w)
-        thd_better(best, kbest, arg_v[0][w], arg_k[0][w]);
+        argmax_better(best, kbest, arg_v[0][w], arg_k[0][w]);
     const double epk = best;
     const uint32_t ipk = kbest;
 
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(WF_XFER_THREADS, 2) void impulse_read_kernel(const 
                 kbest = i;
             }
         }
-        thd_wave_argmax(best, kbest);
+        wave_argmax(best, kbest);
         if(lane == 0u) {
             arg_v[r][wave] = best;
             arg_k[r][wave] = kbest;
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(WF_XFER_THREADS, 2) void impulse_read_kernel(const 
         kbest = arg_k[r][0];
 #pragma unroll
         for(uint32_t w = 1; w < WF_XFER_WAVES; ++w)
-            thd_better(best, kbest, arg_v[r][w], arg_k[r][w]);
+            argmax_better(best, kbest, arg_v[r][w], arg_k[r][w]);
         if(best < 0.0) // (uniform) no candidate is left
             break;
         if(t == 0u)

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -57,18 +58,6 @@ __device__ __forceinline__ void peaks_insert(uint64_t (&best)[WF_HIP_MAX_PEAKS],
         best[i] = gt ? x : best[i];
         x = lo;
     }
-}
-
-__device__ __forceinline__ uint64_t peaks_wave_max(uint64_t v)
-{
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, off, 64);
-        const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), off, 64);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 __device__ __forceinline__ float peaks_lane_bits(float v, int lane)
@@ -136,7 +125,7 @@ __global__ __launch_bounds__(64 * WF_PEAKS_WAVES, 8) void peaks_read_kernel(Peak
     uint32_t count = 0;
 #pragma unroll
     for(int r = 0; r < WF_HIP_MAX_PEAKS; ++r) {
-        const uint64_t m = peaks_wave_max(best[0]);
+        const uint64_t m = wave_max(best[0]);
         if(m == 0ull)
             break; // (wave-uniform)
         if(lane == (uint32_t)r)

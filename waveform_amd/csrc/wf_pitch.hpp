@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include "wf_hip.h"
 #include "wf_ring_view.hpp"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -62,24 +63,7 @@ __device__ __forceinline__ PitchKey pitch_min(PitchKey a, PitchKey b)
 
 __device__ __forceinline__ PitchKey pitch_wave_min(PitchKey k)
 {
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1) {
-        PitchKey o;
-        o.v = __shfl_xor(k.v, off, 64);
-        o.lag = __shfl_xor(k.lag, off, 64);
-        k = pitch_min(k, o);
-    }
-    return k;
-}
-
-__device__ __forceinline__ uint32_t pitch_wave_min(uint32_t v)
-{
-#pragma unroll
-    for(int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
+    return wave_reduce(k, [](PitchKey a, PitchKey b) { return pitch_min(a, b); });
 }
 
 // the 8 steps j = j0 .. j0 + 7 of one thread's lags tau0 .. tau0 + 7
@@ -204,7 +188,7 @@ __global__ __launch_bounds__(WF_PITCH_THREADS, WF_PITCH_OCC) void pitch_read_ker
             best = pitch_min(best, PitchKey{dp[k], tau});
         }
     }
-    first = pitch_wave_min(first);
+    first = wave_min(first);
     best = pitch_wave_min(best);
     if(lane == 0u) {
         lds_idx[0][wave] = first;
@@ -229,7 +213,7 @@ __global__ __launch_bounds__(WF_PITCH_THREADS, WF_PITCH_OCC) void pitch_read_ker
             if(tau >= first && tau < H && stop == NONE && (tau == H - 1u || !(after < dp[k])))
                 stop = tau;
         }
-        stop = pitch_wave_min(stop);
+        stop = wave_min(stop);
         if(lane == 0u)
             lds_idx[1][wave] = stop;
         __syncthreads(); // (voiced is the same in every thread)

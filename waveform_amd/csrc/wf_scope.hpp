@@ -6,10 +6,9 @@
 // issued so far, and copies the result back; nothing runs while the output is not read.
 //
 // One workgroup of WF_SCOPE_THREADS per stream; the ring is read once.
-//   stage    the window is at most two contiguous runs of the ring (the wrap splits it).  Each run goes through wf_signal.hpp's way:
-//            16-B loads over its 16-B aligned body, four per channel in flight per lane, element by element over the at most 3 frames
-//            before and after it.  Frame i of channel c lands in dynamic LDS at x[c][o + i], o = (window start) & 3: the ring's
-//            16-B groups stay 16-B groups in LDS in both runs (the capacity is a multiple of 4), so the body is stored as 16-B words.
+//   stage    wf_ring_stage.hpp's ring_stage_window<CH>: the at most two contiguous runs of the window into dynamic LDS, 16-B words
+//            over the aligned body, four per channel in flight per lane, element by element over the at most 3 frames around it;
+//            frame i of channel c at x[c][o + i], o = (window start) & 3.
 //   level    t = x_0 + x_1 in float64 (exact), its minimum and maximum by a butterfly over the wavefront and the waves' partials
 //            in wave order; level and hysteresis from them, one IEEE operation and one exact scaling each.
 //   scan     frames 0 .. P - V in groups of 64, a wavefront per group: two ballots give the group's LOW and HIGH masks L and H.
@@ -27,6 +26,8 @@
 #include <stdint.h>
 #include "wf_hip.h"
 #include "wf_ring_view.hpp"
+#include "wf_ring_stage.hpp"
+#include "wf_wave_reduce.hpp"
 
 namespace wf {
 
@@ -47,9 +48,6 @@ static_assert(WF_HIP_SCOPE_MAX_WINDOW - WF_HIP_SCOPE_MAX_WINDOW / 2 + 1 <= 64 * 
 static_assert((WF_HIP_SCOPE_MAX_WINDOW / 2 + WF_HIP_SCOPE_COLUMNS - 1) / WF_HIP_SCOPE_COLUMNS <= WF_SCOPE_LANES);
 static_assert(sizeof(wf_hip_scope) % 16 == 0 && WF_SCOPE_MAX_GROUPS <= WF_SCOPE_THREADS);
 
-// floats between the channels' windows in LDS: P + 3 (the window starts up to 3 floats in), rounded up to 16 bytes
-__host__ __device__ inline uint32_t scope_lds_stride(uint32_t P) { return (P + 6u) & ~3u; }
-
 // what follows the staged windows in dynamic LDS
 struct ScopeWork {
     uint32_t image[sizeof(wf_hip_scope) / 4]; // the entry as it leaves
@@ -59,57 +57,11 @@ struct ScopeWork {
 };
 static_assert(offsetof(ScopeWork, low) % 16 == 0);
 
-__host__ __device__ inline size_t scope_lds_bytes(uint32_t channels, uint32_t P)
+__host__ __device__ constexpr size_t scope_lds_bytes(uint32_t channels, uint32_t P)
 {
-    return (size_t)channels * scope_lds_stride(P) * sizeof(float) + sizeof(ScopeWork);
+    return (size_t)channels * ring_stage_stride(P) * sizeof(float) + sizeof(ScopeWork);
 }
-
-// ring positions [b0, b1) of every channel, b0 <= b1 <= ring_cap, to LDS index (ring position + d), d + b0 a multiple of 4 wherever
-// b0 is
-template<int CH>
-__device__ __forceinline__ void scope_stage(float *x, uint32_t S, const float *r0, const float *r1, uint32_t b0, uint32_t b1, uint32_t d)
-{
-    const uint32_t t = threadIdx.x;
-    const uint32_t h = ((b0 + 3u) & ~3u) < b1 ? ((b0 + 3u) & ~3u) : b1; // end of the head
-    const uint32_t e = (b1 & ~3u) > h ? (b1 & ~3u) : h;                 // end of the body
-    const uint32_t nh = h - b0, nt = b1 - e;                            // at most 3 each
-    if(t < nh) {
-        x[b0 + t + d] = r0[b0 + t];
-        if constexpr(CH == 2)
-            x[S + b0 + t + d] = r1[b0 + t];
-    } else if(t - nh < nt) {
-        x[e + t - nh + d] = r0[e + t - nh];
-        if constexpr(CH == 2)
-            x[S + e + t - nh + d] = r1[e + t - nh];
-    }
-    const float4 *p0 = reinterpret_cast<const float4 *>(r0 + h);
-    const float4 *p1 = reinterpret_cast<const float4 *>(r1 + h);
-    float4 *q0 = reinterpret_cast<float4 *>(x + (h + d)); // (h + d: a multiple of 4, as S is)
-    float4 *q1 = reinterpret_cast<float4 *>(x + S + (h + d));
-    const uint32_t n4 = (e - h) / 4u;
-    constexpr uint32_t T = WF_SCOPE_THREADS, U = WF_SCOPE_UNROLL;
-    uint32_t i = t;
-    for(; i + (U - 1u) * T < n4; i += U * T) {
-        float4 l[U], r[U];
-#pragma unroll
-        for(uint32_t u = 0; u < U; ++u) {
-            l[u] = p0[i + u * T];
-            if constexpr(CH == 2)
-                r[u] = p1[i + u * T];
-        }
-#pragma unroll
-        for(uint32_t u = 0; u < U; ++u) {
-            q0[i + u * T] = l[u];
-            if constexpr(CH == 2)
-                q1[i + u * T] = r[u];
-        }
-    }
-    for(; i < n4; i += T) {
-        q0[i] = p0[i];
-        if constexpr(CH == 2)
-            q1[i] = p1[i];
-    }
-}
+static_assert(2 * scope_lds_bytes(2, WF_HIP_SCOPE_MAX_WINDOW) <= WF_LDS_PER_CU, "two workgroups to a CU at the cap");
 
 // index of the highest set bit of a mask that has one
 __device__ __forceinline__ uint32_t scope_top(unsigned long long m) { return 63u - (uint32_t)__builtin_clzll(m); }
@@ -123,7 +75,7 @@ __global__ __launch_bounds__(WF_SCOPE_THREADS, WF_SCOPE_OCC) void scope_read_ker
     const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const uint32_t stream = a.first + blockIdx.x;
     const uint32_t P = a.P, V = a.V, K = a.K;
-    const uint32_t S = scope_lds_stride(P);
+    const uint32_t S = ring_stage_stride(P);
     ScopeWork &w = *reinterpret_cast<ScopeWork *>(scope_x + (size_t)CH * S);
     const uint32_t ring_cap = a.rings.ring_cap;
     const uint32_t s = window_start(a.rings, stream, P) & (ring_cap - 1u);
@@ -132,10 +84,7 @@ __global__ __launch_bounds__(WF_SCOPE_THREADS, WF_SCOPE_OCC) void scope_read_ker
     const float *r1 = CH == 2 ? channel_ring(a.rings, stream, 1, CH) : r0;
     const float *x0 = scope_x + o, *x1 = x0 + S; // x_c[i]
 
-    const uint32_t end = s + P; // <= 2 ring_cap
-    scope_stage<CH>(scope_x, S, r0, r1, s, end < ring_cap ? end : ring_cap, o - s);
-    if(end > ring_cap)
-        scope_stage<CH>(scope_x, S, r0, r1, 0u, end - ring_cap, o + (ring_cap - s));
+    ring_stage_window<CH, WF_SCOPE_THREADS, WF_SCOPE_UNROLL>(scope_x, S, r0, r1, s, P, ring_cap);
     for(uint32_t i = t; i < sizeof(wf_hip_scope) / 4u; i += WF_SCOPE_THREADS)
         w.image[i] = 0u;
     __syncthreads();
@@ -150,11 +99,10 @@ __global__ __launch_bounds__(WF_SCOPE_THREADS, WF_SCOPE_OCC) void scope_read_ker
             tmin = __builtin_fmin(tmin, v);
             tmax = __builtin_fmax(tmax, v);
         }
-#pragma unroll
-        for(int off = 32; off > 0; off >>= 1) {
-            tmin = __builtin_fmin(tmin, __shfl_xor(tmin, off, 64));
-            tmax = __builtin_fmax(tmax, __shfl_xor(tmax, off, 64));
-        }
+        wave_butterfly([&](auto other) {
+            tmin = __builtin_fmin(tmin, other(tmin));
+            tmax = __builtin_fmax(tmax, other(tmax));
+        });
         if(lane == 0) {
             w.tmin[wave] = tmin;
             w.tmax[wave] = tmax;
@@ -262,11 +210,10 @@ __global__ __launch_bounds__(WF_SCOPE_THREADS, WF_SCOPE_OCC) void scope_read_ker
 #pragma unroll
             for(int ch = 0; ch < CH; ++ch) {
                 float lo = (ch ? x1 : x0)[f], hi = lo;
-#pragma unroll
-                for(int off = WF_SCOPE_LANES / 2; off > 0; off >>= 1) {
-                    lo = __builtin_fminf(lo, __shfl_xor(lo, off, 64));
-                    hi = __builtin_fmaxf(hi, __shfl_xor(hi, off, 64));
-                }
+                wave_butterfly<WAVE_DOWN, WF_SCOPE_LANES>([&](auto other) {
+                    lo = __builtin_fminf(lo, other(lo));
+                    hi = __builtin_fmaxf(hi, other(hi));
+                });
                 if(r == 0u && c < K) {
                     w.image[(0 + ch) * WF_HIP_SCOPE_COLUMNS + c] = __float_as_uint(lo);
                     w.image[(2 + ch) * WF_HIP_SCOPE_COLUMNS + c] = __float_as_uint(hi);

@@ -160,11 +160,10 @@ __global__ __launch_bounds__(WF_SIGNAL_THREADS, WF_SIGNAL_OCC) void signal_read_
     for(int c = 0; c < CH; ++c) {
         mx[c] = acc.mx[c];
         clip[c] = acc.clip[c];
-#pragma unroll
-        for(int off = 32; off > 0; off >>= 1) {
-            mx[c] = __builtin_fmaxf(mx[c], __shfl_xor(mx[c], off, 64));
-            clip[c] += __shfl_xor(clip[c], off, 64);
-        }
+        wave_butterfly([&](auto other) {
+            mx[c] = __builtin_fmaxf(mx[c], other(mx[c]));
+            clip[c] += other(clip[c]);
+        });
     }
     if(lane == 0) {
 #pragma unroll

@@ -59,25 +59,6 @@ __device__ __forceinline__ double thd_db(double num, double den)
     return 10.0 * log10(num / den);
 }
 
-// of two (value, bin) candidates of an argmax: the larger value, and the lower bin of equal values (a NaN never wins)
-__device__ __forceinline__ void thd_better(double &v, uint32_t &k, double ov, uint32_t ok)
-{
-    if(ov > v || (ov == v && ok < k)) {
-        v = ov;
-        k = ok;
-    }
-}
-
-__device__ __forceinline__ void thd_wave_argmax(double &v, uint32_t &k)
-{
-#pragma unroll
-    for(int i = 0; i < 6; ++i) {
-        const double ov = __shfl_xor(v, 32 >> i, 64);
-        const uint32_t ok = __shfl_xor(k, 32 >> i, 64);
-        thd_better(v, k, ov, ok);
-    }
-}
-
 // grid: one workgroup per stream of [first, first + gridDim.x); dynamic LDS: P * sizeof(double2)
 template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kernel(const ThdArgs a)
 {
@@ -161,7 +142,7 @@ template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kern
                 k0 = k;
             }
         }
-        thd_wave_argmax(best, k0);
+        wave_argmax(best, k0);
         if(lane == 0u) {
             arg_v[wave] = best;
             arg_k[wave] = k0;
@@ -171,7 +152,7 @@ template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kern
         k0 = arg_k[0];
 #pragma unroll
         for(uint32_t w = 1; w < WF_THD_WAVES; ++w)
-            thd_better(best, k0, arg_v[w], arg_k[w]);
+            argmax_better(best, k0, arg_v[w], arg_k[w]);
 
         // fundamental: every wave sums the same 2H + 1 bins in the same order
         double F, f0;
@@ -229,7 +210,7 @@ template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kern
         D = wave_sum(D);
         N = wave_sum(N);
         n = wave_sum(n);
-        thd_wave_argmax(sv, ks);
+        wave_argmax(sv, ks);
         if(lane == 0u) {
             res_d[wave] = D;
             res_n[wave] = N;
@@ -252,7 +233,7 @@ template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kern
                     D += res_d[w];
                     N += res_n[w];
                     n += res_cnt[w];
-                    thd_better(sv, ks, res_v[w], res_k[w]);
+                    argmax_better(sv, ks, res_v[w], res_k[w]);
                 }
                 double hsum = 0.0;
                 uint32_t bits = 0;

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(WF_XFER_THREADS, 2) void xfer_read_kernel(const Xfe
 #pragma unroll
     for(uint32_t u = 0; u < WF_XFER_OWN; ++u)
         mx = fmax(mx, sxx[u]);
-    mx = delay_wave_max(mx);
+    mx = wave_max(mx);
     if(lane == 0u)
         max_x[wave] = mx;
     __syncthreads();

@@ -18,7 +18,7 @@
 //              both channels the same, takes its spectra from Z[k] alone, and is then exact where the definition is.
 //   lag        behind the pass with n = 0: g = max |Sxy| by wave butterflies and one hand-over; ya[k] = A[k], ya[0] = ya[M] = 0; one
 //              transform of the Hermitian extension Y[k] = A[k], Y[P - k] = conj A[k], fetched from ya while the rows fall
-//              into z, so that they cannot race; r[n] = Re y[-n] / (2 (M - 1)); the argmax as wf_delay.hpp's, thd_better with the
+//              into z, so that they cannot race; r[n] = Re y[-n] / (2 (M - 1)); the argmax as wf_delay.hpp's, argmax_better with the
 //              index n + L: the larger |r| wins and the lower lag a tie.  No cross power at all: lag 0, no transform.
 //   again      the pass once more with n = n0 where that is not 0 (uniform: every thread holds the same n0).
 // The order of every sum and every max follows from P and K alone; there are no atomics and no scratch.  The caller's first access
@@ -31,8 +31,7 @@
 #include "wf_ring_view.hpp"
 #include "wf_wave_reduce.hpp"
 #include "wf_fft64_lds.hpp"
-#include "wf_thd.hpp"   // thd_better, thd_wave_argmax
-#include "wf_delay.hpp" // delay_wave_max, WF_DELAY_BETA
+#include "wf_phat.hpp"
 
 namespace wf {
 
@@ -160,7 +159,7 @@ __device__ __forceinline__ bool xfer_sums(const Args &a, double2 *z, double2 *ya
 #pragma unroll
     for(uint32_t u = 0; u < WF_XFER_OWN; ++u)
         g = fmax(g, sqrt(sxr[u] * sxr[u] + sxi[u] * sxi[u])); // (0 for a bin there is none of)
-    g = delay_wave_max(g);
+    g = wave_max(g);
     if(lane == 0u)
         max_g[wave] = g;
     __syncthreads();
@@ -199,7 +198,7 @@ __device__ __forceinline__ bool xfer_sums(const Args &a, double2 *z, double2 *ya
                 kbest = i;
             }
         }
-        thd_wave_argmax(best, kbest);
+        wave_argmax(best, kbest);
         if(lane == 0u) {
             arg_v[wave] = best;
             arg_k[wave] = kbest;
@@ -209,7 +208,7 @@ __device__ __forceinline__ bool xfer_sums(const Args &a, double2 *z, double2 *ya
         kbest = arg_k[0];
 #pragma unroll
         for(uint32_t w = 1; w < WF_XFER_WAVES; ++w)
-            thd_better(best, kbest, arg_v[w], arg_k[w]);
+            argmax_better(best, kbest, arg_v[w], arg_k[w]);
         n0 = (int32_t)kbest - (int32_t)L;
         peak = R(n0); // (the pass that may follow starts with a barrier)
         if(n0 != 0)   // (uniform; at lag 0 the sums of the first pass are the result)
