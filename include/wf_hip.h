@@ -218,10 +218,29 @@ typedef enum wf_hip_pcm_format {
     WF_HIP_PCM_U8 = 1, WF_HIP_PCM_S16, WF_HIP_PCM_S32, WF_HIP_PCM_F32,                        /* interleaved: [frames][channels] */
     WF_HIP_PCM_U8_PLANAR, WF_HIP_PCM_S16_PLANAR, WF_HIP_PCM_S32_PLANAR, WF_HIP_PCM_F32_PLANAR /* planar: [channels][frames] */
 } wf_hip_pcm_format;
+/* What decoders, network streams and capture devices send and libobs has no name for.  The values go in the same
+ * wf_hip_pcm.format field; 9..15, 21..23 and everything from 29 on are no format. */
+typedef enum wf_hip_wire_format {
+    WF_HIP_WIRE_S24 = 16,   /* 3 bytes, little-endian, two's complement, packed (no padding byte) */
+    WF_HIP_WIRE_S24_BE,     /* 17: the same, big-endian (RTP L24) */
+    WF_HIP_WIRE_S16_BE,     /* 18: big-endian int16 (RTP L16) */
+    WF_HIP_WIRE_ULAW,       /* 19: ITU-T G.711 mu-law, 1 byte */
+    WF_HIP_WIRE_ALAW,       /* 20: ITU-T G.711 A-law, 1 byte */
+    /* planar: the interleaved value + 8 */
+    WF_HIP_WIRE_S24_PLANAR = 24, WF_HIP_WIRE_S24_BE_PLANAR, WF_HIP_WIRE_S16_BE_PLANAR, WF_HIP_WIRE_ULAW_PLANAR, WF_HIP_WIRE_ALAW_PLANAR
+} wf_hip_wire_format;
 /* The conversion to the float32 the rings hold is exact (bit for bit what these expressions give in float):
  *   u8:  (x - 128) * 2^-7      s16: x * 2^-15      s32: (float)x * 2^-31, (float)x rounded to nearest even
  *   f32: the bits pass unchanged
- * -- the full-scale mapping audio converters use. */
+ * -- the full-scale mapping audio converters use.  The wire formats:
+ *   s24, s24_be: the three bytes (least / most significant first) sign-extended to int x, then (float)x * 2^-23: -2^23 reads
+ *                -1.0f, 2^23 - 1 reads 0x1.fffffcp-1f; every 24-bit integer is a float32, so nothing is lost
+ *   s16_be:      the two bytes swapped, then x * 2^-15
+ *   mu-law:      u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 0x84) << e) - 0x84, v = u & 0x80 ? -mag : mag;
+ *                (float)v * 2^-15.  0x00 reads -32124 * 2^-15, 0x80 +32124 * 2^-15, both zero codes (0xFF, 0x7F) +0.0f
+ *   A-law:       a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = e ? ((m << 4) + 0x108) << (e - 1) : (m << 4) + 8,
+ *                v = a & 0x80 ? mag : -mag; (float)v * 2^-15.  0xD5 reads +8 * 2^-15, 0xAA +32256 * 2^-15
+ * -- G.711's 14- and 13-bit linear values at the top of a 16-bit word, as telephony decoders give them. */
 typedef enum wf_hip_pcm_memory {
     WF_HIP_PCM_HOST = 0,   /* any host memory; the call returns once the packet has been copied (wf_hip_push_audio) */
     WF_HIP_PCM_PINNED = 1, /* wf_hip_host_alloc memory; does not wait, `slot` as wf_hip_push_audio_async / wf_hip_ingest_done */
@@ -229,8 +248,8 @@ typedef enum wf_hip_pcm_memory {
 } wf_hip_pcm_memory;
 typedef struct wf_hip_pcm {
     const void *data;                  /* the blocks of streams first .. first+count-1, one after the other: stream i's block
-                                          starts at i * channels * frames * bytes_per_sample */
-    uint32_t format;                   /* wf_hip_pcm_format */
+                                          starts at i * channels * frames * bytes_per_sample (packed 24-bit: any byte) */
+    uint32_t format;                   /* wf_hip_pcm_format or wf_hip_wire_format */
     uint32_t channels;                 /* channels in the packet, 1..8 */
     uint32_t channel_base;             /* first captured channel (m_channel_base): channel_base + capture_channels <= channels;
                                           a two-channel capture needs 0 (the asserts of src/source.cpp:1827-1828) */
@@ -245,7 +264,8 @@ typedef struct wf_hip_pcm {
  * packet longer than the ring keeps its newest ring_frames frames, every handle kind (spectrum, level meter, waveform) takes
  * it.  Host packets cross the bus in their own width; a planar one with more channels than captured sends only the
  * captured planes.  WF_HIP_ERR_INVALID before anything is enqueued for a bad format, channel count, channel pick, memory
- * kind, slot, a NULL pointer, or device data not aligned to its sample size. */
+ * kind, slot, a NULL pointer, or device data not aligned to its sample's natural alignment (its size; 1 for packed 24-bit,
+ * 2 for s16_be). */
 int wf_hip_push_pcm(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm);
 
 /* ---- the tick ------------------------------------------------------------------------- */

@@ -68,18 +68,22 @@ OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST
 # wf_hip_pcm_format / wf_hip_pcm_memory: libobs' enum audio_format, by numpy dtype (the planar format is the interleaved one + 4)
 PCM_FORMAT = {np.dtype(np.uint8): 1, np.dtype(np.int16): 2, np.dtype(np.int32): 3, np.dtype(np.float32): 4}
 PCM_HOST, PCM_PINNED, PCM_DEVICE = 0, 1, 2
+# wf_hip_wire_format: what libobs has no name for, by name (the planar format is the interleaved one + 8), and a sample's bytes
+WIRE_FORMAT = {"s24": 16, "s24_be": 17, "s16_be": 18, "ulaw": 19, "alaw": 20}
+WIRE_BYTES = {"s24": 3, "s24_be": 3, "s16_be": 2, "ulaw": 1, "alaw": 1}
 
 
 class Pcm(C.Structure):
-    """struct wf_hip_pcm (include/wf_hip.h): one packet in any libobs sample format"""
+    """struct wf_hip_pcm (include/wf_hip.h): one packet in any libobs sample format or wire format"""
     _fields_ = [("data", C.c_void_p), ("format", C.c_uint32), ("channels", C.c_uint32), ("channel_base", C.c_uint32),
                 ("frames", C.c_uint32), ("frames_per_stream", C.POINTER(C.c_uint32)), ("memory", C.c_uint32), ("slot", C.c_uint32)]
 
 
-def _pcm(samples, interleaved: bool, channel_base: int, frames, slot):
+def _pcm(samples, interleaved: bool, channel_base: int, frames, slot, wire: str | None = None):
     """(wf_hip_pcm, count, keep-alive) for a numpy array, a PinnedBuffer or a torch tensor on the device.  Shape
     [count, frames, channels] interleaved, [count, channels, frames] planar; `frames`: None, or the per-stream frame counts of
-    a ragged push (the shape's frame axis is then max_frames)."""
+    a ragged push (the shape's frame axis is then max_frames).  wire: a key of WIRE_FORMAT; the array is then uint8 with one
+    more axis, the WIRE_BYTES[wire] bytes of a sample."""
     keep = []
     if isinstance(samples, PinnedBuffer):
         if slot is None:
@@ -94,12 +98,21 @@ def _pcm(samples, interleaved: bool, channel_base: int, frames, slot):
         arr = np.ascontiguousarray(samples)
         keep.append(arr)
         ptr, memory, shape, dtype = arr.ctypes.data, PCM_HOST, arr.shape, arr.dtype
-    if dtype not in PCM_FORMAT or len(shape) != 3:
-        raise ValueError(f"expected a [count, frames, channels] / [count, channels, frames] array of uint8, int16, int32 or float32, "
-                         f"got {dtype} {shape}")
+    if wire is None:
+        if dtype not in PCM_FORMAT or len(shape) != 3:
+            raise ValueError(f"expected a [count, frames, channels] / [count, channels, frames] array of uint8, int16, int32 or float32, "
+                             f"got {dtype} {shape}")
+        fmt = PCM_FORMAT[dtype] + (0 if interleaved else 4)
+    else:
+        if wire not in WIRE_FORMAT:
+            raise ValueError(f"wire format {wire!r}: expected one of {', '.join(WIRE_FORMAT)}")
+        if dtype != np.uint8 or len(shape) != 4 or shape[3] != WIRE_BYTES[wire]:
+            raise ValueError(f"{wire}: expected a uint8 [count, frames, channels, {WIRE_BYTES[wire]}] / [count, channels, frames, "
+                             f"{WIRE_BYTES[wire]}] array, got {dtype} {shape}")
+        fmt = WIRE_FORMAT[wire] + (0 if interleaved else 8)
     count = shape[0]
     block_frames, channels = (shape[1], shape[2]) if interleaved else (shape[2], shape[1])
-    pcm = Pcm(data=ptr, format=PCM_FORMAT[dtype] + (0 if interleaved else 4), channels=channels, channel_base=channel_base,
+    pcm = Pcm(data=ptr, format=fmt, channels=channels, channel_base=channel_base,
               frames=block_frames, memory=memory, slot=0 if slot is None else slot)
     if frames is not None:
         f = np.ascontiguousarray(frames, dtype=np.uint32)
@@ -703,13 +716,18 @@ class SpectrumBatch(_MeasureReaders):
     def push_audio_device(self, dev_ptr: int, count: int, frames: int, first: int = 0):
         self._ck(self.L.wf_hip_push_audio_device(self.h, first, count, C.c_void_p(dev_ptr), frames))
 
-    def push_pcm(self, samples, *, interleaved: bool, channel_base: int = 0, frames=None, slot: int | None = None, first: int = 0):
+    def push_pcm(self, samples, *, interleaved: bool, channel_base: int = 0, frames=None, slot: int | None = None, first: int = 0,
+                 wire: str | None = None):
         """wf_hip_push_pcm: a packet in its own sample format, converted and channel-picked on the device.  The format comes
         from the dtype (uint8, int16, int32, float32); shape [count, frames, channels] interleaved, [count, channels, frames]
         planar.  A numpy array is copied before the call returns; a PinnedBuffer goes through the pipelined form (`slot`,
         ingest_done); a torch tensor on the handle's device is read in place.  frames: per-stream frame counts (ragged,
-        PinnedBuffer only)."""
-        pcm, count, keep = _pcm(samples, interleaved, channel_base, frames, slot)
+        PinnedBuffer only).
+        wire: None, or a wf_hip_wire_format by name ("s24", "s24_be", "s16_be", "ulaw", "alaw": packed 24-bit, big-endian and
+        G.711 samples).  `samples` is then a uint8 array, PinnedBuffer or device tensor whose last axis holds the bytes of one
+        sample as they lie in memory: [count, frames, channels, B] interleaved, [count, channels, frames, B] planar,
+        B = WIRE_BYTES[wire]; anything else raises ValueError.  Without it nothing changes."""
+        pcm, count, keep = _pcm(samples, interleaved, channel_base, frames, slot, wire)
         self._ck(self.L.wf_hip_push_pcm(self.h, first, count, C.byref(pcm)))
         del keep
 
@@ -972,11 +990,13 @@ class MultiBatch(_MeasureReaders):
         assert s.ndim == 3 and s.shape[1] == self.capture_channels, s.shape
         self._ck(self.L.wf_hip_multi_push_audio(self.m, first, s.shape[0], s.ctypes.data_as(C.POINTER(C.c_float)), s.shape[2]))
 
-    def push_pcm(self, samples, *, interleaved: bool, channel_base: int = 0, frames=None, slot: int | None = None, first: int = 0):
-        """wf_hip_multi_push_pcm: SpectrumBatch.push_pcm with global stream indices (host numpy arrays only)"""
+    def push_pcm(self, samples, *, interleaved: bool, channel_base: int = 0, frames=None, slot: int | None = None, first: int = 0,
+                 wire: str | None = None):
+        """wf_hip_multi_push_pcm: SpectrumBatch.push_pcm with global stream indices (host numpy arrays only; `wire` as there:
+        a uint8 array whose last axis holds a sample's bytes)"""
         if frames is not None or slot is not None or not isinstance(samples, np.ndarray):
             raise ValueError("a group takes host numpy packets without per-stream frame counts")
-        pcm, count, keep = _pcm(samples, interleaved, channel_base, None, None)
+        pcm, count, keep = _pcm(samples, interleaved, channel_base, None, None, wire)
         self._ck(self.L.wf_hip_multi_push_pcm(self.m, first, count, C.byref(pcm)))
         del keep
 

@@ -21,6 +21,7 @@
 #include "wf_geometry.hpp"
 #include "wf_ring.hpp"
 #include "wf_pcm.hpp"
+#include "wf_wire.hpp"
 #include "wf_meter.hpp"
 #include "wf_rms.hpp"
 #include "wf_wave.hpp"
@@ -561,34 +562,39 @@ int wait_rows_in_flight(wf_hip *h)
 }
 
 // ---- wf_hip_push_pcm ----------------------------------------------------------------------------------------------------
-uint32_t pcm_sample_bytes(uint32_t format)
-{
-    const uint32_t base = (format - 1u) & 3u; // u8, s16, s32, f32
-    return base == 0 ? 1u : base == 1 ? 2u : 4u;
-}
-
+// (what a format value means -- validity, bytes, layout, sample kind, alignment: wf_pcm_formats.hpp)
 using PcmLaunch = void (*)(dim3, hipStream_t, const wf::PcmPushArgs &);
 template<uint32_t Fmt, bool Interleaved, bool Ragged>
 void launch_pcm(dim3 grid, hipStream_t stream, const wf::PcmPushArgs &a)
 {
     hipLaunchKernelGGL((wf::ring_push_pcm_kernel<Fmt, Interleaved, Ragged>), grid, dim3(wf::PCM_THREADS), 0, stream, a);
 }
-template<bool Interleaved, bool Ragged>
-PcmLaunch pcm_launcher_of(uint32_t base)
+template<uint32_t Fmt, bool Interleaved, bool Ragged>
+void launch_wire(dim3 grid, hipStream_t stream, const wf::PcmPushArgs &a)
 {
-    switch(base) {
+    hipLaunchKernelGGL((wf::ring_push_wire_kernel<Fmt, Interleaved, Ragged>), grid, dim3(wf::PCM_THREADS), 0, stream, a);
+}
+template<bool Interleaved, bool Ragged>
+PcmLaunch pcm_launcher_of(uint32_t kind)
+{
+    switch(kind) {
     case WF_HIP_PCM_U8: return launch_pcm<WF_HIP_PCM_U8, Interleaved, Ragged>;
     case WF_HIP_PCM_S16: return launch_pcm<WF_HIP_PCM_S16, Interleaved, Ragged>;
     case WF_HIP_PCM_S32: return launch_pcm<WF_HIP_PCM_S32, Interleaved, Ragged>;
-    default: return launch_pcm<WF_HIP_PCM_F32, Interleaved, Ragged>;
+    case WF_HIP_PCM_F32: return launch_pcm<WF_HIP_PCM_F32, Interleaved, Ragged>;
+    case WF_HIP_WIRE_S24: return launch_wire<WF_HIP_WIRE_S24, Interleaved, Ragged>;
+    case WF_HIP_WIRE_S24_BE: return launch_wire<WF_HIP_WIRE_S24_BE, Interleaved, Ragged>;
+    case WF_HIP_WIRE_S16_BE: return launch_wire<WF_HIP_WIRE_S16_BE, Interleaved, Ragged>;
+    case WF_HIP_WIRE_ULAW: return launch_wire<WF_HIP_WIRE_ULAW, Interleaved, Ragged>;
+    case WF_HIP_WIRE_ALAW: return launch_wire<WF_HIP_WIRE_ALAW, Interleaved, Ragged>;
+    default: return nullptr; // (no format: pcm_check has refused it)
     }
 }
 PcmLaunch pcm_launcher(uint32_t format, bool ragged)
 {
-    const bool inter = format <= WF_HIP_PCM_F32;
-    const uint32_t base = inter ? format : format - 4u;
-    return inter ? (ragged ? pcm_launcher_of<true, true>(base) : pcm_launcher_of<true, false>(base))
-                 : (ragged ? pcm_launcher_of<false, true>(base) : pcm_launcher_of<false, false>(base));
+    const uint32_t kind = wf::pcm_sample_kind(format);
+    return wf::pcm_is_interleaved(format) ? (ragged ? pcm_launcher_of<true, true>(kind) : pcm_launcher_of<true, false>(kind))
+                                          : (ragged ? pcm_launcher_of<false, true>(kind) : pcm_launcher_of<false, false>(kind));
 }
 
 // the descriptor's rules (include/wf_hip.h); nothing is enqueued before they hold
@@ -596,8 +602,8 @@ int pcm_check(wf_hip *h, uint32_t count, const wf_hip_pcm *pcm)
 {
     if(pcm == nullptr || pcm->data == nullptr)
         return fail(h, WF_HIP_ERR_INVALID, "pcm or pcm->data is NULL");
-    if(pcm->format < WF_HIP_PCM_U8 || pcm->format > WF_HIP_PCM_F32_PLANAR)
-        return fail(h, WF_HIP_ERR_INVALID, "format %u is not a wf_hip_pcm_format", pcm->format);
+    if(!wf::pcm_format_valid(pcm->format))
+        return fail(h, WF_HIP_ERR_INVALID, "format %u is not a wf_hip_pcm_format or a wf_hip_wire_format", pcm->format);
     if(pcm->channels < 1 || pcm->channels > 8)
         return fail(h, WF_HIP_ERR_INVALID, "%u channels: a packet has 1..8", pcm->channels);
     if(pcm->channels < h->cap_ch || pcm->channel_base > pcm->channels - h->cap_ch || (h->cap_ch > 1 && pcm->channel_base != 0))
@@ -605,8 +611,8 @@ int pcm_check(wf_hip *h, uint32_t count, const wf_hip_pcm *pcm)
                     pcm->channels);
     if(pcm->memory > WF_HIP_PCM_DEVICE || (pcm->memory == WF_HIP_PCM_PINNED && pcm->slot > 1))
         return fail(h, WF_HIP_ERR_INVALID, "memory %u / slot %u: expected host, pinned with slot 0 / 1, or device", pcm->memory, pcm->slot);
-    if(pcm->memory == WF_HIP_PCM_DEVICE && (uintptr_t)pcm->data % pcm_sample_bytes(pcm->format))
-        return fail(h, WF_HIP_ERR_INVALID, "device data is not aligned to its sample size");
+    if(pcm->memory == WF_HIP_PCM_DEVICE && (uintptr_t)pcm->data % wf::pcm_device_alignment(pcm->format))
+        return fail(h, WF_HIP_ERR_INVALID, "device data is not aligned to its sample's natural alignment");
     if(pcm->frames_per_stream) {
         if(pcm->memory != WF_HIP_PCM_PINNED || pcm->frames == 0)
             return fail(h, WF_HIP_ERR_INVALID, "a ragged push needs WF_HIP_PCM_PINNED memory and frames (max_frames) > 0");
@@ -619,9 +625,9 @@ int pcm_check(wf_hip *h, uint32_t count, const wf_hip_pcm *pcm)
 // captured: only the captured planes, one 2-D copy over the streams.  Returns the staged layout's channel count and base.
 hipError_t pcm_copy(wf_hip *h, void *dst, const wf_hip_pcm *pcm, uint32_t count, hipStream_t stream, uint32_t *channels, uint32_t *base)
 {
-    const size_t plane = (size_t)pcm->frames * pcm_sample_bytes(pcm->format);
+    const size_t plane = (size_t)pcm->frames * wf::pcm_sample_bytes(pcm->format);
     const size_t block = plane * pcm->channels;
-    if(pcm->format <= WF_HIP_PCM_F32 || pcm->channels == h->cap_ch) {
+    if(wf::pcm_is_interleaved(pcm->format) || pcm->channels == h->cap_ch) {
         *channels = pcm->channels;
         *base = pcm->channel_base;
         return hipMemcpyAsync(dst, pcm->data, block * count, hipMemcpyHostToDevice, stream);
@@ -632,12 +638,12 @@ hipError_t pcm_copy(wf_hip *h, void *dst, const wf_hip_pcm *pcm, uint32_t count,
                             plane * h->cap_ch, count, hipMemcpyHostToDevice, stream);
 }
 
-// the append: ring_push_pcm_kernel over the (staged) packet, then what push_common runs behind ring_push_kernel
+// the append: ring_push_pcm_kernel or ring_push_wire_kernel over the (staged) packet, then what push_common runs behind ring_push_kernel
 int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm, const void *d_src, uint32_t channels, uint32_t base,
                const uint32_t *d_frames)
 {
     const bool ragged = d_frames != nullptr;
-    const uint32_t bps = pcm_sample_bytes(pcm->format), frames = pcm->frames;
+    const uint32_t bps = wf::pcm_sample_bytes(pcm->format), frames = pcm->frames;
     wf::PcmPushArgs a{};
     a.ring = h->d_ring;
     a.wpos = h->d_wpos;
@@ -653,13 +659,15 @@ int pcm_append(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm *pcm,
     a.rms_ring = rms_follows_audio(h) ? h->d_rms_ring : nullptr;
     a.rms_cap = h->rms_cap;
     const PcmLaunch launch = pcm_launcher(pcm->format, ragged);
+    if(launch == nullptr)
+        return fail(h, WF_HIP_ERR_INVALID, "format %u has no append kernel", pcm->format);
     if(ragged) {
         a.first = first;
         a.src = static_cast<const unsigned char *>(d_src);
         launch(dim3(1, count), h->stream, a);
         return finish_push(h, first, count, frames, d_frames);
     }
-    const uint32_t tile = pcm->format <= WF_HIP_PCM_F32 ? wf::PCM_TILE / (channels * bps) : wf::PCM_TILE / bps;
+    const uint32_t tile = wf::wire_tile_frames(wf::pcm_is_interleaved(pcm->format), channels, bps); // (both kernels' tile)
     const uint32_t tiles = (uint32_t)std::min<size_t>(((size_t)frames + tile - 1) / tile, 64);
     for(uint32_t off = 0; off < count; off += PUSH_SLICE) {
         const uint32_t cnt = std::min(PUSH_SLICE, count - off);
@@ -949,11 +957,11 @@ int wf_hip_push_pcm(wf_hip *h, uint32_t first, uint32_t count, const wf_hip_pcm 
     if(pcm->frames == 0)
         return WF_HIP_OK;
     WF_HIP_TRY(h, hipSetDevice(h->device));
-    const uint32_t bps = pcm_sample_bytes(pcm->format);
+    const uint32_t bps = wf::pcm_sample_bytes(pcm->format);
     if(pcm->memory == WF_HIP_PCM_DEVICE)
         return pcm_append(h, first, count, pcm, pcm->data, pcm->channels, pcm->channel_base, nullptr);
     // the bytes that cross the bus: whole frames of an interleaved packet, the captured planes of a planar one
-    const uint32_t staged_ch = pcm->format <= WF_HIP_PCM_F32 ? pcm->channels : h->cap_ch;
+    const uint32_t staged_ch = wf::pcm_is_interleaved(pcm->format) ? pcm->channels : h->cap_ch;
     const size_t floats = ((size_t)count * staged_ch * pcm->frames * bps + 3) / 4; // (the staging blocks are the float paths')
     uint32_t channels = 0, base = 0;
     if(pcm->memory == WF_HIP_PCM_HOST) {

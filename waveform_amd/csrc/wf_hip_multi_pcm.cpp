@@ -3,6 +3,7 @@
 // wf_hip_* entry points it calls (tests/mock), which has no wf_hip_push_pcm.
 #include "wf_hip.h"
 #include "wf_hip_multi_shards.hpp"
+#include "wf_pcm_formats.hpp"
 
 int wf_hip_multi_push_pcm(wf_hip_multi *m, uint32_t first, uint32_t count, const wf_hip_pcm *pcm)
 {
@@ -12,11 +13,10 @@ int wf_hip_multi_push_pcm(wf_hip_multi *m, uint32_t first, uint32_t count, const
         return wf::multi::fail(m, WF_HIP_ERR_INVALID, "pcm or pcm->data is NULL");
     if(pcm->memory != WF_HIP_PCM_HOST || pcm->frames_per_stream != nullptr)
         return wf::multi::fail(m, WF_HIP_ERR_INVALID, "a group takes WF_HIP_PCM_HOST packets without frames_per_stream");
-    if(pcm->format < WF_HIP_PCM_U8 || pcm->format > WF_HIP_PCM_F32_PLANAR || pcm->channels < 1 || pcm->channels > 8)
+    if(!wf::pcm_format_valid(pcm->format) || pcm->channels < 1 || pcm->channels > 8)
         return wf::multi::fail(m, WF_HIP_ERR_INVALID, "bad format or channel count");
     // the channel pick is every shard's own check, made before it enqueues anything; a bad one fails on every shard alike
-    const uint32_t base = (pcm->format - 1u) & 3u;
-    const size_t block = (size_t)pcm->channels * pcm->frames * (base == 0 ? 1u : base == 1 ? 2u : 4u);
+    const size_t block = (size_t)pcm->channels * pcm->frames * wf::pcm_sample_bytes(pcm->format);
     return wf::multi::for_each_shard(m, first, count, [pcm, block](wf_hip *h, uint32_t lf, uint32_t lc, uint32_t off) {
         wf_hip_pcm p = *pcm;
         p.data = static_cast<const unsigned char *>(pcm->data) + (size_t)off * block;
