@@ -19,7 +19,8 @@ Waveform configurations (cfg.waveform) record
 A scenario may carry sync_ms: the source's audio sync offset (P_AUDIO_SYNC_OFFSET), i.e. a constant A/V-sync reserve of
 sync_ms * 48 frames that every backend applies.
 Audio is the counter-hash noise of include/wf_synth.h (tools/synth.py), so fixtures only store
-outputs.
+outputs; a ("signal", frames, spec) step plays the structured audio of tests/signals.py instead
+(tones, DC, square waves, lone samples; spec per channel or one for all).
 """
 from __future__ import annotations
 
@@ -303,6 +304,11 @@ class _Feeder:
         self.pos = 0
 
     def block(self, kind, frames, amp=1.0):
+        if kind == "signal":  # structured audio (tests/signals.py): `amp` is the spec, per channel or one for all
+            import signals
+            a = signals.render_channels(amp, self.channels, self.pos, frames)
+            self.pos += frames
+            return a
         a = synth.block(SEED, self.stream, 1, 2, self.pos, frames)[0]
         self.pos += frames
         if kind == "silence" or kind == "mute":
@@ -347,6 +353,8 @@ def _apply(backend, feeder, step):
     if op in ("noise", "silence", "noise_ch0_only", "noise_ch1_only"):
         backend.push(feeder.block(op, step[1]), muted=False)
     elif op == "noise_amp":
+        backend.push(feeder.block(op, step[1], step[2]), muted=False)
+    elif op == "signal":  # ("signal", frames, spec): tones, DC, lone samples, addressed by the absolute sample index
         backend.push(feeder.block(op, step[1], step[2]), muted=False)
     elif op == "timeout":
         backend.timeout()  # no packet for more than CAPTURE_TIMEOUT (500 ms); the next packet ends it

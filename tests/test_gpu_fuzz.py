@@ -346,42 +346,48 @@ def _compare(got, want, undo, what, cfg_stepped=False, cfg=None):
     the display misses the reference's by more than the pixel tolerance it is held, with the same tolerance, against what the
     restated render loop makes of the *device's own rows* -- a stage is not faulted for the latitude of the stage before it."""
     assert len(got) == len(want)
-    px = _px_tol(cfg)
     for t, (g, w) in enumerate(zip(got, want)):
         assert g["silent"] == w["silent"], f"{what} tick {t}: m_last_silent {g['silent']} != {w['silent']}"
         assert_db_close(g["db"], w["db"], f"{what} tick {t} decibels", undo_db=undo, deep=True)
-        ref_bars, ref_verts = w["bars"], w.get("verts")
-        assert (g["bars"] is None) == (w["bars"] is None), f"{what} tick {t}: one side has no bars"
-        if w["bars"] is not None:
-            err = np.abs(g["bars"].astype(np.float64) - w["bars"])
-            ARM["display_checks"] += 1
-            if not np.all(err <= 1e-5 * np.abs(w["bars"]) + px) and cfg is not None:
-                ARM["display_arm"] += 1
-                ARM["arm_cases"].append(f"{what} tick {t}: {err.max():.2e} px")
-                ref_bars, alt_verts = _render_from_rows(cfg, g["db"])
-                ref_verts = alt_verts if alt_verts is not None else ref_verts
-                err = np.abs(g["bars"].astype(np.float64) - ref_bars)
-            assert np.all(err <= 1e-5 * np.abs(ref_bars) + px), f"{what} tick {t} bars/curve: max err {err.max():.3e} px (tolerance {px:.1e})"
-        if "verts" in w:
-            for c, (gv, wv) in enumerate(zip(g["verts"], ref_verts)):
-                # stepped bars: a bar whose height sits within rounding of a step boundary may gain or lose that step
-                if gv.shape != wv.shape and cfg_stepped:
-                    # bar by bar: the same bars, at most one step apart, and the steps both sides have are the same quads
-                    gq, wq = _quads_by_bar(gv), _quads_by_bar(wv)
-                    assert abs(gv.shape[0] - wv.shape[0]) <= 6 * 2, f"{what} tick {t} channel {c}: {gv.shape[0]} vs {wv.shape[0]} vertices"
-                    for x in sorted(set(gq) | set(wq)):
-                        a, b = gq.get(x, []), wq.get(x, [])
-                        assert abs(len(a) - len(b)) <= 1, f"{what} tick {t} channel {c}: bar at x={x} has {len(a)} vs {len(b)} steps"
-                        for qa, qb in zip(a, b):
-                            assert np.array_equal(qa[:, 0], qb[:, 0]) and np.all(np.abs(qa[:, 1].astype(np.float64) - qb[:, 1]) <= 1e-5 * np.abs(qb[:, 1]) + px), \
-                                f"{what} tick {t} channel {c}: a step of the bar at x={x} differs"
-                    continue
-                assert gv.shape == wv.shape, f"{what} tick {t} channel {c}: vertex count {gv.shape} vs {wv.shape}"
-                assert np.array_equal(gv[..., 0], wv[..., 0]), f"{what} tick {t} channel {c}: vertex x"
-                err = np.abs(gv[..., 1].astype(np.float64) - wv[..., 1])
-                assert np.all(err <= 1e-5 * np.abs(wv[..., 1]) + px), f"{what} tick {t} channel {c} vertex y: max err {err.max():.3e} px"
-        if "rms" in w:
-            assert abs(float(g["rms"]) - float(w["rms"])) <= 1e-5 * abs(float(w["rms"])) + 1e-9, f"{what} tick {t} m_input_rms"
+        _compare_display(g, w, what, t, cfg_stepped=cfg_stepped, cfg=cfg)
+
+
+def _compare_display(g, w, what, t, cfg_stepped=False, cfg=None):
+    """the display part of _compare for the records of one tick: bars / curve points, vertices and m_input_rms (the rows are the
+    caller's: tests/test_gpu_signals.py judges tone rows by another criterion and the display by this one)"""
+    px = _px_tol(cfg)
+    ref_bars, ref_verts = w["bars"], w.get("verts")
+    assert (g["bars"] is None) == (w["bars"] is None), f"{what} tick {t}: one side has no bars"
+    if w["bars"] is not None:
+        err = np.abs(g["bars"].astype(np.float64) - w["bars"])
+        ARM["display_checks"] += 1
+        if not np.all(err <= 1e-5 * np.abs(w["bars"]) + px) and cfg is not None:
+            ARM["display_arm"] += 1
+            ARM["arm_cases"].append(f"{what} tick {t}: {err.max():.2e} px")
+            ref_bars, alt_verts = _render_from_rows(cfg, g["db"])
+            ref_verts = alt_verts if alt_verts is not None else ref_verts
+            err = np.abs(g["bars"].astype(np.float64) - ref_bars)
+        assert np.all(err <= 1e-5 * np.abs(ref_bars) + px), f"{what} tick {t} bars/curve: max err {err.max():.3e} px (tolerance {px:.1e})"
+    if "verts" in w:
+        for c, (gv, wv) in enumerate(zip(g["verts"], ref_verts)):
+            # stepped bars: a bar whose height sits within rounding of a step boundary may gain or lose that step
+            if gv.shape != wv.shape and cfg_stepped:
+                # bar by bar: the same bars, at most one step apart, and the steps both sides have are the same quads
+                gq, wq = _quads_by_bar(gv), _quads_by_bar(wv)
+                assert abs(gv.shape[0] - wv.shape[0]) <= 6 * 2, f"{what} tick {t} channel {c}: {gv.shape[0]} vs {wv.shape[0]} vertices"
+                for x in sorted(set(gq) | set(wq)):
+                    a, b = gq.get(x, []), wq.get(x, [])
+                    assert abs(len(a) - len(b)) <= 1, f"{what} tick {t} channel {c}: bar at x={x} has {len(a)} vs {len(b)} steps"
+                    for qa, qb in zip(a, b):
+                        assert np.array_equal(qa[:, 0], qb[:, 0]) and np.all(np.abs(qa[:, 1].astype(np.float64) - qb[:, 1]) <= 1e-5 * np.abs(qb[:, 1]) + px), \
+                            f"{what} tick {t} channel {c}: a step of the bar at x={x} differs"
+                continue
+            assert gv.shape == wv.shape, f"{what} tick {t} channel {c}: vertex count {gv.shape} vs {wv.shape}"
+            assert np.array_equal(gv[..., 0], wv[..., 0]), f"{what} tick {t} channel {c}: vertex x"
+            err = np.abs(gv[..., 1].astype(np.float64) - wv[..., 1])
+            assert np.all(err <= 1e-5 * np.abs(wv[..., 1]) + px), f"{what} tick {t} channel {c} vertex y: max err {err.max():.3e} px"
+    if "rms" in w:
+        assert abs(float(g["rms"]) - float(w["rms"])) <= 1e-5 * abs(float(w["rms"])) + 1e-9, f"{what} tick {t} m_input_rms"
 
 
 def run_spectrum_case(seed, family, fft_size=None):
