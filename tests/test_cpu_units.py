@@ -551,8 +551,8 @@ def test_library_exports_every_declared_symbol():
 
 def test_release_library_carries_no_laboratory():
     """The release library exports no test aid and at most 75 entry points (the boundary is a thin C ABI: the reference's operator
-    interface is four virtuals, src/source.hpp:273-277); the development build (same kernel objects, -DWF_DEV_BUILD on the two
-    host-side translation units) has the two hooks the tests need.  Every measurement switch in the kernels (WF_EXP_*: kernels that
+    interface is four virtuals, src/source.hpp:273-277); the development build (same kernel objects, -DWF_DEV_BUILD on the
+    host-side translation units: the entry points, the group and the plan with its environment overrides) has the two hooks the tests need.  Every measurement switch in the kernels (WF_EXP_*: kernels that
     end early or skip a phase, with WRONG results) defaults to 0 and is refused by wf_dev_guard.hpp outside development builds."""
     def exported(path):
         nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
@@ -562,6 +562,9 @@ def test_release_library_carries_no_laboratory():
     assert not [n for n in rel if "debug" in n], [n for n in rel if "debug" in n]
     assert len(rel) <= 75, (len(rel), sorted(rel))
     assert dev - rel == {"wf_hip_debug_age", "wf_hip_multi_debug_fail_next_gather"}, sorted(dev - rel)
+    # the plan's environment overrides are read by the development build alone (tests/test_gpu_lanes.py drives WF_HIP_LANES)
+    assert b"WF_HIP_LANES" in (ROOT / "waveform_amd" / "libwaveform_hip_dev.so").read_bytes()
+    assert b"WF_HIP_LANES" not in (ROOT / "waveform_amd" / "libwaveform_hip.so").read_bytes()
     csrc = ROOT / "waveform_amd" / "csrc"
     guard = (csrc / "wf_dev_guard.hpp").read_text()
     seen = set()

@@ -82,6 +82,22 @@ def cfg3_blocks(lanes, streams=4096):
     return tuple(sorted(set(blocks)))
 
 
+def lane_edges(lanes, streams, width=16):
+    """the `width` streams around every boundary between the lanes of a batch, as (first, count)"""
+    return [(streams * l // lanes - width // 2, width) for l in range(1, lanes)]
+
+
+def _one_lane_truth(cfg, first, count, ticks, hop, flags=0):
+    """rows and bars of streams [first, first + count) of a push_synth batch after `ticks` ticks, from a handle of their own: one
+    launch, no lanes, the streams at other positions"""
+    with wf.SpectrumBatch(cfg, count, ring_frames=cfg.fft_size + hop * (ticks + 1)) as s:
+        assert s.launches_per_tick() == 1
+        s.push_synth(SEED, 0, hop * ticks, stream_id0=first)
+        for t in range(ticks):
+            s.tick(delay_frames=hop * (ticks - 1 - t), flags=flags)
+        return s.decibels(), s.bars()
+
+
 def test_cfg3_full_batch_spot_checks_and_determinism():
     """configs[2]: 4096 stereo streams, FFT 4096, EMA + slope.  Device-generated audio (wf_synth) for every stream; 16 warm-up
     ticks (the EMA settles) + 8 checked ticks.  Against the oracle on every checked tick: the first and last 32 streams of the
@@ -143,11 +159,13 @@ def test_cfg3_whole_batch_equals_small_handles():
             assert_db_close(rows, want, f"64-stream handle, streams {base}..{base + part - 1} vs oracle", deep=True)
 
 
-@pytest.mark.parametrize("n,streams,lanes", [(65536, 264, 2), (32768, 520, 3)])
+@pytest.mark.parametrize("n,streams,lanes", [(65536, 264, 2), (32768, 520, 3), (48000, 264, 2), (16400, 264, 2), (32000, 264, 2)])
 def test_lanes_on_the_one_workgroup_per_cu_kernels(n, streams, lanes):
     """fft_size 65536 (big_whole_kernel) and 32768 take two / three lanes once the batch is two rounds of one-workgroup-per-CU
-    workgroups: the whole batch after a few ticks must equal, bit for bit, the same streams replayed through small one-lane handles
-    (every stream, across both lane boundaries), and one small block -- the one that straddles the first boundary -- the oracle."""
+    workgroups, and the rows families beyond a CU's LDS (48000: big_mr_rows_kernel, 16400: the Bluestein rows, 32000:
+    big_mr_whole_kernel) two from two spectra per CU on: the whole batch after a few ticks must equal, bit for bit, the same
+    streams replayed through small one-lane handles (every stream, across both lane boundaries), and one small block -- the one
+    that straddles the first boundary -- the oracle."""
     cfg = wf.Config.defaults(fft_size=n, stereo=1, slope=1.0)
     ticks, hop, part = 5, 800, 24
     with wf.SpectrumBatch(cfg, streams, ring_frames=n + hop * (ticks + 1)) as b:
@@ -202,23 +220,30 @@ def test_cfg2_256_consecutive_frames():
 
 def test_cfg5_per_gpu_shape_bars_only():
     """configs[4] per GPU: 8192 stereo streams, FFT 4096, EMA + slope, 26 Lanczos bars per channel, bars-only ticks
-    (WF_HIP_TICK_NO_DECIBELS); 16 warm-up + 8 checked ticks, first / last 32 streams' bars against the oracle."""
+    (WF_HIP_TICK_NO_DECIBELS); 16 warm-up + 8 checked ticks, first / last 32 streams' bars against the oracle.  After the last
+    tick the bars of the 16 streams around every lane boundary must equal, bit for bit, those of a 16-stream one-lane handle."""
     cfg = wf.Config.defaults(fft_size=4096, stereo=1, slope=1.0, bars=1, interp_mode=wf.INTERP["lanczos"])
     streams, warm, checked, hop = 8192, 16, 8, 800
     ticks = warm + checked
     ids = list(range(32)) + list(range(streams - 32, streams))
     got = []
     with wf.SpectrumBatch(cfg, streams, ring_frames=4096 + hop * (ticks + 1)) as b:
+        assert b.launches_per_tick() >= 2, "the lane boundaries this test straddles"
+        edges = lane_edges(b.launches_per_tick(), streams)
         b.push_synth(SEED, 0, hop * ticks)
         for t in range(ticks):
             b.tick(delay_frames=hop * (ticks - 1 - t), flags=wf.TICK_NO_DECIBELS)
             if t >= warm:
                 got.append(np.concatenate([b.bars(0, 32), b.bars(streams - 32, 32)]))
         assert b.bars().shape == (streams, 2, 26)
+        edge_bars = [b.bars(first, n) for first, n in edges]
     got = np.stack(got, axis=1)
     _, want = _oracle_ticks(cfg, ids, ticks, hop, checked, bars=True)
     err = np.abs(got.astype(np.float64) - want)
     assert np.all(err <= 1e-5 * np.abs(want) + 2e-3), f"cfg5 per-GPU shape bars: max err {err.max():.3e} px"
+    for (first, n), eb in zip(edges, edge_bars):
+        _, bars = _one_lane_truth(cfg, first, n, ticks, hop, flags=wf.TICK_NO_DECIBELS)
+        assert eb.tobytes() == bars.tobytes(), f"cfg5 per-GPU shape: bars of streams {first}..{first + n - 1} (a lane boundary) differ from a {n}-stream one-lane handle"
 
 
 def test_cfg5_full_size_65536_streams_in_eight_shards():
@@ -430,6 +455,8 @@ def test_cfg4_full_batch_bars():
     for rep in range(2):
         rows, bars = [], []
         with wf.SpectrumBatch(cfg, streams, ring_frames=16384 + hop * (ticks + 1)) as b:
+            assert b.launches_per_tick() >= 2, "the lane boundaries this test straddles"
+            edges = lane_edges(b.launches_per_tick(), streams)
             b.push_synth(SEED, 0, hop * ticks)
             for t in range(ticks):
                 b.tick(delay_frames=hop * (ticks - 1 - t))
@@ -440,6 +467,11 @@ def test_cfg4_full_batch_bars():
         res.append((np.stack(rows, axis=1), np.stack(bars, axis=1), full_rows, full_bars))
     for a, c, what in zip(res[0], res[1], ("checked rows", "checked bars", "rows of the whole batch", "bars of the whole batch")):
         assert np.array_equal(a, c), f"cfg4: {what} differ between two identical runs"
+    # the 16 streams around every lane boundary, after the last tick: bit for bit what a 16-stream one-lane handle computes
+    for first, n in edges:
+        one_rows, one_bars = _one_lane_truth(cfg, first, n, ticks, hop)
+        assert res[0][2][first:first + n].tobytes() == one_rows.tobytes(), f"cfg4: rows of streams {first}..{first + n - 1} (a lane boundary) differ from a {n}-stream one-lane handle"
+        assert res[0][3][first:first + n].tobytes() == one_bars.tobytes(), f"cfg4: bars of streams {first}..{first + n - 1} (a lane boundary) differ from a {n}-stream one-lane handle"
     assert res[0][3].shape == (streams, 2, 26) and np.all(np.isfinite(res[0][3])) and np.all(np.isfinite(res[0][2]))
     want, wantb = _oracle_ticks(cfg, ids, ticks, hop, checked, bars=True)
     for k in range(checked):

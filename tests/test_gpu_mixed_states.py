@@ -157,39 +157,60 @@ def fixed_rms(scripts):
     return [(0.5, 0.0316, 0.0, 1e-4, 0.1, 0.02, 0.25)[sc["noise_id"] - 1] for sc in scripts]
 
 
+class Case:
+    """what run_case plays: the configuration, the scripts of its streams, the tick flags and the fixed m_input_rms values"""
+
+    def __init__(self, n, layout, display, seed, aligned=False, extra=None, rms=None, kernel=None):
+        self.n = n
+        self.cfg = scenarios.make_config(case_config(n, layout, display, extra))
+        self.S = streams_for(n, int(self.cfg.capture_channels))
+        self.scripts = scenarios.draw_mixed(seed, self.cfg, self.S, aligned=aligned, base_sync_ms=5 if aligned else None)
+        self.what = f"mixed batch {n} {layout} {display} seed {seed}{' aligned' if aligned else ''}"
+        self.flags = scenarios.WF_HIP_TICK_NO_DECIBELS if display == "nodb" else 0
+        self.fixed = fixed_rms(self.scripts) if rms == "set" else None
+        self.kernel = kernel if kernel is not None else SHAPES[n][0]
+
+
+def play_hip(case):
+    """the batch on the device: (records per stream, kernel_name(), launches_per_tick())"""
+    cfg, n, what = case.cfg, case.n, case.what
+    hip = scenarios.HipBatch(cfg, case.S, rms=case.fixed, flags=case.flags)
+    try:
+        name = hip.kernel_name()
+        assert case.kernel in name, (what, name)
+        if n in SPLIT_SIZES:
+            assert ("split" in name) == (cfg.capture_channels == 2 and (bool(cfg.stereo) or n == 32768)), (what, name)
+        if n == 128:
+            assert "SPW=2" in name, (what, name)
+        launches = hip.batch.launches_per_tick()
+        got = scenarios.play_batch(hip, case.scripts)
+    finally:
+        hip.close()
+    return got, name, launches
+
+
+def compare_with_solo(case, got):
+    """every stream's records against its own script played alone on the checker"""
+    cfg, scripts, what, fixed = case.cfg, case.scripts, case.what, case.fixed
+    want = []
+    for i, sc in enumerate(scripts):
+        want.append(scenarios.play(solo_backend(cfg, None if fixed is None else fixed[i]), sc))
+    assert_mixed(cfg, scripts, want, what)
+    undo = fuzz._undo_db(cfg)
+    for i, sc in enumerate(scripts):
+        w = f"{what} stream {i} ({sc['role']}, sync {sc['sync_ms']} ms)"
+        if case.flags:
+            _compare_display_only(got[i], want[i], cfg, w)
+        else:
+            fuzz._compare(got[i], want[i], undo, w, cfg_stepped=int(cfg.vertices) == 3, cfg=cfg)  # (stepped bars: as run_spectrum_case)
+    assert_twins_equal(scripts, got, what)
+
+
 def run_case(n, layout, display, seed, aligned=False, extra=None, rms=None, kernel=None):
-    cfg_dict = case_config(n, layout, display, extra)
-    cfg = scenarios.make_config(cfg_dict)
-    S = streams_for(n, int(cfg.capture_channels))
-    scripts = scenarios.draw_mixed(seed, cfg, S, aligned=aligned, base_sync_ms=5 if aligned else None)
-    what = f"mixed batch {n} {layout} {display} seed {seed}{' aligned' if aligned else ''}"
-    flags = scenarios.WF_HIP_TICK_NO_DECIBELS if display == "nodb" else 0
-    fixed = fixed_rms(scripts) if rms == "set" else None
+    case = Case(n, layout, display, seed, aligned, extra, rms, kernel)
     with _Counted():
-        hip = scenarios.HipBatch(cfg, S, rms=fixed, flags=flags)
-        try:
-            name = hip.kernel_name()
-            part = kernel if kernel is not None else SHAPES[n][0]
-            assert part in name, (what, name)
-            if n in SPLIT_SIZES:
-                assert ("split" in name) == (cfg.capture_channels == 2 and (bool(cfg.stereo) or n == 32768)), (what, name)
-            if n == 128:
-                assert "SPW=2" in name, (what, name)
-            got = scenarios.play_batch(hip, scripts)
-        finally:
-            hip.close()
-        want = []
-        for i, sc in enumerate(scripts):
-            want.append(scenarios.play(solo_backend(cfg, None if fixed is None else fixed[i]), sc))
-        assert_mixed(cfg, scripts, want, what)
-        undo = fuzz._undo_db(cfg)
-        for i, sc in enumerate(scripts):
-            w = f"{what} stream {i} ({sc['role']}, sync {sc['sync_ms']} ms)"
-            if flags:
-                _compare_display_only(got[i], want[i], cfg, w)
-            else:
-                fuzz._compare(got[i], want[i], undo, w, cfg=cfg)
-        assert_twins_equal(scripts, got, what)
+        got, _, _ = play_hip(case)
+        compare_with_solo(case, got)
 
 
 @pytest.mark.gpu
