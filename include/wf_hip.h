@@ -74,6 +74,10 @@
  *   WF_HIP_OUT_CLICK     not in the reference: a click detector, per captured channel the clicks, pops and splices of every
  *                        stream's newest window of audio -- the frames that a linear predictor fitted to the window cannot account
  *                        for -- as a count, a rate and the up to eight strongest events, in float64 on the device when read
+ *   WF_HIP_OUT_IMD       not in the reference: a two-tone intermodulation analyser, per captured channel the two tones of a
+ *                        twin-tone stimulus, their sum and difference products of orders 2 .. 5, total IMD, the difference-frequency
+ *                        (IEC 60268-3) and modulation (DIN / SMPTE) distortion and the noise floor, from the distortion analyser's
+ *                        float64 spectrum of every stream's newest window on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -483,11 +487,16 @@ typedef enum wf_hip_output {
                                   frames before the delay taken out and 3 L behind it, its envelope in dB and the up to 8 strongest
                                   arrivals (spectrum and meter batches of at least 256 frames with two captured channels;
                                   definition below) */
-    WF_HIP_OUT_CLICK           /* wf_hip_click                               clicks: per captured channel the clicks, pops and
+    WF_HIP_OUT_CLICK,          /* wf_hip_click                               clicks: per captured channel the clicks, pops and
                                   splices of the newest min(wf_hip_fft_size(), 8192) frames in the rings as of the pushes issued so
                                   far, the frames a linear predictor fitted to the window cannot account for, as a count, a rate
                                   and the up to 8 strongest events (spectrum and meter batches of at least 256 frames; definition
                                   below) */
+    WF_HIP_OUT_IMD             /* wf_hip_imd                                 intermodulation: per captured channel the two tones
+                                  of a twin-tone stimulus, their 20 products of orders 2 .. 5, total IMD, DFD, modulation
+                                  distortion, distortion + noise and the noise floor of the newest P frames in the rings as of the
+                                  pushes issued so far, P as WF_HIP_OUT_THD's (spectrum and meter batches of at least 512 frames;
+                                  definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -1468,6 +1477,89 @@ typedef struct wf_hip_click {
     wf_hip_click_channel ch[2];   /* captured channels 0 and 1; with one captured channel ch[1] is all zero bytes */
     uint32_t window, order, reserved[2];   /* P, p, 0 */
 } wf_hip_click;              /* 464 bytes, a multiple of 16 */
+/* ---- intermodulation (WF_HIP_OUT_IMD) ---------------------------------------------------------------------------------------------
+ * Per stream and captured channel, the measurement that stands beside THD on an audio analyser: intermodulation distortion from a
+ * two-tone stimulus.  WF_HIP_OUT_THD cannot stand in for it: at 48 kHz a tone above 8 kHz has every harmonic from the third up
+ * beyond Nyquist, so the top octave and a half of a codec, a resampler, an interface or a limiter is measured on one harmonic or on
+ * none, while a twin tone at 19 + 20 kHz puts its products at 1, 18 and 21 kHz, in band; and a low tone with a high one shows the
+ * modulation a limiter or a class-D stage adds (the DIN / SMPTE method).  No host can make it from the tick's rows: they are
+ * float32 behind a Hann-class window, with a leakage floor far above a product at -100 dB.  W = wf_hip_fft_size(),
+ * sr = cfg.sample_rate; everything is float64 unless it says otherwise.
+ *   window, taper, spectrum   exactly WF_HIP_OUT_THD's: P the largest power of two <= min(W, WF_HIP_THD_MAX_WINDOW = 8192), the newest
+ *                  P frames with the rules of WF_HIP_OUT_SIGNAL, the periodic 7-term Blackman-Harris taper, H = WF_HIP_THD_LOBE = 8,
+ *                  M = P / 2, p[k] = |X_c[k]|^2 for 1 <= k < M, S = P sum w^2 / 4.  With two captured channels both come out of
+ *                  one complex transform; a channel of all zeros has p = 0 exactly; a NaN or an infinity in either window makes
+ *                  both channels read valid = 0; with one captured channel ch[1] is all zero bytes.
+ *   tones          k_a = the argmax of p over k in [2H + 1, M - H - 1]: the search starts from best = 0 and only a strictly
+ *                  greater value wins, so the lowest index wins a tie and a NaN never wins.  F_a = the sum of p[k] over
+ *                  |k - k_a| <= H and f_a = (sum k p[k]) / F_a over the same bins.  If F_a is not a finite number > 0: tones = 0,
+ *                  valid = 0 and every other field of the channel is 0.  k_b = the same argmax over the bins with
+ *                  |k - k_a| > 2H, so the two regions share no bin, and F_b, f_b from it.  If no such bin has p > 0, or F_b is
+ *                  not finite, or F_b < WF_HIP_IMD_MIN_RATIO F_a (1e-3: 30 dB): tones = 1, valid = 0 and every other field is 0.
+ *                  Otherwise tones = 2 and valid = 1.  lo is the tone of the lower f and hi the other; T = F_lo + F_hi.
+ *   products       q = 0 .. 19 (WF_HIP_IMD_PRODUCTS = 20) enumerates the orders o = 2 .. 5, within an order m = 1 .. o - 1 (the
+ *                  multiple of f_hi) with n = o - m, and for each (m, n) first |m f_hi - n f_lo|, then m f_hi + n f_lo:
+ *                  q0 = f_hi - f_lo, q1 = f_hi + f_lo, q2 = |f_hi - 2 f_lo|, q3 = f_hi + 2 f_lo, q4 = 2 f_hi - f_lo,
+ *                  q5 = 2 f_hi + f_lo, q6 = |f_hi - 3 f_lo| ... q18 = 4 f_hi - f_lo, q19 = 4 f_hi + f_lo.  k_q = floor(f + 0.5).
+ *                  Product q is clear iff k_q >= 2H + 1, k_q + H <= M - 1, |k_q - k_lo| > 2H and |k_q - k_hi| > 2H; then
+ *                  R_q = the sum of p[k] over |k - k_q| <= H and bit q of `products` is set.  Products beyond the band are not
+ *                  folded back.
+ *   harmonics      for h = 2 .. 5 of each tone k = floor(h f + 0.5); the harmonic is in band iff k + H <= M - 1.  Their regions
+ *                  are only kept out of the noise estimate.
+ *   residue        one pass over H < k < M outside both tones' regions.  D sums every such bin.  A bin in the region of any clear
+ *                  product goes to I, once however many regions hold it; otherwise a bin in an in-band harmonic's region goes
+ *                  nowhere else; otherwise it goes to N, and n counts it.  N_s = N (M - 5H - 3) / n, or 0 when n = 0.
+ *   levels         dB(x, y) is WF_HIP_OUT_THD's.  Each float32 field is rounded once from float64.
+ *                    lo_hz, hi_hz (double)   f sr / P           lo_db, hi_db     dB(F, S): a sine of amplitude A reads 20 log10 A
+ *                    ratio_db                dB(F_hi, F_lo)
+ *                    product_db[q]           dB(R_q, T); -INFINITY when product q is not clear
+ *                    order_db[o - 2]         dB(the sum of the clear R_q of order o, q ascending, T); -INFINITY when none is clear
+ *                    imd_db                  dB(I, T); -INFINITY when no product is clear
+ *                    dfd2_db                 20 log10(sqrt R_0 / (sqrt F_lo + sqrt F_hi)), the difference-frequency distortion of
+ *                                            IEC 60268-3, second order; -INFINITY when q0 is not clear
+ *                    dfd3_db                 the same with sqrt R_2 + sqrt R_4 over the clear ones; -INFINITY when neither is clear
+ *                    mod_db                  dB(the sum of the clear R_q of q in {0, 1, 2, 3, 6, 7, 12, 13}, F_hi): the modulation
+ *                                            distortion of the DIN / SMPTE method, the sidebands f_hi +- n f_lo for n = 1 .. 4
+ *                                            against the upper tone
+ *                    tdn_db                  dB(D, T)           noise_db         dB(N_s, 2S): white noise of variance s^2 reads
+ *                                                                                10 log10 s^2
+ *                    lo_bin k_lo, hi_bin k_hi, products, tones, valid (uint32)
+ *                  Nothing reads NaN while valid is 1.
+ *   determinism    the order of every sum follows from P, the two bins and the k_q alone and there are no atomics: the same ring
+ *                  contents read bit-identically across push paths, repeated reads, slices and shards.
+ * What follows from the definition.  A tone must lie at least 17 bins up: about 100 Hz at P = 8192 and 48 kHz, so SMPTE's 60 Hz is
+ * out of reach at 48 kHz and DIN's 250 Hz + 8 kHz is not.  With one tone and a loud harmonic (above -30 dBc), the harmonic is taken
+ * for the second tone.  Two tones an exact octave apart have q0 on the lower tone, not clear.
+ * Computed when read, by one kernel on the handle's stream behind the pushes issued so far (one workgroup of 512 threads per stream,
+ * the distortion analyser's transform of P points in up to 128 KB of LDS), into a block the first read allocates; the tables are
+ * WF_HIP_OUT_THD's, built by whichever of the two outputs is read first.  A handle that never reads it allocates and launches
+ * nothing new, nothing is added to the tick, and no state is kept between reads.
+ * Cost on an MI355X, 4096 stereo streams, read into page-locked memory (1.5 MB back): 0.35 ms at W = 4096 against 0.29 ms for a
+ * WF_HIP_OUT_THD read in the same process and 2.36 ms for copying the 134.2 MB of windows to the host, and 0.71 ms against 0.63 and
+ * 4.71 ms at W = 16384 (P = 8192): 1.23 and 1.14 times the THD read's time, which it loses to, and 6.7 and 6.6 times faster than
+ * the copy.  Into a fresh pageable numpy array (the Python reader) a read takes 0.36 and 0.72 ms.  The kernel's own time without its
+ * copy is unmeasured (tools/imd_bench.py, profiles/imd_kernel_stats.json; INTEGRATION.md, "Intermodulation").
+ * Spectrum and meter batches with one or two captured channels and W >= 512 are served; on waveform batches and below 512 frames
+ * wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_IMD_PRODUCTS 20
+#define WF_HIP_IMD_MIN_RATIO 1e-3
+typedef struct wf_hip_imd_channel {
+    double lo_hz, hi_hz;
+    float lo_db, hi_db, ratio_db, imd_db;
+    float order_db[4];       /* [o - 2] */
+    float dfd2_db, dfd3_db, mod_db, tdn_db, noise_db;
+    float product_db[WF_HIP_IMD_PRODUCTS]; /* [q], against T */
+    uint32_t lo_bin, hi_bin;
+    uint32_t products;       /* bit q: product q is clear */
+    uint32_t tones;          /* 0, 1 or 2 tones found */
+    uint32_t valid;
+    uint32_t reserved[2];    /* 0 */
+} wf_hip_imd_channel;        /* 176 bytes */
+typedef struct wf_hip_imd {
+    wf_hip_imd_channel ch[2]; /* captured channels 0 and 1; with one captured channel ch[1] is all zero bytes */
+    uint32_t window;         /* P */
+    uint32_t reserved[3];    /* 0 */
+} wf_hip_imd;                /* 368 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

@@ -60,7 +60,7 @@ TICK_NO_DECIBELS = 1
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
     OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET, \
-    OUT_XFER, OUT_IMPULSE, OUT_CLICK = range(27)
+    OUT_XFER, OUT_IMPULSE, OUT_CLICK, OUT_IMD = range(28)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -295,6 +295,21 @@ CLICK_CHANNEL_DTYPE = np.dtype([("valid", np.uint32), ("events", np.uint32), ("h
                                 ("ev", CLICK_EVENT_DTYPE, (CLICK_MAX_EVENTS,))])
 CLICK_DTYPE = np.dtype([("ch", CLICK_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("order", np.uint32), ("reserved", np.uint32, (2,))])
 
+# struct wf_hip_imd (include/wf_hip.h): the two-tone intermodulation analyser, per captured channel the two tones of a twin-tone
+# stimulus, their IMD_PRODUCTS sum and difference products of orders 2 .. 5 against the two tones' power, total IMD, the
+# difference-frequency (IEC 60268-3) and modulation (DIN / SMPTE) distortion, distortion + noise and the noise floor of the newest P
+# frames of the ring through the distortion analyser's taper, P as THD's
+IMD_PRODUCTS = 20  # WF_HIP_IMD_PRODUCTS
+IMD_MIN_RATIO = 1e-3  # WF_HIP_IMD_MIN_RATIO
+IMD_ORDERS = 4  # orders 2 .. 5
+IMD_CHANNEL_DTYPE = np.dtype([("lo_hz", np.float64), ("hi_hz", np.float64), ("lo_db", np.float32), ("hi_db", np.float32),
+                              ("ratio_db", np.float32), ("imd_db", np.float32), ("order_db", np.float32, (IMD_ORDERS,)),
+                              ("dfd2_db", np.float32), ("dfd3_db", np.float32), ("mod_db", np.float32), ("tdn_db", np.float32),
+                              ("noise_db", np.float32), ("product_db", np.float32, (IMD_PRODUCTS,)), ("lo_bin", np.uint32),
+                              ("hi_bin", np.uint32), ("products", np.uint32), ("tones", np.uint32), ("valid", np.uint32),
+                              ("reserved", np.uint32, (2,))])
+IMD_DTYPE = np.dtype([("ch", IMD_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("reserved", np.uint32, (3,))])
+
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -317,11 +332,16 @@ MEASURES = {
     "impulse": (OUT_IMPULSE, IMPULSE_DTYPE, False),
     "click": (OUT_CLICK, CLICK_DTYPE, False),
 }
+# its continuation (MEASURES_MORE there): MEASURES is pinned at its seventeen names (tests/test_measure_tables_cpu.py), so the
+# outputs behind OUT_CLICK are listed here
+MEASURES_MORE = {
+    "imd": (OUT_IMD, IMD_DTYPE, False),
+}
 
 
 def _read_measure(batch, name: str, first: int, count: int | None) -> np.ndarray:
     """the reader `name` of a SpectrumBatch or MultiBatch: [count] or [count, output_channels] entries"""
-    what, dtype, per_row = MEASURES[name]
+    what, dtype, per_row = MEASURES[name] if name in MEASURES else MEASURES_MORE[name]
     return batch._read(what, first, count, (batch.output_channels,) if per_row else (), dtype)
 
 
@@ -608,6 +628,16 @@ class _MeasureReaders:
         an event it has seen by), strength_db and amplitude; valid = 0 for digital silence, a NaN or an infinity.  Fitted in float64
         on the device when read (batches of at least 256 frames).  With one captured channel ch[1] is all zero"""
         return _read_measure(self, "click", first, count)
+
+    def imd(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_imd (IMD_DTYPE): the two-tone intermodulation analyser, per captured channel ch[c]
+        the two strongest tones of the newest P = `window` frames of the ring as of the pushes issued so far (lo_hz, hi_hz, lo_db,
+        hi_db, ratio_db, lo_bin, hi_bin; `tones` = 0, 1 or 2 found, valid = 1 with two at most 30 dB apart), their IMD_PRODUCTS
+        products |m f_hi -+ n f_lo| of orders 2 .. 5 against the two tones' power (product_db[q], order_db[o - 2], the mask `products`
+        of those clear of the band's ends and of the tones; -inf otherwise), imd_db over all clear products, dfd2_db and dfd3_db
+        (IEC 60268-3), mod_db (DIN / SMPTE: the sidebands of the upper tone against it), tdn_db and noise_db.  P and the taper are
+        thd()'s; in float64 on the device when read (batches of at least 512 frames).  With one captured channel ch[1] is all zero"""
+        return _read_measure(self, "imd", first, count)
 
 
 class SpectrumBatch(_MeasureReaders):

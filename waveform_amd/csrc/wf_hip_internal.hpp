@@ -133,9 +133,10 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    static constexpr int N_MEASURES = 17;
-    char *d_measure[N_MEASURES] = {};
-    bool measure_ready[N_MEASURES] = {};
+    // (N_MEASURES rows in the table, N_MEASURES_MORE in its continuation, whose rows follow the table's here)
+    static constexpr int N_MEASURES = 17, N_MEASURES_MORE = 1;
+    char *d_measure[N_MEASURES + N_MEASURES_MORE] = {};
+    bool measure_ready[N_MEASURES + N_MEASURES_MORE] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
         wf::LoudState *d_state = nullptr;         // [n_streams]
@@ -168,7 +169,8 @@ struct wf_hip {
         uint32_t columns = 0;                     // T
         uint32_t first_covered = 0, end_covered = 0;
     } sono;
-    // what WF_HIP_OUT_THD derives from the configuration (setup_thd, at its first read: wf::host::thd_tables; wf_thd.hpp)
+    // what WF_HIP_OUT_THD and WF_HIP_OUT_IMD derive from the configuration (setup_thd or setup_imd, whichever output is read
+    // first: wf::host::thd_tables; wf_thd.hpp, wf_imd.hpp)
     struct Thd {
         double *d_tab = nullptr;                  // [P] taper, [P / 2][2] twiddles
         uint32_t P = 0, log2p = 0;                // the window: a power of two

@@ -1,7 +1,8 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE and _CLICK.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK and _IMD.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
-// sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from the configuration alone
+// sets up and how it is launched (MEASURES_MORE continues it); one reader (measure_read) does the rest.  What an output derives
+// from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
 // keeps state between reads: it follows every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip)
 // and is switched on by wf_hip_enable_loudness.  gfx950 only.
@@ -9,10 +10,11 @@
 // A new measurement output: its kernel in a header of its own, included here and nowhere else, with a wf::RingView in its
 // arguments if it reads the rings.  What kernels share lies in headers that hold no kernel (wf_wave_reduce.hpp, wf_ring_stage.hpp,
 // wf_fft64_lds.hpp, wf_phat.hpp): no kernel header includes another output's, but for wf_xfer.hpp and wf_impulse.hpp over
-// wf_xfer_sums.hpp, the head they share.  If it needs tables, a builder in wf_measure_tables.cpp that sees no handle and no HIP, and a
+// wf_xfer_sums.hpp, and wf_thd.hpp and wf_imd.hpp over wf_thd_spectrum.hpp, the heads they share.  If it needs tables, a builder in
+// wf_measure_tables.cpp that sees no handle and no HIP, and a
 // setup function here that calls it, keeps the scalars on the handle, states its kernels' dynamic LDS (allow_lds) and uploads; a
 // launch function (launch_by_channels where the kernel is instantiated per captured channels), a refusal function and a row of
-// MEASURES below; a row of MEASURES and a reader on _MeasureReaders in waveform_amd/binding.py.
+// MEASURES_MORE below; a row of MEASURES_MORE and a reader on _MeasureReaders in waveform_amd/binding.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +41,7 @@
 #include "wf_xfer.hpp"
 #include "wf_impulse.hpp"
 #include "wf_click.hpp"
+#include "wf_imd.hpp"
 
 namespace {
 
@@ -343,19 +346,30 @@ int launch_bits(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
-// what the distortion analyser derives from the configuration alone (wf::host::thd_tables), in one block
-int setup_thd(wf_hip *h)
+// what the distortion and the intermodulation analyser derive from the configuration alone (wf::host::thd_tables), in one block:
+// built by whichever of the two outputs is read first
+int setup_thd_tables(wf_hip *h)
 {
     wf_hip::Thd &d = h->thd;
+    if(d.d_tab != nullptr)
+        return WF_HIP_OK;
     const ThdTables t = thd_tables(h->cfg.sample_rate, h->N);
     d.P = t.P;
     d.log2p = t.log2p;
     d.S = t.S;
+    const int rc = upload(h, &d.d_tab, t.tab); // (pageable memory: staged before the call returns)
+    if(rc)
+        d.d_tab = nullptr; // (the next first read builds them again)
+    return rc;
+}
+
+int setup_thd(wf_hip *h)
+{
     // (128 KB at P = 8192: twice what a workgroup gets without asking, and one workgroup to a CU)
     const int lds = (int)(WF_HIP_THD_MAX_WINDOW * sizeof(double2));
     WF_TRY_RC(allow_lds(h, wf::thd_read_kernel<1>, lds));
     WF_TRY_RC(allow_lds(h, wf::thd_read_kernel<2>, lds));
-    return upload(h, &d.d_tab, t.tab); // (pageable memory: staged before the call returns)
+    return setup_thd_tables(h);
 }
 
 // one workgroup per stream over its newest P frames of every captured channel, behind the pushes issued
@@ -516,6 +530,35 @@ int launch_click(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// the intermodulation analyser's window and tables are the distortion analyser's
+int setup_imd(wf_hip *h)
+{
+    // (128 KB at P = 8192, as setup_thd)
+    const int lds = (int)(WF_HIP_THD_MAX_WINDOW * sizeof(double2));
+    WF_TRY_RC(allow_lds(h, wf::imd_read_kernel<1>, lds));
+    WF_TRY_RC(allow_lds(h, wf::imd_read_kernel<2>, lds));
+    return setup_thd_tables(h);
+}
+
+// one workgroup per stream over its newest P frames of every captured channel, behind the pushes issued
+int launch_imd(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Thd &d = h->thd;
+    wf::ImdArgs a{};
+    a.rings = ring_view(h);
+    a.out = static_cast<wf_hip_imd *>(d_block) + first;
+    a.window = d.d_tab;
+    a.tw = reinterpret_cast<const double2 *>(d.d_tab + d.P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    a.S = d.S;
+    a.sample_rate = (double)h->cfg.sample_rate;
+    a.first = first;
+    a.P = d.P; // (<= fft_size <= ring_cap)
+    a.log2p = d.log2p;
+    const size_t lds = (size_t)d.P * sizeof(double2);
+    launch_by_channels(h, wf::imd_read_kernel<1>, wf::imd_read_kernel<2>, dim3(count), wf::WF_THD_THREADS, lds, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -621,6 +664,13 @@ const char *why_no_click(const wf_hip *h)
     return h->N < 256 ? "the click detector needs a window of at least 256 frames" : nullptr;
 }
 
+const char *why_no_imd(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the intermodulation analyser belongs to spectrum and meter batches (a window of fft_size frames)";
+    return h->N < 512 ? "the intermodulation analyser needs a window of at least 512 frames" : nullptr;
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -651,13 +701,24 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_CLICK, sizeof(wf_hip_click), false, why_no_click, setup_click, launch_click},
 };
 
-int measure_row(wf_hip_output what) // -1: not a measurement output
+// The table's continuation, of the same row type: MEASURES is pinned at its seventeen rows (tests/test_measure_tables_cpu.py reads
+// them from this text), so the outputs behind WF_HIP_OUT_CLICK are listed here.  Row i's block is wf_hip::d_measure[N_MEASURES + i]
+constexpr Measure MEASURES_MORE[wf_hip::N_MEASURES_MORE] = {
+    {WF_HIP_OUT_IMD, sizeof(wf_hip_imd), false, why_no_imd, setup_imd, launch_imd},
+};
+
+int measure_row(wf_hip_output what) // over both tables; -1: not a measurement output
 {
     for(int i = 0; i < wf_hip::N_MEASURES; ++i)
         if(MEASURES[i].what == what)
             return i;
+    for(int i = 0; i < wf_hip::N_MEASURES_MORE; ++i)
+        if(MEASURES_MORE[i].what == what)
+            return wf_hip::N_MEASURES + i;
     return -1;
 }
+
+const Measure &measure_at(int row) { return row < wf_hip::N_MEASURES ? MEASURES[row] : MEASURES_MORE[row - wf_hip::N_MEASURES]; }
 
 size_t bytes_per_stream(const wf_hip *h, const Measure &m) { return m.entry_bytes * (m.per_row ? h->out_ch : 1u); }
 
@@ -694,15 +755,15 @@ bool wf::host::measure_source(const wf_hip *h, wf_hip_output what, size_t *per_s
     const int i = measure_row(what);
     if(i < 0)
         return false;
-    *why = MEASURES[i].why_not(h);
-    *per_stream = *why ? 0 : bytes_per_stream(h, MEASURES[i]);
+    *why = measure_at(i).why_not(h);
+    *per_stream = *why ? 0 : bytes_per_stream(h, measure_at(i));
     return true;
 }
 
 int wf::host::measure_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, void *out)
 {
     const int i = measure_row(what);
-    const Measure &m = MEASURES[i];
+    const Measure &m = measure_at(i);
     if(const char *why = m.why_not(h))
         return fail(h, WF_HIP_ERR_INVALID, "%s", why);
     if(out == nullptr)

@@ -62,7 +62,7 @@ SonoTables sono_tables(uint32_t sample_rate, uint32_t ring_cap);
 // the distortion analyser's window: the largest power of two <= min(fft_size, WF_HIP_THD_MAX_WINDOW) (<= ring_cap)
 uint32_t thd_window(uint32_t fft_size);
 
-// WF_HIP_OUT_THD (wf_thd.hpp): the periodic 7-term Blackman-Harris taper and the twiddles e^(-j 2 pi m / P) in float64, from long
+// WF_HIP_OUT_THD and WF_HIP_OUT_IMD (wf_thd.hpp, wf_imd.hpp): the periodic 7-term Blackman-Harris taper and the twiddles e^(-j 2 pi m / P) in float64, from long
 // double arguments, and S = P sum w^2 / 4, the lobe power of a sine of amplitude 1 (the sample rate changes none of them)
 struct ThdTables {
     uint32_t P = 0, log2p = 0;

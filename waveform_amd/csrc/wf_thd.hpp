@@ -8,7 +8,8 @@
 // One workgroup of WF_THD_THREADS per stream; the transform lives in LDS as P complex float64 (16 B each: 128 KB at P = 8192, one
 // workgroup to a CU).  The transform itself is wf_fft64_lds.hpp's, shared with the stereo image and the sonogram, as are its
 // swizzled slots: every phase below has consecutive lanes on consecutive bins and reads whole 16-byte slots, so 16 lanes cover one
-// 256-byte row whatever its permutation and no read conflicts.  Behind the transform:
+// 256-byte row whatever its permutation and no read conflicts.  The load, the transform and the bins' powers are
+// wf_thd_spectrum.hpp's, the head shared with the intermodulation analyser (wf_imd.hpp):
 //   bins       thread per pair (k, P - k): slot k becomes (p_0[k], p_1[k]), as wf_stereo.hpp does it; a channel whose window is
 //              all zeros, which the load has noted, reads 0 exactly.
 // then per channel
@@ -25,9 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wf_hip.h"
-#include "wf_ring_view.hpp"
-#include "wf_wave_reduce.hpp"
-#include "wf_fft64_lds.hpp"
+#include "wf_thd_spectrum.hpp"
 
 namespace wf {
 
@@ -42,22 +41,7 @@ struct ThdArgs {
     uint32_t P;              // window frames: a power of two, 512 <= P <= min(ring_cap, WF_HIP_THD_MAX_WINDOW)
     uint32_t log2p;
 };
-
-constexpr uint32_t WF_THD_THREADS = 512;
-constexpr uint32_t WF_THD_WAVES = WF_THD_THREADS / 64;
-static_assert(WF_THD_THREADS * 16 == WF_HIP_THD_MAX_WINDOW, "one thread per 16 frames of the largest window");
-static_assert(2 * WF_HIP_THD_LOBE + 1 <= 64, "a region is summed by the lanes of one wavefront");
 static_assert(WF_HIP_THD_HARMONICS <= 2 * WF_THD_WAVES, "at most two harmonics to a wavefront");
-
-// dB(x, y) of the definition: -inf where the numerator is 0, else +inf where the denominator is 0
-__device__ __forceinline__ double thd_db(double num, double den)
-{
-    if(num == 0.0)
-        return -INFINITY;
-    if(den == 0.0)
-        return INFINITY;
-    return 10.0 * log10(num / den);
-}
 
 // grid: one workgroup per stream of [first, first + gridDim.x); dynamic LDS: P * sizeof(double2)
 template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kernel(const ThdArgs a)
@@ -71,57 +55,13 @@ template<int CH> __global__ __launch_bounds__(WF_THD_THREADS) void thd_read_kern
     __shared__ uint32_t harm_k[WF_HIP_THD_HARMONICS]; // (~0: not in band)
     __shared__ double res_d[WF_THD_WAVES], res_n[WF_THD_WAVES], res_v[WF_THD_WAVES];
     __shared__ uint32_t res_cnt[WF_THD_WAVES], res_k[WF_THD_WAVES];
-    __shared__ uint32_t live[WF_THD_WAVES];           // (bit c: the wave has loaded a non-zero sample of channel c)
 
     constexpr uint32_t H = WF_HIP_THD_LOBE, NH = WF_HIP_THD_HARMONICS;
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const uint32_t stream = a.first + blockIdx.x;
     const uint32_t P = a.P, cb = a.log2p - 4u, M = P / 2u;
-    const uint32_t mask = a.rings.ring_cap - 1u;
-    const uint32_t s = window_start(a.rings, stream, P);
-    const float *r0 = channel_ring(a.rings, stream, 0, CH);
-    const float *r1 = channel_ring(a.rings, stream, CH - 1, CH);
 
-    // load: the 16-point transform of frames c' + m P/16 in registers; then the passes.  With two channels the load also notes
-    // which of them hold anything but zeros (`live`: the OR of the samples' magnitude bits, per wave, handed over before the
-    // passes' first barrier and read behind their last)
-    uint32_t any0 = 0, any1 = 0;
-    fft64_load16(lds, a.tw, t, P, cb, [&](uint32_t i) {
-        const uint32_t pos = (s + i) & mask;
-        const double w = a.window[i];
-        const float x0 = r0[pos], x1 = CH == 2 ? r1[pos] : 0.f;
-        any0 |= __float_as_uint(x0) & 0x7fffffffu;
-        any1 |= __float_as_uint(x1) & 0x7fffffffu;
-        return make_double2(w * (double)x0, w * (double)x1);
-    });
-    if(CH == 2) {
-        const bool w0 = __ballot(any0 != 0u) != 0ull, w1 = __ballot(any1 != 0u) != 0ull;
-        if(lane == 0u)
-            live[wave] = (w0 ? 1u : 0u) | (w1 ? 2u : 0u);
-    }
-    fft64_passes<WF_THD_THREADS>(lds, a.tw, t, P, cb, fft64_block_sync{});
-    uint32_t alive = 3u;
-    if(CH == 2) {
-        alive = 0u;
-#pragma unroll
-        for(uint32_t w = 0; w < WF_THD_WAVES; ++w)
-            alive |= live[w];
-    }
-
-    // bins: X_0 = (Z[k] + conj Z[P-k]) / 2, X_1 = (Z[k] - conj Z[P-k]) / 2j; slot k: |X_0|^2, |X_1|^2.  One channel: X_0 = Z
-    for(uint32_t k = 1u + t; k < M; k += WF_THD_THREADS) {
-        const uint32_t ia = fft64_at(k, cb);
-        const double2 za = lds[ia];
-        if(CH == 2) {
-            const double2 zb = lds[fft64_at(P - k, cb)];
-            const double lr = 0.5 * (za.x + zb.x), li = 0.5 * (za.y - zb.y);
-            const double rr = 0.5 * (za.y + zb.y), ri = -0.5 * (za.x - zb.x);
-            // (an all-zero channel is exact silence: the shared transform's rounding would leave it some 1e-32 of the other's power)
-            lds[ia] = make_double2((alive & 1u) ? lr * lr + li * li : 0.0, (alive & 2u) ? rr * rr + ri * ri : 0.0);
-        } else
-            lds[ia] = make_double2(za.x * za.x + za.y * za.y, 0.0);
-    }
-    __syncthreads();
+    // load, transform and bins: slot k becomes (p_0[k], p_1[k])
+    thd_spectrum<CH>(lds, a, t);
 
     wf_hip_thd *out = a.out + blockIdx.x;
 #pragma unroll
