@@ -78,6 +78,9 @@
  *                        twin-tone stimulus, their sum and difference products of orders 2 .. 5, total IMD, the difference-frequency
  *                        (IEC 60268-3) and modulation (DIN / SMPTE) distortion and the noise floor, from the distortion analyser's
  *                        float64 spectrum of every stream's newest window on the device when read
+ *   WF_HIP_OUT_TEMPO     not in the reference: tempo and beat phase, the onset strength of up to 2048 columns of every stream's
+ *                        rings, its autocorrelation, the tempo with a second candidate, and the frames of the last and the next
+ *                        beat on the sample counter, in float64 on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -492,11 +495,15 @@ typedef enum wf_hip_output {
                                   far, the frames a linear predictor fitted to the window cannot account for, as a count, a rate
                                   and the up to 8 strongest events (spectrum and meter batches of at least 256 frames; definition
                                   below) */
-    WF_HIP_OUT_IMD             /* wf_hip_imd                                 intermodulation: per captured channel the two tones
+    WF_HIP_OUT_IMD,            /* wf_hip_imd                                 intermodulation: per captured channel the two tones
                                   of a twin-tone stimulus, their 20 products of orders 2 .. 5, total IMD, DFD, modulation
                                   distortion, distortion + noise and the noise floor of the newest P frames in the rings as of the
                                   pushes issued so far, P as WF_HIP_OUT_THD's (spectrum and meter batches of at least 512 frames;
                                   definition below) */
+    WF_HIP_OUT_TEMPO           /* wf_hip_tempo                               tempo: the onset strength of the newest up to 2048
+                                  columns of 256 frames in the rings as of the pushes issued so far, its autocorrelation, the tempo
+                                  and a second candidate, and the frame of the last and the next beat on the sample counter
+                                  (spectrum and meter batches with a ring of at least 131072 frames; definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -1560,6 +1567,88 @@ typedef struct wf_hip_imd {
     uint32_t window;         /* P */
     uint32_t reserved[3];    /* 0 */
 } wf_hip_imd;                /* 368 bytes, a multiple of 16 */
+/* ---- tempo (WF_HIP_OUT_TEMPO) ------------------------------------------------------------------------------------------------
+ * Per stream, how fast the beat is and where it falls: the onset strength of WF_HIP_OUT_ONSET over seconds instead of 0.68 s, the
+ * periodicity of that curve, and the beat phase on the sample counter, so that a host can schedule the next beat instead of
+ * learning about the last.  sr = cfg.sample_rate; every sum is float64 in the order stated, on the float32 strengths.
+ *   columns        WF_HIP_OUT_ONSET's, bit for bit: P = WF_HIP_TEMPO_WINDOW = 1024, H = WF_HIP_TEMPO_HOP = 256, the same window,
+ *                  transform, bands, level S and strength (low + mid) + high rounded to float32 once; only the total is used.
+ *                  T = min(WF_HIP_TEMPO_COLUMNS, (ring_cap - P) / H - 1) strength columns: 507 for a ring of 131072 frames, 1019
+ *                  for 2^18, 2043 for 2^19, 2048 from 2^20 up (wf_hip_create's ring_frames).  strength[age], age 0 the newest,
+ *                  column newest - age with newest = wpos / H; ages >= T read 0.  Where WF_HIP_OUT_ONSET exists, strength[0 .. 127]
+ *                  is what it returns from the same handle at the same moment.  Below, o[n] is the curve oldest first,
+ *                  o[n] = strength[T - 1 - n].
+ *   lags           lag_lo = ceil(60 sr / (240 H)), lag_hi = min(floor(60 sr / (40 H)), T / 4, WF_HIP_TEMPO_MAX_LAG = 287) columns:
+ *                  240 down to 40 BPM where the ring and the rate allow it (47 .. 126 at 48 kHz with T = 507, which cannot read
+ *                  60 BPM; 47 .. 254 with T = 1019; 47 .. 281 from T = 2043 on).  Both are returned.
+ *   mean           mean = (o[0] + o[1] + ... + o[T - 1]) / T, added oldest first; e[n] = (double)o[n] - mean.
+ *   acf            r[L] = (sum over n = L .. T - 1 ascending of e[n] e[n - L]) / (T - L) for L = 0 .. 2 lag_hi + 1, each product
+ *                  rounded before it is added; acf[L] = r[L] / r[0], returned as float32, 0 from 2 lag_hi + 2 on.
+ *   salience       c[L] = (acf[L] + 0.5 acf[2 L]) w[L] for lag_lo <= L <= lag_hi, with w[L] = exp(-0.5 log2(bpm(L) / 120)^2) and
+ *                  bpm(L) = 60 sr / (H L): a preference of one octave's width around 120 BPM, which settles the octave question
+ *                  by a stated rule (w is a float64 table made by the host).
+ *   best           lag = the L with the largest c, the lowest on ties.  For lag_lo < lag < lag_hi the parabola through
+ *                  a = c[lag - 1], b = c[lag], g = c[lag + 1]: p = 0.5 (a - g) / (a - 2 b + g) when that denominator is
+ *                  negative, else 0; at either end of the range p = 0.  period = rint(16 (lag + p)) / 16 columns,
+ *                  bpm = 60 sr / (H (lag + p)), period_frames = period H (a whole number of frames), confidence = acf[lag],
+ *                  salience = c[lag].
+ *   second         among the L with lag_lo < L < lag_hi, c[L] > c[L - 1], c[L] >= c[L + 1] and |L - lag| > max(2, lag / 16)
+ *                  (integer division) the one with the largest c, the lowest on ties: lag2, bpm2 = 60 sr / (H lag2),
+ *                  salience2 = c[lag2], ambiguity = salience2 / salience (0 unless salience > 0); all 0 if there is none.  A
+ *                  bare pulse train is as much 87 as 174 BPM: this is where the entry says so.
+ *   phase          phi[k] = sum over j = 0, 1, ... of e[T - 1 - k - rint(j period)] while that index is >= 0, ascending j, for
+ *                  k = 0 .. ceil(period) - 1 (j period is exact in float64; rint rounds ties to even).  beat_age = the k with the
+ *                  largest phi, the lowest on ties; last_beat_frame = (newest - beat_age) H - 3 P / 8, WF_HIP_OUT_ONSET's
+ *                  convention for where an event starts (uint32, wraps with the counter); next_beat_frame = last_beat_frame +
+ *                  period_frames.
+ *   validity       valid = 1 if and only if every strength is finite, r[0] > 0 and the largest strength is at least
+ *                  WF_HIP_TEMPO_MARGIN = 2.0, the onset rule's margin: a curve that stays below it holds no onset by this
+ *                  library's own definition (a steady sine peaks at 0.007, noise at -60 dBFS at 0.06, noise at -20 dBFS at 3.3
+ *                  and reads valid with a confidence below 0.2).  With valid = 0 acf and every field but strength, columns,
+ *                  newest, lag_lo, lag_hi, window and hop are 0.  strength_max and strength_mean are the largest strength and
+ *                  `mean`.
+ *   determinism    no atomics, and every sum runs in a fixed order: the same frames read bit-identically across reads, push paths,
+ *                  slices and shards.
+ * What it reads on synthetic pulse trains (tests/tempo_ref.py, 48 kHz; 60 Hz kicks and 50 ms noise bursts over noise at -40 dBFS):
+ * 90, 120, 128 and 150 BPM at T = 507 and 60, 72.5, 90, 120, 128 and 150 BPM at T = 1019 and 2043 within 0.13 % (119.84 for 120)
+ * with a confidence of 0.80 or more and last_beat_frame within 432 frames of a true beat.  Not recovered: 174 BPM reads 87 from
+ * T = 1019 on (bpm2 reads 173); 200 BPM bursts read 100 (bpm2 201); 60 BPM at T = 507 reads 120.  The prior and the onset constants
+ * were chosen on synthetic signals and have not been tuned on recorded music.  Nothing is kept between reads: smoothing the tempo
+ * over time, time signatures and downbeats are the host's.
+ * Computed when read, by two kernels on the handle's stream behind the pushes issued so far -- the columns spread over the grid
+ * in chunks of 64 (256 threads, one wavefront per spectral column, float64 transforms in LDS) into a scratch block of 8 KB per
+ * stream, then one workgroup per stream for the rule -- into blocks the first read allocates together with its tables.  Cost on an
+ * MI355X: unmeasured (tools/tempo_bench.py).
+ * Spectrum and meter batches with one or two captured channels and any FFT size are served; on waveform batches, on handles
+ * whose ring holds fewer than WF_HIP_TEMPO_MIN_RING = 131072 frames and at sample rates for which lag_hi < lag_lo + 2 wf_hip_read
+ * returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device group reads it through wf_hip_multi_read. */
+#define WF_HIP_TEMPO_WINDOW 1024
+#define WF_HIP_TEMPO_HOP 256
+#define WF_HIP_TEMPO_COLUMNS 2048
+#define WF_HIP_TEMPO_LAGS 576
+#define WF_HIP_TEMPO_MAX_LAG 287
+#define WF_HIP_TEMPO_MIN_RING 131072
+#define WF_HIP_TEMPO_MARGIN 2.0
+typedef struct wf_hip_tempo {
+    float strength[WF_HIP_TEMPO_COLUMNS]; /* [age] */
+    float acf[WF_HIP_TEMPO_LAGS];         /* [L] */
+    float bpm, period;       /* of the best lag: beats per minute, and columns in sixteenths */
+    float confidence;        /* acf[lag] */
+    float salience;          /* c[lag] */
+    float bpm2, salience2;   /* of the second candidate */
+    float ambiguity;         /* salience2 / salience */
+    float strength_max, strength_mean;
+    uint32_t valid;
+    uint32_t columns;        /* T */
+    uint32_t newest;         /* wpos / H: the absolute index of the column of age 0 */
+    uint32_t lag_lo, lag_hi;
+    uint32_t lag, lag2;
+    uint32_t beat_age;       /* the age of the column the newest beat falls into */
+    uint32_t period_frames;  /* period H */
+    uint32_t last_beat_frame, next_beat_frame; /* on the sample counter, uint32 */
+    uint32_t window, hop;    /* P, H */
+    uint32_t reserved[2];    /* 0 */
+} wf_hip_tempo;              /* 10592 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

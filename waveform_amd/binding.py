@@ -60,7 +60,7 @@ TICK_NO_DECIBELS = 1
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
     OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET, \
-    OUT_XFER, OUT_IMPULSE, OUT_CLICK, OUT_IMD = range(28)
+    OUT_XFER, OUT_IMPULSE, OUT_CLICK, OUT_IMD, OUT_TEMPO = range(29)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -310,6 +310,24 @@ IMD_CHANNEL_DTYPE = np.dtype([("lo_hz", np.float64), ("hi_hz", np.float64), ("lo
                               ("reserved", np.uint32, (2,))])
 IMD_DTYPE = np.dtype([("ch", IMD_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("reserved", np.uint32, (3,))])
 
+# struct wf_hip_tempo (include/wf_hip.h): tempo and beat phase, strength[age] = the onset detector's total strength of the column
+# that ends at counter frame (newest - age) * TEMPO_HOP, for age < columns (0 beyond); acf[L] its autocorrelation at a lag of L
+# columns; the best lag as bpm and period, a second candidate, and the frames of the last and the next beat on the sample counter
+TEMPO_WINDOW = 1024  # WF_HIP_TEMPO_WINDOW
+TEMPO_HOP = 256  # WF_HIP_TEMPO_HOP
+TEMPO_COLUMNS = 2048  # WF_HIP_TEMPO_COLUMNS
+TEMPO_LAGS = 576  # WF_HIP_TEMPO_LAGS
+TEMPO_MAX_LAG = 287  # WF_HIP_TEMPO_MAX_LAG
+TEMPO_MIN_RING = 131072  # WF_HIP_TEMPO_MIN_RING
+TEMPO_MARGIN = 2.0  # WF_HIP_TEMPO_MARGIN
+TEMPO_DTYPE = np.dtype([("strength", np.float32, (TEMPO_COLUMNS,)), ("acf", np.float32, (TEMPO_LAGS,)), ("bpm", np.float32),
+                        ("period", np.float32), ("confidence", np.float32), ("salience", np.float32), ("bpm2", np.float32),
+                        ("salience2", np.float32), ("ambiguity", np.float32), ("strength_max", np.float32),
+                        ("strength_mean", np.float32), ("valid", np.uint32), ("columns", np.uint32), ("newest", np.uint32),
+                        ("lag_lo", np.uint32), ("lag_hi", np.uint32), ("lag", np.uint32), ("lag2", np.uint32), ("beat_age", np.uint32),
+                        ("period_frames", np.uint32), ("last_beat_frame", np.uint32), ("next_beat_frame", np.uint32),
+                        ("window", np.uint32), ("hop", np.uint32), ("reserved", np.uint32, (2,))])
+
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -337,11 +355,16 @@ MEASURES = {
 MEASURES_MORE = {
     "imd": (OUT_IMD, IMD_DTYPE, False),
 }
+# ... and its second (MEASURES_REST there): MEASURES_MORE is pinned at its one name in the same way (tests/test_imd_cpu.py), so the
+# outputs behind OUT_IMD are listed here; no test pins the length of this one
+MEASURES_REST = {
+    "tempo": (OUT_TEMPO, TEMPO_DTYPE, False),
+}
 
 
 def _read_measure(batch, name: str, first: int, count: int | None) -> np.ndarray:
     """the reader `name` of a SpectrumBatch or MultiBatch: [count] or [count, output_channels] entries"""
-    what, dtype, per_row = MEASURES[name] if name in MEASURES else MEASURES_MORE[name]
+    what, dtype, per_row = next(table[name] for table in (MEASURES, MEASURES_MORE, MEASURES_REST) if name in table)
     return batch._read(what, first, count, (batch.output_channels,) if per_row else (), dtype)
 
 
@@ -638,6 +661,19 @@ class _MeasureReaders:
         (IEC 60268-3), mod_db (DIN / SMPTE: the sidebands of the upper tone against it), tdn_db and noise_db.  P and the taper are
         thd()'s; in float64 on the device when read (batches of at least 512 frames).  With one captured channel ch[1] is all zero"""
         return _read_measure(self, "imd", first, count)
+
+    def tempo(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_tempo (TEMPO_DTYPE): tempo and beat phase.  strength[age] is onset()'s total strength
+        over the newest `columns` = up to TEMPO_COLUMNS columns of TEMPO_HOP frames in the ring as of the pushes issued so far (507
+        with ring_frames = 131072, 2043 with 2^19; 0 beyond), acf[L] its autocorrelation at a lag of L columns.  With valid = 1:
+        `lag` (of lag_lo .. lag_hi, 240 down to 40 BPM where the ring allows it) is the lag of the largest salience
+        (acf[L] + 0.5 acf[2 L]) w[L] under a preference of one octave around 120 BPM, bpm and period (columns) its parabolic
+        refinement, period_frames = period * TEMPO_HOP, confidence = acf[lag]; lag2, bpm2, salience2 and ambiguity =
+        salience2 / salience the second candidate (0: none); beat_age the age of the column of the newest beat, last_beat_frame
+        and next_beat_frame = last_beat_frame + period_frames its place on the uint32 sample counter.  valid = 0 (a non-finite
+        strength, a flat curve, or no strength of at least TEMPO_MARGIN) leaves everything but strength, columns, newest, lag_lo,
+        lag_hi, window and hop 0.  In float64 on the device when read (rings of at least TEMPO_MIN_RING frames)"""
+        return _read_measure(self, "tempo", first, count)
 
 
 class SpectrumBatch(_MeasureReaders):

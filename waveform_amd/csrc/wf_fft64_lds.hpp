@@ -1,7 +1,7 @@
 // wf_fft64_lds.hpp -- the complex float64 transform in LDS that the read kernels of WF_HIP_OUT_STEREO (wf_stereo.hpp: one
 // transform per workgroup of 256 threads), WF_HIP_OUT_SONO (wf_sono.hpp: one per wavefront), WF_HIP_OUT_THD and WF_HIP_OUT_IMD (wf_thd_spectrum.hpp for wf_thd.hpp and wf_imd.hpp: one
 // per workgroup of 512 threads, up to P = 8192), WF_HIP_OUT_DELAY (wf_delay.hpp: two per workgroup of 256 threads, one behind
-// the other in two regions), WF_HIP_OUT_ONSET (wf_onset.hpp: one per wavefront and round, as the sonogram's), WF_HIP_OUT_XFER
+// the other in two regions), WF_HIP_OUT_ONSET and WF_HIP_OUT_TEMPO (wf_onset_column.hpp for wf_onset.hpp and wf_tempo.hpp: one per wavefront and round, as the sonogram's), WF_HIP_OUT_XFER
 // (wf_xfer.hpp by wf_xfer_sums.hpp: up to 65 per workgroup of 256 threads, one behind the other in one region) and
 // WF_HIP_OUT_IMPULSE (wf_impulse.hpp: the same and two more) share (device code only; hipcc).
 //

@@ -133,10 +133,13 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    // (N_MEASURES rows in the table, N_MEASURES_MORE in its continuation, whose rows follow the table's here)
+    // (N_MEASURES rows in the table, N_MEASURES_MORE and N_MEASURES_REST in its two continuations, whose rows follow the table's
+    // here in that order)
     static constexpr int N_MEASURES = 17, N_MEASURES_MORE = 1;
-    char *d_measure[N_MEASURES + N_MEASURES_MORE] = {};
-    bool measure_ready[N_MEASURES + N_MEASURES_MORE] = {};
+    static constexpr int N_MEASURES_REST = 1;
+    static constexpr int N_MEASURES_ALL = N_MEASURES + N_MEASURES_MORE + N_MEASURES_REST;
+    char *d_measure[N_MEASURES_ALL] = {};
+    bool measure_ready[N_MEASURES_ALL] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
         wf::LoudState *d_state = nullptr;         // [n_streams]
@@ -186,6 +189,15 @@ struct wf_hip {
         double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_ONSET_BANDS + 1] band edges in bins of P
         uint32_t spectral = 0;                    // Ts = T + 1 spectral columns
     } onset;
+    // what WF_HIP_OUT_TEMPO derives from the sample rate and the ring (setup_tempo, at its first read: wf::host::sono_tables and
+    // wf::host::tempo_tables; wf_tempo.hpp)
+    struct Tempo {
+        double *d_tab = nullptr;                  // [P] window, [P / 2][2] twiddles, [WF_HIP_ONSET_BANDS + 1] band edges in bins of P
+        double *d_prior = nullptr;                // [WF_HIP_TEMPO_MAX_LAG + 1] w[L]
+        float *d_strength = nullptr;              // [n_streams][WF_HIP_TEMPO_COLUMNS] the columns kernel's strengths, by age
+        uint32_t columns = 0;                     // T
+        uint32_t lag_lo = 0, lag_hi = 0;
+    } tempo;
     // what WF_HIP_OUT_XFER and WF_HIP_OUT_IMPULSE derive from the configuration and the ring (setup_xfer_plan, at each output's first
     // read: wf::host::delay_tables at their own P; wf_xfer.hpp, wf_impulse.hpp).  A plan and a block each, so that neither output
     // needs the other read first

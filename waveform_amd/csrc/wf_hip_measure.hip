@@ -1,7 +1,7 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK and _IMD.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK, _IMD and _TEMPO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
-// sets up and how it is launched (MEASURES_MORE continues it); one reader (measure_read) does the rest.  What an output derives
+// sets up and how it is launched (MEASURES_MORE and MEASURES_REST continue it); one reader (measure_read) does the rest.  What an output derives
 // from the configuration alone
 // is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
 // keeps state between reads: it follows every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip)
@@ -10,11 +10,12 @@
 // A new measurement output: its kernel in a header of its own, included here and nowhere else, with a wf::RingView in its
 // arguments if it reads the rings.  What kernels share lies in headers that hold no kernel (wf_wave_reduce.hpp, wf_ring_stage.hpp,
 // wf_fft64_lds.hpp, wf_phat.hpp): no kernel header includes another output's, but for wf_xfer.hpp and wf_impulse.hpp over
-// wf_xfer_sums.hpp, and wf_thd.hpp and wf_imd.hpp over wf_thd_spectrum.hpp, the heads they share.  If it needs tables, a builder in
+// wf_xfer_sums.hpp, wf_thd.hpp and wf_imd.hpp over wf_thd_spectrum.hpp, and wf_onset.hpp and wf_tempo.hpp over wf_onset_column.hpp,
+// the heads they share.  If it needs tables, a builder in
 // wf_measure_tables.cpp that sees no handle and no HIP, and a
 // setup function here that calls it, keeps the scalars on the handle, states its kernels' dynamic LDS (allow_lds) and uploads; a
 // launch function (launch_by_channels where the kernel is instantiated per captured channels), a refusal function and a row of
-// MEASURES_MORE below; a row of MEASURES_MORE and a reader on _MeasureReaders in waveform_amd/binding.py.
+// MEASURES_REST below; a row of MEASURES_REST and a reader on _MeasureReaders in waveform_amd/binding.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +43,7 @@
 #include "wf_impulse.hpp"
 #include "wf_click.hpp"
 #include "wf_imd.hpp"
+#include "wf_tempo.hpp"
 
 namespace {
 
@@ -559,6 +561,64 @@ int launch_imd(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the tempo output derives from the sample rate and the ring alone: the sonogram's tables (wf::host::sono_tables) for its
+// columns, the lags and the preference (wf::host::tempo_tables), and the block its columns kernel leaves the strengths in
+int setup_tempo(wf_hip *h)
+{
+    wf_hip::Tempo &m = h->tempo;
+    const TempoTables t = tempo_tables(h->cfg.sample_rate, h->ring_cap); // (served: why_no_tempo)
+    m.columns = t.plan.columns;
+    m.lag_lo = t.plan.lag_lo;
+    m.lag_hi = t.plan.lag_hi;
+    // (66.5 KB, four columns' transforms and the round's levels: more than a workgroup gets without asking, and two workgroups to a CU)
+    WF_TRY_RC(allow_lds(h, wf::tempo_columns_kernel<1>, wf::WF_TEMPO_LDS_BYTES));
+    WF_TRY_RC(allow_lds(h, wf::tempo_columns_kernel<2>, wf::WF_TEMPO_LDS_BYTES));
+    // (a retry after a failed allocation or upload keeps what succeeded)
+    if(m.d_strength == nullptr)
+        WF_TRY_RC(dev_alloc(h, &m.d_strength, (size_t)h->n_streams * WF_HIP_TEMPO_COLUMNS));
+    if(m.d_tab == nullptr) {
+        const int rc = upload(h, &m.d_tab, sono_tables(h->cfg.sample_rate, h->ring_cap).tab); // (pageable memory: staged before the call returns)
+        if(rc) {
+            m.d_tab = nullptr; // (the next first read builds them again)
+            return rc;
+        }
+    }
+    return upload(h, &m.d_prior, t.prior);
+}
+
+// the columns in chunks of 64 over the grid, one wavefront per spectral column in rounds of four, then one workgroup per stream
+// for the rule: over the newest T + 1 columns of every captured channel's ring, behind the pushes issued
+int launch_tempo(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Tempo &m = h->tempo;
+    constexpr uint32_t P = WF_HIP_TEMPO_WINDOW;
+    wf::TempoColumnsArgs c{};
+    c.rings = ring_view(h);
+    c.strength = m.d_strength;
+    c.window = m.d_tab;
+    c.tw = reinterpret_cast<const double2 *>(m.d_tab + P); // (16-byte aligned: P doubles behind a hipMalloc'ed block)
+    c.edges = m.d_tab + 2 * (size_t)P;
+    c.columns = m.columns;
+    wf::TempoArgs a{};
+    a.rings = c.rings;
+    a.strength = m.d_strength;
+    a.prior = m.d_prior;
+    a.beats = 60.0 * (double)h->cfg.sample_rate / (double)WF_HIP_TEMPO_HOP;
+    a.columns = m.columns;
+    a.lag_lo = m.lag_lo;
+    a.lag_hi = m.lag_hi;
+    // (the columns kernel indexes streams by blockIdx.y, at most 65535: larger ranges go out in parts)
+    for(uint32_t off = 0; off < count; off += 65535u) {
+        const uint32_t part = std::min(65535u, count - off);
+        c.first = a.first = first + off;
+        a.out = static_cast<wf_hip_tempo *>(d_block) + first + off;
+        const dim3 grid((m.columns + wf::WF_TEMPO_CHUNK - 1) / wf::WF_TEMPO_CHUNK, part);
+        launch_by_channels(h, wf::tempo_columns_kernel<1>, wf::tempo_columns_kernel<2>, grid, wf::WF_ONSET_THREADS, wf::WF_TEMPO_LDS_BYTES, c);
+        hipLaunchKernelGGL(wf::tempo_read_kernel, dim3(part), dim3(wf::WF_TEMPO_THREADS), 0, h->stream, a);
+    }
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -671,6 +731,16 @@ const char *why_no_imd(const wf_hip *h)
     return h->N < 512 ? "the intermodulation analyser needs a window of at least 512 frames" : nullptr;
 }
 
+const char *why_no_tempo(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the tempo belongs to spectrum and meter batches";
+    if(h->ring_cap < WF_HIP_TEMPO_MIN_RING)
+        return "the tempo needs a ring of at least 131072 frames (wf_hip_create's ring_frames)";
+    return tempo_plan(h->cfg.sample_rate, h->ring_cap).served() ? nullptr
+                                                                 : "the tempo has fewer than three lags between 240 and 40 BPM at this sample rate";
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -707,7 +777,13 @@ constexpr Measure MEASURES_MORE[wf_hip::N_MEASURES_MORE] = {
     {WF_HIP_OUT_IMD, sizeof(wf_hip_imd), false, why_no_imd, setup_imd, launch_imd},
 };
 
-int measure_row(wf_hip_output what) // over both tables; -1: not a measurement output
+// ... and its second: tests/test_imd_cpu.py pins MEASURES_MORE at its one row in the same way, so the outputs behind WF_HIP_OUT_IMD
+// are listed here.  Row i's block is wf_hip::d_measure[N_MEASURES + N_MEASURES_MORE + i].  No test pins the length of this one
+constexpr Measure MEASURES_REST[wf_hip::N_MEASURES_REST] = {
+    {WF_HIP_OUT_TEMPO, sizeof(wf_hip_tempo), false, why_no_tempo, setup_tempo, launch_tempo},
+};
+
+int measure_row(wf_hip_output what) // over the three tables; -1: not a measurement output
 {
     for(int i = 0; i < wf_hip::N_MEASURES; ++i)
         if(MEASURES[i].what == what)
@@ -715,10 +791,19 @@ int measure_row(wf_hip_output what) // over both tables; -1: not a measurement o
     for(int i = 0; i < wf_hip::N_MEASURES_MORE; ++i)
         if(MEASURES_MORE[i].what == what)
             return wf_hip::N_MEASURES + i;
+    for(int i = 0; i < wf_hip::N_MEASURES_REST; ++i)
+        if(MEASURES_REST[i].what == what)
+            return wf_hip::N_MEASURES + wf_hip::N_MEASURES_MORE + i;
     return -1;
 }
 
-const Measure &measure_at(int row) { return row < wf_hip::N_MEASURES ? MEASURES[row] : MEASURES_MORE[row - wf_hip::N_MEASURES]; }
+const Measure &measure_at(int row)
+{
+    if(row < wf_hip::N_MEASURES)
+        return MEASURES[row];
+    row -= wf_hip::N_MEASURES;
+    return row < wf_hip::N_MEASURES_MORE ? MEASURES_MORE[row] : MEASURES_REST[row - wf_hip::N_MEASURES_MORE];
+}
 
 size_t bytes_per_stream(const wf_hip *h, const Measure &m) { return m.entry_bytes * (m.per_row ? h->out_ch : 1u); }
 

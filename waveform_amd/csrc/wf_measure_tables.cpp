@@ -260,4 +260,32 @@ uint32_t xfer_window(uint32_t fft_size, uint32_t ring_cap)
 
 uint32_t xfer_segments(uint32_t P, uint32_t ring_cap) { return std::min<uint32_t>(WF_HIP_XFER_MAX_SEGMENTS, 2 * ring_cap / P - 3); }
 
+static_assert(2 * WF_HIP_TEMPO_MAX_LAG + 2 == WF_HIP_TEMPO_LAGS, "acf[0 .. 2 lag_hi + 1] fits the entry");
+TempoPlan tempo_plan(uint32_t sample_rate, uint32_t ring_cap)
+{
+    constexpr uint64_t P = WF_HIP_TEMPO_WINDOW, H = WF_HIP_TEMPO_HOP;
+    TempoPlan t;
+    if(ring_cap < WF_HIP_TEMPO_MIN_RING || sample_rate == 0)
+        return t;
+    t.columns = (uint32_t)std::min<uint64_t>(WF_HIP_TEMPO_COLUMNS, (ring_cap - P) / H - 1);
+    const uint64_t beats = 60ull * sample_rate; // frames per minute: lag = beats / (bpm H)
+    const uint64_t lo = (beats + 240 * H - 1) / (240 * H);
+    t.lag_lo = (uint32_t)std::min<uint64_t>(lo, 0xFFFFFFFFu);
+    t.lag_hi = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(beats / (40 * H), t.columns / 4), WF_HIP_TEMPO_MAX_LAG);
+    return t;
+}
+
+TempoTables tempo_tables(uint32_t sample_rate, uint32_t ring_cap)
+{
+    TempoTables t;
+    t.plan = tempo_plan(sample_rate, ring_cap);
+    t.prior.assign(WF_HIP_TEMPO_MAX_LAG + 1, 0.0);
+    for(uint32_t L = 1; L <= WF_HIP_TEMPO_MAX_LAG; ++L) {
+        const double bpm = 60.0 * (double)sample_rate / ((double)WF_HIP_TEMPO_HOP * (double)L);
+        const double octaves = std::log2(bpm / 120.0);
+        t.prior[L] = std::exp(-0.5 * (octaves * octaves));
+    }
+    return t;
+}
+
 } // namespace wf::host

@@ -1,4 +1,4 @@
-// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD, _DELAY, _XFER and _IMPULSE derive from the configuration alone,
+// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD, _DELAY, _XFER, _IMPULSE and _TEMPO derive from the configuration alone,
 // built on the host (wf_measure_tables.cpp) at the output's first read and uploaded by wf_hip_measure.hip.  Plain C++: no HIP
 // and no handle, so the arithmetic also compiles into a program of its own (tests/test_measure_tables_cpu.py).  The sizes of
 // the constant-Q tables are in wf_cq_sizes.hpp, shared with the kernel (wf_cq.hpp).
@@ -88,5 +88,23 @@ DelayTables delay_tables(uint32_t N);
 // Its tables are delay_tables(P)
 uint32_t xfer_window(uint32_t fft_size, uint32_t ring_cap);
 uint32_t xfer_segments(uint32_t P, uint32_t ring_cap);
+
+// WF_HIP_OUT_TEMPO (wf_tempo.hpp): how many strength columns the ring holds, T = min(WF_HIP_TEMPO_COLUMNS, (ring_cap - P) / H - 1),
+// and the lags searched, lag_lo = ceil(60 sr / (240 H)) .. lag_hi = min(floor(60 sr / (40 H)), T / 4, WF_HIP_TEMPO_MAX_LAG), in
+// integer arithmetic.  columns == 0: the ring holds fewer than WF_HIP_TEMPO_MIN_RING frames.  served(): the output exists
+struct TempoPlan {
+    uint32_t columns = 0;
+    uint32_t lag_lo = 0, lag_hi = 0;
+    bool served() const { return columns != 0 && lag_hi >= lag_lo + 2; }
+};
+TempoPlan tempo_plan(uint32_t sample_rate, uint32_t ring_cap);
+
+// ... and the preference w[L] = exp(-0.5 log2(bpm(L) / 120)^2), bpm(L) = 60 sr / (H L), for L = 1 .. WF_HIP_TEMPO_MAX_LAG (w[0] = 0).
+// The window, twiddles and band edges of its columns are sono_tables(...).tab
+struct TempoTables {
+    TempoPlan plan;
+    std::vector<double> prior; // [WF_HIP_TEMPO_MAX_LAG + 1]
+};
+TempoTables tempo_tables(uint32_t sample_rate, uint32_t ring_cap);
 
 } // namespace wf::host

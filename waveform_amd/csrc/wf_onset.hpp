@@ -5,7 +5,8 @@
 // one fixed rule (the definition is in include/wf_hip.h, "onsets").  wf_hip_read launches it on the handle's stream, behind every
 // push issued so far, and copies the result back; nothing runs while the output is not read and nothing is kept between reads.
 //
-// One workgroup of 256 threads per stream, one wavefront per spectral column.  The columns are the sonogram's (wf_sono.hpp): the
+// One workgroup of 256 threads per stream, one wavefront per spectral column.  A column's level and flux are the functions of
+// wf_onset_column.hpp, the head this kernel shares with WF_HIP_OUT_TEMPO's (wf_tempo.hpp).  The columns are the sonogram's (wf_sono.hpp): the
 // same window, the same transform of P = 1024 points in 16 KB of LDS with wave-wide ordering points (wf_fft64_lds.hpp, unchanged),
 // the same bins and the same band sums, so that lane b ends up holding band b.  The Ts = T + 1 spectral columns go oldest first in
 // rounds of four, wave w of round r on column 4 r + w:
@@ -29,7 +30,7 @@
 #include <stdint.h>
 #include "wf_hip.h"
 #include "wf_ring_view.hpp"
-#include "wf_fft64_lds.hpp"
+#include "wf_onset_column.hpp"
 
 namespace wf {
 
@@ -43,22 +44,12 @@ struct OnsetArgs {
     uint32_t spectral;       // Ts, 2 <= Ts <= WF_HIP_ONSET_COLUMNS + 1: Ts H + P <= ring_cap
 };
 
-constexpr uint32_t WF_ONSET_P = WF_HIP_ONSET_WINDOW, WF_ONSET_H = WF_HIP_ONSET_HOP;
-constexpr uint32_t WF_ONSET_WAVES = 4;                     // spectral columns per round
-constexpr uint32_t WF_ONSET_THREADS = 64 * WF_ONSET_WAVES;
-constexpr uint32_t WF_ONSET_CB = 6;                        // log2 P - 4
 constexpr uint32_t WF_ONSET_A = WF_HIP_ONSET_COLUMNS;      // ages of an entry
 constexpr uint32_t WF_ONSET_BEFORE = 6, WF_ONSET_AFTER = 3, WF_ONSET_MEAN = 16; // the picking windows
-constexpr double WF_ONSET_KNEE = 100.0, WF_ONSET_MARGIN = 2.0;
-constexpr uint32_t WF_ONSET_LOW_END = 16, WF_ONSET_MID_END = 40; // the groups: bands [0, 16), [16, 40), [40, 64)
+constexpr double WF_ONSET_MARGIN = 2.0;
 // dynamic LDS: the four transforms, the round's table of S (five columns), the entry's 4 x 128 strengths, its 128 flag bytes
 constexpr size_t WF_ONSET_LDS_BYTES = (size_t)WF_ONSET_WAVES * WF_ONSET_P * sizeof(double2) + (WF_ONSET_WAVES + 1) * 64 * sizeof(double) +
                                       4 * WF_ONSET_A * sizeof(float) + WF_ONSET_A;
-static_assert(WF_ONSET_P == WF_HIP_SONO_WINDOW && WF_ONSET_H == WF_HIP_SONO_HOP && WF_HIP_ONSET_BANDS == WF_HIP_SONO_BANDS,
-              "the sonogram's columns and tables");
-static_assert(WF_ONSET_P == 16u << WF_ONSET_CB && WF_ONSET_P / 16 == 64, "one lane per 16 frames of a column");
-static_assert(WF_HIP_ONSET_BANDS == 64, "one lane per band");
-static_assert((WF_ONSET_H & (WF_ONSET_H - 1)) == 0, "the hop divides 2^32");
 static_assert(WF_ONSET_A <= WF_ONSET_THREADS && 4 * WF_ONSET_A == 2 * WF_ONSET_THREADS, "one thread per age; two floats per thread");
 static_assert(sizeof(wf_hip_onset) == 2240 && offsetof(wf_hip_onset, group) == WF_ONSET_A * sizeof(float) &&
                   offsetof(wf_hip_onset, flags) == 4 * WF_ONSET_A * sizeof(float),
@@ -68,7 +59,7 @@ static_assert(sizeof(wf_hip_onset) == 2240 && offsetof(wf_hip_onset, group) == W
 template<int CH> __global__ __launch_bounds__(WF_ONSET_THREADS) void onset_read_kernel(const OnsetArgs a)
 {
     extern __shared__ __align__(16) double2 onset_lds[];
-    constexpr uint32_t P = WF_ONSET_P, H = WF_ONSET_H, cb = WF_ONSET_CB, M = P / 2u, A = WF_ONSET_A;
+    constexpr uint32_t P = WF_ONSET_P, H = WF_ONSET_H, A = WF_ONSET_A;
     double *const stab = reinterpret_cast<double *>(onset_lds + WF_ONSET_WAVES * P); // [5][64]: row 0 the column before the round's
     float *const str = reinterpret_cast<float *>(stab + (WF_ONSET_WAVES + 1) * 64);  // [4][A]: total, low, mid, high by age
     uint8_t *const fl = reinterpret_cast<uint8_t *>(str + 4 * A);                    // [A]
@@ -89,14 +80,7 @@ template<int CH> __global__ __launch_bounds__(WF_ONSET_THREADS) void onset_read_
     const float *r1 = channel_ring(a.rings, stream, CH - 1, CH);
     double2 *lds = onset_lds + wave * P;
 
-    // lane b's band: the bins that can overlap [lo, hi], generously (a bin outside it has the weight 0 and adds nothing)
-    const double lo = a.edges[lane], hi = a.edges[lane + 1u];
-    const double f0 = floor(lo - 0.5), f1 = ceil(hi + 0.5) + 1.0;
-    const uint32_t k0 = f0 > 1.0 ? (f0 < (double)M ? (uint32_t)f0 : M) : 1u;
-    const uint32_t k1 = f1 < (double)M ? (f1 > 0.0 ? (uint32_t)f1 : 0u) : M;
-    // the sonogram's factor (a sine of amplitude A reads A^2) over the captured channels
-    constexpr double scale = 32.0 / (3.0 * (double)P * (double)P * (double)CH);
-    constexpr double ln10 = 2.302585092994045684;
+    const OnsetBand band = onset_band(a.edges, lane);
 
     const uint32_t rounds = (Ts + WF_ONSET_WAVES - 1u) / WF_ONSET_WAVES;
     for(uint32_t r = 0; r < rounds; ++r) {
@@ -106,58 +90,14 @@ template<int CH> __global__ __launch_bounds__(WF_ONSET_THREADS) void onset_read_
         double s_cur = 0.0;
         if(active) {
             const uint32_t s = newest_end - age * H - P; // the column's first frame, unmasked
-            fft64_load16(lds, a.tw, lane, P, cb, [&](uint32_t i) {
-                const uint32_t pos = (s + i) & mask;
-                const double w = a.window[i];
-                if constexpr(CH == 2)
-                    return make_double2(w * (double)r0[pos], w * (double)r1[pos]);
-                else
-                    return make_double2(w * (double)r0[pos], 0.0);
-            });
-            fft64_passes<64>(lds, a.tw, lane, P, cb, fft64_wave_sync{});
-
-            // bins: L = (Z[k] + conj Z[P-k]) / 2, R = (Z[k] - conj Z[P-k]) / 2j; slot k: |L|^2, |R|^2.  Slot P - k is read by this lane alone
-            for(uint32_t k = 1u + lane; k < M; k += 64u) {
-                const uint32_t ia = fft64_at(k, cb);
-                const double2 za = lds[ia];
-                if constexpr(CH == 2) {
-                    const double2 zb = lds[fft64_at(P - k, cb)];
-                    const double lr = 0.5 * (za.x + zb.x), li = 0.5 * (za.y - zb.y);
-                    const double rr = 0.5 * (za.y + zb.y), ri = -0.5 * (za.x - zb.x);
-                    lds[ia] = make_double2(lr * lr + li * li, rr * rr + ri * ri);
-                } else
-                    lds[ia] = make_double2(za.x * za.x + za.y * za.y, 0.0);
-            }
-            fft64_wave_sync{}();
-
-            // bands: lane b sums band b of each channel, ascending
-            double sa = 0.0, sb = 0.0;
-            for(uint32_t k = k0; k < k1; ++k) {
-                const double2 p = lds[fft64_at(k, cb)];
-                const double kk = (double)k;
-                const double w = fmax(fmin(kk + 0.5, hi) - fmax(kk - 0.5, lo), 0.0);
-                sa = fma(w, p.x, sa);
-                if constexpr(CH == 2)
-                    sb = fma(w, p.y, sb);
-            }
-            s_cur = log1p(WF_ONSET_KNEE * sqrt((sa + sb) * scale)) / ln10;
+            s_cur = onset_column_level<CH>(lds, r0, r1, a.window, a.tw, s, mask, lane, band);
             stab[(1u + wave) * 64u + lane] = s_cur;
         }
         __syncthreads(); // the round's table is written (and every lane of this wave is done with its transform region)
 
         if(active && j >= 1u) {
-            const double d = fmax(s_cur - stab[wave * 64u + lane], 0.0);
-            double *const dl = reinterpret_cast<double *>(lds);
-            dl[lane] = d;
-            fft64_wave_sync{}();
-            double sum = 0.0;
-            if(lane < 3u) {
-                const uint32_t b0 = lane == 0u ? 0u : (lane == 1u ? WF_ONSET_LOW_END : WF_ONSET_MID_END);
-                const uint32_t b1 = lane == 0u ? WF_ONSET_LOW_END : (lane == 1u ? WF_ONSET_MID_END : (uint32_t)WF_HIP_ONSET_BANDS);
-                for(uint32_t b = b0; b < b1; ++b)
-                    sum += dl[b];
-            }
-            const double low = __shfl(sum, 0), mid = __shfl(sum, 1), high = __shfl(sum, 2);
+            double low, mid, high;
+            onset_column_flux(lds, lane, s_cur, stab[wave * 64u + lane], low, mid, high);
             if(lane == 0u) { // (age < T: j >= 1)
                 str[age] = (float)((low + mid) + high);
                 str[A + age] = (float)low;
