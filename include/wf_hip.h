@@ -81,6 +81,10 @@
  *   WF_HIP_OUT_TEMPO     not in the reference: tempo and beat phase, the onset strength of up to 2048 columns of every stream's
  *                        rings, its autocorrelation, the tempo with a second candidate, and the frames of the last and the next
  *                        beat on the sample counter, in float64 on the device when read
+ *   WF_HIP_OUT_HUM       not in the reference: a mains hum detector, per captured channel whether a 50 or a 60 Hz line with its
+ *                        harmonics up to the 8th stands above the programme, the mains frequency, the level of the hum against the
+ *                        total and of every line, from the low bins of an exact float64 transform of the newest up to 32768 frames
+ *                        of every stream's rings on the device when read
  * FFT sizes: every multiple of 16 from 128 to 65536, the reference's own range with "enable large FFT" (src/source.cpp:349,
  * :359-363, :562-565).  Powers of two up to 32768 and the other sizes up to 16384 -- as a mixed-radix transform where the
  * size has small prime factors and at most one prime factor of up to 127 (the automatic sizes, 114 of the slider's 120
@@ -500,10 +504,15 @@ typedef enum wf_hip_output {
                                   distortion, distortion + noise and the noise floor of the newest P frames in the rings as of the
                                   pushes issued so far, P as WF_HIP_OUT_THD's (spectrum and meter batches of at least 512 frames;
                                   definition below) */
-    WF_HIP_OUT_TEMPO           /* wf_hip_tempo                               tempo: the onset strength of the newest up to 2048
+    WF_HIP_OUT_TEMPO,          /* wf_hip_tempo                               tempo: the onset strength of the newest up to 2048
                                   columns of 256 frames in the rings as of the pushes issued so far, its autocorrelation, the tempo
                                   and a second candidate, and the frame of the last and the next beat on the sample counter
                                   (spectrum and meter batches with a ring of at least 131072 frames; definition below) */
+    WF_HIP_OUT_HUM             /* wf_hip_hum                                 mains hum: per captured channel the family (50 or
+                                  60 Hz), the mains frequency, the qualified harmonics 1 .. 8 with their levels, the hum's level
+                                  against the total and the noise floor of the newest N <= 32768 frames in the rings as of the
+                                  pushes issued so far (spectrum and meter batches with a ring of at least sample_rate / 3 frames;
+                                  definition below) */
 } wf_hip_output;
 /* ---- spectral peaks (WF_HIP_OUT_PEAKS) ------------------------------------------------------------------------------------
  * Per stream and output channel, let d[0..M-1] be the row exactly as WF_HIP_OUT_DECIBELS returns it, M = fft_size / 2.
@@ -1649,6 +1658,91 @@ typedef struct wf_hip_tempo {
     uint32_t window, hop;    /* P, H */
     uint32_t reserved[2];    /* 0 */
 } wf_hip_tempo;              /* 10592 bytes, a multiple of 16 */
+/* ---- mains hum (WF_HIP_OUT_HUM) ----------------------------------------------------------------------------------------------
+ * Per captured channel, "is it humming": whether a line at 50 or 60 Hz and its harmonics stand above the programme -- a ground
+ * loop, a bad DI box, a dimmer beside a cable -- which family it is, the mains frequency, and how strong the hum is against the
+ * total.  sr = cfg.sample_rate; everything is float64; every sum runs in ascending harmonic order.
+ *   plan           D = the largest power of two with 1280 D <= sr (the decimation), N = min(ring_cap, WF_HIP_HUM_MAX_WINDOW,
+ *                  1024 D) the newest frames read, M = N / D (512 or 1024), hz = sr / N, K = ceil(8 * 60.5 / hz) + 22 bins.  48 kHz:
+ *                  N = 16384 and 2.93 Hz with a ring of 16384 frames, 32768 and 1.46 Hz from a ring of 32768 on.  fft_size plays
+ *                  no part.
+ *   spectrum       with x the newest N frames of the channel, float32 taken to float64, X[k] for k = -1 .. K is the N-point
+ *                  transform of x, formed exactly from D / 2 complex M-point transforms of the branches x[r], x[r + D], ... in
+ *                  pairs; H[k] = (0.5 X[k] - 0.25 (X[k - 1] + X[k + 1])) 4 / N for k = 0 .. K - 1, the transform of x through
+ *                  the periodic Hann window: a sine of amplitude A at a bin centre reads |H| = A.  p[k] = |H[k]|^2.
+ *   lines          for each family fam = 50, 60 and harmonic h = 1 .. WF_HIP_HUM_HARMONICS = 8:
+ *                  1. the bins lo = max(ceil(h (fam - 0.5) / hz - 0.5), 6) .. hi = floor(h (fam + 0.5) / hz + 0.5), in exact
+ *                     integer arithmetic; k = the bin of the largest |H| in it, the lowest on ties; none if hi < lo.
+ *                  2. it must be a local maximum: |H[k]| > |H[k - 1]| and |H[k]| >= |H[k + 1]|.
+ *                  3. alpha = the larger neighbour / |H[k]|, d = (2 alpha - 1) / (alpha + 1) held to [0, 0.5];
+ *                     amp = |H[k]| (1 - d^2) pi d / sin(pi d) (amp = |H[k]| at d = 0); f = (k + d) hz / h, k - d where the lower
+ *                     neighbour is the larger.
+ *                  4. |f - fam| <= WF_HIP_HUM_TOL_HZ = 0.5, else it is not mains (no equal-tempered note at A = 440 Hz falls
+ *                     inside either range: G1 = 49.0, G#1 = 51.9, A#1 = 58.3, B1 = 61.7 Hz).
+ *                  5. the local floor: the powers p of the bins [max(2, k - 20), max(2, k - 3)) and [k + 4, k + 21)
+ *                     (WF_HIP_HUM_FLOOR_SPAN = 20, WF_HIP_HUM_FLOOR_GUARD = 3), n of them, sorted; the one of rank n / 2 (integer
+ *                     division), divided by ln 2, which turns the median of an exponential distribution into its mean; at least
+ *                     1e-300.
+ *                  6. snr_db = 10 log10(amp^2 / floor); the line qualifies at snr_db >= WF_HIP_HUM_MARGIN_DB = 15.0.
+ *   family         per family: f0 = the mean of the qualified f weighted by (h amp)^2; lines with |f - f0| h > hz are dropped;
+ *                  hum = the sum of amp^2 / 2 over the rest.  The family with the larger hum wins, 50 on a tie; with no line in
+ *                  either, family = 0 and mains_hz, hum_db, ratio_db, odd_db, even_db, lines, mask and the three arrays are 0.
+ *                  A lone line at 300 Hz is the 6th harmonic of 50 and the 5th of 60 Hz alike: it reads 50, by the tie rule.
+ *   fields         mains_hz = the winner's f0; lines and mask (bit h - 1) its remaining harmonics; hz[h - 1] = f,
+ *                  level_db[h - 1] = 10 log10(amp^2) (dB re full scale, a sine of amplitude 1 reads 0), snr_db[h - 1], 0 where
+ *                  the mask bit is clear; hum_db = 10 log10(hum); total_db = 10 log10 of the mean square of the N frames (each
+ *                  thread of 256 adds the squares of frames t, t + 256, ... ascending, the 64 lanes of a wavefront combine at
+ *                  distances 32, 16 .. 1, the four wavefronts are added in ascending order); ratio_db = hum_db - total_db;
+ *                  odd_db and even_db = 10 log10 of the sums of amp^2 / 2 over the remaining harmonics 3, 5, 7 and 2, 4, 6, 8
+ *                  (0 where there is none): a rectifier's buzz and a transformer's hum read differently; noise_db = the rule of
+ *                  step 5 over the bins ceil(20 / hz) .. floor(8 * 60.5 / hz) outside +-3 bins of every remaining line, in
+ *                  level_db's scale: with nothing found, a line would have had to reach about noise_db + 15 to be seen.
+ *   validity       valid = 0 and every other field of the channel 0 for a window of zeros and for one that holds a NaN or an
+ *                  infinity.  A channel the batch does not capture reads zeros.
+ *   determinism    no atomics, and every sum runs in a fixed order: the same frames read bit-identically across reads, push
+ *                  paths, slices and shards.
+ * What it sees is hum that stands above the programme's density in its bin: in pauses, under speech, on idle lines.  On the numpy
+ * restatement (tests/hum_ref.py) lines at -40 / -46 / -43 / -52 dBFS on harmonics 1, 2, 3, 5 of 50 or 60 +- 0.2 Hz under white
+ * noise at -40 dBFS are found in every one of 30 seeds per plan, exactly those four, mains_hz within 0.027 Hz at N = 16384 and
+ * 0.011 Hz at N = 32768 / 48 kHz, levels within 1.43 dB; noise alone finds nothing in 200 seeds per plan.  White noise at -30 dBFS
+ * hides a -50 dBFS hum at N = 16384, and bass-heavy music hides more: no detection is promised under it.
+ * Computed when read, by one workgroup of 256 threads per stream and captured channel on the handle's stream behind the pushes
+ * issued so far: the window staged branch-major in LDS (128 KB at N = 32768), D / 2 transforms in a 16 KB region, the lines on
+ * sixteen lanes, the medians by exact selection.  Cost on an MI355X at 4096 stereo streams and 48 kHz, the copy to the host included:
+ * 2.27 ms per read with a ring of 16384 frames, 6.05 ms with 32768 (tools/hum_bench.py).
+ * Spectrum and meter batches with one or two captured channels and any FFT size are served; on waveform batches, on handles whose
+ * ring holds fewer than sample_rate / 3 frames (the default ring at 48 kHz: 5.9 Hz bins), and at sample rates under 2560 Hz or so
+ * high that no ring serves (above 3 * 32768 Hz) wf_hip_read returns WF_HIP_ERR_INVALID and wf_hip_output_bytes 0.  A multi-device
+ * group reads it through wf_hip_multi_read. */
+#define WF_HIP_HUM_HARMONICS 8
+#define WF_HIP_HUM_MARGIN_DB 15.0
+#define WF_HIP_HUM_TOL_HZ 0.5
+#define WF_HIP_HUM_FLOOR_SPAN 20
+#define WF_HIP_HUM_FLOOR_GUARD 3
+#define WF_HIP_HUM_MAX_WINDOW 32768
+typedef struct wf_hip_hum_channel {
+    float mains_hz;          /* f0 of the winning family */
+    float hum_db;            /* 10 log10 of the sum of amp^2 / 2 over its lines */
+    float total_db;          /* 10 log10 of the mean square of the N frames */
+    float ratio_db;          /* hum_db - total_db */
+    float odd_db, even_db;   /* over harmonics 3, 5, 7 and 2, 4, 6, 8 */
+    float noise_db;          /* the floor between the lines, in level_db's scale */
+    uint32_t valid;
+    uint32_t family;         /* 0, 50 or 60 */
+    uint32_t lines;          /* how many bits mask has */
+    uint32_t mask;           /* bit h - 1: harmonic h qualified */
+    float hz[WF_HIP_HUM_HARMONICS];       /* the line's frequency over h */
+    float level_db[WF_HIP_HUM_HARMONICS]; /* 10 log10(amp^2) */
+    float snr_db[WF_HIP_HUM_HARMONICS];   /* over the local floor */
+    uint32_t reserved;       /* 0 */
+} wf_hip_hum_channel;        /* 144 bytes */
+typedef struct wf_hip_hum {
+    wf_hip_hum_channel ch[2];
+    uint32_t window;         /* N */
+    uint32_t decimation;     /* D */
+    float resolution_hz;     /* sr / N */
+    uint32_t reserved;       /* 0 */
+} wf_hip_hum;                /* 304 bytes, a multiple of 16 */
 /* bytes per stream of an output of this batch (0: the batch has no such output) */
 size_t wf_hip_output_bytes(const wf_hip *h, wf_hip_output what);
 /* `what` of streams [first, first+count) as the ticks issued so far leave it, into `out` ([count] x the shape above); waits for

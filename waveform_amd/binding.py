@@ -60,7 +60,7 @@ TICK_NO_DECIBELS = 1
 # wf_hip_output / wf_hip_table_id (include/wf_hip.h)
 OUT_DECIBELS, OUT_BARS, OUT_PREMIRROR, OUT_VERTICES, OUT_VERTEX_COUNTS, OUT_LAST_SILENT, OUT_TSMOOTH, OUT_METER, OUT_INPUT_RMS, OUT_WAVEFORM_TS, \
     OUT_LOUDNESS, OUT_PEAKS, OUT_SIGNAL, OUT_PITCH, OUT_BANDS, OUT_STEREO, OUT_CQ, OUT_SCOPE, OUT_GONIO, OUT_SONO, OUT_BITS, OUT_THD, OUT_DELAY, OUT_ONSET, \
-    OUT_XFER, OUT_IMPULSE, OUT_CLICK, OUT_IMD, OUT_TEMPO = range(29)
+    OUT_XFER, OUT_IMPULSE, OUT_CLICK, OUT_IMD, OUT_TEMPO, OUT_HUM = range(30)
 (TABLE_WINDOW, TABLE_WINDOW_SUM, TABLE_SLOPE, TABLE_ROLLOFF, TABLE_INTERP_INDICES, TABLE_BAND_WIDTHS, TABLE_INTERP_WEIGHTS,
  TABLE_INTERP_SHAPE) = range(8)
 
@@ -328,6 +328,23 @@ TEMPO_DTYPE = np.dtype([("strength", np.float32, (TEMPO_COLUMNS,)), ("acf", np.f
                         ("period_frames", np.uint32), ("last_beat_frame", np.uint32), ("next_beat_frame", np.uint32),
                         ("window", np.uint32), ("hop", np.uint32), ("reserved", np.uint32, (2,))])
 
+# struct wf_hip_hum (include/wf_hip.h): mains hum, per captured channel the family (0 / 50 / 60), the mains frequency, the
+# qualified harmonics (mask bit h - 1; hz, level_db and snr_db at [h - 1], 0 where the bit is clear) and the hum's level against
+# the total, from the newest `window` frames at a resolution of resolution_hz
+HUM_HARMONICS = 8  # WF_HIP_HUM_HARMONICS
+HUM_MARGIN_DB = 15.0  # WF_HIP_HUM_MARGIN_DB
+HUM_TOL_HZ = 0.5  # WF_HIP_HUM_TOL_HZ
+HUM_FLOOR_SPAN = 20  # WF_HIP_HUM_FLOOR_SPAN
+HUM_FLOOR_GUARD = 3  # WF_HIP_HUM_FLOOR_GUARD
+HUM_MAX_WINDOW = 32768  # WF_HIP_HUM_MAX_WINDOW
+HUM_CHANNEL_DTYPE = np.dtype([("mains_hz", np.float32), ("hum_db", np.float32), ("total_db", np.float32), ("ratio_db", np.float32),
+                              ("odd_db", np.float32), ("even_db", np.float32), ("noise_db", np.float32), ("valid", np.uint32),
+                              ("family", np.uint32), ("lines", np.uint32), ("mask", np.uint32), ("hz", np.float32, (HUM_HARMONICS,)),
+                              ("level_db", np.float32, (HUM_HARMONICS,)), ("snr_db", np.float32, (HUM_HARMONICS,)),
+                              ("reserved", np.uint32)])
+HUM_DTYPE = np.dtype([("ch", HUM_CHANNEL_DTYPE, (2,)), ("window", np.uint32), ("decimation", np.uint32), ("resolution_hz", np.float32),
+                      ("reserved", np.uint32)])
+
 
 # the measurement outputs (csrc/wf_hip_measure.hip, MEASURES): reader -> (output, the dtype of an entry, one entry per m_decibels
 # row -- output_channels per stream -- rather than one per stream)
@@ -359,6 +376,7 @@ MEASURES_MORE = {
 # outputs behind OUT_IMD are listed here; no test pins the length of this one
 MEASURES_REST = {
     "tempo": (OUT_TEMPO, TEMPO_DTYPE, False),
+    "hum": (OUT_HUM, HUM_DTYPE, False),
 }
 
 
@@ -674,6 +692,21 @@ class _MeasureReaders:
         strength, a flat curve, or no strength of at least TEMPO_MARGIN) leaves everything but strength, columns, newest, lag_lo,
         lag_hi, window and hop 0.  In float64 on the device when read (rings of at least TEMPO_MIN_RING frames)"""
         return _read_measure(self, "tempo", first, count)
+
+    def hum(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """[count] structured array of wf_hip_hum (HUM_DTYPE): mains hum.  Per captured channel ch[c] of the newest `window` = N
+        frames in the ring as of the pushes issued so far (N = 16384 at 48 kHz with ring_frames = 16384, 32768 from 32768 on;
+        resolution_hz = sample_rate / N): `family` 50 or 60 where lines at h times 50 +- 0.5 or 60 +- 0.5 Hz, h = 1 .. HUM_HARMONICS,
+        stand HUM_MARGIN_DB above the local floor and agree on one mains frequency, else 0; `mask` (bit h - 1) and `lines` the
+        harmonics found, hz[h - 1] each line's frequency over h, level_db[h - 1] its level (a sine of amplitude 1 reads 0) and
+        snr_db[h - 1] its height over the floor, 0 where the bit is clear; mains_hz their weighted mean; hum_db the lines' power,
+        total_db the window's mean square, ratio_db = hum_db - total_db; odd_db and even_db the harmonics 3, 5, 7 and 2, 4, 6, 8
+        (0: none); noise_db the floor between the lines: with nothing found, a line would have had to reach about noise_db + 15.
+        valid = 0 (a window of zeros, a NaN or an infinity) leaves the channel 0, as is a channel the batch does not capture.  A
+        lone 300 Hz line reads as the 6th of 50 Hz.  It sees hum above the programme's density in its bin -- pauses, speech, idle
+        lines -- and promises nothing under bass-heavy music.  In float64 on the device when read (rings of at least
+        sample_rate / 3 frames)"""
+        return _read_measure(self, "hum", first, count)
 
 
 class SpectrumBatch(_MeasureReaders):

@@ -2,8 +2,9 @@
 // transform per workgroup of 256 threads), WF_HIP_OUT_SONO (wf_sono.hpp: one per wavefront), WF_HIP_OUT_THD and WF_HIP_OUT_IMD (wf_thd_spectrum.hpp for wf_thd.hpp and wf_imd.hpp: one
 // per workgroup of 512 threads, up to P = 8192), WF_HIP_OUT_DELAY (wf_delay.hpp: two per workgroup of 256 threads, one behind
 // the other in two regions), WF_HIP_OUT_ONSET and WF_HIP_OUT_TEMPO (wf_onset_column.hpp for wf_onset.hpp and wf_tempo.hpp: one per wavefront and round, as the sonogram's), WF_HIP_OUT_XFER
-// (wf_xfer.hpp by wf_xfer_sums.hpp: up to 65 per workgroup of 256 threads, one behind the other in one region) and
-// WF_HIP_OUT_IMPULSE (wf_impulse.hpp: the same and two more) share (device code only; hipcc).
+// (wf_xfer.hpp by wf_xfer_sums.hpp: up to 65 per workgroup of 256 threads, one behind the other in one region),
+// WF_HIP_OUT_IMPULSE (wf_impulse.hpp: the same and two more) and WF_HIP_OUT_HUM (wf_hum.hpp: up to 32 of 512 or 1024 points per
+// workgroup of 256 threads, one behind the other in one region) share (device code only; hipcc).
 //
 // P complex float64 (16 B each), P a power of two >= 64, decimation in time, natural order out:
 //   load    thread c' < P / 16 takes the 16 elements c' + m P/16, m = 0 .. 15 (consecutive lanes on consecutive elements) from

@@ -1408,6 +1408,7 @@ static const void *output_source(const wf_hip *h, wf_hip_output what, size_t *pe
     case WF_HIP_OUT_CLICK:
     case WF_HIP_OUT_IMD:
     case WF_HIP_OUT_TEMPO:
+    case WF_HIP_OUT_HUM:
         break; // (never asked here: measure_source answers for them)
     }
     *why = "unknown output";

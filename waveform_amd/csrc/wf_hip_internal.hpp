@@ -136,7 +136,7 @@ struct wf_hip {
     // (N_MEASURES rows in the table, N_MEASURES_MORE and N_MEASURES_REST in its two continuations, whose rows follow the table's
     // here in that order)
     static constexpr int N_MEASURES = 17, N_MEASURES_MORE = 1;
-    static constexpr int N_MEASURES_REST = 1;
+    static constexpr int N_MEASURES_REST = 2;
     static constexpr int N_MEASURES_ALL = N_MEASURES + N_MEASURES_MORE + N_MEASURES_REST;
     char *d_measure[N_MEASURES_ALL] = {};
     bool measure_ready[N_MEASURES_ALL] = {};
@@ -198,6 +198,15 @@ struct wf_hip {
         uint32_t columns = 0;                     // T
         uint32_t lag_lo = 0, lag_hi = 0;
     } tempo;
+    // what WF_HIP_OUT_HUM derives from the sample rate and the ring (setup_hum, at its first read: wf::host::hum_tables; wf_hum.hpp)
+    struct Hum {
+        double *d_tw = nullptr;                   // [M / 2][2] twiddles of the M-point transform
+        double *d_comb = nullptr;                 // [D][K + 2][2] the combination twiddles W_N^(r k), k = -1 .. K
+        uint32_t *d_ranges = nullptr;             // [2][16] the bins searched for every (family, harmonic): first, then last
+        uint32_t D = 0, N = 0, M = 0, log2m = 0, K = 0;
+        uint32_t noise_lo = 0, noise_hi = 0;
+        double hz = 0.0;
+    } hum;
     // what WF_HIP_OUT_XFER and WF_HIP_OUT_IMPULSE derive from the configuration and the ring (setup_xfer_plan, at each output's first
     // read: wf::host::delay_tables at their own P; wf_xfer.hpp, wf_impulse.hpp).  A plan and a block each, so that neither output
     // needs the other read first

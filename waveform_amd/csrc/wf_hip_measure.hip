@@ -1,5 +1,5 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK, _IMD and _TEMPO.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK, _IMD, _TEMPO and _HUM.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
 // of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
 // sets up and how it is launched (MEASURES_MORE and MEASURES_REST continue it); one reader (measure_read) does the rest.  What an output derives
 // from the configuration alone
@@ -44,6 +44,7 @@
 #include "wf_click.hpp"
 #include "wf_imd.hpp"
 #include "wf_tempo.hpp"
+#include "wf_hum.hpp"
 
 namespace {
 
@@ -619,6 +620,59 @@ int launch_tempo(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
     return WF_HIP_OK;
 }
 
+// what the hum detector derives from the sample rate and the ring alone (wf::host::hum_tables): the plan's scalars, the twiddles of
+// the M-point transform, the combination twiddles and the search ranges
+int setup_hum(wf_hip *h)
+{
+    wf_hip::Hum &m = h->hum;
+    const HumTables t = hum_tables(h->cfg.sample_rate, h->ring_cap); // (served: why_no_hum)
+    const HumPlan &p = t.plan;
+    m.D = p.D;
+    m.N = p.N;
+    m.M = p.M;
+    m.log2m = p.log2m;
+    m.K = p.K;
+    m.noise_lo = p.noise_lo;
+    m.noise_hi = p.noise_hi;
+    m.hz = p.hz;
+    // (the staged window, 128 KB at N = 32768, the transform's 16 KB and the bins: the most of every plan, 157.1 KB, with the
+    // hand-overs inside the 160 KiB a workgroup may hold -- wf_hum.hpp asserts it -- and one workgroup to a CU)
+    WF_TRY_RC(allow_lds(h, wf::hum_read_kernel, wf::hum_lds_bytes(32, 1024, wf::WF_HUM_MAX_BINS - 2)));
+    // (a retry after a failed allocation or upload keeps what succeeded; pageable memory: staged before the calls return)
+    if(m.d_tw == nullptr)
+        WF_TRY_RC(upload(h, &m.d_tw, t.tw));
+    if(m.d_comb == nullptr)
+        WF_TRY_RC(upload(h, &m.d_comb, t.comb));
+    return upload(h, &m.d_ranges, t.ranges);
+}
+
+// one workgroup per stream and captured channel over the newest N frames of its ring, behind the pushes issued
+int launch_hum(wf_hip *h, uint32_t first, uint32_t count, void *d_block)
+{
+    const wf_hip::Hum &m = h->hum;
+    wf::HumArgs a{};
+    a.rings = ring_view(h);
+    a.tw = reinterpret_cast<const double2 *>(m.d_tw); // (16-byte aligned: hipMalloc'ed blocks)
+    a.comb = reinterpret_cast<const double2 *>(m.d_comb);
+    a.ranges = m.d_ranges;
+    a.hz = m.hz;
+    a.channels = h->cap_ch;
+    a.D = m.D;
+    a.log2d = (uint32_t)__builtin_ctz(m.D);
+    a.N = m.N; // (<= ring_cap)
+    a.M = m.M;
+    a.log2m = m.log2m;
+    a.K = m.K;
+    a.noise_lo = m.noise_lo;
+    a.noise_hi = m.noise_hi;
+    const size_t lds = wf::hum_lds_bytes(m.D, m.M, m.K);
+    // (streams by blockIdx.x, channels by blockIdx.y; a grid's x holds any count of streams there is)
+    a.first = first;
+    a.out = static_cast<wf_hip_hum *>(d_block) + first;
+    hipLaunchKernelGGL(wf::hum_read_kernel, dim3(count, h->cap_ch), dim3(wf::WF_HUM_THREADS), lds, h->stream, a);
+    return WF_HIP_OK;
+}
+
 // why a batch has no such output (nullptr: it has)
 const char *why_no_loudness(const wf_hip *h) { return loudness_on(h) ? nullptr : "the loudness producer is not enabled (wf_hip_enable_loudness)"; }
 const char *why_no_peaks(const wf_hip *h) { return (h->meter || h->wave) ? "meter / waveform batch: spectral peaks belong to spectrum batches" : nullptr; }
@@ -741,6 +795,17 @@ const char *why_no_tempo(const wf_hip *h)
                                                                  : "the tempo has fewer than three lags between 240 and 40 BPM at this sample rate";
 }
 
+const char *why_no_hum(const wf_hip *h)
+{
+    if(h->wave)
+        return "waveform batch: the hum detector belongs to spectrum and meter batches";
+    const HumPlan p = hum_plan(h->cfg.sample_rate, h->ring_cap);
+    if(p.served())
+        return nullptr;
+    return p.too_fast() ? "the hum detector serves no sample rate under 2560 Hz or above 98304 Hz (bins of at most 3 Hz from 32768 frames)"
+                        : "the hum detector needs a ring of at least sample_rate / 3 frames (wf_hip_create's ring_frames)";
+}
+
 struct Measure {
     wf_hip_output what;
     size_t entry_bytes;
@@ -781,6 +846,7 @@ constexpr Measure MEASURES_MORE[wf_hip::N_MEASURES_MORE] = {
 // are listed here.  Row i's block is wf_hip::d_measure[N_MEASURES + N_MEASURES_MORE + i].  No test pins the length of this one
 constexpr Measure MEASURES_REST[wf_hip::N_MEASURES_REST] = {
     {WF_HIP_OUT_TEMPO, sizeof(wf_hip_tempo), false, why_no_tempo, setup_tempo, launch_tempo},
+    {WF_HIP_OUT_HUM, sizeof(wf_hip_hum), false, why_no_hum, setup_hum, launch_hum},
 };
 
 int measure_row(wf_hip_output what) // over the three tables; -1: not a measurement output

@@ -2,6 +2,7 @@
 #include "wf_measure_tables.hpp"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 
 namespace wf::host {
@@ -285,6 +286,65 @@ TempoTables tempo_tables(uint32_t sample_rate, uint32_t ring_cap)
         const double octaves = std::log2(bpm / 120.0);
         t.prior[L] = std::exp(-0.5 * (octaves * octaves));
     }
+    return t;
+}
+
+static_assert(WF_HIP_HUM_MAX_WINDOW == 32768 && (WF_HIP_HUM_MAX_WINDOW & (WF_HIP_HUM_MAX_WINDOW - 1)) == 0, "the hum detector's largest window");
+HumPlan hum_plan(uint32_t sample_rate, uint32_t ring_cap)
+{
+    HumPlan p;
+    const uint64_t sr = sample_rate;
+    if(sr < 1280 || ring_cap == 0)
+        return p;
+    uint64_t D = 1;
+    while(1280 * 2 * D <= sr)
+        D *= 2;
+    const uint64_t N = std::min<uint64_t>(std::min<uint64_t>(ring_cap, WF_HIP_HUM_MAX_WINDOW), 1024 * D);
+    p.D = (uint32_t)D;
+    p.N = (uint32_t)N;
+    p.M = (uint32_t)(N / D);
+    while((2u << p.log2m) <= p.M)
+        ++p.log2m;
+    p.hz = (double)sample_rate / (double)p.N;
+    p.K = (uint32_t)((484 * N + sr - 1) / sr) + 22u;
+    p.noise_lo = (uint32_t)((20 * N + sr - 1) / sr);
+    p.noise_hi = (uint32_t)(484 * N / sr);
+    p.any_ring = D >= 2 && sr <= 3ull * WF_HIP_HUM_MAX_WINDOW;
+    p.fits = D >= 2 && sr <= 3 * N && p.M >= 64; // (hz <= 3.0; a ring that is a power of two gives M = 512 or 1024 here)
+    if(!p.fits)
+        return p;
+    for(uint32_t i = 0; i < 2 * WF_HIP_HUM_HARMONICS; ++i) {
+        const uint64_t fam = i < WF_HIP_HUM_HARMONICS ? 50 : 60, h = 1 + i % WF_HIP_HUM_HARMONICS;
+        // ceil((h (2 fam - 1) N - sr) / (2 sr)) and floor((h (2 fam + 1) N + sr) / (2 sr)): 99 N >= 33 sr, so nothing is negative
+        const uint64_t lo = (h * (2 * fam - 1) * N - sr + 2 * sr - 1) / (2 * sr);
+        p.lo[i] = (uint32_t)std::max<uint64_t>(lo, 6);
+        p.hi[i] = (uint32_t)((h * (2 * fam + 1) * N + sr) / (2 * sr));
+    }
+    return p;
+}
+
+HumTables hum_tables(uint32_t sample_rate, uint32_t ring_cap)
+{
+    HumTables t;
+    t.plan = hum_plan(sample_rate, ring_cap);
+    const HumPlan &p = t.plan;
+    if(!p.served())
+        return t;
+    assert(p.K + 1 < p.M / 2 && p.hi[2 * WF_HIP_HUM_HARMONICS - 1] + WF_HIP_HUM_FLOOR_SPAN < p.K);
+    t.tw.resize(p.M);
+    twiddles_from_long_double(t.tw.data(), p.M);
+    const size_t bins = (size_t)p.K + 2;
+    t.comb.resize((size_t)p.D * bins * 2);
+    for(uint32_t r = 0; r < p.D; ++r)
+        for(size_t i = 0; i < bins; ++i) {
+            // r k modulo N, k = i - 1 (k = -1: N - r)
+            const uint64_t rk = i == 0 ? (p.N - r) % p.N : ((uint64_t)r * (i - 1)) % p.N;
+            const long double x = TWO_PI_L * (long double)rk / (long double)p.N;
+            t.comb[2 * (r * bins + i)] = (double)std::cos(x);
+            t.comb[2 * (r * bins + i) + 1] = (double)-sin_alone(x);
+        }
+    t.ranges.assign(p.lo, p.lo + 2 * WF_HIP_HUM_HARMONICS);
+    t.ranges.insert(t.ranges.end(), p.hi, p.hi + 2 * WF_HIP_HUM_HARMONICS);
     return t;
 }
 

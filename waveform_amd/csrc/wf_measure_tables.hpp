@@ -1,4 +1,4 @@
-// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD, _DELAY, _XFER, _IMPULSE and _TEMPO derive from the configuration alone,
+// wf_measure_tables.hpp -- what the measurement outputs WF_HIP_OUT_BANDS, _STEREO, _CQ, _SONO, _THD, _DELAY, _XFER, _IMPULSE, _TEMPO and _HUM derive from the configuration alone,
 // built on the host (wf_measure_tables.cpp) at the output's first read and uploaded by wf_hip_measure.hip.  Plain C++: no HIP
 // and no handle, so the arithmetic also compiles into a program of its own (tests/test_measure_tables_cpu.py).  The sizes of
 // the constant-Q tables are in wf_cq_sizes.hpp, shared with the kernel (wf_cq.hpp).
@@ -106,5 +106,32 @@ struct TempoTables {
     std::vector<double> prior; // [WF_HIP_TEMPO_MAX_LAG + 1]
 };
 TempoTables tempo_tables(uint32_t sample_rate, uint32_t ring_cap);
+
+// WF_HIP_OUT_HUM (wf_hum.hpp): the decimation D = the largest power of two with 1280 D <= sample_rate, the window N = min(ring_cap,
+// WF_HIP_HUM_MAX_WINDOW, 1024 D), M = N / D points per transform, K = ceil(8 * 60.5 N / sr) + 22 bins beside bin -1, the bins
+// noise_lo = ceil(20 N / sr) .. noise_hi = floor(484 N / sr) of the noise floor, and the bins lo[i] .. hi[i] searched for harmonic
+// h = 1 + i % 8 of family 50 (i < 8) or 60: max(ceil(h (fam - 0.5) N / sr - 0.5), 6) .. floor(h (fam + 0.5) N / sr + 0.5), all in
+// integer arithmetic.  served(): the output exists (D >= 2 and bins of at most 3 Hz); too_fast(): no ring would do
+struct HumPlan {
+    uint32_t D = 0, N = 0, M = 0, log2m = 0, K = 0;
+    uint32_t noise_lo = 0, noise_hi = 0;
+    uint32_t lo[2 * WF_HIP_HUM_HARMONICS] = {}, hi[2 * WF_HIP_HUM_HARMONICS] = {};
+    double hz = 0.0;
+    bool fits = false, any_ring = false;
+    bool served() const { return fits; }
+    bool too_fast() const { return !any_ring; }
+};
+HumPlan hum_plan(uint32_t sample_rate, uint32_t ring_cap);
+
+// ... and its tables: the twiddles e^(-j 2 pi m / M) of the M-point transform, the combination twiddles W_N^(r k) =
+// e^(-j 2 pi r k / N) for r < D and k = -1 .. K as comb[r (K + 2) + k + 1], both in float64 from long double arguments reduced
+// modulo the period, and the search ranges as words: ranges[i] = lo[i], ranges[16 + i] = hi[i]
+struct HumTables {
+    HumPlan plan;
+    std::vector<double> tw;       // [M / 2][2]
+    std::vector<double> comb;     // [D][K + 2][2]
+    std::vector<uint32_t> ranges; // [2][2 * WF_HIP_HUM_HARMONICS]
+};
+HumTables hum_tables(uint32_t sample_rate, uint32_t ring_cap);
 
 } // namespace wf::host

@@ -1,4 +1,4 @@
-// wf_ring_view.hpp -- how the measurement kernels (wf_signal.hpp, wf_pitch.hpp, wf_stereo.hpp, wf_cq.hpp, wf_scope.hpp, wf_gonio.hpp, wf_sono.hpp, wf_bits.hpp, wf_thd.hpp and wf_imd.hpp through wf_thd_spectrum.hpp, wf_delay.hpp, wf_onset.hpp, wf_tempo.hpp, wf_xfer_sums.hpp for wf_xfer.hpp and wf_impulse.hpp, wf_click.hpp, and the
+// wf_ring_view.hpp -- how the measurement kernels (wf_signal.hpp, wf_pitch.hpp, wf_stereo.hpp, wf_cq.hpp, wf_scope.hpp, wf_gonio.hpp, wf_sono.hpp, wf_bits.hpp, wf_thd.hpp and wf_imd.hpp through wf_thd_spectrum.hpp, wf_delay.hpp, wf_onset.hpp, wf_tempo.hpp, wf_hum.hpp, wf_xfer_sums.hpp for wf_xfer.hpp and wf_impulse.hpp, wf_click.hpp, and the
 // loudness push kernel of wf_loudness.hpp) see the audio rings: the four words every one of them takes, where a stream's newest
 // frames start and where a channel's ring lies.  Filled by ring_view() in wf_hip_measure.hip.  How each kernel fetches its window
 // from there is its own business; wf_ring_stage.hpp is how wf_scope.hpp, wf_gonio.hpp and wf_bits.hpp copy theirs into LDS.

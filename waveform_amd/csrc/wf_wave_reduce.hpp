@@ -8,7 +8,7 @@
 // (the oscilloscope's sixteen lanes per column).
 //
 // Users among the measurement kernels: wf_loudness.hpp, wf_peaks.hpp, wf_signal.hpp, wf_pitch.hpp, wf_bands.hpp, wf_scope.hpp,
-// wf_gonio.hpp, wf_bits.hpp, wf_thd.hpp, wf_imd.hpp, wf_delay.hpp, wf_xfer_sums.hpp with wf_xfer.hpp and wf_impulse.hpp, wf_click.hpp.  The
+// wf_gonio.hpp, wf_bits.hpp, wf_thd.hpp, wf_imd.hpp, wf_delay.hpp, wf_xfer_sums.hpp with wf_xfer.hpp and wf_impulse.hpp, wf_click.hpp, wf_hum.hpp.  The
 // tick path (wf_kernels.hpp, wf_big.hpp, wf_meter.hpp) keeps reductions of its own.
 #pragma once
 #include <hip/hip_runtime.h>
