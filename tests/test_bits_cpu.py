@@ -7,7 +7,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import bits_ref as ref
 from kernel_usage import kernel_usage
@@ -37,24 +36,6 @@ def test_bits_dtype_matches_the_c_layout(tmp_path):
     assert [dt.fields[n][1] for n in ref.FIELDS] == [0, 1344, 1348]
     assert ch.fields["hist"][0].shape == (256,) and ch.fields["hist"][0].base == np.uint16 and ch.fields["max_run_value"][0] == np.float32
     assert ref.MAX_WINDOW == binding.BITS_MAX_WINDOW == 8192
-
-
-def test_bits_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_BITS == binding.OUT_SONO + 1 == 20  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_BITS) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.bits
-    assert reader is binding.MultiBatch.bits is binding._MeasureReaders.bits
-    assert reader.__doc__ and "bits" not in vars(binding.SpectrumBatch) and "bits" not in vars(binding.MultiBatch)
-    assert binding.MEASURES["bits"] == (binding.OUT_BITS, binding.BITS_DTYPE, False)
 
 
 def _one(kind, p, seed=1):

@@ -12,7 +12,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import click_ref as ref
 
@@ -45,23 +44,6 @@ def test_click_dtype_matches_the_c_layout(tmp_path):
     assert dt.itemsize == 464 and ch.itemsize == 224 and ev.itemsize == 24 and dt.itemsize % 16 == 0
     assert dt.names == FIELDS and ch.names == CHANNEL_FIELDS and ev.names == EVENT_FIELDS
     assert binding.CLICK_THRESHOLD == 16.0 and ref.MAX_WINDOW == 8192 and ref.ORDER == 16
-
-
-def test_click_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_CLICK == binding.OUT_IMPULSE + 1 == 26  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_CLICK) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.click
-    assert reader is binding.MultiBatch.click is binding._MeasureReaders.click
-    assert reader.__doc__ and "click" not in vars(binding.SpectrumBatch) and "click" not in vars(binding.MultiBatch)
 
 
 def _read(kind, p):

@@ -7,7 +7,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import cq_ref as ref
 from kernel_usage import kernel_usage
@@ -36,17 +35,6 @@ def test_cq_dtype_matches_the_c_layout(tmp_path):
     assert ref.BINS == binding.CQ_BINS == 120 and ref.MAX_WINDOW == binding.CQ_MAX_WINDOW == 16384
     assert binding.MEASURES["cq"] == (binding.OUT_CQ, dt, False)
     assert np.array_equal(binding.CQ_CENTRES_HZ, ref.centres())
-
-
-def test_cq_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_CQ == binding.OUT_STEREO + 1 == 16  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_CQ) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
 
 
 def test_bin_centres():

@@ -41,24 +41,6 @@ def test_delay_dtype_matches_the_c_layout(tmp_path):
     assert (ref.MAX_WINDOW, ref.CURVE) == (binding.DELAY_MAX_WINDOW, binding.DELAY_CURVE) == (4096, 65)
 
 
-def test_delay_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_DELAY == binding.OUT_THD + 1 == 22  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_DELAY) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.delay
-    assert reader is binding.MultiBatch.delay is binding._MeasureReaders.delay
-    assert reader.__doc__ and "delay" not in vars(binding.SpectrumBatch) and "delay" not in vars(binding.MultiBatch)
-    assert binding.MEASURES["delay"] == (binding.OUT_DELAY, binding.DELAY_DTYPE, False)
-
-
 # ---- the host tables ----------------------------------------------------------------------------------------------------------------
 
 TABLE_SIZES = (128, 144, 2064, 4096, 16384, 65536)  # fft sizes: P = 128, 128, 2048, 4096, 4096, 4096

@@ -7,7 +7,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import gonio_ref as ref
 from kernel_usage import kernel_usage
@@ -36,23 +35,6 @@ def test_gonio_dtype_matches_the_c_layout(tmp_path):
     assert dt.fields["window"][1] == 8192 and dt.fields["occupied"][1] == 8220
     assert dt.fields["cell"][0].shape == (64, 64) and dt.fields["cell"][0].base == np.uint16 and dt.fields["zoom"][0] == np.int32
     assert (ref.GRID, ref.MAX_WINDOW, ref.MIN_EXP) == (binding.GONIO_GRID, binding.GONIO_MAX_WINDOW, binding.GONIO_MIN_EXP) == (64, 8192, -24)
-
-
-def test_gonio_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_GONIO == binding.OUT_SCOPE + 1 == 18  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_GONIO) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.gonio
-    assert reader is binding.MultiBatch.gonio is binding._MeasureReaders.gonio
-    assert reader.__doc__ and "gonio" not in vars(binding.SpectrumBatch) and "gonio" not in vars(binding.MultiBatch)
 
 
 def _noise(seed, p, scale=1.0):

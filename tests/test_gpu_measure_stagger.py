@@ -2,7 +2,8 @@
 (tests/measure_stagger.py): stereo, cq, scope, gonio, sono, bits, thd, delay and onset, with signal and pitch on the same script,
 each stream against the float64 restatement of its own ring at its own counter -- at every read of the plan, straight after the reset
 of one stream and after a packet longer than the ring among them --; slices as a handle's first read; the outputs read in either
-order; a three-shard group; one stream of the seven carried across 2^32.
+order; a three-shard group; one stream of the seven carried across 2^32.  And, on a batch that has all twenty measurement outputs,
+every one of them on one handle, forwards against backwards with slices first.
 
 A kernel that takes the write position, the alignment of its float4 fetch or the column anchor from another stream than its own --
 wpos[0], wpos[slice index], a shard's wpos at the group's index -- passes every other module, where all streams of a batch have
@@ -147,6 +148,43 @@ def test_three_shards_match_one_handle(case):
             assert m.gathered(d).tobytes() == bars.tobytes(), d
         for o in outputs:  # (a tick does not move the rings)
             assert getattr(m, o)().tobytes() == getattr(one, o)().tobytes(), o
+
+
+def test_all_twenty_outputs_on_one_handle_in_either_order(monkeypatch):
+    """every row of binding.MEASURES on twin handles fed the same audio -- the smallest ring the tempo serves, filled once, then one
+    tick --: `a` reads them in table order, `b` in reverse with the slice (first=1, count=2) as each output's first read there.  The
+    bytes are the same, so no row, block or setup flag is another output's; no two streams read alike, so a wrong entry would
+    show; guard bytes behind every block intact (wf_hip_sync checks them under WF_HIP_CANARY).  No tolerance: twin handles read
+    the same bits"""
+    monkeypatch.setenv("WF_HIP_CANARY", "1")
+    names, streams, ring = list(binding.MEASURES), 3, 131072
+    assert len(names) == 20
+    cfg = wf.Config.defaults(fft_size=1024, sample_rate=48000, stereo=1, bars=1)
+    rng = np.random.default_rng(20)
+    t = np.arange(ring, dtype=np.float64) / 48000.0
+    hz = 110.0 * (1.0 + np.arange(streams * 2, dtype=np.float64)).reshape(streams, 2, 1)
+    audio = (0.1 * rng.standard_normal((streams, 2, ring)) + 0.3 * np.sin(2.0 * np.pi * hz * t)).astype(np.float32)
+    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as a, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as b:
+        for h in (a, b):
+            assert (h.fft_size, h.ring_frames, h.capture_channels) == (1024, ring, 2)
+            h.enable_loudness()
+            for at in range(0, ring, 32768):
+                h.push_audio(audio[:, :, at:at + 32768])
+            h.tick()
+            for name in names:
+                assert int(wf.lib().wf_hip_output_bytes(h.h, binding.MEASURES[name][0])) != 0, name
+        up = {name: getattr(a, name)() for name in names}
+        part, down = {}, {}
+        for name in reversed(names):
+            part[name] = getattr(b, name)(1, 2)
+            down[name] = getattr(b, name)()
+        a.sync()
+        b.sync()
+    for name in names:
+        assert up[name].shape[0] == streams and part[name].shape[0] == 2, name
+        assert down[name].tobytes() == up[name].tobytes(), name
+        assert part[name].tobytes() == up[name][1:3].tobytes(), name
+        assert len({up[name][s].tobytes() for s in range(streams)}) == streams, name
 
 
 def test_one_stream_across_the_2_to_the_32_wrap():

@@ -1,5 +1,5 @@
 """The mains hum detector (WF_HIP_OUT_HUM) without a device: the structured dtype against the C layout, the appended output number,
-the tables of the measurement outputs, the library's own plan and tables against the restatement (tests/hum_ref.py), the polyphase
+the library's own plan and tables against the restatement (tests/hum_ref.py), the polyphase
 form of the spectrum against numpy's windowed FFT, what the restatement reads on the issue's cases, the clearance of every window
 of the device comparison, and a gfx950 compile of the kernel with no scratch and no spills.
 
@@ -59,31 +59,6 @@ def test_hum_dtype_matches_the_c_layout(tmp_path):
     assert (ref.HARMONICS, ref.MARGIN_DB, ref.TOL_HZ, ref.FLOOR_SPAN, ref.FLOOR_GUARD, ref.MAX_WINDOW) == \
         (binding.HUM_HARMONICS, binding.HUM_MARGIN_DB, binding.HUM_TOL_HZ, binding.HUM_FLOOR_SPAN, binding.HUM_FLOOR_GUARD,
          binding.HUM_MAX_WINDOW) == (8, 15.0, 0.5, 20, 3, 32768)
-
-
-def test_hum_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_HUM == binding.OUT_TEMPO + 1 == 29  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_HUM) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader_and_the_row_is_in_the_last_table():
-    reader = binding.SpectrumBatch.hum
-    assert reader is binding.MultiBatch.hum is binding._MeasureReaders.hum
-    assert reader.__doc__ and "hum" not in vars(binding.SpectrumBatch) and "hum" not in vars(binding.MultiBatch)
-    assert list(binding.MEASURES_REST) == ["tempo", "hum"]
-    assert binding.MEASURES_REST["hum"] == (binding.OUT_HUM, binding.HUM_DTYPE, False)
-    text = (CSRC / "wf_hip_measure.hip").read_text()
-    table = text[text.index("constexpr Measure MEASURES_REST["):]
-    assert "{WF_HIP_OUT_HUM, sizeof(wf_hip_hum), false, why_no_hum, setup_hum, launch_hum}" in table[:table.index("};")]
-    internal = (CSRC / "wf_hip_internal.hpp").read_text()
-    assert "N_MEASURES_REST = 2" in internal and "N_MEASURES = 17, N_MEASURES_MORE = 1" in internal
-    assert '#include "wf_hum.hpp"' in text and "wf_hum.hpp" in (CSRC / "Makefile").read_text()
 
 
 # ---- the host's builder ---------------------------------------------------------------------------------------------------------

@@ -1,22 +1,19 @@
 """Two-tone intermodulation analyser (WF_HIP_OUT_IMD) without a device: the structured dtype against the C layout, the appended
-output number, the continuation tables of the measurement outputs, closed forms of a polynomial non-linearity on the restatement
+output number, closed forms of a polynomial non-linearity on the restatement
 (tests/imd_ref.py), its behaviour on one tone, silence, an octave and products beyond the band, the conditions of the device
 comparison on its own seeds and shapes, and a gfx950 compile of the read kernels with no scratch, no spills and next to no static
 LDS."""
-import re
 import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import imd_ref as ref
 from kernel_usage import kernel_usage
 
 ROOT = Path(__file__).resolve().parents[1]
-CSRC = ROOT / "waveform_amd" / "csrc"
 
 
 def test_imd_dtype_matches_the_c_layout(tmp_path):
@@ -46,39 +43,6 @@ def test_imd_dtype_matches_the_c_layout(tmp_path):
     assert ch.fields["product_db"][0].shape == (20,) and ch.fields["order_db"][0].shape == (4,) and ch.fields["reserved"][0].shape == (2,)
     assert ch.fields["product_db"][0].base == np.float32 and dt.fields["reserved"][0].shape == (3,)
     assert (ref.PRODUCTS, ref.MIN_RATIO, ref.LOBE) == (binding.IMD_PRODUCTS, binding.IMD_MIN_RATIO, binding.THD_LOBE) == (20, 1e-3, 8)
-
-
-def test_imd_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_IMD == binding.OUT_CLICK + 1 == 27  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_IMD) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader_and_the_continuation_tables_are_twins():
-    reader = binding.SpectrumBatch.imd
-    assert reader is binding.MultiBatch.imd is binding._MeasureReaders.imd
-    assert reader.__doc__ and "imd" not in vars(binding.SpectrumBatch) and "imd" not in vars(binding.MultiBatch)
-    assert list(binding.MEASURES_MORE) == ["imd"] and not set(binding.MEASURES) & set(binding.MEASURES_MORE)
-    assert binding.MEASURES_MORE["imd"] == (binding.OUT_IMD, binding.IMD_DTYPE, False)
-    # the rows of MEASURES_MORE in wf_hip_measure.hip, from the source text: {WF_HIP_OUT_X, sizeof(wf_hip_x), per_row, ...}
-    text = (CSRC / "wf_hip_measure.hip").read_text()
-    table = text[text.index("constexpr Measure MEASURES_MORE["):]
-    table = table[:table.index("};")]
-    rows = re.findall(r"\{WF_HIP_OUT_(\w+), sizeof\(wf_hip_(\w+)\), (true|false),", table)
-    assert len(rows) == len(binding.MEASURES_MORE) == table.count("{WF_HIP_OUT_")
-    for (out, struct, per_row), (name, (what, dtype, py_per_row)) in zip(rows, binding.MEASURES_MORE.items()):
-        assert out.lower() == struct == name, (out, struct, name)
-        assert what == getattr(binding, "OUT_" + out) and dtype is getattr(binding, out + "_DTYPE"), name
-        assert py_per_row is (per_row == "true"), name
-    n_more = int(re.search(r"N_MEASURES_MORE = (\d+)", (CSRC / "wf_hip_internal.hpp").read_text()).group(1))
-    assert n_more == len(rows)
-    outputs = [binding.MEASURES[n][0] for n in binding.MEASURES] + [binding.MEASURES_MORE[n][0] for n in binding.MEASURES_MORE]
-    assert outputs == list(range(binding.OUT_LOUDNESS, binding.OUT_IMD + 1))  # every measurement output in one of the two
 
 
 def test_the_products_are_enumerated_as_the_definition_says():

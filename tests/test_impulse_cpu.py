@@ -7,7 +7,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import measure_stagger as ms
 import impulse_ref as ref
@@ -56,15 +55,6 @@ def test_impulse_dtype_matches_the_c_layout(tmp_path):
     assert (ref.FRAMES, ref.ARRIVALS, ref.GUARD, ref.DIRECT) == (2048, 8, 8, 16)
     for n in ref.SHARED_FIELDS:  # the head of the record is wf_hip_xfer's
         assert dt.fields[n] == binding.XFER_DTYPE.fields[n], n
-
-
-def test_impulse_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_IMPULSE == binding.OUT_XFER + 1 == 25  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_IMPULSE) == 0
-    reader = binding.SpectrumBatch.impulse
-    assert reader is binding.MultiBatch.impulse is binding._MeasureReaders.impulse and reader.__doc__
 
 
 def test_impulse_kernel_has_no_scratch():

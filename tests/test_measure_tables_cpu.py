@@ -1,7 +1,8 @@
 """The host tables of the measurement outputs (waveform_amd/csrc/wf_measure_tables.cpp) without a device: the library's own
 builders, compiled into a program of their own, against the float64 restatements (tests/bands_ref.py, stereo_ref.py, cq_ref.py)
-and numpy; the same program once more under the address and undefined-behaviour sanitizers; and the readers of the two batch
-classes being the same functions.
+and numpy; the same program once more under the address and undefined-behaviour sanitizers; the readers of the two batch
+classes being the same functions over one table that is the C table's twin; and, once for all measurement outputs, the ABI version,
+the exported entry points and every output's number.
 
 Bound of the float64 comparisons: rtol 1e-12 (atol 1e-300 for exact zeros), the figure test_loudness_cpu.py uses for the filter
 design: four orders of magnitude above what a handful of correctly rounded double operations and two libm calls can differ by,
@@ -205,11 +206,18 @@ def test_the_program_is_clean_under_the_sanitizers(tables, tmp_path):
 
 
 NAMES = ["loudness", "peaks", "signal", "pitch", "bands", "stereo", "cq", "scope", "gonio", "sono", "bits", "thd", "delay", "onset", "xfer",
-         "impulse", "click"]
+         "impulse", "click", "imd", "tempo", "hum"]
+# wf_hip_output (include/wf_hip.h), every number written out: a new output is appended, the others keep theirs
+OUTPUT_NUMBERS = {"OUT_DECIBELS": 0, "OUT_BARS": 1, "OUT_PREMIRROR": 2, "OUT_VERTICES": 3, "OUT_VERTEX_COUNTS": 4, "OUT_LAST_SILENT": 5,
+                  "OUT_TSMOOTH": 6, "OUT_METER": 7, "OUT_INPUT_RMS": 8, "OUT_WAVEFORM_TS": 9, "OUT_LOUDNESS": 10, "OUT_PEAKS": 11,
+                  "OUT_SIGNAL": 12, "OUT_PITCH": 13, "OUT_BANDS": 14, "OUT_STEREO": 15, "OUT_CQ": 16, "OUT_SCOPE": 17, "OUT_GONIO": 18,
+                  "OUT_SONO": 19, "OUT_BITS": 20, "OUT_THD": 21, "OUT_DELAY": 22, "OUT_ONSET": 23, "OUT_XFER": 24, "OUT_IMPULSE": 25,
+                  "OUT_CLICK": 26, "OUT_IMD": 27, "OUT_TEMPO": 28, "OUT_HUM": 29}
 
 
 def test_both_batch_classes_share_the_readers():
-    """all seventeen readers: one function on both batch classes, documented, and the Python table the C table's twin"""
+    """all twenty readers: one function on both batch classes, documented, and the Python table the twin of the one C table, whose
+    row i is output OUT_LOUDNESS + i"""
     assert list(binding.MEASURES) == NAMES
     for name in binding.MEASURES:
         reader = getattr(binding.SpectrumBatch, name)
@@ -217,11 +225,50 @@ def test_both_batch_classes_share_the_readers():
         assert reader.__doc__ and name not in vars(binding.SpectrumBatch) and name not in vars(binding.MultiBatch)
     # the rows of MEASURES in wf_hip_measure.hip, from the source text: {WF_HIP_OUT_X, sizeof(wf_hip_x), per_row, ...}
     text = (CSRC / "wf_hip_measure.hip").read_text()
+    internal = (CSRC / "wf_hip_internal.hpp").read_text()
+    assert text.count("constexpr Measure ") == 1
     table = text[text.index("constexpr Measure MEASURES["):]
     table = table[:table.index("};")]
     rows = re.findall(r"\{WF_HIP_OUT_(\w+), sizeof\(wf_hip_(\w+)\), (true|false),", table)
-    assert len(rows) == len(NAMES) == 17 and table.count("{WF_HIP_OUT_") == 17
+    assert len(rows) == len(NAMES) == 20 == table.count("{WF_HIP_OUT_")
+    assert [int(n) for n in re.findall(r"N_MEASURES = (\d+)", internal)] == [20]
     for (out, struct, per_row), (name, (what, dtype, py_per_row)) in zip(rows, binding.MEASURES.items()):
         assert out.lower() == struct == name, (out, struct, name)
         assert what == getattr(binding, "OUT_" + out) and dtype is getattr(binding, out + "_DTYPE"), name
-        assert py_per_row is (per_row == "true"), name
+        assert py_per_row is (per_row == "true") is (name in ("peaks", "bands")), name
+    # every measurement output -- OUT_LOUDNESS up to the last output there is -- once, at its own position
+    last = max(v for k, v in vars(binding).items() if k.startswith("OUT_") and isinstance(v, int))
+    assert [what for what, _, _ in binding.MEASURES.values()] == list(range(binding.OUT_LOUDNESS, last + 1))
+    # the newest row word for word, its kernel header in the unit and in the Makefile
+    assert "{WF_HIP_OUT_HUM, sizeof(wf_hip_hum), false, why_no_hum, setup_hum, launch_hum}" in table
+    assert '#include "wf_hum.hpp"' in text and "wf_hum.hpp" in (CSRC / "Makefile").read_text()
+    # one table on either side: the continuations it once had are gone
+    for source in (text, internal, (ROOT / "waveform_amd" / "binding.py").read_text()):
+        assert "MEASURES_MORE" not in source and "MEASURES_REST" not in source and "N_MEASURES_ALL" not in source
+
+
+def test_every_reader_is_pinned_to_its_output_its_dtype_and_its_shape():
+    """what each output's own module said of its reader, written out and not read from the C text: the number it reads, the dtype
+    by name, one entry per stream but for peaks and bands, and one documented function on both batch classes"""
+    assert len(binding.MEASURES) == len(NAMES) == 20
+    for name in NAMES:
+        number, per_row = OUTPUT_NUMBERS["OUT_" + name.upper()], name in ("peaks", "bands")
+        assert binding.MEASURES[name] == (number, getattr(binding, name.upper() + "_DTYPE"), per_row), name
+        reader = getattr(binding._MeasureReaders, name)
+        assert reader is getattr(binding.SpectrumBatch, name) is getattr(binding.MultiBatch, name) and reader.__doc__, name
+
+
+def test_the_abi_and_the_output_numbers_are_unchanged():
+    """ABI version 13, 75 exported entry points, and every output at its number"""
+    assert {k: v for k, v in vars(binding).items() if k.startswith("OUT_") and isinstance(v, int)} == OUTPUT_NUMBERS
+    assert [OUTPUT_NUMBERS["OUT_" + name.upper()] for name in NAMES] == list(range(10, 30))
+    assert binding.lib().wf_hip_abi_version() == 13
+    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
+    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
+    assert len(exported) == 75, sorted(exported)  # no new entry point
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_a_measurement_output_has_no_bytes_without_a_handle(name):
+    assert binding.lib().wf_hip_output_bytes(None, OUTPUT_NUMBERS["OUT_" + name.upper()]) == 0

@@ -9,7 +9,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import onset_ref as ref
 from kernel_usage import kernel_usage
@@ -47,24 +46,6 @@ def test_onset_dtype_matches_the_c_layout(tmp_path):
     # the groups' edges: 62.5 Hz, 250 Hz, 2 kHz, 16 kHz
     e = binding.SONO_EDGES_HZ
     assert [float(round(e[i], 6)) for i in (0, 16, 40, 64)] == [62.5, 250.0, 2000.0, 16000.0] and ref.GROUPS == ((0, 16), (16, 40), (40, 64))
-
-
-def test_onset_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_ONSET == binding.OUT_DELAY + 1 == 23 and binding.OUT_DELAY == 22  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_ONSET) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.onset
-    assert reader is binding.MultiBatch.onset is binding._MeasureReaders.onset
-    assert reader.__doc__ and "onset" not in vars(binding.SpectrumBatch) and "onset" not in vars(binding.MultiBatch)
-    assert binding.MEASURES["onset"] == (binding.OUT_ONSET, binding.ONSET_DTYPE, False)
 
 
 def test_columns_and_the_decided_range_per_ring():

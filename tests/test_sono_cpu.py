@@ -8,7 +8,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import sono_ref as ref
 from kernel_usage import kernel_usage
@@ -40,24 +39,6 @@ def test_sono_dtype_matches_the_c_layout(tmp_path):
         == (1024, 256, 64, 64)
     assert np.array_equal(binding.SONO_EDGES_HZ, ref.EDGES_HZ) and binding.SONO_EDGES_HZ[0] == 62.5
     assert abs(binding.SONO_EDGES_HZ[64] - 16000.0) < 1e-9 and binding.SONO_EDGES_HZ[8] == 125.0
-
-
-def test_sono_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_SONO == binding.OUT_GONIO + 1 == 19  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_SONO) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.sono
-    assert reader is binding.MultiBatch.sono is binding._MeasureReaders.sono
-    assert reader.__doc__ and "sono" not in vars(binding.SpectrumBatch) and "sono" not in vars(binding.MultiBatch)
-    assert binding.MEASURES["sono"] == (binding.OUT_SONO, binding.SONO_DTYPE, False)
 
 
 def _tone(freq, amp, frames, sr=SR):

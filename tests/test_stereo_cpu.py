@@ -7,7 +7,6 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import waveform_amd as wf
 from waveform_amd import binding
 import stereo_ref as ref
 from kernel_usage import kernel_usage
@@ -36,17 +35,6 @@ def test_stereo_dtype_matches_the_c_layout(tmp_path):
     assert dt.itemsize == 504 and dt == ref.STEREO_DTYPE and ref.MAX_WINDOW == binding.STEREO_MAX_WINDOW == 4096
     assert all(dt.fields[n][0].shape == (31,) for n in ref.FIELDS)
     assert binding.MEASURES["stereo"] == (binding.OUT_STEREO, dt, False)
-
-
-def test_stereo_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_STEREO == binding.OUT_BANDS + 1 == 15  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_STEREO) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
 
 
 def test_window_is_the_largest_power_of_two():

@@ -1,5 +1,5 @@
 """Tempo and beat phase (WF_HIP_OUT_TEMPO) without a device: the structured dtype against the C layout, the appended output number,
-the three tables of the measurement outputs, the library's own builder of the lags and the preference against the restatement
+the library's own builder of the lags and the preference against the restatement
 (tests/tempo_ref.py), what the restatement reads on pulse trains, noise, a sine and silence, the margins of the signals of the
 device comparison, and a gfx950 compile of the kernels with no scratch and no spills.
 
@@ -54,50 +54,6 @@ def test_tempo_dtype_matches_the_c_layout(tmp_path):
         (binding.TEMPO_WINDOW, binding.TEMPO_HOP, binding.TEMPO_COLUMNS, binding.TEMPO_LAGS, binding.TEMPO_MAX_LAG, binding.TEMPO_MIN_RING,
          binding.TEMPO_MARGIN) == (1024, 256, 2048, 576, 287, 131072, 2.0)
     assert 2 * ref.MAX_LAG + 2 == ref.LAGS
-
-
-def test_tempo_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_TEMPO == binding.OUT_IMD + 1 == 28  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_TEMPO) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def _c_rows(name):
-    """the rows of a table in wf_hip_measure.hip, from the source text: {WF_HIP_OUT_X, sizeof(wf_hip_x), per_row, ...}"""
-    text = (CSRC / "wf_hip_measure.hip").read_text()
-    table = text[text.index(f"constexpr Measure {name}["):]
-    table = table[:table.index("};")]
-    rows = re.findall(r"\{WF_HIP_OUT_(\w+), sizeof\(wf_hip_(\w+)\), (true|false),", table)
-    assert len(rows) == table.count("{WF_HIP_OUT_")
-    return rows
-
-
-def test_both_batch_classes_share_the_reader_and_the_three_tables_are_twins():
-    reader = binding.SpectrumBatch.tempo
-    assert reader is binding.MultiBatch.tempo is binding._MeasureReaders.tempo
-    assert reader.__doc__ and "tempo" not in vars(binding.SpectrumBatch) and "tempo" not in vars(binding.MultiBatch)
-    assert binding.MEASURES_REST["tempo"] == (binding.OUT_TEMPO, binding.TEMPO_DTYPE, False)
-    tables = (("MEASURES", binding.MEASURES), ("MEASURES_MORE", binding.MEASURES_MORE), ("MEASURES_REST", binding.MEASURES_REST))
-    internal = (CSRC / "wf_hip_internal.hpp").read_text()
-    outputs = []
-    for c_name, py in tables:
-        rows = _c_rows(c_name)
-        assert len(rows) == len(py) == int(re.search(rf"N_{c_name} = (\d+)", internal).group(1)), c_name
-        for (out, struct, per_row), (name, (what, dtype, py_per_row)) in zip(rows, py.items()):
-            assert out.lower() == struct == name, (out, struct, name)
-            assert what == getattr(binding, "OUT_" + out) and dtype is getattr(binding, out + "_DTYPE"), name
-            assert py_per_row is (per_row == "true"), name
-            assert getattr(binding._MeasureReaders, name).__doc__, name
-        outputs += [what for what, _, _ in py.values()]
-    # every measurement output -- OUT_LOUDNESS up to the last output there is -- in exactly one of the three
-    last = max(v for k, v in vars(binding).items() if k.startswith("OUT_") and isinstance(v, int))
-    assert sorted(outputs) == list(range(binding.OUT_LOUDNESS, last + 1)) and len(set(outputs)) == len(outputs)
-    assert "N_MEASURES = 17, N_MEASURES_MORE = 1" in internal
 
 
 # ---- the host's builder ---------------------------------------------------------------------------------------------------------

@@ -45,24 +45,6 @@ def test_thd_dtype_matches_the_c_layout(tmp_path):
     assert (ref.MAX_WINDOW, ref.LOBE, ref.HARMONICS) == (binding.THD_MAX_WINDOW, binding.THD_LOBE, binding.THD_HARMONICS) == (8192, 8, 9)
 
 
-def test_thd_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_THD == binding.OUT_BITS + 1 == 21  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_THD) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.thd
-    assert reader is binding.MultiBatch.thd is binding._MeasureReaders.thd
-    assert reader.__doc__ and "thd" not in vars(binding.SpectrumBatch) and "thd" not in vars(binding.MultiBatch)
-    assert binding.MEASURES["thd"] == (binding.OUT_THD, binding.THD_DTYPE, False)
-
-
 # ---- the host tables ----------------------------------------------------------------------------------------------------------------
 
 TABLE_SIZES = (512, 2064, 4096, 8192, 16384, 65536)  # fft sizes: P = 512, 2048, 4096, 8192, 8192, 8192

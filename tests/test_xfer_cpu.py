@@ -50,24 +50,6 @@ def test_xfer_dtype_matches_the_c_layout(tmp_path):
     assert (ref.MAX_WINDOW, ref.MAX_SEGMENTS, ref.BINS) == (binding.XFER_MAX_WINDOW, binding.XFER_MAX_SEGMENTS, binding.XFER_BINS) == (2048, 32, 1024)
 
 
-def test_xfer_output_is_appended_and_the_abi_is_unchanged():
-    assert binding.OUT_XFER == binding.OUT_ONSET + 1 == 24  # the existing outputs keep their numbers
-    L = wf.lib()
-    assert L.wf_hip_abi_version() == 13
-    assert L.wf_hip_output_bytes(None, binding.OUT_XFER) == 0
-    path = ROOT / "waveform_amd" / "libwaveform_hip.so"
-    nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line and line.split()[-1].startswith("wf_hip_")}
-    assert len(exported) == 75, sorted(exported)  # no new entry point
-
-
-def test_both_batch_classes_share_the_reader():
-    reader = binding.SpectrumBatch.xfer
-    assert reader is binding.MultiBatch.xfer is binding._MeasureReaders.xfer
-    assert reader.__doc__ and "xfer" not in vars(binding.SpectrumBatch) and "xfer" not in vars(binding.MultiBatch)
-    assert binding.MEASURES["xfer"] == (binding.OUT_XFER, binding.XFER_DTYPE, False)
-
-
 # ---- P and K of every ring the library makes ----------------------------------------------------------------------------------------
 
 PROGRAM = r"""

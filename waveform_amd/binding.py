@@ -366,15 +366,7 @@ MEASURES = {
     "xfer": (OUT_XFER, XFER_DTYPE, False),
     "impulse": (OUT_IMPULSE, IMPULSE_DTYPE, False),
     "click": (OUT_CLICK, CLICK_DTYPE, False),
-}
-# its continuation (MEASURES_MORE there): MEASURES is pinned at its seventeen names (tests/test_measure_tables_cpu.py), so the
-# outputs behind OUT_CLICK are listed here
-MEASURES_MORE = {
     "imd": (OUT_IMD, IMD_DTYPE, False),
-}
-# ... and its second (MEASURES_REST there): MEASURES_MORE is pinned at its one name in the same way (tests/test_imd_cpu.py), so the
-# outputs behind OUT_IMD are listed here; no test pins the length of this one
-MEASURES_REST = {
     "tempo": (OUT_TEMPO, TEMPO_DTYPE, False),
     "hum": (OUT_HUM, HUM_DTYPE, False),
 }
@@ -382,7 +374,7 @@ MEASURES_REST = {
 
 def _read_measure(batch, name: str, first: int, count: int | None) -> np.ndarray:
     """the reader `name` of a SpectrumBatch or MultiBatch: [count] or [count, output_channels] entries"""
-    what, dtype, per_row = next(table[name] for table in (MEASURES, MEASURES_MORE, MEASURES_REST) if name in table)
+    what, dtype, per_row = MEASURES[name]
     return batch._read(what, first, count, (batch.output_channels,) if per_row else (), dtype)
 
 

@@ -133,13 +133,10 @@ struct wf_hip {
     float *d_input_rms = nullptr;    // [n_streams] m_input_rms
     // the measurement outputs (wf_hip_measure.hip): the block of each row of its table, [n_streams] entries or
     // [n_streams][out_ch], allocated by the output's first read, which also runs the row's setup (measure_ready: it has succeeded)
-    // (N_MEASURES rows in the table, N_MEASURES_MORE and N_MEASURES_REST in its two continuations, whose rows follow the table's
-    // here in that order)
-    static constexpr int N_MEASURES = 17, N_MEASURES_MORE = 1;
-    static constexpr int N_MEASURES_REST = 2;
-    static constexpr int N_MEASURES_ALL = N_MEASURES + N_MEASURES_MORE + N_MEASURES_REST;
-    char *d_measure[N_MEASURES_ALL] = {};
-    bool measure_ready[N_MEASURES_ALL] = {};
+    // (N_MEASURES: the rows of that table, WF_HIP_OUT_LOUDNESS to the last wf_hip_output; a static_assert there holds the two together)
+    static constexpr int N_MEASURES = 20;
+    char *d_measure[N_MEASURES] = {};
+    bool measure_ready[N_MEASURES] = {};
     // the loudness producer (wf_hip_enable_loudness; wf_loudness.hpp), d_state == nullptr while it is off
     struct Loudness {
         wf::LoudState *d_state = nullptr;         // [n_streams]

@@ -1,21 +1,21 @@
 // wf_hip_measure.hip -- the measurement outputs of the C ABI in include/wf_hip.h: WF_HIP_OUT_LOUDNESS, _PEAKS, _SIGNAL, _PITCH,
-// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK, _IMD, _TEMPO and _HUM.  None of them is in the reference and none is part of the tick: each is computed when it is read, by a kernel
-// of its own header, into a block the first read allocates.  One table (MEASURES) says what each output is, what its first read
-// sets up and how it is launched (MEASURES_MORE and MEASURES_REST continue it); one reader (measure_read) does the rest.  What an output derives
-// from the configuration alone
-// is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The loudness producer alone also
-// keeps state between reads: it follows every push (measure_check_push / measure_after_push, called by the ingest in wf_hip.hip)
-// and is switched on by wf_hip_enable_loudness.  gfx950 only.
+// _BANDS, _STEREO, _CQ, _SCOPE, _GONIO, _SONO, _BITS, _THD, _DELAY, _ONSET, _XFER, _IMPULSE, _CLICK, _IMD, _TEMPO and _HUM.  None of
+// them is in the reference and none is part of the tick: each is computed when it is read, by a kernel of its own header, into a
+// block the first read allocates.  One table (MEASURES, a row per output in the order of wf_hip_output) says what each output
+// is, what its first read sets up and how it is launched; one reader (measure_read) does the rest.  What an output derives from
+// the configuration alone is built by plain C++ (wf_measure_tables.cpp, wf_loudness_tables.cpp) and only uploaded here.  The
+// loudness producer alone also keeps state between reads: it follows every push (measure_check_push / measure_after_push, called
+// by the ingest in wf_hip.hip) and is switched on by wf_hip_enable_loudness.  gfx950 only.
 //
 // A new measurement output: its kernel in a header of its own, included here and nowhere else, with a wf::RingView in its
 // arguments if it reads the rings.  What kernels share lies in headers that hold no kernel (wf_wave_reduce.hpp, wf_ring_stage.hpp,
 // wf_fft64_lds.hpp, wf_phat.hpp): no kernel header includes another output's, but for wf_xfer.hpp and wf_impulse.hpp over
 // wf_xfer_sums.hpp, wf_thd.hpp and wf_imd.hpp over wf_thd_spectrum.hpp, and wf_onset.hpp and wf_tempo.hpp over wf_onset_column.hpp,
-// the heads they share.  If it needs tables, a builder in
-// wf_measure_tables.cpp that sees no handle and no HIP, and a
-// setup function here that calls it, keeps the scalars on the handle, states its kernels' dynamic LDS (allow_lds) and uploads; a
-// launch function (launch_by_channels where the kernel is instantiated per captured channels), a refusal function and a row of
-// MEASURES_REST below; a row of MEASURES_REST and a reader on _MeasureReaders in waveform_amd/binding.py.
+// the heads they share.  If it needs tables, a builder in wf_measure_tables.cpp that sees no handle and no HIP, and a setup
+// function here that calls it, keeps the scalars on the handle, states its kernels' dynamic LDS (allow_lds) and uploads; a launch
+// function (launch_by_channels where the kernel is instantiated per captured channels), a refusal function and a row at the end
+// of MEASURES below, with wf_hip::N_MEASURES one larger; a row of MEASURES and a reader on _MeasureReaders in
+// waveform_amd/binding.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -815,8 +815,9 @@ struct Measure {
     int (*launch)(wf_hip *, uint32_t first, uint32_t count, void *d_block);
 };
 
-// row i's block is wf_hip::d_measure[i], and wf_hip::measure_ready[i] says that its setup has been done
-constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
+// Row i is output WF_HIP_OUT_LOUDNESS + i: its block is wf_hip::d_measure[i], and wf_hip::measure_ready[i] says that its setup has
+// been done
+constexpr Measure MEASURES[] = {
     {WF_HIP_OUT_LOUDNESS, sizeof(wf_hip_loudness), false, why_no_loudness, nullptr, launch_loudness},
     {WF_HIP_OUT_PEAKS, sizeof(wf_hip_peaks), true, why_no_peaks, nullptr, launch_peaks},
     {WF_HIP_OUT_SIGNAL, sizeof(wf_hip_signal), false, why_no_signal, nullptr, launch_signal},
@@ -834,41 +835,25 @@ constexpr Measure MEASURES[wf_hip::N_MEASURES] = {
     {WF_HIP_OUT_XFER, sizeof(wf_hip_xfer), false, why_no_xfer, setup_xfer, launch_xfer},
     {WF_HIP_OUT_IMPULSE, sizeof(wf_hip_impulse), false, why_no_impulse, setup_impulse, launch_impulse},
     {WF_HIP_OUT_CLICK, sizeof(wf_hip_click), false, why_no_click, setup_click, launch_click},
-};
-
-// The table's continuation, of the same row type: MEASURES is pinned at its seventeen rows (tests/test_measure_tables_cpu.py reads
-// them from this text), so the outputs behind WF_HIP_OUT_CLICK are listed here.  Row i's block is wf_hip::d_measure[N_MEASURES + i]
-constexpr Measure MEASURES_MORE[wf_hip::N_MEASURES_MORE] = {
     {WF_HIP_OUT_IMD, sizeof(wf_hip_imd), false, why_no_imd, setup_imd, launch_imd},
-};
-
-// ... and its second: tests/test_imd_cpu.py pins MEASURES_MORE at its one row in the same way, so the outputs behind WF_HIP_OUT_IMD
-// are listed here.  Row i's block is wf_hip::d_measure[N_MEASURES + N_MEASURES_MORE + i].  No test pins the length of this one
-constexpr Measure MEASURES_REST[wf_hip::N_MEASURES_REST] = {
     {WF_HIP_OUT_TEMPO, sizeof(wf_hip_tempo), false, why_no_tempo, setup_tempo, launch_tempo},
     {WF_HIP_OUT_HUM, sizeof(wf_hip_hum), false, why_no_hum, setup_hum, launch_hum},
 };
+static_assert(sizeof(MEASURES) / sizeof(MEASURES[0]) == wf_hip::N_MEASURES, "a row of MEASURES for each of wf_hip's N_MEASURES blocks");
 
-int measure_row(wf_hip_output what) // over the three tables; -1: not a measurement output
+constexpr bool rows_follow_the_enum()
 {
     for(int i = 0; i < wf_hip::N_MEASURES; ++i)
-        if(MEASURES[i].what == what)
-            return i;
-    for(int i = 0; i < wf_hip::N_MEASURES_MORE; ++i)
-        if(MEASURES_MORE[i].what == what)
-            return wf_hip::N_MEASURES + i;
-    for(int i = 0; i < wf_hip::N_MEASURES_REST; ++i)
-        if(MEASURES_REST[i].what == what)
-            return wf_hip::N_MEASURES + wf_hip::N_MEASURES_MORE + i;
-    return -1;
+        if(MEASURES[i].what != WF_HIP_OUT_LOUDNESS + i)
+            return false;
+    return true;
 }
+static_assert(rows_follow_the_enum(), "row i of MEASURES is output WF_HIP_OUT_LOUDNESS + i");
 
-const Measure &measure_at(int row)
+int measure_row(wf_hip_output what) // -1: not a measurement output
 {
-    if(row < wf_hip::N_MEASURES)
-        return MEASURES[row];
-    row -= wf_hip::N_MEASURES;
-    return row < wf_hip::N_MEASURES_MORE ? MEASURES_MORE[row] : MEASURES_REST[row - wf_hip::N_MEASURES_MORE];
+    const int i = (int)what - (int)WF_HIP_OUT_LOUDNESS;
+    return i >= 0 && i < wf_hip::N_MEASURES ? i : -1;
 }
 
 size_t bytes_per_stream(const wf_hip *h, const Measure &m) { return m.entry_bytes * (m.per_row ? h->out_ch : 1u); }
@@ -906,15 +891,15 @@ bool wf::host::measure_source(const wf_hip *h, wf_hip_output what, size_t *per_s
     const int i = measure_row(what);
     if(i < 0)
         return false;
-    *why = measure_at(i).why_not(h);
-    *per_stream = *why ? 0 : bytes_per_stream(h, measure_at(i));
+    *why = MEASURES[i].why_not(h);
+    *per_stream = *why ? 0 : bytes_per_stream(h, MEASURES[i]);
     return true;
 }
 
 int wf::host::measure_read(wf_hip *h, wf_hip_output what, uint32_t first, uint32_t count, void *out)
 {
     const int i = measure_row(what);
-    const Measure &m = measure_at(i);
+    const Measure &m = MEASURES[i];
     if(const char *why = m.why_not(h))
         return fail(h, WF_HIP_ERR_INVALID, "%s", why);
     if(out == nullptr)
