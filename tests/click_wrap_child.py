@@ -18,39 +18,30 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import waveform_amd as wf  # noqa: E402
 import click_ref as ref  # noqa: E402
-from wrap_child import HOPS, Schedule, _dev  # noqa: E402
+from wrap_child import Walk, twins  # noqa: E402
 
 
 def run():
-    L = _dev()
     fft, ring, streams, sr = 2048, 8192, 3, 48000
     cfg = wf.Config.defaults(fft_size=fft, sample_rate=sr, stereo=1, slope=1.0, bars=1)
-    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
-        assert old.ring_frames == ring and old.fft_size == fft
-        # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft and fft,
-        # the window starting at position 0, at T = R
-        R = 2 * ring
-        sch = Schedule(R, fft, 0, big=ring // 2, fine=True)
-        sch.check([0])
-        wrap = R - fft
+    # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft and fft,
+    # the window starting at position 0, at T = R
+    with twins(cfg, streams, ring, fft, R=2 * ring, win=fft) as (fresh, old, sch):
         age = (1 << 32) - 2 * ring
-        assert L.wf_hip_debug_age(old.h, 0, streams, age) == 0, L.wf_hip_last_error(old.h)
         rng = np.random.default_rng(ref.SEED)
-        hist = np.zeros((streams, 2, fft), np.float32)
-        T, before, straddling, exact, behind, wrapped_frames = 0, 0, 0, 0, 0, 0
-        for i, p in enumerate(sch.pushes):
+
+        def audio(i, T, p):
             a = rng.uniform(-0.005, 0.005, (streams, 2, p)).astype(np.float32)
             if p >= 64:  # a click per packet, channel and stream, no two alike
                 for s in range(streams):
                     for c in range(2):
                         a[s, c, p // 2 + 5 * s + 2 * c] += np.float32((0.3 + 0.011 * (i % 9) + 0.02 * s) * (-1) ** (i + c))
-            T += p
-            for b in (fresh, old):
-                b.push_audio(a)
-            hist = np.concatenate([hist, a], axis=2)[:, :, -fft:]
-            if T < wrap - sum(HOPS):
-                continue
-            what = f"read {i} at wpos = 2^32{T - wrap:+d}"
+            return a
+
+        walk = Walk((fresh, old), sch.pushes, 2 * ring - fft, fft, audio, hist=np.zeros((streams, 2, fft), np.float32))
+        wrapped_frames = 0
+        for i, T, what in walk:
+            hist = walk.hist
             for s in range(streams):
                 for c in range(2):
                     assert ref.margins_hold(ref.margins(hist[s, c], sr)), (what, s, c, ref.margins(hist[s, c], sr))
@@ -63,11 +54,7 @@ def run():
                 z["ch"]["ev"]["frame"] = 0
             assert x.tobytes() == y.tobytes(), f"{what}: the twins differ beyond `frame`"
             assert np.all(y["ch"]["events"] >= 1), what
-            before += int(T <= wrap)
-            straddling += int(0 < T - wrap < fft)
-            exact += int(T == R)
-            behind += int(T > R)
-        assert before >= 2 and straddling >= 3 and exact == 1 and behind >= 3, (before, straddling, exact, behind)
+        assert walk.before >= 2 and walk.straddling >= 3 and walk.exact == 1 and walk.behind >= 3, walk.counts
         assert wrapped_frames >= 3  # events whose counter position lies before 2^32 were read, and after it
         assert np.all(y["window"] == fft) and np.all(y["order"] == ref.ORDER) and np.all(y["ch"]["valid"] == 1)
 

@@ -16,41 +16,29 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import waveform_amd as wf  # noqa: E402
 import hum_ref as ref  # noqa: E402
-from wrap_child import _dev  # noqa: E402
+from wrap_child import Walk, slices, twins  # noqa: E402
 
 
 def run():
-    L = _dev()
     sr, ring, fft, streams = ref.SR, ref.RING, 1024, 3
     n = ref.plan(sr, ring).N
     cfg = wf.Config.defaults(fft_size=fft, sample_rate=sr, stereo=1, slope=1.0, bars=1)
     audio = ref.wrap_audio()
-    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
-        assert old.ring_frames == ring and old.fft_size == fft and n == ring
-        # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
-        wrap = 2 * ring - fft
-        age = (1 << 32) - 2 * ring
-        assert L.wf_hip_debug_age(old.h, 0, streams, age) == 0, L.wf_hip_last_error(old.h)
-        T, before, exact, straddling, behind = 0, 0, 0, 0, 0
-        for i, (p, read) in enumerate(ref.WRAP_PUSHES):
-            a = np.ascontiguousarray(audio[:, :, T:T + p])
-            T += p
-            for b in (fresh, old):
-                b.push_audio(a)
-            if not read:
-                continue
-            what = f"read {i} at wpos = 2^32{T - wrap:+d}"
+    # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
+    wrap = 2 * ring - fft
+    with twins(cfg, streams, ring, fft) as (fresh, old, _):
+        assert n == ring
+        walk = Walk((fresh, old), ref.WRAP_PUSHES, wrap, n, slices(audio))
+        for i, T, what in walk:
             x, y = fresh.hum(), old.hum()
             assert x.tobytes() == y.tobytes(), f"{what}: the twins differ"
             assert x["ch"]["family"].tolist() == [[50, 60], [60, 0], [0, 50]], (what, x["ch"]["family"].tolist())
             hist = np.concatenate([np.zeros((streams, 2, n), np.float32), audio[:, :, :T]], axis=2)
             bad = ref.mismatches(x, hist, sr, ring)
             assert not bad, (what, bad[:4])
-            before += int(T < wrap)
-            exact += int(T == wrap)
-            straddling += int(0 < T - wrap < n)
-            behind += int(T - wrap >= n)
-        assert T == audio.shape[-1] and before == 2 and exact == 1 and straddling >= 4 and behind >= 2, (before, exact, straddling, behind)
+        # (here `exact` is the read at the wrap itself, and a read that starts at position 0 counts as behind)
+        before, exact, straddling, behind = walk.before - walk.at, walk.at, walk.straddling, walk.exact + walk.behind
+        assert walk.T == audio.shape[-1] and before == 2 and exact == 1 and straddling >= 4 and behind >= 2, (before, exact, straddling, behind)
         print(f"{before} reads before the wrap, one at it, {straddling} with the window across it, {behind} behind it")
 
 

@@ -16,47 +16,27 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import waveform_amd as wf  # noqa: E402
 import imd_ref as ref  # noqa: E402
-from wrap_child import HOPS, Schedule, _dev  # noqa: E402
+from wrap_child import Walk, slices, twins  # noqa: E402
 
 KINDS = (("twin", "wide"), ("octave", "single"), ("silence", "clean"))
 
 
 def run():
-    L = _dev()
     fft, ring, streams, sr = 2048, 8192, len(KINDS), 48000
     cfg = wf.Config.defaults(fft_size=fft, sample_rate=sr, stereo=1, slope=1.0, bars=1)
-    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
-        assert old.ring_frames == ring and old.fft_size == fft
-        # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft and fft,
-        # the window starting at position 0, at T = R
-        R = 2 * ring
-        sch = Schedule(R, fft, 0, big=ring // 2, fine=True)
-        sch.check([0])
-        wrap = R - fft
-        assert L.wf_hip_debug_age(old.h, 0, streams, (1 << 32) - 2 * ring) == 0, L.wf_hip_last_error(old.h)
+    # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft and fft,
+    # the window starting at position 0, at T = R
+    with twins(cfg, streams, ring, fft, R=2 * ring, win=fft) as (fresh, old, sch):
         rng = np.random.default_rng(ref.GPU_SEED)
         total = int(sum(sch.pushes))
         audio = np.stack([np.stack([ref.signal(k, rng, total, fft) for k in pair]) for pair in KINDS])  # one run of every signal
-        hist = np.zeros((streams, 2, fft), np.float32)
-        T, before, straddling, exact, behind = 0, 0, 0, 0, 0
-        for i, p in enumerate(sch.pushes):
-            a = np.ascontiguousarray(audio[:, :, T:T + p])
-            T += p
-            for b in (fresh, old):
-                b.push_audio(a)
-            hist = np.concatenate([hist, a], axis=2)[:, :, -fft:]
-            if T < wrap - sum(HOPS):
-                continue
-            what = f"read {i} at wpos = 2^32{T - wrap:+d}"
+        walk = Walk((fresh, old), sch.pushes, 2 * ring - fft, fft, slices(audio), hist=np.zeros((streams, 2, fft), np.float32))
+        for i, T, what in walk:
             x, y = fresh.imd(), old.imd()
             assert x.tobytes() == y.tobytes(), f"{what}: the twins differ"
-            bad = ref.mismatches(y, ref.imd(hist, fft, sr))
+            bad = ref.mismatches(y, ref.imd(walk.hist, fft, sr))
             assert not bad, (what, bad[:4])
-            before += int(T <= wrap)
-            straddling += int(0 < T - wrap < fft)
-            exact += int(T == R)
-            behind += int(T > R)
-        assert before >= 2 and straddling >= 3 and exact == 1 and behind >= 3, (before, straddling, exact, behind)
+        assert walk.before >= 2 and walk.straddling >= 3 and walk.exact == 1 and walk.behind >= 3, walk.counts
         assert np.all(y["window"] == fft) and y["ch"]["tones"].tolist() == [[2, 2], [2, 1], [0, 2]]
         assert y["ch"]["lo_bin"][0].tolist() == [809, 19] and y["ch"]["products"][0].tolist() == [0x14115, 0x30cf]
 

@@ -17,36 +17,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import waveform_amd as wf  # noqa: E402
 import sono_ref as ref  # noqa: E402
-from wrap_child import HOPS, Schedule, _dev  # noqa: E402
+from wrap_child import Walk, slices, twins  # noqa: E402
 
 
 def run():
-    L = _dev()
     fft, ring, streams = 1024, 8192, len(ref.KINDS)
     t = ref.columns(ring)
     span = (t - 1) * ref.H + ref.P + ref.H - 1  # the most frames a read looks back over
     cfg = wf.Config.defaults(fft_size=fft, stereo=1, slope=1.0, bars=1)
-    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
-        assert old.ring_frames == ring and old.fft_size == fft and t == 28 and span == ring - 1
-        # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
-        R = 2 * ring - fft + ring
-        sch = Schedule(R, ring, 0, big=ring // 2, fine=True)
-        sch.check([0])
-        wrap = R - ring
-        age = (1 << 32) - 2 * ring
-        assert L.wf_hip_debug_age(old.h, 0, streams, age) == 0, L.wf_hip_last_error(old.h)
+    # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
+    wrap, age = 2 * ring - fft, (1 << 32) - 2 * ring
+    with twins(cfg, streams, ring, fft, R=wrap + ring, win=ring) as (fresh, old, sch):
+        assert t == 28 and span == ring - 1
         rng = np.random.default_rng(ref.GPU_SEED)
         total = int(sum(sch.pushes))
         audio = np.stack([ref.signal(k, rng, total, 2, span) for k in ref.KINDS])
-        T, before, straddling, behind = 0, 0, 0, 0
-        for i, p in enumerate(sch.pushes):
-            a = np.ascontiguousarray(audio[:, :, T:T + p])
-            T += p
-            for b in (fresh, old):
-                b.push_audio(a)
-            if T < wrap - sum(HOPS):
-                continue
-            what = f"read {i} at wpos = 2^32{T - wrap:+d}"
+        walk = Walk((fresh, old), sch.pushes, wrap, span, slices(audio))
+        for i, T, what in walk:
             x, y = fresh.sono(), old.sono()
             assert x["db"].tobytes() == y["db"].tobytes(), f"{what}: the twins' cells differ"
             assert np.all(x["newest"] == (fft + T) // ref.H), what
@@ -57,9 +44,7 @@ def run():
             hist = np.concatenate([np.zeros((streams, 2, fft), np.float32), audio[:, :, :T]], axis=2)
             bad, arm2 = ref.mismatches(x, hist, fft + T, 48000, ring)
             assert not bad, (what, bad[:4])
-            before += int(T <= wrap)
-            straddling += int(0 < T - wrap < span)
-            behind += int(T - wrap >= span)
+        before, straddling, behind = walk.before, walk.straddling, walk.exact + walk.behind  # (the exact hit counts as behind here)
         assert before >= 2 and straddling >= 3 and behind >= 3, (before, straddling, behind)
         assert np.all(np.isfinite(y["db"][0, :, :t]))
         print(f"{before} reads before the wrap, {straddling} with the span across it, {behind} behind it")

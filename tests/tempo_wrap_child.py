@@ -18,23 +18,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import waveform_amd as wf  # noqa: E402
 import tempo_ref as ref  # noqa: E402
-from wrap_child import _dev  # noqa: E402
+from wrap_child import Walk, slices, twins  # noqa: E402
 
 COUNTER = ("newest", "last_beat_frame", "next_beat_frame")
 
 
 def run():
-    L = _dev()
     fft, sr, ch, kw, ring, t, kinds = ref.GPU_CASES[0]
     streams = len(kinds)
     span = (t + 1) * ref.H + ref.P + ref.H - 1  # the most frames a read looks back over
     cfg = wf.Config.defaults(fft_size=fft, sample_rate=sr, stereo=1, slope=1.0, bars=1)
-    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
-        assert old.ring_frames == ring and old.fft_size == fft and t == 507 and span == ring + ref.H - 1
-        # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
-        wrap = 2 * ring - fft
-        age = (1 << 32) - 2 * ring
-        assert L.wf_hip_debug_age(old.h, 0, streams, age) == 0, L.wf_hip_last_error(old.h)
+    # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
+    wrap, age = 2 * ring - fft, (1 << 32) - 2 * ring
+    with twins(cfg, streams, ring, fft) as (fresh, old, _):
+        assert t == 507 and span == ring + ref.H - 1
         # (frames pushed, read behind it): the approach in half rings, two reads before the wrap, the exact hit, the span across it
         # at uneven places, and behind it
         pushes = [(ring // 2, False)] * 3 + [(ring // 2 - fft - 1278, False), (800, True), (441, True), (37, True), (800, True), (30011, True),
@@ -43,15 +40,9 @@ def run():
         audio = np.stack([np.stack([x, np.float32(0.25) * x]) for x in (ref.kicks(np.random.default_rng(ref.GPU_SEED), 120.0, total, sr)[0],
                                                                        ref.bursts(np.random.default_rng(ref.GPU_SEED + 1), 150.0, total, sr)[0],
                                                                        ref.noise(np.random.default_rng(ref.GPU_SEED + 2), -20.0, total))])
-        T, before, exact, straddling, behind, worst = 0, 0, 0, 0, 0, 0.0
-        for i, (p, read) in enumerate(pushes):
-            a = np.ascontiguousarray(audio[:, :, T:T + p])
-            T += p
-            for b in (fresh, old):
-                b.push_audio(a)
-            if not read:
-                continue
-            what = f"read {i} at wpos = 2^32{T - wrap:+d}"
+        worst = 0.0
+        walk = Walk((fresh, old), pushes, wrap, span, slices(audio))
+        for i, T, what in walk:
             x, y = fresh.tempo(), old.tempo()
             for name in ref.FIELDS:
                 if name not in COUNTER:
@@ -69,11 +60,9 @@ def run():
             bad, w = ref.mismatches(x, hist, fft + T, sr, ring, integers=False)
             assert not bad, (what, bad[:4])
             worst = max(worst, w)
-            before += int(T < wrap)
-            exact += int(T == wrap)
-            straddling += int(0 < T - wrap < span)
-            behind += int(T - wrap >= span)
-        assert T == total and before == 2 and exact == 1 and straddling >= 4 and behind >= 2, (before, exact, straddling, behind)
+        # (here `exact` is the read at the wrap itself, and a read that starts at position 0 counts as behind)
+        before, exact, straddling, behind = walk.before - walk.at, walk.at, walk.straddling, walk.exact + walk.behind
+        assert walk.T == total and before == 2 and exact == 1 and straddling >= 4 and behind >= 2, (before, exact, straddling, behind)
         assert y["lag"][:2].tolist() == [94, 75] and np.all(y["strength"][:, :t].max(axis=1) >= 2.0)
         print(f"{before} reads before the wrap, one at it, {straddling} with the span across it, {behind} behind it; largest difference of a "
               f"strength {worst:.2f} ulps")

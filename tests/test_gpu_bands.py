@@ -6,7 +6,6 @@ The bound against the restatement is derived, not measured (include/wf_hip.h, "d
 same float32 row and differ in exp10 and in the order of at most 32768 positive additions, below 2e-11 dB before the one
 rounding to float32.  So |got - want| <= max(1 float32 ulp of want, 1e-9 dB), -INFINITY exactly where the restatement has it,
 `covered` and `reserved` equal (bands_ref.mismatches)."""
-import ctypes as C
 import subprocess
 import sys
 from pathlib import Path
@@ -19,6 +18,7 @@ from waveform_amd import binding
 import bands_ref as ref
 from test_gpu_peaks import CASES, _audio
 from tools import synth
+from measure_common import check_abi_refusals
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID = -1
@@ -153,14 +153,7 @@ def test_meter_waveform_and_bad_arguments_are_refused():
             assert e.value.code == ERR_INVALID and "band levels" in str(e.value)
     with wf.SpectrumBatch(wf.Config.defaults(fft_size=1024, stereo=1), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_BANDS) == 2 * 144  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_BANDS, 0, 1, None) == ERR_INVALID
-        out = np.empty((3, 2), binding.BANDS_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_BANDS, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_BANDS, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_BANDS, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_BANDS, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_BANDS, 0, 2, ptr) == 0
+        check_abi_refusals(b, binding.OUT_BANDS, np.dtype((binding.BANDS_DTYPE, (2,))), 2)  # (an entry is both channels' rows)
 
 
 def test_nothing_else_moves(monkeypatch):

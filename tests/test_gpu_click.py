@@ -12,10 +12,6 @@ r in the order include/wf_hip.h fixes, so the residual is the same bits on both 
 wf_hip_read_async carries the eight outputs of the tick in a fixed record (wf_hip_readback) and no measurement output: there is
 nothing of this output to compare through it without a new field, which the ABI does not get here."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -24,10 +20,10 @@ import waveform_amd as wf
 from waveform_amd import binding
 import measure_stagger as ms
 import click_ref as ref
+from measure_common import check_abi_refusals, run_wrap_child
 
 pytestmark = pytest.mark.gpu
 OUT_CLICK = binding.OUT_CLICK  # (the output these tests are about: a library without it fails every one of them)
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 ENTRY = 464
 SR = 48000
@@ -101,14 +97,8 @@ def test_refusals():
         assert b.bits().shape == (2,)  # the other readers of such a batch are unharmed
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, OUT_CLICK) == ENTRY  # before the first read
-        assert L.wf_hip_read(b.h, OUT_CLICK, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.CLICK_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, OUT_CLICK, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, OUT_CLICK, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(b.h, OUT_CLICK, 0, 2, ptr) == 0
         silent = ref.click(np.zeros((2, 2, 1024), np.float32), SR, [1024, 1024])  # freshly created: valid = 0
-        assert out[:2].tobytes() == silent.tobytes()
+        check_abi_refusals(b, OUT_CLICK, binding.CLICK_DTYPE, 2, silent)
 
 
 def test_a_one_device_group_reads_the_same():
@@ -132,7 +122,4 @@ def test_across_the_2_to_the_32_wrap():
     """tests/click_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in
     small hops with a click on each side; each equal to the restatement of its own ring and counter, `frame` included, at every hop.
     One child process (the release library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run(["timeout", "-k", "10", "90", sys.executable, str(ROOT / "tests" / "click_wrap_child.py")], capture_output=True,
-                       text=True, env=env)
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("click_wrap_child.py", 90)

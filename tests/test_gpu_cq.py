@@ -17,6 +17,7 @@ from waveform_amd import binding
 import cq_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, packets
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID = -1
@@ -28,16 +29,6 @@ A4, A1 = 57, 21
 def _cfg(fft=4096, sr=48000, channels=2, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=channels, stereo=1 if channels == 2 else 0, slope=1.0,
                                         bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 700)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _check(got, frames, sr, ring_frames, what=""):
@@ -57,7 +48,7 @@ def test_cq_equals_the_reference_of_the_frames(case):
     x = ref.case_audio(case)  # Lmax + 2 * 801 frames: the window wraps the ring and ends at no aligned position
     with wf.SpectrumBatch(_cfg(fft, sr, ch, **kw), x.shape[0], ring_frames=ring) as b:
         assert ref.max_window(b.ring_frames) == lmax
-        for lo, hi in _packets(np.random.default_rng(fft), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(fft), x.shape[-1], 699):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.cq()
         assert wf.lib().wf_hip_output_bytes(b.h, binding.OUT_CQ) == 976
@@ -91,30 +82,13 @@ def test_sines_at_a4_and_a1():
     assert short["max_window"][0] == 4096 and short["first_resolved"][0] == 44 > A1
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same frames through push_audio, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
     streams, fft, frames = 3, 1024, 801
     rng = np.random.default_rng(2)
     pkts = [rng.integers(-32768, 32768, (streams, frames, 2)).astype(np.int16) for _ in range(6)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft), streams) as b:
@@ -146,14 +120,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == fft
         b.push_audio(np.ascontiguousarray(x[..., :2000]))
         b.push_audio(np.ascontiguousarray(x[..., 2000:]))
-        part = b.cq(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.cq()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.cq(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.cq().tobytes() == full.tobytes()
-        b.tick()
-        assert b.cq().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "cq")
     _check(full, x, sr, fft, "wrapped ring")
 
 
@@ -189,14 +156,7 @@ def test_refusals():
         assert b"constant-Q" in L.wf_hip_last_error(b.h)
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_CQ) == 976  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_CQ, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.CQ_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_CQ, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_CQ, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_CQ, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_CQ, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_CQ, 0, 2, ptr) == 0
+        out = check_abi_refusals(b, binding.OUT_CQ, binding.CQ_DTYPE, 2)
         assert np.all(out["max_window"][:2] == 4096)
 
 
@@ -240,8 +200,5 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.cq()
-        assert m.cq().tobytes() == want.tobytes()
-        assert m.cq(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.cq().shape == (streams,)
+        want = check_shards_match(one, m, "cq", (2, 4))
         assert np.all(np.isfinite(want["db"]))

@@ -8,10 +8,6 @@ definition consists of comparisons, integer counts, exact float64 operations and
 field is equal bit for bit.  test_gonio_cpu.py shows that the pictures compared here are spread ones, with the three signs of zoom
 among them."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -21,9 +17,9 @@ from waveform_amd import binding
 import gonio_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, packets, run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 SEED = ref.GPU_SEED
 HOP = 801
@@ -33,16 +29,6 @@ G = ref.GRID
 def _cfg(fft=4096, sr=48000, channels=2, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=channels, stereo=1 if channels == 2 else 0, slope=1.0,
                                         bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths of 1..700 frames that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 701)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _check(got, frames, w, what=""):
@@ -68,7 +54,7 @@ def test_gonio_equals_the_restatement_of_the_frames(case):
     with wf.SpectrumBatch(_cfg(fft, sr, 2, **kw), x.shape[0]) as b:
         assert b.fft_size == w and b.ring_frames == ref.ring_frames(w)
         assert wf.lib().wf_hip_output_bytes(b.h, binding.OUT_GONIO) == 8224  # before the first read
-        for lo, hi in _packets(np.random.default_rng(w), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(w), x.shape[-1], 700):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.gonio()
     assert np.all(got["window"] == ref.window_frames(w))
@@ -89,23 +75,6 @@ def test_the_clamp_of_the_range():
     _check(got, x, 1024, "scaled by 2^-30")
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same frames through push_audio, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
@@ -113,7 +82,7 @@ def test_every_push_path_counts():
     rng = np.random.default_rng(2)
     wave = (8000.0 * np.sin(2.0 * np.pi * np.arange(6 * frames) / 57.3))[None, :, None]
     pkts = [(wave[:, i * frames:(i + 1) * frames] + rng.integers(-5000, 5000, (streams, frames, 2))).astype(np.int16) for i in range(6)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft), streams) as b:
@@ -145,14 +114,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == fft
         b.push_audio(np.ascontiguousarray(x[..., :2000]))
         b.push_audio(np.ascontiguousarray(x[..., 2000:]))
-        part = b.gonio(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.gonio()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.gonio(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.gonio().tobytes() == full.tobytes()
-        b.tick()
-        assert b.gonio().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "gonio")
     _check(full, x, fft, "the window is the whole ring")
 
 
@@ -197,15 +159,7 @@ def test_refusals():
         assert b.signal().shape == (2,)  # nothing was enqueued that would trouble the next call
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_GONIO) == 8224  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_GONIO, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.GONIO_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_GONIO, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_GONIO, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_GONIO, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_GONIO, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_GONIO, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == _silence(1024, 2).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_GONIO, binding.GONIO_DTYPE, 2, _silence(1024, 2))
 
 
 def test_a_small_meter_buffer_is_served():
@@ -255,16 +209,11 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.gonio()
-        assert m.gonio().tobytes() == want.tobytes()
-        assert m.gonio(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.gonio().shape == (streams,)
+        want = check_shards_match(one, m, "gonio", (2, 4))
         assert np.all(want["window"] == 2048) and np.all(want["occupied"] > 8) and len(set(want["zoom"].tolist())) >= 3
 
 
 def test_across_the_2_to_the_32_wrap():
     """tests/gonio_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in small
     hops with gonio() equal at every hop.  One child process (the release library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "gonio_wrap_child.py")], capture_output=True, text=True, timeout=60, env=env)
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("gonio_wrap_child.py", 60)

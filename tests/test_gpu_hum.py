@@ -10,10 +10,6 @@ The bound (hum_ref.mismatches): every integer field equal to the restatement's a
 of the restatement's float64 value -- mains_hz, hz[] and total_db included.  tests/test_hum_cpu.py asserts that every candidate
 line of every window read here stands at least 3 dB from the 15 dB margin, so no rounding of the device can move an integer."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -22,9 +18,9 @@ import waveform_amd as wf
 from waveform_amd import binding
 import hum_ref as ref
 from tools import synth
+from measure_common import check_abi_refusals, check_shards_match, run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 ENTRY = 304
 SR, RING = ref.SR, ref.RING
@@ -197,13 +193,7 @@ def test_refusals():
         assert e.value.code == ERR_INVALID and "hum" in str(e.value) and "sample rate" in str(e.value), str(e.value)
     with wf.SpectrumBatch(_cfg(), 2, ring_frames=RING) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_HUM) == ENTRY
-        assert L.wf_hip_read(b.h, binding.OUT_HUM, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.HUM_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_HUM, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_HUM, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(b.h, binding.OUT_HUM, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == ref.fresh(2, SR, RING).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_HUM, binding.HUM_DTYPE, 2, ref.fresh(2, SR, RING))
 
 
 def test_two_shards_match_one_handle():
@@ -213,16 +203,11 @@ def test_two_shards_match_one_handle():
         one.push_audio(x)
         m.push_audio(x)
         m.sync()
-        want = one.hum()
-        assert m.hum().tobytes() == want.tobytes()
-        assert m.hum(1, 2).tobytes() == want[1:].tobytes()  # a range that spans the shards
+        want = check_shards_match(one, m, "hum", (1, 2))
     assert want["ch"]["family"].tolist() == [[50, 60], [60, 0], [0, 50]]
 
 
 def test_across_the_2_to_the_32_wrap():
     """tests/hum_wrap_child.py: twin handles on the development build, one aged to just below 2^32, read before the wrap, at it,
     with the window across it and behind it.  One child process (the release library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "hum_wrap_child.py")], capture_output=True, text=True, timeout=120, env=env)
-    print(r.stdout[-1500:])
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("hum_wrap_child.py", 120)

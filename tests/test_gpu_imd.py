@@ -10,10 +10,6 @@ samples and differ in the order of operations, and tests/test_imd_cpu.py shows o
 product's or harmonic's bin and not the 30 dB decision is near a tie and that two orderings agree to 1e-7 dB, so one float32
 rounding is all that can separate them."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -23,9 +19,9 @@ from waveform_amd import binding
 import imd_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, packets, run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 HOP = 801
 ENTRY = 368
@@ -33,16 +29,6 @@ ENTRY = 368
 
 def _cfg(fft=4096, sr=48000, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=2, stereo=1, slope=1.0, bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths of 1..700 frames that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 701)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _check(got, frames, w, sr, what=""):
@@ -77,7 +63,7 @@ def test_imd_equals_the_restatement_of_the_frames(case):
     with wf.SpectrumBatch(_cfg(fft, sr, **kw), x.shape[0]) as b:
         assert b.fft_size == w and b.ring_frames == ref.ring_frames(w) and b.capture_channels == channels
         assert wf.lib().wf_hip_output_bytes(b.h, binding.OUT_IMD) == ENTRY  # before the first read
-        for lo, hi in _packets(np.random.default_rng(w), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(w), x.shape[-1], 700):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.imd()
     p = ref.window_frames(w)
@@ -91,23 +77,6 @@ def test_imd_equals_the_restatement_of_the_frames(case):
         assert not got["ch"][:, 1].tobytes().strip(b"\0")  # all zero bytes
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same s16 frames through push_audio, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
@@ -117,7 +86,7 @@ def test_every_push_path_counts():
     pairs = ((21.37, 133.21), (33.87, 301.13), (57.21, 240.59))  # bins of 1024
     wave = np.stack([32768.0 * ref.polynomial(ref.two_tones(n, lo / fft, hi / fft, 0.4, 0.3), 1e-2, 1e-2) for lo, hi in pairs])[:, :, None]
     pkts = [np.round(wave[:, i * frames:(i + 1) * frames] + rng.integers(-3, 4, (streams, frames, 2))).astype(np.int16) for i in range(6)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft, sr), streams) as b:
@@ -151,14 +120,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == fft
         b.push_audio(np.ascontiguousarray(x[..., :2000]))
         b.push_audio(np.ascontiguousarray(x[..., 2000:]))
-        part = b.imd(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.imd()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.imd(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.imd().tobytes() == full.tobytes()
-        b.tick()
-        assert b.imd().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "imd")
     _check(full, x, fft, sr, "the window is the whole ring")
     assert full["ch"]["tones"][:, 0].tolist() == [2, 2, 1, 0, 2]
 
@@ -203,15 +165,7 @@ def test_refusals():
         assert b.bits().shape == (2,)  # the other readers of such a batch are unharmed
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_IMD) == ENTRY  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_IMD, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.IMD_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_IMD, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_IMD, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_IMD, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_IMD, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_IMD, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == _zero(1024, 2).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_IMD, binding.IMD_DTYPE, 2, _zero(1024, 2))
 
 
 def test_nothing_else_moves_on_a_twin(monkeypatch):
@@ -258,10 +212,7 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.imd()
-        assert m.imd().tobytes() == want.tobytes()
-        assert m.imd(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.imd().shape == (streams,)
+        want = check_shards_match(one, m, "imd", (2, 4))
     assert np.all(want["window"] == fft) and want["ch"]["tones"][:, 0].tolist() == [2, 2, 2, 0, 2, 1, 2]
     _check(want, x, fft, sr, "one handle of the seven streams")
 
@@ -270,6 +221,4 @@ def test_across_the_2_to_the_32_wrap():
     """tests/imd_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in small
     hops with imd() equal on both and within the bound of the restatement at every hop.  One child process (the release library
     has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "imd_wrap_child.py")], capture_output=True, text=True, timeout=60, env=env)
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("imd_wrap_child.py", 60)

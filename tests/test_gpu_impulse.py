@@ -19,10 +19,6 @@ delay_ms at lag 0 differed by 6e-16 frames at the most, which the bound's FRAC_F
 The margins asked are impulse_ref.margins_hold's: 1e-3 in every figure, but 1e-5 in the prominence of a stream that lists maxima
 of its noise floor -- the stream under equal noise, and in the staggered batch a stream whose ring the audio has not filled yet."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -34,10 +30,10 @@ import impulse_ref as ref
 import xfer_ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, packets, run_wrap_child
 
 pytestmark = pytest.mark.gpu
 OUT_IMPULSE = binding.OUT_IMPULSE  # (the output these tests are about: a library without it fails every one of them)
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 ENTRY = 16576
 INDEPENDENT = ref.KINDS.index("independent")
@@ -46,16 +42,6 @@ NOISY = ref.KINDS.index("three taps, noise")
 
 def _cfg(fft=4096, sr=48000, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=2, stereo=1, slope=1.0, bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths of 1..700 frames that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 701)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _padding_is_zero(got):
@@ -104,7 +90,7 @@ def test_impulse_equals_the_restatement_of_the_frames(index):
     with wf.SpectrumBatch(_cfg(fft, sr, **kw), x.shape[0], ring_frames=ring or 0) as b:
         assert b.fft_size == w and b.ring_frames == cap and b.capture_channels == 2
         assert wf.lib().wf_hip_output_bytes(b.h, OUT_IMPULSE) == ENTRY  # before the first read
-        for lo, hi in _packets(np.random.default_rng(w), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(w), x.shape[-1], 700):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.impulse()
         xf = b.xfer()
@@ -133,23 +119,6 @@ def test_impulse_equals_the_restatement_of_the_frames(index):
     assert none["peak_index"] == 0 and not any(none[n] for n in ("peak_db", "delay_ms", "energy_db", "direct_db", "lag", "lag_peak"))
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same s16 frames through push_audio, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
@@ -159,7 +128,7 @@ def test_every_push_path_counts():
     base = np.stack([ref.stream(k, rng, packets * frames, 512) for k in ("three taps", "delay -(L-1), echo", "guarded echoes")])
     wave = np.round(32768.0 * 0.5 * np.clip(base, -2.0, 2.0)).astype(np.int16).transpose(0, 2, 1)  # [streams, n, 2]
     pkts = [np.ascontiguousarray(wave[:, i * frames:(i + 1) * frames]) for i in range(packets)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft, sr), streams) as b:
@@ -280,15 +249,7 @@ def test_refusals():
         assert e.value.code == ERR_INVALID and "ring of at least 512 frames" in str(e.value), str(e.value)
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, OUT_IMPULSE) == ENTRY  # before the first read
-        assert L.wf_hip_read(b.h, OUT_IMPULSE, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.IMPULSE_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, OUT_IMPULSE, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, OUT_IMPULSE, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, OUT_IMPULSE, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, OUT_IMPULSE, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, OUT_IMPULSE, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == ref.zero_record(1024, b.ring_frames, 2).tobytes()  # the next good read is correct
+        check_abi_refusals(b, OUT_IMPULSE, binding.IMPULSE_DTYPE, 2, ref.zero_record(1024, b.ring_frames, 2))
 
 
 def test_nothing_else_moves_on_a_twin(monkeypatch):
@@ -335,11 +296,8 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.impulse()
+        want = check_shards_match(one, m, "impulse", (2, 4))
         xf = one.xfer()
-        assert m.impulse().tobytes() == want.tobytes()
-        assert m.impulse(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.impulse().shape == (streams,)
     assert np.all(want["window"] == 512) and want["valid"].tolist() == [1, 1, 1, 0, 1, 1, 1]
     assert want["lag"].tolist() == [37, -127, 0, 0, 12, 0, 0] and want["count"].tolist() == [3, 2, 1, 0, 2, 1, 0]
     _check(want, xf, x, fft, 4096, sr, fft + hops * hop, "one handle of the seven streams")
@@ -370,7 +328,4 @@ def test_across_the_2_to_the_32_wrap():
     """tests/impulse_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in
     small hops with impulse() equal on both and within the bound of the restatement at every hop.  One child process (the release
     library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run(["timeout", "-k", "10", "90", sys.executable, str(ROOT / "tests" / "impulse_wrap_child.py")], capture_output=True,
-                       text=True, env=env)
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("impulse_wrap_child.py", 90)

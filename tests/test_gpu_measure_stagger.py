@@ -10,10 +10,6 @@ wpos[0], wpos[slice index], a shard's wpos at the group's index -- passes every 
 received the same number of frames before every read.  tests/test_measure_stagger_cpu.py shows that it cannot pass here, and that
 every window compared meets the conditions of its module's bound.  No tolerance is defined here: every bound is the output's own
 (measure_stagger.mismatches)."""
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -22,9 +18,9 @@ import waveform_amd as wf
 from waveform_amd import binding
 import measure_stagger as ms
 import sono_ref
+from measure_common import run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 S = ms.STREAMS
 OUT = {name: getattr(binding, "OUT_" + name.upper()) for name in ms.OUTPUTS}
 SPREAD = "cq"  # the audio of the tests of bit identity: noise and two sines, different in every stream and channel
@@ -192,7 +188,4 @@ def test_one_stream_across_the_2_to_the_32_wrap():
     aged to just below 2^32 and walked across the wrap in small hops while its neighbours stay young; every output equal on both
     twins for all streams, the aged stream within its bound of the restatement.  One child process (the release library has no test
     aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "measure_stagger_wrap_child.py")], capture_output=True, text=True, timeout=60, env=env)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("measure_stagger_wrap_child.py", 60)

@@ -11,10 +11,6 @@ per sum, so two correctly rounded float32 values can differ by one step and no m
 pick() of the device's own strengths, and equal to the restatement's, which test_onset_cpu.py makes legitimate: on these cases no
 decision of the restatement lies within four ulps of flipping."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -24,9 +20,9 @@ from waveform_amd import binding
 import onset_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 P, H = ref.P, ref.H
 ENTRY = 2240
@@ -110,23 +106,6 @@ def test_columns_and_decided_flags_stand_still():
     assert np.all((err <= np.spacing(np.abs(want)).astype(np.float64)) | (err <= ref.ABS_TOL))
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def _strengths_hold(got, hist, sr, ring_cap, what):
     """audio that is no committed case: the header exactly, the strengths within the bound, the flags and the summary bit for bit
     pick() of the device's own strengths"""
@@ -153,7 +132,7 @@ def test_every_push_path_counts():
     pkts = [(wave[:, i * frames:(i + 1) * frames] + rng.integers(-5000, 5000, (streams, frames, 2))).astype(np.int16) for i in range(n_pkts)]
     convs = [np.ascontiguousarray(captured(pkt, True, 0, 2)) for pkt in pkts]  # [streams, 2, frames] float32
     split = np.array([0, int(0.4 * frames), frames], np.uint32)  # a packet in two ragged pushes: the streams differ in how it is cut
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pinned", "ragged", "pcm", "device", "synth", "muted"):
         with wf.SpectrumBatch(_cfg(fft), streams, ring_frames=ring_cap) as b:
@@ -213,14 +192,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == ring_cap
         b.push_audio(np.ascontiguousarray(x[..., :4000]))
         b.push_audio(np.ascontiguousarray(x[..., 4000:]))
-        part = b.onset(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.onset()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.onset(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.onset().tobytes() == full.tobytes()
-        b.tick()
-        assert b.onset().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "onset")
     _strengths_hold(full, _hist(fft, x), 48000, ring_cap, "five streams")
 
 
@@ -262,15 +234,7 @@ def test_refusals():
         assert b.signal().shape == (2,)  # nothing was enqueued that would trouble the next call
     with wf.SpectrumBatch(_cfg(4096), 2) as b:
         assert b.ring_frames == 8192 and L.wf_hip_output_bytes(b.h, binding.OUT_ONSET) == ENTRY  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_ONSET, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.ONSET_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_ONSET, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_ONSET, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_ONSET, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_ONSET, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_ONSET, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == _fresh(2, 8192, 4096).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_ONSET, binding.ONSET_DTYPE, 2, _fresh(2, 8192, 4096))
 
 
 def test_nothing_else_moves(monkeypatch):
@@ -307,17 +271,11 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.onset()
-        assert m.onset().tobytes() == want.tobytes()
-        assert m.onset(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.onset().shape == (streams,)
+        want = check_shards_match(one, m, "onset", (2, 4))
         assert np.all(want["columns"] == 27) and np.all(want["strength"][[0, 1, 3, 4, 6], :18] > 0)
 
 
 def test_across_the_2_to_the_32_wrap():
     """tests/onset_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in
     small hops with the strengths and flags of onset() equal at every hop.  One child process (the release library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "onset_wrap_child.py")], capture_output=True, text=True, timeout=120, env=env)
-    print(r.stdout[-1500:])
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("onset_wrap_child.py", 120)

@@ -18,6 +18,7 @@ from waveform_amd import binding
 import scope_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, packets
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID = -1
@@ -28,16 +29,6 @@ HOP = 801
 def _cfg(fft=4096, sr=48000, channels=2, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=channels, stereo=1 if channels == 2 else 0, slope=1.0,
                                         bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 700)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _check(got, frames, w, what=""):
@@ -56,7 +47,7 @@ def test_scope_equals_the_restatement_of_the_frames(case):
     with wf.SpectrumBatch(_cfg(fft, sr, ch, **kw), x.shape[0]) as b:
         assert b.fft_size == w and b.ring_frames == ref.ring_frames(w)
         assert wf.lib().wf_hip_output_bytes(b.h, binding.OUT_SCOPE) == 4128  # before the first read
-        for lo, hi in _packets(np.random.default_rng(w), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(w), x.shape[-1], 699):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.scope()
     p, v, k = ref.geometry(w)
@@ -92,23 +83,6 @@ def test_the_trace_stands_still():
     assert len(set(starts)) >= 2  # the view really moved in the ring
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same frames through push_audio, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
@@ -116,7 +90,7 @@ def test_every_push_path_counts():
     rng = np.random.default_rng(2)
     wave = (8000.0 * np.sin(2.0 * np.pi * np.arange(6 * frames) / 57.3))[None, :, None]
     pkts = [(wave[:, i * frames:(i + 1) * frames] + rng.integers(-500, 500, (streams, frames, 2))).astype(np.int16) for i in range(6)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft), streams) as b:
@@ -147,14 +121,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == fft
         b.push_audio(np.ascontiguousarray(x[..., :2000]))
         b.push_audio(np.ascontiguousarray(x[..., 2000:]))
-        part = b.scope(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.scope()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.scope(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.scope().tobytes() == full.tobytes()
-        b.tick()
-        assert b.scope().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "scope")
     _check(full, x, fft, "the window is the whole ring")
 
 
@@ -196,14 +163,7 @@ def test_refusals():
         assert e.value.code == ERR_INVALID and "oscilloscope" in str(e.value) and "64 frames" in str(e.value), str(e.value)
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_SCOPE) == 4128  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_SCOPE, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.SCOPE_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_SCOPE, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_SCOPE, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_SCOPE, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_SCOPE, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_SCOPE, 0, 2, ptr) == 0
+        out = check_abi_refusals(b, binding.OUT_SCOPE, binding.SCOPE_DTYPE, 2)
         assert np.all(out["window"][:2] == 1024) and np.all(out["start"][:2] == 512)
 
 
@@ -246,8 +206,5 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.scope()
-        assert m.scope().tobytes() == want.tobytes()
-        assert m.scope(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.scope().shape == (streams,)
+        want = check_shards_match(one, m, "scope", (2, 4))
         assert np.all(want["window"] == 2048) and want["hi"][:, :, :256].any()

@@ -10,10 +10,6 @@ band power is at least 1e-9 of its column's largest within two float32 ulps of t
 ulp of 4e-6 dB at -60 dB, and the second ulp is for a value on a rounding boundary --; the remaining cells with their linear power
 within 1e-10 of the column's largest.  The noise streams pass by the first arm alone (test_sono_cpu.py shows they can)."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -23,9 +19,9 @@ from waveform_amd import binding
 import sono_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 P, H = ref.P, ref.H
 ENTRY = 32800
@@ -111,23 +107,6 @@ def test_columns_stand_still():
     _check(two, _hist(fft, x, more), sr, ring_cap, "300 frames later")
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same frames through push_audio, the pinned asynchronous push, two ragged pushes per packet, wf_hip_push_pcm (s16
     interleaved: every value exact in float32) and push_audio_device read bit-identically; push_synth and muted packets advance
@@ -138,7 +117,7 @@ def test_every_push_path_counts():
     pkts = [(wave[:, i * frames:(i + 1) * frames] + rng.integers(-5000, 5000, (streams, frames, 2))).astype(np.int16) for i in range(6)]
     convs = [np.ascontiguousarray(captured(pkt, True, 0, 2)) for pkt in pkts]  # [streams, 2, frames] float32
     split = np.array([0, int(0.4 * frames), frames], np.uint32)  # a packet in two ragged pushes: the streams differ in how it is cut
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pinned", "ragged", "pcm", "device", "synth", "muted"):
         with wf.SpectrumBatch(_cfg(fft), streams) as b:
@@ -197,14 +176,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == 4096
         b.push_audio(np.ascontiguousarray(x[..., :2000]))
         b.push_audio(np.ascontiguousarray(x[..., 2000:]))
-        part = b.sono(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.sono()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.sono(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.sono().tobytes() == full.tobytes()
-        b.tick()
-        assert b.sono().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "sono")
     _check(full, _hist(fft, x), 48000, 4096, "five streams", noise=())
 
 
@@ -245,15 +217,7 @@ def test_refusals():
         assert b.signal().shape == (2,)  # nothing was enqueued that would trouble the next call
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_SONO) == ENTRY  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_SONO, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.SONO_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_SONO, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_SONO, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_SONO, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_SONO, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_SONO, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == _fresh(2, 4096, 1024).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_SONO, binding.SONO_DTYPE, 2, _fresh(2, 4096, 1024))
 
 
 def test_nothing_else_moves(monkeypatch):
@@ -290,17 +254,11 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.sono()
-        assert m.sono().tobytes() == want.tobytes()
-        assert m.sono(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.sono().shape == (streams,)
+        want = check_shards_match(one, m, "sono", (2, 4))
         assert np.all(want["columns"] == 12) and np.all(np.isfinite(want["db"][0, :, :12]))
 
 
 def test_across_the_2_to_the_32_wrap():
     """tests/sono_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in small
     hops with the cells of sono() equal at every hop.  One child process (the release library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "sono_wrap_child.py")], capture_output=True, text=True, timeout=120, env=env)
-    print(r.stdout[-1500:])
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("sono_wrap_child.py", 120)

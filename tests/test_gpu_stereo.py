@@ -9,7 +9,6 @@ the same float32 samples and differ in the order of the transform's operations, 
 rounding to float32.  So |got - want| <= max(1 float32 ulp of want, 1e-9) for correlation, coherence and balance_db, and for
 phase_deg wherever the restatement's coherence is >= 0.01; `covered` and `window` are equal (stereo_ref.mismatches).  The bands
 under 0.01, where the phase is not compared, must be at most 1 % of those that overlap the bins."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ from waveform_amd import binding
 import stereo_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, packets
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID = -1
@@ -28,16 +28,6 @@ HOP = 800
 
 def _cfg(fft=4096, sr=48000, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=2, stereo=1, slope=1.0, bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 700)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _check(got, want, sr, what=""):
@@ -65,7 +55,7 @@ def test_stereo_equals_the_reference_of_the_frames(fft, sr, kw):
     with wf.SpectrumBatch(_cfg(fft, sr, **kw), streams) as b:
         p = ref.window_frames(b.fft_size)
         x = ref.audio(rng, streams, p + 2 * HOP, sr)
-        for lo, hi in _packets(np.random.default_rng(fft), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(fft), x.shape[-1], 699):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.stereo()
         assert wf.lib().wf_hip_output_bytes(b.h, binding.OUT_STEREO) == 504
@@ -99,30 +89,13 @@ def test_a_delayed_sine_and_an_inverted_channel():
     assert not ref.mismatches(got[1:], want[1:]) and abs(float(want["phase_deg"][0, 17]) - float(g["phase_deg"][17])) < 1e-4
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same frames through push_audio, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
     streams, fft, frames = 3, 1024, 801
     rng = np.random.default_rng(2)
     pkts = [rng.integers(-32768, 32768, (streams, frames, 2)).astype(np.int16) for _ in range(3)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft), streams) as b:
@@ -153,14 +126,7 @@ def test_repeated_reads_and_slices():
         assert b.ring_frames == fft
         b.push_audio(np.ascontiguousarray(x[..., :2000]))
         b.push_audio(np.ascontiguousarray(x[..., 2000:]))
-        part = b.stereo(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.stereo()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.stereo(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.stereo().tobytes() == full.tobytes()
-        b.tick()
-        assert b.stereo().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "stereo")
     _check(full, ref.stereo(x[..., -fft:], sr), sr, "wrapped ring")
 
 
@@ -197,14 +163,7 @@ def test_refusals():
             assert e.value.code == ERR_INVALID and text in str(e.value), str(e.value)
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_STEREO) == 504  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_STEREO, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.STEREO_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_STEREO, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_STEREO, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_STEREO, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_STEREO, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_STEREO, 0, 2, ptr) == 0
+        out = check_abi_refusals(b, binding.OUT_STEREO, binding.STEREO_DTYPE, 2)
         assert np.all(out["window"][:2] == 1024)
 
 
@@ -243,7 +202,4 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.stereo()
-        assert m.stereo().tobytes() == want.tobytes()
-        assert m.stereo(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.stereo().shape == (streams,)
+        want = check_shards_match(one, m, "stereo", (2, 4))

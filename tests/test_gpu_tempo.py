@@ -11,10 +11,6 @@ own strengths, every integer equal to it; and on the committed cases the integer
 strengths, which test_tempo_cpu.py makes legitimate: their decisions stand at least four times farther from flipping than a change
 of every strength by one ulp can move them."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -24,9 +20,9 @@ from waveform_amd import binding
 import tempo_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import check_abi_refusals, check_shards_match, run_wrap_child
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 P, H = ref.P, ref.H
 ENTRY = 10592
@@ -219,13 +215,7 @@ def test_refusals():
         assert e.value.code == ERR_INVALID and "tempo" in str(e.value) and "sample rate" in str(e.value), str(e.value)
     with wf.SpectrumBatch(_cfg(1024), 2, ring_frames=RING) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_TEMPO) == ENTRY
-        assert L.wf_hip_read(b.h, binding.OUT_TEMPO, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.TEMPO_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_TEMPO, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_TEMPO, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(b.h, binding.OUT_TEMPO, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == _fresh(2, 48000, RING, 1024).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_TEMPO, binding.TEMPO_DTYPE, 2, _fresh(2, 48000, RING, 1024))
 
 
 def test_two_shards_match_one_handle():
@@ -237,16 +227,11 @@ def test_two_shards_match_one_handle():
         one.push_audio(x)
         m.push_audio(x)
         m.sync()
-        want = one.tempo()
-        assert m.tempo().tobytes() == want.tobytes()
-        assert m.tempo(1, 2).tobytes() == want[1:].tobytes()  # a range that spans the shards
+        want = check_shards_match(one, m, "tempo", (1, 2))
     assert want["valid"].tolist() == [1, 1, 1] and want["lag"][:2].tolist() == [94, 75]
 
 
 def test_across_the_2_to_the_32_wrap():
     """tests/tempo_wrap_child.py: twin handles on the development build, one aged to just below 2^32, read before the wrap, with the
     span read across it and behind it.  One child process (the release library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run([sys.executable, str(ROOT / "tests" / "tempo_wrap_child.py")], capture_output=True, text=True, timeout=120, env=env)
-    print(r.stdout[-1500:])
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("tempo_wrap_child.py", 120)

@@ -18,10 +18,6 @@ The measured channel of stream 7 is +0.0 in every frame a segment of channel 0 c
 slack behind them: the definition calls a channel silent when its whole span is +-0, slack included, so this is how Syy == 0 on
 live bins and valid == 1 come together."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -32,10 +28,10 @@ import measure_stagger as ms
 import xfer_ref as ref
 from pcm_convert import captured
 from tools import synth
+from measure_common import Hip, check_abi_refusals, check_shards_match, check_slices_and_repeats, packets, run_wrap_child
 
 pytestmark = pytest.mark.gpu
 OUT_XFER = binding.OUT_XFER  # (the output these tests are about: a library without it fails every one of them)
-ROOT = Path(__file__).resolve().parent.parent
 ERR_INVALID = -1
 ENTRY = 12336
 INDEPENDENT = ref.KINDS.index("independent")
@@ -43,16 +39,6 @@ INDEPENDENT = ref.KINDS.index("independent")
 
 def _cfg(fft=4096, sr=48000, **kw):
     return wf.Config.defaults(**{**dict(fft_size=fft, sample_rate=sr, capture_channels=2, stereo=1, slope=1.0, bars=1, floor_db=-70), **kw})
-
-
-def _packets(rng, total):
-    """uneven packet lengths of 1..700 frames that add up to `total`"""
-    cuts, at = [], 0
-    while at < total:
-        n = min(int(rng.integers(1, 701)), total - at)
-        cuts.append((at, at + n))
-        at += n
-    return cuts
 
 
 def _check(got, frames, w, ring, sr, wpos, what="", free=()):
@@ -86,7 +72,7 @@ def test_xfer_equals_the_restatement_of_the_frames(case):
     with wf.SpectrumBatch(_cfg(fft, sr, **kw), x.shape[0], ring_frames=ring or 0) as b:
         assert b.fft_size == w and b.ring_frames == cap and b.capture_channels == 2
         assert wf.lib().wf_hip_output_bytes(b.h, binding.OUT_XFER) == ENTRY  # before the first read
-        for lo, hi in _packets(np.random.default_rng(w), x.shape[-1]):
+        for lo, hi in packets(np.random.default_rng(w), x.shape[-1], 700):
             b.push_audio(np.ascontiguousarray(x[:, :, lo:hi]))
         got = b.xfer()
     wpos = ref.case_wpos0(case) + x.shape[-1]
@@ -130,23 +116,6 @@ def test_dual_mono_reads_exactly(case):
     assert np.all(dual["gain_db"][live] == 0.0) and np.all(dual["phase"][live] == 0.0)
 
 
-class _Hip:
-    """device buffers from the HIP runtime the library is linked against, looked up through the library's own handle"""
-
-    def __init__(self):
-        L = wf.lib()
-        self.malloc, self.free, self.memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        self.malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.free.argtypes = [C.c_void_p]
-        self.memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-
-    def upload(self, arr):
-        p = C.c_void_p()
-        assert self.malloc(C.byref(p), arr.nbytes) == 0
-        assert self.memcpy(p, arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        return p.value
-
-
 def test_every_push_path_counts():
     """the same s16 frames through push_audio, its async form, wf_hip_push_pcm (s16 interleaved: every value exact in float32) and
     push_audio_device read bit-identically"""
@@ -156,7 +125,7 @@ def test_every_push_path_counts():
     base = np.stack([ref.stream(k, rng, packets * frames, 512) for k in ("fir +37", "delay -(L-1)", "added noise")])  # [streams, 2, n]
     wave = np.round(32768.0 * 0.9 * np.clip(base, -1.0, 1.0)).astype(np.int16).transpose(0, 2, 1)  # [streams, n, 2]
     pkts = [np.ascontiguousarray(wave[:, i * frames:(i + 1) * frames]) for i in range(packets)]
-    hip = _Hip()
+    hip = Hip()
     reads = {}
     for path in ("float", "async", "pcm", "device"):
         with wf.SpectrumBatch(_cfg(fft, sr), streams) as b:
@@ -205,14 +174,7 @@ def test_repeated_reads_slices_and_pushes_within_a_hop():
         assert b.ring_frames == ring and (fft + total) % h == 3
         b.push_audio(np.ascontiguousarray(x[..., :5000]))
         b.push_audio(np.ascontiguousarray(x[..., 5000:total]))
-        part = b.xfer(1, 1)  # the first read is a slice: the block is allocated whole
-        full = b.xfer()
-        assert part.shape == (1,) and part.tobytes() == full[1:2].tobytes()
-        assert b.xfer(3, 2).tobytes() == full[3:].tobytes()
-        for _ in range(3):
-            assert b.xfer().tobytes() == full.tobytes()
-        b.tick()
-        assert b.xfer().tobytes() == full.tobytes()  # a tick does not move the rings
+        full = check_slices_and_repeats(b, "xfer")
         b.push_audio(np.ascontiguousarray(x[..., total:total + h - 4]))  # one frame short of the next anchor
         assert b.xfer().tobytes() == full.tobytes()
         b.push_audio(np.ascontiguousarray(x[..., total + h - 4:total + h - 3]))  # the anchor
@@ -276,15 +238,7 @@ def test_refusals():
         assert e.value.code == ERR_INVALID and "ring of at least 512 frames" in str(e.value), str(e.value)
     with wf.SpectrumBatch(_cfg(1024), 2) as b:
         assert L.wf_hip_output_bytes(b.h, binding.OUT_XFER) == ENTRY  # before the first read
-        assert L.wf_hip_read(b.h, binding.OUT_XFER, 0, 1, None) == ERR_INVALID
-        out = np.empty(3, binding.XFER_DTYPE)
-        ptr = out.ctypes.data_as(C.c_void_p)
-        assert L.wf_hip_read(b.h, binding.OUT_XFER, 0, 3, ptr) == ERR_INVALID  # past the batch
-        assert L.wf_hip_read(b.h, binding.OUT_XFER, 2, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_XFER, 0, 0, ptr) == ERR_INVALID  # count 0
-        assert L.wf_hip_read(None, binding.OUT_XFER, 0, 1, ptr) == ERR_INVALID
-        assert L.wf_hip_read(b.h, binding.OUT_XFER, 0, 2, ptr) == 0
-        assert out[:2].tobytes() == ref.zero_record(1024, b.ring_frames, 2).tobytes()  # the next good read is correct
+        check_abi_refusals(b, binding.OUT_XFER, binding.XFER_DTYPE, 2, ref.zero_record(1024, b.ring_frames, 2))
 
 
 def test_nothing_else_moves_on_a_twin(monkeypatch):
@@ -332,10 +286,7 @@ def test_three_shards_match_one_handle():
             one.tick()
             m.tick()
         m.sync()
-        want = one.xfer()
-        assert m.xfer().tobytes() == want.tobytes()
-        assert m.xfer(2, 4).tobytes() == want[2:6].tobytes()  # a range that spans the shards
-        assert m.xfer().shape == (streams,)
+        want = check_shards_match(one, m, "xfer", (2, 4))
     assert np.all(want["window"] == 512) and want["valid"].tolist() == [1, 1, 1, 0, 1, 1, 1]
     assert want["lag"].tolist() == [37, -127, 0, 0, 0, 0, 0]
     _check(want, x, fft, 4096, sr, fft + hops * hop, "one handle of the seven streams")
@@ -372,7 +323,4 @@ def test_across_the_2_to_the_32_wrap():
     """tests/xfer_wrap_child.py: twin handles on the development build, one aged to just below 2^32, walked across the wrap in
     small hops with xfer() equal on both and within the bound of the restatement at every hop.  One child process (the release
     library has no test aids)"""
-    env = dict(os.environ, WF_HIP_LIB=str(ROOT / "waveform_amd" / "libwaveform_hip_dev.so"))
-    r = subprocess.run(["timeout", "-k", "10", "60", sys.executable, str(ROOT / "tests" / "xfer_wrap_child.py")], capture_output=True, text=True,
-                       env=env)
-    assert r.returncode == 0 and "wrapped ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+    run_wrap_child("xfer_wrap_child.py", 60)

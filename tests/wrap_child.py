@@ -11,6 +11,7 @@ yet".  Each kind asserts by arithmetic on its own schedule that those positions 
 
 usage: python tests/wrap_child.py spectrum_normalize|meter|spectrum_delay_<fft>|push_paths|reset_after_wrap|meter_delay|rms_feed|
                                   waveform|measure"""
+import contextlib
 import os
 import sys
 
@@ -152,6 +153,63 @@ def _age(L, old, R):
     assert R % old.ring_frames == 0, (R, old.ring_frames)
     rc = L.wf_hip_debug_age(old.h, 0, old.streams, (1 << 32) - R)
     assert rc == 0, L.wf_hip_last_error(old.h)
+
+
+@contextlib.contextmanager
+def twins(cfg, streams, ring, fft, R=None, win=None):
+    """The twins of the children of the measurement outputs (tests/<out>_wrap_child.py): spectrum batches `fresh` and `old` of this
+    ring and fft size, old's write positions aged by 2^32 - 2 rings.  A spectrum batch's wpos starts at fft (the zeros of create), so
+    the aged wpos is 0 after wrap = 2 rings - fft pushed frames.  With R and win, the fine Schedule of them, checked, else None."""
+    L = _dev()
+    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
+        assert old.ring_frames == ring and old.fft_size == fft
+        sch = None
+        if R is not None:
+            sch = Schedule(R, win, 0, big=ring // 2, fine=True)
+            sch.check([0])
+        assert L.wf_hip_debug_age(old.h, 0, streams, (1 << 32) - 2 * ring) == 0, L.wf_hip_last_error(old.h)
+        yield fresh, old, sch
+
+
+def slices(audio):
+    """the audio of a push, for a child that draws one long run and cuts it"""
+    return lambda i, T, p: np.ascontiguousarray(audio[:, :, T:T + p])
+
+
+class Walk:
+    """The twins' walk across the wrap.  Iterating it pushes audio(i, T, p) -- the child's audio of push i, p frames behind the T
+    pushed so far -- to both twins and yields (i, T, what) behind every push that is read, T counting that push: every one from
+    sum(HOPS) frames before the wrap on, or, where `pushes` holds (frames, read), those it marks.  `hist`, where given (the zeros
+    of create), is kept as the newest frames of that length.  It counts the reads with the aged wpos = T - wrap at or before
+    2^32 (`before`; `at`: those of them at it exactly), with the span read across it (`straddling`), starting at position 0
+    exactly (`exact`) and behind it (`behind`); which of them a child needs, and how many, it asserts itself."""
+
+    def __init__(self, both, pushes, wrap, span, audio, hist=None):
+        self.both, self.pushes, self.wrap, self.span, self.audio, self.hist = both, pushes, wrap, span, audio, hist
+        self.T = self.before = self.at = self.straddling = self.exact = self.behind = 0
+
+    @property
+    def counts(self):
+        return self.before, self.straddling, self.exact, self.behind
+
+    def __iter__(self):
+        for i, p in enumerate(self.pushes):
+            p, read = p if isinstance(p, tuple) else (p, None)
+            a = self.audio(i, self.T, p)
+            self.T = T = self.T + p
+            for b in self.both:
+                b.push_audio(a)
+            if self.hist is not None:
+                self.hist = np.concatenate([self.hist, a], axis=2)[:, :, -self.hist.shape[2]:]
+            if (T < self.wrap - sum(HOPS)) if read is None else not read:
+                continue
+            d = T - self.wrap
+            self.before += int(d <= 0)
+            self.at += int(d == 0)
+            self.straddling += int(0 < d < self.span)
+            self.exact += int(d == self.span)
+            self.behind += int(d > self.span)
+            yield i, T, f"read {i} at wpos = 2^32{d:+d}"
 
 
 def _bits(a):

@@ -16,39 +16,27 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import waveform_amd as wf  # noqa: E402
 import xfer_ref as ref  # noqa: E402
-from wrap_child import HOPS, Schedule, _dev  # noqa: E402
+from wrap_child import Walk, slices, twins  # noqa: E402
 
 KINDS = ("fir +37", "delay -(L-1)", "added noise")  # (kinds whose every span reads far from a tie, wherever it is cut)
 
 
 def run():
-    L = _dev()
     fft, ring, streams, sr = 2048, 8192, len(KINDS), 48000
     p, k = ref.geometry(fft, ring)
     h = p // 2
     span = ref.span_frames(p, k) + h - 1  # the most frames a read looks back over
     cfg = wf.Config.defaults(fft_size=fft, sample_rate=sr, stereo=1, slope=1.0, bars=1)
-    with wf.SpectrumBatch(cfg, streams, ring_frames=ring) as fresh, wf.SpectrumBatch(cfg, streams, ring_frames=ring) as old:
-        assert old.ring_frames == ring and old.fft_size == fft and (p, k) == (1024, 13) and span == ring - 1
-        # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
-        R = 2 * ring - fft + ring
-        sch = Schedule(R, ring, 0, big=ring // 2, fine=True)
-        sch.check([0])
-        wrap = R - ring
-        age = (1 << 32) - 2 * ring
-        assert L.wf_hip_debug_age(old.h, 0, streams, age) == 0, L.wf_hip_last_error(old.h)
+    # a spectrum batch's wpos starts at fft (the zeros of create): aged by 2^32 - 2 rings it is 0 at T = 2 rings - fft
+    wrap, age = 2 * ring - fft, (1 << 32) - 2 * ring
+    with twins(cfg, streams, ring, fft, R=wrap + ring, win=ring) as (fresh, old, sch):
+        assert (p, k) == (1024, 13) and span == ring - 1
         rng = np.random.default_rng(ref.GPU_SEED)
         total = int(sum(sch.pushes))
         audio = np.stack([ref.stream(name, rng, total, p) for name in KINDS])
-        T, before, straddling, behind, worst = 0, 0, 0, 0, 0.0
-        for i, n in enumerate(sch.pushes):
-            a = np.ascontiguousarray(audio[:, :, T:T + n])
-            T += n
-            for b in (fresh, old):
-                b.push_audio(a)
-            if T < wrap - sum(HOPS):
-                continue
-            what = f"read {i} at wpos = 2^32{T - wrap:+d}"
+        worst = 0.0
+        walk = Walk((fresh, old), sch.pushes, wrap, span, slices(audio))
+        for i, T, what in walk:
             x, y = fresh.xfer(), old.xfer()
             for name in ref.FIELDS:
                 if name != "newest":
@@ -61,9 +49,7 @@ def run():
             bad = ref.mismatches(x, want)
             assert not bad, (what, bad[:4])
             worst = max(worst, max(ref.worst(x, want).values()))
-            before += int(T <= wrap)
-            straddling += int(0 < T - wrap < span)
-            behind += int(T - wrap >= span)
+        before, straddling, behind = walk.before, walk.straddling, walk.exact + walk.behind  # (the exact hit counts as behind here)
         assert before >= 2 and straddling >= 3 and behind >= 3, (before, straddling, behind)
         assert np.all(y["valid"] == 1) and y["lag"].tolist() == [37, -(p // 4 - 1), 0]
         print(f"{before} reads before the wrap, {straddling} with the span across it, {behind} behind it; largest difference of a field "

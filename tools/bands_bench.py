@@ -6,49 +6,18 @@ the rows to the host that the output replaces.  Every figure is the median of `r
 calls, with the smallest and largest round beside it.  One JSON line.  The kernels' own times come from a
 rocprofv3 --kernel-trace --stats run of this tool (a run of its own).
 usage: python tools/bands_bench.py [--streams 4096] [--fft 4096] [--warmup 10] [--reads 50] [--rounds 5] [--out FILE.json]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import waveform_amd as wf
 
-
-def _rounds(b, fn, warmup, reads, rounds):
-    """per call, in us, [median, min, max] over the rounds: by the host clock, and by device events around the calls -- which
-    bracket whatever the call enqueues, a read's copy to the host included: not a kernel's time"""
-    L = wf.lib()
-    for _ in range(warmup):
-        fn()
-    host, dev = [], []
-    ms = C.c_float(0.0)
-    for _ in range(rounds):
-        b.sync()
-        assert L.wf_hip_time_begin(b.h) == 0
-        t0 = time.perf_counter()
-        for _ in range(reads):
-            fn()
-        t1 = time.perf_counter()
-        assert L.wf_hip_time_end(b.h, C.byref(ms)) == 0
-        host.append((t1 - t0) / reads * 1e6)
-        dev.append(float(ms.value) / reads * 1e3)
-    s = lambda v: [round(float(np.median(v)), 2), round(min(v), 2), round(max(v), 2)]  # noqa: E731
-    return dict(host_us=s(host), device_us_incl_copy=s(dev))
+from bench_common import emit, parser, rounds
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--fft", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reads", type=int, default=50)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(10, 50, streams=4096, fft=4096).parse_args()
     cfg = wf.Config.defaults(fft_size=a.fft, sample_rate=48000, stereo=1, slope=1.0, bars=1, floor_db=-70)
     seed = 0x5741564546524D31
     with wf.SpectrumBatch(cfg, a.streams, ring_frames=a.fft + 800) as b:
@@ -68,20 +37,17 @@ def main():
             return fn
         res = dict(streams=a.streams, fft=a.fft, rows=rows, row_MB=round(rows * (a.fft // 2) * 4 / 1e6, 1),
                    bands_MB=round(rows * 144 / 1e6, 2), peaks_MB=round(rows * 72 / 1e6, 2), reads=a.reads, warmup=a.warmup, rounds=a.rounds,
-                   bands_read=_rounds(b, b.bands, a.warmup, a.reads, a.rounds),
-                   peaks_read=_rounds(b, b.peaks, a.warmup, a.reads, a.rounds),
-                   push_tick=_rounds(b, hop(None), a.warmup, a.reads, a.rounds),
-                   push_tick_bands_read=_rounds(b, hop(b.bands), a.warmup, a.reads, a.rounds),
-                   push_tick_peaks_read=_rounds(b, hop(b.peaks), a.warmup, a.reads, a.rounds),
-                   decibels_read=_rounds(b, b.decibels, 2, max(a.reads // 5, 5), a.rounds))
+                   bands_read=rounds(b, b.bands, a.warmup, a.reads, a.rounds),
+                   peaks_read=rounds(b, b.peaks, a.warmup, a.reads, a.rounds),
+                   push_tick=rounds(b, hop(None), a.warmup, a.reads, a.rounds),
+                   push_tick_bands_read=rounds(b, hop(b.bands), a.warmup, a.reads, a.rounds),
+                   push_tick_peaks_read=rounds(b, hop(b.peaks), a.warmup, a.reads, a.rounds),
+                   decibels_read=rounds(b, b.decibels, 2, max(a.reads // 5, 5), a.rounds))
         got = b.bands()
         res["mean_total_db"] = float(np.mean(got["total_db"]))
         res["mean_a_minus_total_db"] = float(np.mean(got["a_db"] - got["total_db"]))
     res["speedup_over_row_copy"] = round(res["decibels_read"]["host_us"][0] / res["bands_read"]["host_us"][0], 1)
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

@@ -12,9 +12,7 @@ counting the host would then run is not counted.  Every figure is the median of 
 calls, with the smallest and largest round beside it.  One JSON line.  The kernel's own time without its copy is not measured
 here.
 usage: python tools/bits_bench.py [--streams 4096] [--ffts 4096,16384] [--warmup 3] [--reads 10] [--rounds 5] [--out FILE.json]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -23,8 +21,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy
 
 KINDS = ("noise", "sine100", "silence")
 CHUNK = 256  # streams per host push of the sine
@@ -68,26 +65,15 @@ def one_fft(a, fft):
             read_pinned()
             assert out.array.tobytes() == got.tobytes()
             ch = got["ch"]
-            res["kinds"][kind] = dict(bits_read_pinned=_rounds(b, read_pinned, a.warmup, a.reads, a.rounds),
-                                      bits_read=_rounds(b, b.bits, a.warmup, a.reads, a.rounds),
+            res["kinds"][kind] = dict(bits_read_pinned=rounds(b, read_pinned, a.warmup, a.reads, a.rounds),
+                                      bits_read=rounds(b, b.bits, a.warmup, a.reads, a.rounds),
                                       mean_bins=round(float(np.mean(np.count_nonzero(ch["hist"], axis=2))), 1),
                                       mean_longest_run=round(float(np.mean(ch["max_run"])), 1),
                                       word_lengths=sorted(set(ch["word_length"].reshape(-1).tolist())))
             assert np.all(ch["hist"].astype(np.int64).sum(axis=2) == window) and np.all(ch["mag"].astype(np.int64).sum(axis=2) == window)
         out.close()
-        res["signal_read"] = _rounds(b, b.signal, a.warmup, a.reads, a.rounds)
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, window))
-        try:
-            res["windows_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+        res["signal_read"] = rounds(b, b.signal, a.warmup, a.reads, a.rounds)
+        res["windows_copy_pinned"] = windows_copy((a.streams, 2, window), max(a.reads // 2, 3), a.rounds)
     copy = res["windows_copy_pinned"]["host_us"][0]
     for kind in KINDS:
         res["kinds"][kind]["copy_over_read_pinned"] = round(copy / res["kinds"][kind]["bits_read_pinned"]["host_us"][0], 2)
@@ -97,19 +83,9 @@ def one_fft(a, fft):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--ffts", default="4096,16384")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reads", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(3, 10, streams=4096, ffts="4096,16384").parse_args()
     res = dict(streams=a.streams, reads=a.reads, warmup=a.warmup, rounds=a.rounds, ffts=[one_fft(a, int(f)) for f in a.ffts.split(",")])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

@@ -9,9 +9,6 @@ counted from the shapes: sample pairs = streams x sum of L_b over the covered bi
 channel pair (two complex rotations, the window, the product and four multiply-adds).  One JSON line.  The kernel's own time
 comes from a rocprofv3 --kernel-trace --stats run of this tool (a run of its own).
 usage: python tools/cq_bench.py [--streams 4096] [--fft 4096] [--warmup 3] [--reads 10] [--rounds 5] [--rings 0,16384] [--out FILE.json]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
 
@@ -20,8 +17,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy
 
 OPS_PER_PAIR = 15
 Q = 1.0 / (2.0 ** (1.0 / 12.0) - 1.0)
@@ -37,7 +33,6 @@ def pairs_per_stream(sr, lmax):
 def one_ring(a, ring):
     cfg = wf.Config.defaults(fft_size=a.fft, sample_rate=48000, stereo=1, slope=1.0, bars=1, floor_db=-70)
     seed = 0x5741564546524D31
-    L = wf.lib()
     with wf.SpectrumBatch(cfg, a.streams, ring_frames=ring) as b:
         b.push_synth(seed, 0, b.ring_frames)
         b.push_synth(seed, b.ring_frames, 801)
@@ -49,20 +44,9 @@ def one_ring(a, ring):
         res = dict(ring_frames=b.ring_frames, max_window=lmax, windows_MB=round(nbytes / 1e6, 1),
                    cq_MB=round(a.streams * wf.binding.CQ_DTYPE.itemsize / 1e6, 2), sample_pairs_per_stream=pairs,
                    float64_Gops=round(a.streams * pairs * OPS_PER_PAIR / 1e9, 2),
-                   cq_read=_rounds(b, b.cq, a.warmup, a.reads, a.rounds),
-                   signal_read=_rounds(b, b.signal, a.warmup, a.reads, a.rounds))
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, lmax))
-        try:
-            res["windows_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+                   cq_read=rounds(b, b.cq, a.warmup, a.reads, a.rounds),
+                   signal_read=rounds(b, b.signal, a.warmup, a.reads, a.rounds))
+        res["windows_copy_pinned"] = windows_copy((a.streams, 2, lmax), max(a.reads // 2, 3), a.rounds)
         got = b.cq()
         res["mean_db"] = float(np.mean(got["db"][np.isfinite(got["db"])]))
         res["first_resolved"] = int(got["first_resolved"][0])
@@ -72,21 +56,10 @@ def one_ring(a, ring):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--fft", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reads", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--rings", default="0,16384")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(3, 10, streams=4096, fft=4096, rings="0,16384").parse_args()
     res = dict(streams=a.streams, fft=a.fft, reads=a.reads, warmup=a.warmup, rounds=a.rounds, ops_per_pair=OPS_PER_PAIR,
                rings=[one_ring(a, int(r)) for r in a.rings.split(",")])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

@@ -11,9 +11,7 @@ times add up.  The transform and the rule the host would then run are not counte
 of `reads` calls after `warmup` calls, with the smallest and largest round beside it.  One JSON line.  The kernel's own time
 without the copy is not measured here.
 usage: python tools/hum_bench.py [--streams 4096] [--rings 16384,32768] [--warmup 2] [--reads 5] [--rounds 5] [--out FILE.json]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -24,10 +22,8 @@ import numpy as np
 import waveform_amd as wf
 
 import hum_ref as ref
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy_in_parts
 
-PART_BYTES = 512 << 20
 SR = 48000
 DISTINCT = 64
 
@@ -68,27 +64,11 @@ def one_shape(a, streams, ring_frames):
             want = {"hum": (1, 50), "noise": (1, 0), "silence": (0, 0)}[kind]
             assert np.all(got["ch"]["valid"] == want[0]) and np.mean(got["ch"]["family"] == want[1]) > 0.95, kind
             r = dict(lines=int(got["ch"]["lines"].sum()), family_found=round(float(np.mean(got["ch"]["family"] != 0)), 4))
-            r["read_pinned"] = _rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
-            r["read"] = _rounds(b, b.hum, a.warmup, a.reads, a.rounds)
+            r["read_pinned"] = rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
+            r["read"] = rounds(b, b.hum, a.warmup, a.reads, a.rounds)
             out.close()
             res[kind] = r
-    malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-    malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    free.argtypes = [C.c_void_p]
-    memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    part = max(1, min(streams, PART_BYTES // per_stream))
-    parts = -(-streams // part)
-    d = C.c_void_p()
-    assert malloc(C.byref(d), part * per_stream) == 0
-    pinned = wf.PinnedBuffer((part, 2, pl.N))
-    try:
-        one = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, part * per_stream, 2), 2, max(a.reads // 2, 3), a.rounds)
-    finally:
-        pinned.close()
-        assert free(d) == 0
-    scale = streams / part  # (every part but the last is full: the bytes are what counts)
-    res["windows_copy_parts"] = parts
-    res["windows_copy_pinned"] = {k: [round(v * scale, 1) for v in vals] if isinstance(vals, list) else vals for k, vals in one.items()}
+    res["windows_copy_parts"], res["windows_copy_pinned"] = windows_copy_in_parts(streams, pl.N, max(a.reads // 2, 3), a.rounds)
     copy = res["windows_copy_pinned"]["host_us"][0]
     for kind in ("hum", "noise", "silence"):
         res[kind]["copy_over_read_pinned"] = round(copy / res[kind]["read_pinned"]["host_us"][0], 2)
@@ -96,20 +76,10 @@ def one_shape(a, streams, ring_frames):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--rings", default="16384,32768")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reads", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(2, 5, streams=4096, rings="16384,32768").parse_args()
     res = dict(sample_rate=SR, reads=a.reads, warmup=a.warmup, rounds=a.rounds,
                shapes=[one_shape(a, a.streams, int(r)) for r in a.rings.split(",")])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import waveform_amd as wf
 from tools import synth
+from tools.bench_common import device_block
 
 FORMATS = [("f32_planar", np.float32, False), ("s16_interleaved", np.int16, True), ("u8_interleaved", np.uint8, True),
            ("s32_interleaved", np.int32, True)]
@@ -76,16 +77,10 @@ def append_alone(b, a, packets):
     """device microseconds of one push from device memory (the append kernel, the write-position update and whatever follows a
     push; no copy, no tick), per format: the median over a.rounds brackets of a.append_pushes pushes each"""
     L = wf.lib()
-    malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-    malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    free.argtypes = [C.c_void_p]
-    memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     out = {}
     for name, (fmt, p) in packets.items():
         host = np.ascontiguousarray(p)
-        d = C.c_void_p()
-        assert malloc(C.byref(d), host.nbytes) == 0
-        try:
+        with device_block(host.nbytes) as (d, memcpy):
             assert memcpy(d, C.c_void_p(host.ctypes.data), host.nbytes, 1) == 0
             pcm = wf.binding.Pcm(data=d.value, format=fmt, channels=2, channel_base=0, frames=a.hop, memory=wf.binding.PCM_DEVICE, slot=0)
             us = []
@@ -96,8 +91,6 @@ def append_alone(b, a, packets):
                 us.append(b.time_end() * 1e3 / a.append_pushes)
             out[name] = dict(us_per_push=round(float(np.median(us[1:])), 2), rounds_us=[round(u, 2) for u in us[1:]], bytes=host.nbytes,
                              read_GBps=round(host.nbytes / (float(np.median(us[1:])) * 1e-6) / 1e9, 1))
-        finally:
-            assert free(d) == 0
     return out
 
 

@@ -11,25 +11,16 @@ host time is then of the whole hop.
 usage: python tools/pitch_bench.py [--mode repeat|hop] [--streams 4096] [--fft 4096] [--warmup 3] [--reads 20] [--no-yardstick] [--out FILE.json]"""
 import argparse
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-
-def _time(fn, warmup, reads):
-    for _ in range(warmup):
-        fn()
-    t0 = time.perf_counter()
-    for _ in range(reads):
-        fn()
-    return (time.perf_counter() - t0) / reads
+from bench_common import emit, timed
 
 
 def yardstick():
@@ -71,8 +62,8 @@ def main():
             hop[0] += 800
             b.tick()
             b.pitch()
-        t_pitch = _time(b.pitch if a.mode == "repeat" else one_hop, a.warmup, a.reads)
-        t_signal = _time(b.signal, 3, 20)
+        t_pitch = timed(b.pitch if a.mode == "repeat" else one_hop, a.warmup, a.reads)
+        t_signal = timed(b.signal, 3, 20)
         got = b.pitch()
         ring_frames = b.ring_frames
     P = min(a.fft, wf.binding.PITCH_MAX_WINDOW)
@@ -95,10 +86,7 @@ def main():
         n = blocks * 256 * Y.yard_fma_per_thread(iters)
         res["yardstick"] = dict(fma_G=round(n / 1e9, 2), fma_ms=round(ms, 4), TFMA_per_s=round(n / ms / 1e9, 3) if ms > 0 else None,
                                 d2h_pageable_ms=round(Y.yard_d2h_ms(window_bytes, 0, 3), 3), d2h_pinned_ms=round(Y.yard_d2h_ms(window_bytes, 1, 3), 3))
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

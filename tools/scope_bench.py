@@ -9,9 +9,6 @@ The trigger search and the column minima the host would then run are not counted
 kernel reads the windows once and writes the entries.  One JSON line.  The kernel's own time comes from a
 rocprofv3 --kernel-trace --stats run of this tool (a run of its own).
 usage: python tools/scope_bench.py [--streams 4096] [--ffts 4096,16384] [--warmup 3] [--reads 10] [--rounds 5] [--out FILE.json]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
 
@@ -20,14 +17,12 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy
 
 
 def one_fft(a, fft):
     cfg = wf.Config.defaults(fft_size=fft, sample_rate=48000, stereo=1, slope=1.0, bars=1, floor_db=-70)
     seed = 0x5741564546524D31
-    L = wf.lib()
     with wf.SpectrumBatch(cfg, a.streams) as b:
         b.push_synth(seed, 0, b.ring_frames)
         b.push_synth(seed, b.ring_frames, 801)
@@ -38,20 +33,9 @@ def one_fft(a, fft):
         entry = wf.binding.SCOPE_DTYPE.itemsize
         res = dict(fft=fft, ring_frames=b.ring_frames, window=window, windows_MB=round(nbytes / 1e6, 1),
                    scope_MB=round(a.streams * entry / 1e6, 2),
-                   scope_read=_rounds(b, b.scope, a.warmup, a.reads, a.rounds),
-                   signal_read=_rounds(b, b.signal, a.warmup, a.reads, a.rounds))
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, window))
-        try:
-            res["windows_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+                   scope_read=rounds(b, b.scope, a.warmup, a.reads, a.rounds),
+                   signal_read=rounds(b, b.signal, a.warmup, a.reads, a.rounds))
+        res["windows_copy_pinned"] = windows_copy((a.streams, 2, window), max(a.reads // 2, 3), a.rounds)
         got = b.scope()
         res["triggered_share"] = float(np.mean(got["triggered"]))
         res["mean_swing"] = float(np.mean(got["hi"][:, 0, :int(got["columns"][0])] - got["lo"][:, 0, :int(got["columns"][0])]))
@@ -61,19 +45,9 @@ def one_fft(a, fft):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--ffts", default="4096,16384")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reads", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(3, 10, streams=4096, ffts="4096,16384").parse_args()
     res = dict(streams=a.streams, reads=a.reads, warmup=a.warmup, rounds=a.rounds, ffts=[one_fft(a, int(f)) for f in a.ffts.split(",")])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

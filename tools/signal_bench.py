@@ -7,23 +7,14 @@ read kernel's own time comes from a rocprofv3 --kernel-trace run of this tool.
 so the window has just been written; the host time is then of the whole hop.
 usage: python tools/signal_bench.py [--mode repeat|hop] [--streams 4096] [--fft 4096] [--warmup 20] [--reads 200] [--out FILE.json]"""
 import argparse
-import json
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import waveform_amd as wf
 
-
-def _time(fn, warmup, reads):
-    for _ in range(warmup):
-        fn()
-    t0 = time.perf_counter()
-    for _ in range(reads):
-        fn()
-    return (time.perf_counter() - t0) / reads
+from bench_common import emit, timed
 
 
 def main():
@@ -47,8 +38,8 @@ def main():
             hop[0] += 800
             b.tick()
             b.signal()
-        t_signal = _time(b.signal if a.mode == "repeat" else one_hop, a.warmup, a.reads)
-        t_rows = _time(b.decibels, max(a.warmup // 4, 2), max(a.reads // 4, 10))
+        t_signal = timed(b.signal if a.mode == "repeat" else one_hop, a.warmup, a.reads)
+        t_rows = timed(b.decibels, max(a.warmup // 4, 2), max(a.reads // 4, 10))
         sig = b.signal()
         ring_frames = b.ring_frames
     window_bytes = a.streams * 2 * a.fft * 4
@@ -57,10 +48,7 @@ def main():
                **{"ms_per_signal_read" if a.mode == "repeat" else "ms_per_hop_push_tick_signal": round(t_signal * 1e3, 4)}, ms_per_decibels_read=round(t_rows * 1e3, 4),
                mean_rms_db=float(np.mean(sig["ch"]["rms_db"])), mean_abs_correlation=float(np.mean(np.abs(sig["correlation"]))),
                reads=a.reads, warmup=a.warmup)
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

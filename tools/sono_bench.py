@@ -9,9 +9,7 @@ per channel, copied to the host -- a device block of that size (the library has 
 page-locked memory.  The transforms the host would then run are not counted.  Every figure is the median of `rounds` rounds of
 `reads` calls after `warmup` calls, with the smallest and largest round beside it.  One JSON line.
 usage: python tools/sono_bench.py [--streams 4096] [--rings 0,32768] [--warmup 3] [--reads 10] [--rounds 5] [--out FILE.json]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -20,8 +18,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy
 
 
 def one_ring(a, ring_frames):
@@ -49,22 +46,11 @@ def one_ring(a, ring_frames):
         assert out.array.tobytes() == got.tobytes()
         assert np.all(np.isfinite(got["db"][:, :, :t])) and np.all(np.isneginf(got["db"][:, :, t:]))
         res["mean_db"] = round(float(np.mean(got["db"][:, :, :t])), 2)
-        res["sono_read_pinned"] = _rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
-        res["sono_read"] = _rounds(b, b.sono, a.warmup, a.reads, a.rounds)
-        res["signal_read"] = _rounds(b, b.signal, a.warmup, a.reads, a.rounds)
+        res["sono_read_pinned"] = rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
+        res["sono_read"] = rounds(b, b.sono, a.warmup, a.reads, a.rounds)
+        res["signal_read"] = rounds(b, b.signal, a.warmup, a.reads, a.rounds)
         out.close()
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, span))
-        try:
-            res["span_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+        res["span_copy_pinned"] = windows_copy((a.streams, 2, span), max(a.reads // 2, 3), a.rounds)
     copy = res["span_copy_pinned"]["host_us"][0]
     res["copy_over_read_pinned"] = round(copy / res["sono_read_pinned"]["host_us"][0], 2)
     res["copy_over_read"] = round(copy / res["sono_read"]["host_us"][0], 2)
@@ -72,20 +58,10 @@ def one_ring(a, ring_frames):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--rings", default="0,32768")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reads", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(3, 10, streams=4096, rings="0,32768").parse_args()
     res = dict(streams=a.streams, fft=4096, reads=a.reads, warmup=a.warmup, rounds=a.rounds,
                rings=[one_ring(a, int(r)) for r in a.rings.split(",")])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

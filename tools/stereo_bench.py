@@ -7,44 +7,20 @@ The transform the host would then run is not counted.  Every figure is the media
 `warmup` calls, with the smallest and largest round beside it.  One JSON line.  The kernel's own time comes from a
 rocprofv3 --kernel-trace --stats run of this tool (a run of its own).
 usage: python tools/stereo_bench.py [--streams 4096] [--fft 4096] [--warmup 5] [--reads 20] [--rounds 5] [--out FILE.json]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-
-
-def _host_rounds(fn, warmup, reads, rounds):
-    for _ in range(warmup):
-        fn()
-    us = []
-    for _ in range(rounds):
-        t0 = time.perf_counter()
-        for _ in range(reads):
-            fn()
-        us.append((time.perf_counter() - t0) / reads * 1e6)
-    return dict(host_us=[round(float(np.median(us)), 2), round(min(us), 2), round(max(us), 2)])
+from bench_common import emit, parser, rounds, windows_copy
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--fft", type=int, default=4096)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reads", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(5, 20, streams=4096, fft=4096).parse_args()
     cfg = wf.Config.defaults(fft_size=a.fft, sample_rate=48000, stereo=1, slope=1.0, bars=1, floor_db=-70)
     seed = 0x5741564546524D31
-    L = wf.lib()
     with wf.SpectrumBatch(cfg, a.streams) as b:
         b.push_synth(seed, 0, a.fft + 801)
         b.tick()
@@ -53,33 +29,15 @@ def main():
         nbytes = a.streams * 2 * p * 4
         res = dict(streams=a.streams, fft=a.fft, window=p, windows_MB=round(nbytes / 1e6, 1), stereo_MB=round(a.streams * 504 / 1e6, 2),
                    reads=a.reads, warmup=a.warmup, rounds=a.rounds,
-                   stereo_read=_rounds(b, b.stereo, a.warmup, a.reads, a.rounds),
-                   signal_read=_rounds(b, b.signal, a.warmup, a.reads, a.rounds),
-                   pitch_read=_rounds(b, b.pitch, 2, max(a.reads // 4, 3), a.rounds))
-        # the windows to the host
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, p))
-        pageable = np.empty((a.streams, 2, p), np.float32)
-        try:
-            res["windows_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 4, 3), a.rounds)
-            res["windows_copy_pageable"] = _host_rounds(lambda: memcpy(pageable.ctypes.data_as(C.c_void_p), d, nbytes, 2), 2,
-                                                        max(a.reads // 4, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+                   stereo_read=rounds(b, b.stereo, a.warmup, a.reads, a.rounds),
+                   signal_read=rounds(b, b.signal, a.warmup, a.reads, a.rounds),
+                   pitch_read=rounds(b, b.pitch, 2, max(a.reads // 4, 3), a.rounds))
+        res["windows_copy_pinned"], res["windows_copy_pageable"] = windows_copy((a.streams, 2, p), max(a.reads // 4, 3), a.rounds, pageable=True)
         got = b.stereo()
         res["mean_coherence"] = float(np.mean(got["coherence"]))
         res["mean_correlation"] = float(np.mean(got["correlation"]))
     res["speedup_over_pinned_copy"] = round(res["windows_copy_pinned"]["host_us"][0] / res["stereo_read"]["host_us"][0], 1)
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

@@ -12,9 +12,7 @@ read is timed and scaled).  The transforms and the stitching the host would then
 of `rounds` rounds of `reads` calls after `warmup` calls, with the smallest and largest round beside it.  One JSON line.  The
 kernels' own times without the copy are not measured here.
 usage: python tools/tempo_bench.py [--shapes 4096:131072,64:524288] [--warmup 2] [--reads 5] [--rounds 5] [--out FILE.json]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -23,10 +21,8 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy_in_parts
 
-PART_BYTES = 512 << 20
 
 
 def one_shape(a, streams, ring_frames):
@@ -56,27 +52,11 @@ def one_shape(a, streams, ring_frames):
         assert np.all(got["strength"][:, :t] > 0) and not np.any(got["strength"][:, t:]) and np.all(got["columns"] == t)
         res["valid"] = int(got["valid"].sum())
         res["mean_strength"] = round(float(np.mean(got["strength"][:, :t])), 3)
-        res["tempo_read_pinned"] = _rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
-        res["tempo_read"] = _rounds(b, b.tempo, a.warmup, a.reads, a.rounds)
+        res["tempo_read_pinned"] = rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
+        res["tempo_read"] = rounds(b, b.tempo, a.warmup, a.reads, a.rounds)
         out.close()
-        res["onset_read"] = _rounds(b, b.onset, a.warmup, a.reads, a.rounds)
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        part = max(1, min(streams, PART_BYTES // per_stream))
-        parts = -(-streams // part)
-        d = C.c_void_p()
-        assert malloc(C.byref(d), part * per_stream) == 0
-        pinned = wf.PinnedBuffer((part, 2, span))
-        try:
-            one = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, part * per_stream, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
-        scale = streams / part  # (every part but the last is full: the bytes are what counts)
-        res["span_copy_parts"] = parts
-        res["span_copy_pinned"] = {k: [round(v * scale, 1) for v in vals] if isinstance(vals, list) else vals for k, vals in one.items()}
+        res["onset_read"] = rounds(b, b.onset, a.warmup, a.reads, a.rounds)
+        res["span_copy_parts"], res["span_copy_pinned"] = windows_copy_in_parts(streams, span, max(a.reads // 2, 3), a.rounds)
     copy = res["span_copy_pinned"]["host_us"][0]
     polls = res["onset_read"]["host_us"][0] * t / B.ONSET_COLUMNS
     res["onset_polling_us"] = round(polls, 1)
@@ -86,19 +66,10 @@ def one_shape(a, streams, ring_frames):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="4096:131072,64:524288")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reads", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(2, 5, shapes="4096:131072,64:524288").parse_args()
     shapes = [tuple(int(v) for v in s.split(":")) for s in a.shapes.split(",")]
     res = dict(fft=1024, sample_rate=48000, reads=a.reads, warmup=a.warmup, rounds=a.rounds, shapes=[one_shape(a, s, r) for s, r in shapes])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

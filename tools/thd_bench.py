@@ -10,9 +10,7 @@ for the rings) by hipMemcpy into page-locked memory.  The transforms the host wo
 median of `rounds` rounds of `reads` calls after `warmup` calls, with the smallest and largest round beside it.  One JSON line.
 The kernel's own time without its copy is not measured here.
 usage: python tools/thd_bench.py [--streams 4096] [--ffts 4096,16384] [--warmup 3] [--reads 10] [--rounds 5] [--out FILE.json]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -21,8 +19,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy
 
 
 def one_fft(a, fft):
@@ -45,23 +42,12 @@ def one_fft(a, fft):
         got = b.thd()
         read_pinned()
         assert out.array.tobytes() == got.tobytes() and np.all(got["ch"]["valid"] == 1) and np.all(got["window"] == window)
-        res["thd_read_pinned"] = _rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
-        res["thd_read"] = _rounds(b, b.thd, a.warmup, a.reads, a.rounds)
+        res["thd_read_pinned"] = rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
+        res["thd_read"] = rounds(b, b.thd, a.warmup, a.reads, a.rounds)
         res["mean_thdn_db"] = round(float(np.mean(got["ch"]["thdn_db"])), 2)
         out.close()
-        res["stereo_read"] = _rounds(b, b.stereo, a.warmup, a.reads, a.rounds)
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, window))
-        try:
-            res["windows_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+        res["stereo_read"] = rounds(b, b.stereo, a.warmup, a.reads, a.rounds)
+        res["windows_copy_pinned"] = windows_copy((a.streams, 2, window), max(a.reads // 2, 3), a.rounds)
     copy = res["windows_copy_pinned"]["host_us"][0]
     res["copy_over_read_pinned"] = round(copy / res["thd_read_pinned"]["host_us"][0], 2)
     res["copy_over_read"] = round(copy / res["thd_read"]["host_us"][0], 2)
@@ -70,19 +56,9 @@ def one_fft(a, fft):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--ffts", default="4096,16384")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reads", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(3, 10, streams=4096, ffts="4096,16384").parse_args()
     res = dict(streams=a.streams, reads=a.reads, warmup=a.warmup, rounds=a.rounds, ffts=[one_fft(a, int(f)) for f in a.ffts.split(",")])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":

@@ -11,9 +11,7 @@ rings) by hipMemcpy into page-locked memory.  The transforms the host would then
 `rounds` rounds of `reads` calls after `warmup` calls, with the smallest and largest round beside it.  One JSON line.  The kernel's
 own time without its copy is not measured here.
 usage: python tools/xfer_bench.py [--streams 4096] [--rings 0,65536] [--warmup 2] [--reads 5] [--rounds 5] [--out FILE.json]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -22,8 +20,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import waveform_amd as wf
 
-from bands_bench import _rounds
-from stereo_bench import _host_rounds
+from bench_common import emit, parser, rounds, windows_copy
 
 CHUNK = 2053  # frames per push of the dual-mono leg
 
@@ -62,23 +59,12 @@ def one_leg(a, ring_frames, dual):
         res["transforms_per_stream"] = round(float(np.mean(np.where(got["lag"] == 0, k + 1, 2 * k + 1))), 2)
         res["mean_coherence"] = round(float(np.mean(got["mean_coherence"])), 4)
         assert (res["lag_zero_streams"] == a.streams) == dual
-        res["xfer_read_pinned"] = _rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
-        res["xfer_read"] = _rounds(b, b.xfer, a.warmup, a.reads, a.rounds)
+        res["xfer_read_pinned"] = rounds(b, read_pinned, a.warmup, a.reads, a.rounds)
+        res["xfer_read"] = rounds(b, b.xfer, a.warmup, a.reads, a.rounds)
         out.close()
-        res["delay_read"] = _rounds(b, b.delay, a.warmup, a.reads, a.rounds)
-        res["signal_read"] = _rounds(b, b.signal, a.warmup, a.reads, a.rounds)
-        malloc, free, memcpy = L["hipMalloc"], L["hipFree"], L["hipMemcpy"]
-        malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        free.argtypes = [C.c_void_p]
-        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        d = C.c_void_p()
-        assert malloc(C.byref(d), nbytes) == 0
-        pinned = wf.PinnedBuffer((a.streams, 2, span))
-        try:
-            res["span_copy_pinned"] = _host_rounds(lambda: memcpy(C.c_void_p(pinned.ptr), d, nbytes, 2), 2, max(a.reads // 2, 3), a.rounds)
-        finally:
-            pinned.close()
-            assert free(d) == 0
+        res["delay_read"] = rounds(b, b.delay, a.warmup, a.reads, a.rounds)
+        res["signal_read"] = rounds(b, b.signal, a.warmup, a.reads, a.rounds)
+        res["span_copy_pinned"] = windows_copy((a.streams, 2, span), max(a.reads // 2, 3), a.rounds)
     copy = res["span_copy_pinned"]["host_us"][0]
     res["copy_over_read_pinned"] = round(copy / res["xfer_read_pinned"]["host_us"][0], 2)
     res["copy_over_read"] = round(copy / res["xfer_read"]["host_us"][0], 2)
@@ -86,20 +72,10 @@ def one_leg(a, ring_frames, dual):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=4096)
-    ap.add_argument("--rings", default="0,65536")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reads", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(2, 5, streams=4096, rings="0,65536").parse_args()
     res = dict(streams=a.streams, fft=4096, reads=a.reads, warmup=a.warmup, rounds=a.rounds,
                legs=[one_leg(a, int(r), dual) for r in a.rings.split(",") for dual in (False, True)])
-    print(json.dumps(res), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(a, res)
 
 
 if __name__ == "__main__":
