@@ -1,7 +1,7 @@
 // wf_emu.cpp -- TEST HARNESS: a lane-by-lane wavefront emulator for the tick kernel.
 //
 // Compiles the *same* phase functions the gfx950 kernel is made of
-// (waveform_amd/csrc/wf_tick_phases.hpp) with g++ and runs them thread by thread on
+// (waveform_amd/csrc/wf_tick_phases.hpp, over wf_tick_args.hpp and wf_dev_helpers.hpp) with g++ and runs them thread by thread on
 // the host, phase by phase, so that on the GPU-less build box we can check the FFT
 // index algebra / epilogue against the oracle and count LDS bank conflicts with the
 // bank model of MI355X_MICROARCH.md (LDS section).  Nothing here is part of the

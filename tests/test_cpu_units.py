@@ -191,7 +191,7 @@ def test_bar_segment_tables_are_a_permutation_of_the_flat_tables():
 
 
 def test_slope_factors_formed_on_the_device_stay_next_to_the_reference_table():
-    """Policy<G>::SLOPE_LINEAR (wf_tick_phases.hpp): the geometries from 2048 samples form m_slope_modifiers[k] as
+    """Policy<G>::SLOPE_LINEAR (wf_tick_phases.hpp; the mixed-radix epilogue in wf_mixed.hpp forms them the same way): the geometries from 2048 samples form m_slope_modifiers[k] as
     fma(k, 3 * slope / (M - 1), 1) instead of loading the reference's table log10f(10 * powf(1000, k * slope / (M - 1)))
     (src/source.cpp:1283-1290; bit-identical in wf_host_tables.cpp).  The two differ by the table's own powf / log10f roundings:
     pinned here at 5e-7 relative over the reference's slider range, 1/20 of the parity tolerance."""
@@ -281,7 +281,7 @@ def test_bar_piece_tables_replayed_lane_by_lane():
 
 
 def _replay_bar_ps(tab, M, T, P, db):
-    """what spectrum_tick_kernel does with wf::bar_ps' lane table (ps_park / ps_finish, wf_tick_phases.hpp), lane by lane: the
+    """what spectrum_tick_kernel does with wf::bar_ps' lane table (ps_park / ps_finish, wf_tick_display.hpp), lane by lane: the
     parked row with its guard zeros, the thread-major group sums, the float64 prefix over 16-bin quads, one look-up and one 7-tap
     window per lane (two lanes per sub-band), the swap between the lanes of a pair, the segmented scan over a bar's lanes.
     Returns {bar: sum / count} in float64 arithmetic on the float32 table values (the device's float32 roundings are the GPU
@@ -576,7 +576,7 @@ def test_release_library_carries_no_laboratory():
         for name, val in re.findall(r"#define\s+(WF_EXP_[A-Z0-9_]+)\s+(\S+)", txt):
             assert val == "0", f"{p.name}: {name} defaults to {val}"
         if "WF_PHASE_TIMING" in txt or "WF_EXP_" in txt:
-            assert "wf_dev_guard.hpp" in txt or p.name in ("wf_tick_phases.hpp", "wf_big.hpp", "wf_hip.hip", "wf_hip_plan.hip"), p.name  # (those include it through wf_hip_internal.hpp / wf_kernels.hpp)
+            assert "wf_dev_guard.hpp" in txt or p.name in ("wf_tick_args.hpp", "wf_big.hpp", "wf_hip.hip", "wf_hip_plan.hip"), p.name  # (wf_tick_args.hpp: plain structs, included behind the guard by wf_hip_internal.hpp and wf_tick_display.hpp; the others include it through wf_hip_internal.hpp / wf_kernels.hpp)
     assert seen <= {"WF_EXP_NO_TAIL", "WF_EXP_CUT_AT"}, f"measurement switches in the product kernels: {sorted(seen)}"
     for name in seen:
         assert name in guard, f"{name} is not refused by wf_dev_guard.hpp outside development builds"
@@ -586,6 +586,46 @@ def test_release_library_carries_no_laboratory():
     assert r.returncode != 0 and "WF_DEV_BUILD" in r.stderr
     r = subprocess.run(["g++", "-fsyntax-only", "-x", "c++", "-DWF_DEV_BUILD", "-I", str(csrc), "-"], input=src, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_tick_headers_stand_alone_and_keep_their_layers(tmp_path):
+    """The tick's headers by role.  Self-containment: each of them compiles as the only include of an otherwise empty file, with
+    g++ (the host sees the argument structs; tests/emu compiles the rest) and with hipcc for gfx950.  Layering: wf_tick_args.hpp
+    includes nothing of the project but wf_fft_core.hpp (types) and the public headers, and no header of the small kernels, nor
+    wf_hip_internal.hpp -- i.e. no host translation unit --, reaches the FFT phases or the display code through its includes."""
+    from concurrent.futures import ThreadPoolExecutor
+    csrc = ROOT / "waveform_amd" / "csrc"
+    headers = ["wf_tick_args.hpp", "wf_dev_helpers.hpp", "wf_tick_phases.hpp", "wf_bluestein.hpp", "wf_mixed.hpp", "wf_tick_display.hpp"]
+    inc = ["-I", str(ROOT / "include"), "-I", str(csrc)]
+    jobs = []
+    for h in headers:
+        tu = tmp_path / (h[:-4] + ".cpp")
+        tu.write_text(f'#include "{h}"\n')
+        jobs.append((h, ["g++", "-std=c++20", "-fsyntax-only", *inc, str(tu)]))
+        jobs.append((h, ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++20", "-fsyntax-only", *inc, "-x", "hip", str(tu)]))
+    with ThreadPoolExecutor(4) as pool:
+        done = list(pool.map(lambda j: subprocess.run(j[1], capture_output=True, text=True), jobs))
+    for (h, cmd), r in zip(jobs, done):
+        assert r.returncode == 0, f"{h} does not compile on its own with {Path(cmd[0]).name}:\n{r.stderr[-1500:]}"
+
+    def includes(name):
+        return re.findall(r'^\s*#\s*include\s+"([^"]+)"', (csrc / name).read_text(), re.M)
+
+    def reach(name):
+        seen, todo = set(), [name]
+        while todo:
+            for i in includes(todo.pop()):
+                if i not in seen and (csrc / i).exists():  # (the public headers live in include/: leaves)
+                    seen.add(i)
+                    todo.append(i)
+        return seen
+    public = {p.name for p in (ROOT / "include").glob("*.h")}
+    assert set(includes("wf_tick_args.hpp")) <= {"wf_fft_core.hpp"} | public, includes("wf_tick_args.hpp")
+    assert not reach("wf_fft_core.hpp"), "wf_fft_core.hpp is a leaf"
+    kernel_code = {"wf_tick_phases.hpp", "wf_tick_display.hpp", "wf_bluestein.hpp", "wf_mixed.hpp", "wf_kernels.hpp", "wf_big.hpp"}
+    for h in ("wf_ring.hpp", "wf_pcm.hpp", "wf_wire.hpp", "wf_meter.hpp", "wf_rms.hpp", "wf_wave.hpp", "wf_hip_internal.hpp"):
+        assert not (reach(h) & kernel_code), (h, sorted(reach(h) & kernel_code))
+    assert {"wf_tick_phases.hpp", "wf_tick_display.hpp"} <= reach("wf_kernels.hpp")  # (the walk does see them where they are)
 
 
 def test_no_device_fails_loudly():

@@ -41,6 +41,7 @@ K = 8  # one binary order of magnitude over the reference's own error against th
 # scale, smoothing and hardware log2 leave the one or two peak bins 2 to 3 ulps of their float32 dB value away (4e-8 to 6e-8 of
 # a 0.18 peak).  Every other bin of those frames is inside K.  A library built with WF_TW1_POW2=0 (every pass-1 twiddle row loaded
 # from its table) misses the same cases by the same figures; one built with WF_FAST_DB=0 (log10f) misses eleven, in other families too.
+# (Both build switches are retired since; commit 0c206e5 is the last that has them.)
 LIN_EPS_FAMILIES = {"ZERO_PADDED": 23.58, "POW2": 22.74, "MR_TWO_ROWS": 17.42}  # family -> its worst measured ratio (needed k: 11.8, 11.4, 11.6)
 
 

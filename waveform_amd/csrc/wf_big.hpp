@@ -21,7 +21,9 @@
 #include <hip/hip_runtime.h>
 #include "wf_geometry.hpp"
 #include "wf_tick_phases.hpp"
+#include "wf_bluestein.hpp"
 #include "wf_mixed.hpp"
+#include "wf_tick_display.hpp"
 
 namespace wf {
 
@@ -325,9 +327,9 @@ WF_DEV void big_finish(const TickArgs &a, int t, int kbase, uint32_t spec, bool 
 #pragma unroll
         for(int i = 0; i < RP; ++i)
             exceeds = exceeds || (4 * (t + RG::T * (i / 4)) < NB && d[i] > a.silent_floor);
-        store_row<RG, true, WF_NT_ROWS>(rows + (size_t)ch * MO, t, d, NB);
+        store_row<RG, true, true>(rows + (size_t)ch * MO, t, d, NB);
         if(dup_row)
-            store_row<RG, true, WF_NT_ROWS>(rows + (size_t)MO, t, d, NB);
+            store_row<RG, true, true>(rows + (size_t)MO, t, d, NB);
     } else if(!(hidden && !was_silent)) // row untouched this tick (the reset branch leaves DB_MIN everywhere: below)
         exceeds = (ch == 0 ? vin0 : vin1) != 0u;
     if(ch == 0 && t == 0)
@@ -370,28 +372,18 @@ template<int MODE> __global__ __launch_bounds__(GBig::T, 4) void big_epilogue_ke
 
 // the 16 points per row this thread feeds into pass 1: u0 +- u1 (times W_L^n2 for row 1), u = windowed sample pairs.
 // Eight to ten registers per point are in flight until its sums are formed, so the burst goes out in groups of rows.
-#ifndef BIG_FETCH_ROWS
-#define BIG_FETCH_ROWS 4
-#endif
+constexpr int BIG_FETCH_ROWS = 4;
 // (32-bit byte offsets from a uniform base: the loads take the SGPR-base + VGPR-offset form instead of a 64-bit address pair
 // per request -- sixty-four of those do not fit the register file)
-#ifdef BIG_PLAIN_INDEX
-WF_DEV float big_ring1(const float *x, uint32_t i) { return x[i]; }
-WF_DEV f2 big_ring2(const float *x, uint32_t i) { return ld2(x + i); }
-WF_DEV f4 big_ring4(const float *x, uint32_t i) { return ld4(x + i); }
-#else
 WF_DEV float big_ring1(const float *x, uint32_t i) { return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(x) + (size_t)(i * 4u)); }
 WF_DEV f2 big_ring2(const float *x, uint32_t i) { return *reinterpret_cast<const f2 *>(reinterpret_cast<const char *>(x) + (size_t)(i * 4u)); }
 WF_DEV f4 big_ring4(const float *x, uint32_t i) { return *reinterpret_cast<const f4 *>(reinterpret_cast<const char *>(x) + (size_t)(i * 4u)); }
-#endif
 // The row transform of the fused path runs on 512 threads of 32 points (two waves per SIMD, 256 registers each) rather than
 // GBig's 1024 of 16: at 128 registers the fused fetch and split spilled 196 B per lane, and with one workgroup per CU the
 // spill traffic of 1024 workgroups went all the way to device memory -- 420 MB of the 770 MB a launch moved for 201 MB of
 // payload (profiles/r03a_n65536_pmc.json).
-#ifndef WF_FOLD_T
-#define WF_FOLD_T 512
-#endif
-using GFold = Geom<32768, WF_FOLD_T, 16, 32, 32>;
+constexpr int FOLD_T = 512;
+using GFold = Geom<32768, FOLD_T, 16, 32, 32>;
 static_assert(GFold::LDS_CF == GBig::LDS_CF && GFold::R2 == GBig::R2 && GFold::R3 == GBig::R3 && GFold::R1 == GBig::R1, "the fused rows use GBig's tables and LDS budget");
 
 // Both rows from ONE pass over the window: row 0's sums u0 + u1 are parked in the exchange buffer, in the very slots this thread's
@@ -462,10 +454,8 @@ template<class G, bool ALIGNED, int BURST = BIG_FETCH_ROWS> WF_DEV uint32_t big_
             else
                 lds_st2(lds, ex1_addr<G>(j, t), pt[0]);
         }
-#ifndef BIG_NO_FENCE
         if(j0 + ROWS < R1)
             __builtin_amdgcn_sched_barrier(0); // the next group's requests stay behind this group's sums
-#endif
     }
     // ... and back: the thread's own slots, read through an index the compiler cannot match with the stores above (it
     // would forward the stored values and keep them in registers after all)
@@ -528,9 +518,7 @@ template<class G, int K1> WF_DEV void big_fused_split(const TickArgs &a, int t, 
 // well (big_fused_fetch2); the silence facts come from the fetch itself as in spectrum_tick_kernel's split mode.
 // Against round 3's two kernels (magnitudes through device memory, 1.45 x the algorithmic bytes, profiles/r04f_n65536_pmc.json):
 // 256 stereo streams 0.336 -> 0.445 of the HBM peak on one lane, 0.557 on two (profiles/r04g_n65536_whole.txt).
-#ifndef WF_WHOLE_BURST
-#define WF_WHOLE_BURST 2 // (rows per burst of the joint fetch: 2 is +3 % over BIG_FETCH_ROWS' 4 here -- row 1's sums fill up the registers)
-#endif
+constexpr int WHOLE_BURST = 2; // (rows per burst of the joint fetch: 2 is +3 % over BIG_FETCH_ROWS' 4 here -- row 1's sums fill up the registers)
 // the three LDS passes of the 32768-sample geometry on the row whose pass-1 inputs are in r, then its real split into mag
 template<class G, int K1>
 WF_DEV void big_whole_row(const TickArgs &a, int t, P1Regs<G> &r, cf *lds, const cf *tw2_lds, float (&mag)[2 * G::P])
@@ -550,18 +538,16 @@ WF_DEV void big_whole_row(const TickArgs &a, int t, P1Regs<G> &r, cf *lds, const
     big_fused_split<G, K1>(a, t, lds, mag);
 }
 
-// slope, smoothing and the state store of the whole row.  The operands of WF_WHOLE_BATCH groups of four bins are requested
+// slope, smoothing and the state store of the whole row.  The operands of WHOLE_BATCH groups of four bins are requested
 // together and consumed behind them: written group by group (load, load, wait, store) the state stores fence the next group's
 // loads -- the compiler cannot tell the rows apart -- and a thread pays sixteen trips to device memory one after the other
 // (20 of a workgroup's 46 us, profiles/r04g_n65536_whole_cuts.txt).
-#ifndef WF_WHOLE_BATCH
-#define WF_WHOLE_BATCH 8
-#endif
+constexpr int WHOLE_BATCH = 8;
 // (measured and dropped, profiles/r04g_n65536_whole.txt: the state row's lines touched ahead of the fetch -- 0.557 -> 0.452 with two
 // lanes --; the first batch requested in front of row 1's real split -- the fetch's register allocation falls over: 800 B of scratch)
 template<class RG, bool TS, bool FPK> WF_DEV void p4_whole_impl(const TickArgs &a, int t, float *ts, float (&mag)[RG::P])
 {
-    constexpr int NB = WF_WHOLE_BATCH;
+    constexpr int NB = WHOLE_BATCH;
     static_assert((RG::P / 4) % NB == 0);
 #pragma unroll
     for(int u0 = 0; u0 < RG::P / 4; u0 += NB) {
@@ -613,7 +599,7 @@ template<bool ALIGNED> __global__ __launch_bounds__(GFold::T, GFold::T / 256) vo
     }
     float mag[RG::P];
     P1Regs<G> r0, r1;
-    const uint32_t acc = big_fused_fetch2<G, ALIGNED, WF_WHOLE_BURST>(a, t, x, start, r0, r1, lds);
+    const uint32_t acc = big_fused_fetch2<G, ALIGNED, WHOLE_BURST>(a, t, x, start, r0, r1, lds);
     big_whole_row<G, 0>(a, t, r0, lds, tw2_lds, mag);
 #pragma unroll
     for(int j = 1; j < G::R1; ++j) // (the pass-1 twiddles again: row 0's copies are not kept across its transform)
@@ -739,7 +725,7 @@ __global__ __launch_bounds__(GBig::T, 4) void big_mr_rows_kernel(const TickArgs 
 // 16448 ... 32704).
 template<class RG, bool TS, bool FPK> WF_DEV void p4_part_impl(const TickArgs &a, int t, float *ts, int nb, float (&mag)[RG::P])
 {
-    constexpr int NBT = WF_WHOLE_BATCH; // (as p4_whole_impl, on a row that need not fill the layout: groups at or beyond nb sit out)
+    constexpr int NBT = WHOLE_BATCH; // (as p4_whole_impl, on a row that need not fill the layout: groups at or beyond nb sit out)
     static_assert((RG::P / 4) % NBT == 0);
 #pragma unroll
     for(int u0 = 0; u0 < RG::P / 4; u0 += NBT) {

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define WF_DEV __device__ __forceinline__
 #define WF_UNROLL _Pragma("unroll")
 #else

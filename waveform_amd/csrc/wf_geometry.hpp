@@ -19,10 +19,8 @@ using G8192 = Geom<8192, 256, 8, 16, 32>;     // four wavefronts; radix 8 first 
 // (measured alternatives in steady state: 2048 as 8x8x16 +-0, 4096 as 8x32x8 -2.5 %, 8192 as 8x32x16 -2 %)
 using G16384 = Geom<16384, 512, 8, 32, 32>;   // eight wavefronts; radix 8 first (16-byte pass-1 vectors: 51.7 -> 53.5 % over
                                               // 16x16x32), both radix-32 passes shared by thread pairs
-#ifndef WF_G32768_T
-#define WF_G32768_T 512 // (1024 threads of 16 points: 0.54 / 0.48 of the HBM peak at 512 / 2048 streams where 512 threads of 32 reach 0.56 / 0.53)
-#endif
-using G32768 = Geom<32768, WF_G32768_T, 16, 32, 32>; // eight wavefronts of 32 points per thread = one workgroup per spectrum (132 KB of LDS: one per CU,
+// (1024 threads of 16 points: 0.54 / 0.48 of the HBM peak at 512 / 2048 streams where 512 threads of 32 reach 0.56 / 0.53)
+using G32768 = Geom<32768, 512, 16, 32, 32>; // eight wavefronts of 32 points per thread = one workgroup per spectrum (132 KB of LDS: one per CU,
                                               // two waves per SIMD with 256 registers each -- 177-199 used, no scratch); both radix-32 passes
                                               // whole in a thread.  The reference's "large FFT" range.
 

@@ -20,7 +20,7 @@ namespace wf::host { struct SmallArgs; }
 #include "wf_dev_guard.hpp"
 #include "wf_host_tables.hpp"
 #include "wf_loudness_tables.hpp"
-#include "wf_tick_phases.hpp" // TickArgs, BarsOnlyState (plain structs: no kernel is instantiated by including it)
+#include "wf_tick_args.hpp" // TickArgs, BarsOnlyState (plain structs, no device code)
 #include "wf_tick_plan.hpp"
 
 struct wf_hip {

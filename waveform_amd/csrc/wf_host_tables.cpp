@@ -285,7 +285,7 @@ void build_bars(const wf_config &cfg, HostTables &t)
         }
     }
 
-    // ---- composite per-bar kernels for the device (see BarArgs in wf_tick_phases.hpp) ---------------------------------
+    // ---- composite per-bar kernels for the device (see BarArgs in wf_tick_args.hpp) ---------------------------------
     const intmax_t M = (intmax_t)(cfg.fft_size / 2);
     t.bar_rows_bins = (int)M;
     t.bar_off.assign((size_t)num_bars + 1, 0);
@@ -1017,9 +1017,7 @@ void build_bluestein(const wf_config &cfg, const HostTables &t, BluesteinTables 
     }
 }
 
-#ifndef WF_MR_PASS_COST
-#define WF_MR_PASS_COST 24.0
-#endif
+constexpr double MR_PASS_COST = 24.0; // a pass's barrier and loop set-up, in the cost model's units (plan_mixed_radix)
 int plan_mixed_radix(uint32_t np, uint32_t threads, int radix[4], uint64_t bluestein_points)
 {
     static const int kRadices[] = {25, 23, 20, 19, 17, 16, 15, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2};
@@ -1080,7 +1078,7 @@ int plan_mixed_radix(uint32_t np, uint32_t threads, int radix[4], uint64_t blues
                     g *= 2;
                 per += 1.5 * R * (g - 1);                           // first-pass stores, stride R: g-way bank conflicts
             }
-            c += iters * per + WF_MR_PASS_COST;                      // + the pass's barrier and loop set-up
+            c += iters * per + MR_PASS_COST;                      // + the pass's barrier and loop set-up
         }
         return c;
     };

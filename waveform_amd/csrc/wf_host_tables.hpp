@@ -170,7 +170,7 @@ uint32_t build_bluestein_rows(uint32_t np, uint32_t C, std::vector<cfloat> &rowt
 // factor or no ordering fits: radices above 16 only in the first pass (the twiddled passes hold 2 (R - 1) more registers), and
 // the last pass has one butterfly per thread at most (np / radix[last] <= threads).
 int plan_mixed_radix(uint32_t np, uint32_t threads, int radix[4], uint64_t bluestein_points = 0);
-// The exchange buffer of a mixed-radix spectrum of np complex points (MrPlan::half / s3 / lds_cf, wf_tick_phases.hpp): two halves of
+// The exchange buffer of a mixed-radix spectrum of np complex points (MrPlan::half / s3 / lds_cf, wf_tick_args.hpp): two halves of
 // `half` = np rounded up to 16 points; never less than 576 complex units (the display phase parks the dB row and stages its
 // inputs there: Geom::LDS_CF's floor) and never more than the container geometry's buffer (np <= M / 2).
 inline uint32_t mr_exchange_half(uint32_t np) { return (np + 15u) & ~15u; }

@@ -14,7 +14,9 @@
 #include <hip/hip_runtime.h>
 #include "wf_geometry.hpp"
 #include "wf_tick_phases.hpp"
+#include "wf_bluestein.hpp"
 #include "wf_mixed.hpp"
+#include "wf_tick_display.hpp"
 #include "wf_hip.h"
 #ifndef WF_EXP_NO_TAIL
 #define WF_EXP_NO_TAIL 0 // 1 (development builds, measurement only: the bars come out wrong): the display phase skipped -- what a tick would cost if the tail were free
@@ -63,42 +65,6 @@ template<class G, int SPW> constexpr size_t tick_lds_bytes()
 {
     return (size_t)SPW * G::LDS_CF * sizeof(cf) + (size_t)G::R2 * G::R3 * sizeof(cf) + 2 * (size_t)SPW * (G::T / 64) * sizeof(int) + 16;
 }
-
-// register budget: waves per SIMD the kernel is compiled for (launch_bounds' second argument) -- 3 only for the
-// one-wavefront 16-point geometry (N = 2048), whose register prefetch of the smoothing state needs ~140 VGPRs
-#ifndef WF_TRACK
-#define WF_TRACK 1
-#endif
-#ifndef WF_DEFER_STATE
-#define WF_DEFER_STATE 0 // 1: smoothing-state stores issued behind the display's table requests (p4_split_smooth<.., DEFER>)
-#endif
-#ifndef WF_WPS_SMALL
-#define WF_WPS_SMALL 4 // 8-point geometry (N = 1024): 5 waves per SIMD was +4 % in round 1 (84 VGPRs); with what the kernel has
-                       // learned since (paused streams, underflow, bars-only tracking, lanes) it spilled 36 B per lane at the
-                       // 96-register cap and ran 10 % slower than at 4 (tests/test_cpu_units.py now checks for scratch)
-#endif
-#ifndef WF_WPS_2048_BLU
-#define WF_WPS_2048_BLU 4 // (+3-4 % over three waves and no scratch, measured: 52 B of scratch per lane weigh less than a fourth wave) the Bluestein instantiation of the same geometry (fft sizes 528 ... 1008, the automatic size 800 among them)
-#endif
-#ifndef WF_MR_FIXED_PLANS
-#define WF_MR_FIXED_PLANS 1 // 0: every mixed-radix size through the run-time plan (A/B)
-#endif
-#ifndef WF_WPS_2048_MRS
-#define WF_WPS_2048_MRS 5 // 96 registers, 12 B of scratch per lane
-#endif
-#ifndef WF_WPS_2048
-#define WF_WPS_2048 3
-#endif
-#ifndef WF_WPS_512
-#define WF_WPS_512 6 // four points per thread: 80 VGPRs; 0.60 of the HBM peak at N = 512 against 0.53 at 4 and 5 waves, 0.44 at 8 (spills)
-#endif
-#ifndef WF_WPS_LARGE
-#define WF_WPS_LARGE 4 // sixteen points per thread on two wavefronts and more: 104-115 VGPRs.  Five waves per SIMD (96 VGPRs: the
-                       // register file hands out blocks of 8) were compiled for the record at the end of round 3
-                       // (profiles/r03_occupancy5_isa.txt): the N = 4096 kernel then keeps 72 B per lane in scratch, the 16384 one 48 B --
-                       // and a fifth workgroup per CU would also need its LDS down from 36.9 KB to 32 KB
-#endif
-#define WF_WAVES_PER_SIMD(G) ((G::P > 16) ? 2 : (G::P > 8 && G::T <= 64) ? WF_WPS_2048 : (G::P <= 4) ? WF_WPS_512 : (G::P <= 8) ? WF_WPS_SMALL : WF_WPS_LARGE)
 
 #ifdef WF_PHASE_TIMING
 #define WF_STAMP(i)                                                                      \
@@ -186,9 +152,34 @@ struct Variant {
     int disp = 0;         // DISP
     int plan = 0;         // PLAN
 };
+// register budget: waves per SIMD the kernel is compiled for (launch_bounds' second argument).  Every figure is the measured
+// choice; the alternatives are in EXPERIMENTS.md ("Retired build switches").
 template<class G, Variant V> constexpr int tick_waves_per_simd()
 {
-    return V.mrs ? WF_WPS_2048_MRS : (V.blu && G::P > 8 && G::T <= 64) ? WF_WPS_2048_BLU : WF_WAVES_PER_SIMD(G);
+    if(V.mrs)
+        return 5; // the mixed-radix instantiation: 96 registers, 12 B of scratch per lane
+    if(V.blu && G::P > 8 && G::T <= 64) {
+        // the Bluestein instantiation of the one-wavefront 16-point geometry (N = 2048: fft sizes 528 ... 1008): +3-4 % over three
+        // waves and no scratch, measured: 52 B of scratch per lane weigh less than a fourth wave
+        return 4;
+    }
+    if(G::P > 16)
+        return 2; // 32 points per thread (N = 32768)
+    if(G::P > 8 && G::T <= 64)
+        return 3; // the one-wavefront 16-point geometry (N = 2048): its register prefetch of the smoothing state needs ~140 VGPRs
+    if(G::P <= 4)
+        return 6; // four points per thread: 80 VGPRs; 0.60 of the HBM peak at N = 512 against 0.53 at 4 and 5 waves, 0.44 at 8 (spills)
+    if(G::P <= 8) {
+        // 8-point geometry (N = 1024): 5 waves per SIMD was +4 % in round 1 (84 VGPRs); with what the kernel has learned since
+        // (paused streams, underflow, bars-only tracking, lanes) it spilled 36 B per lane at the 96-register cap and ran 10 %
+        // slower than at 4 (tests/test_cpu_units.py now checks for scratch)
+        return 4;
+    }
+    // sixteen points per thread on two wavefronts and more: 104-115 VGPRs.  Five waves per SIMD (96 VGPRs: the register file hands
+    // out blocks of 8) were compiled for the record at the end of round 3 (profiles/r03_occupancy5_isa.txt): the N = 4096 kernel
+    // then keeps 72 B per lane in scratch, the 16384 one 48 B -- and a fifth workgroup per CU would also need its LDS down from
+    // 36.9 KB to 32 KB
+    return 4;
 }
 template<class G, Variant V>
 __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void spectrum_tick_kernel(const TickArgs a)
@@ -291,7 +282,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
     bool nz = false;
     float mr_touch[2] = {0.0f, 0.0f};
     MrOps<G> mr_ops;
-    constexpr bool MR_EARLY = BLU && MR && WF_MR_PREFETCH && G::T == 64; // the epilogue's operands requested behind the window (one-wavefront containers)
+    constexpr bool MR_EARLY = BLU && MR && G::T == 64; // the epilogue's operands requested behind the window (one-wavefront containers)
     if constexpr(BLU && MR) {
         if(active) // windowed sample pairs straight into the exchange buffer, natural order (wf_mixed.hpp)
             nz = mr_fetch<G>(a, t, x, start, lds) && !hidden;
@@ -328,7 +319,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
     WF_STAMP(1);
     bool wave_below = true;
     if(active && !hidden && !wave_nz) { // wave-uniform and rare: the whole slice of this wave is digital silence
-        if(!SPLIT && (WF_TRACK && a.bars_only != nullptr) && a.bars_only->use_verdict) // rows in HBM are stale: the word this wave left instead
+        if(!SPLIT && a.bars_only != nullptr && a.bars_only->use_verdict) // rows in HBM are stale: the word this wave left instead
             wave_below = a.bars_only->row_verdict[(size_t)(spec - (stereo ? 0u : ch)) * WPS + (wave_in_block - sub * WPS)] == 0u;
         else
             wave_below = __all(!row_thread || row_all_below<RG, BLU>(rows + (size_t)(stereo ? ch : 0u) * MO, t, a.silent_floor, NB)) != 0;
@@ -430,21 +421,21 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
             mr_transform_fixed<G, 10, 10, 10>(a.mr, process, t, lds, sp_sync);
         else if constexpr(PLAN == 8) // 1760
             mr_transform_fixed<G, 10, 8, 11>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 2048 && plan_is(5, 10, 8)) // 800
+        else if(MRS && G::N == 2048 && plan_is(5, 10, 8)) // 800
             mr_transform_fixed<G, 5, 10, 8>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 2048 && plan_is(5, 12, 8)) // 960
+        else if(MRS && G::N == 2048 && plan_is(5, 12, 8)) // 960
             mr_transform_fixed<G, 5, 12, 8>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 2048 && plan_is(10, 6, 6)) // 720
+        else if(MRS && G::N == 2048 && plan_is(10, 6, 6)) // 720
             mr_transform_fixed<G, 10, 6, 6>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 2048 && plan_is(11, 5, 8)) // 880
+        else if(MRS && G::N == 2048 && plan_is(11, 5, 8)) // 880
             mr_transform_fixed<G, 11, 5, 8>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 4096 && plan_is(10, 8, 10)) // 1600
+        else if(MRS && G::N == 4096 && plan_is(10, 8, 10)) // 1600
             mr_transform_fixed<G, 10, 8, 10>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 4096 && plan_is(10, 8, 12)) // 1920
+        else if(MRS && G::N == 4096 && plan_is(10, 8, 12)) // 1920
             mr_transform_fixed<G, 10, 8, 12>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 4096 && plan_is(10, 10, 10)) // 2000
+        else if(MRS && G::N == 4096 && plan_is(10, 10, 10)) // 2000
             mr_transform_fixed<G, 10, 10, 10>(a.mr, process, t, lds, sp_sync);
-        else if(MRS && WF_MR_FIXED_PLANS && G::N == 4096 && plan_is(10, 8, 11)) // 1760
+        else if(MRS && G::N == 4096 && plan_is(10, 8, 11)) // 1760
             mr_transform_fixed<G, 10, 8, 11>(a.mr, process, t, lds, sp_sync);
         else
             mr_transform<G, MRS>(a.mr, process, (int)a.row_bins, t, lds, tw2_lds, [] { spectrum_sync<G>(); }); // (tw2_lds: the prime pass's W_p^m, staged where the power-of-two kernels keep their pass-2 twiddles: TickArgs::tw2 points at it)
@@ -474,7 +465,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
                 p1_window_pass1<G>(a, t, r1, lds);
             if constexpr(DEC > 0)
                 p4_prefetch_dec<G, DEC>(a, t, ts, r4);
-            else if constexpr(!BLU && !Policy<G>::PREFETCH_LATE) // the Bluestein epilogue loads its (shorter) rows itself
+            else if constexpr(!BLU) // the Bluestein epilogue loads its (shorter) rows itself
                 p4_prefetch<G>(a, t, ts, r4);
         }
         __builtin_amdgcn_sched_barrier(0); // keep the prefetch up here: do not sink it to its first use in P4
@@ -494,11 +485,6 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         WF_STAMP(6);
         if(process)
             p3_pass3_write<G>(t, lds, v);
-        if constexpr(!BLU && DEC == 0 && Policy<G>::PREFETCH_LATE) {
-            if(process)
-                p4_prefetch<G>(a, t, ts, r4);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         WF_STAMP(7);
         spectrum_sync<G>();
         if constexpr(BLU) {
@@ -546,27 +532,18 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         if constexpr(BLU) {
             if constexpr(MR) {
                 asm volatile("" ::"v"(mr_touch[0]), "v"(mr_touch[1])); // (waited for here at the latest; see the fetch)
-#if WF_MR_PREFETCH
                 if constexpr(MR_EARLY)
                     mr_ops_request<G, false, true>(a, t, ts, mr_ops);
                 else
                     mr_ops_request<G, true, true>(a, t, ts, mr_ops); // all of the epilogue's operands at once, from the lines touched above
                 p4_mr<G>(a, t, lds, ts, mr_ops, mag);
-#else
-                p4_direct<G, MR>(a, t, lds, ts, mag);
-#endif
             } else
-                p4_direct<G, MR>(a, t, lds, ts, mag);
+                p4_direct<G>(a, t, lds, ts, mag);
         } else if constexpr(DEC > 0) {
             if(row_thread)
                 p4_split_smooth_dec<G, DEC>(a, t, lds, ts, r1.wb, r4, mag);
-        } else {
-            p4_split_smooth<G, WF_DEFER_STATE != 0>(a, t, lds, ts, r1.wb, r4, mag);
-            if(WF_DEFER_STATE && mono_mix) // (the mixdown below overwrites mag[]: no deferral there)
-                p4_store_state<G>(a, t, ts, mag);
-            if(Policy<G>::TOUCH_STATE)
-                asm volatile("" ::"v"(r4.touch[0]), "v"(r4.touch[1])); // the touched dwords are only ever waited for
-        }
+        } else
+            p4_split_smooth<G>(a, t, lds, ts, r1.wb, r4, mag);
     } else if(do_db && (!(mono_mix && ch == 1) || underflow) && row_thread) {
         // skipped channel of a live stream: its stale row is re-dBFS'ed (Appendix C.3).  A channel is only skipped when that
         // row is entirely <= floor - 10 < 0, and dbfs() of a negative number is DB_MIN: when the row in HBM is not current
@@ -580,7 +557,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         // :150-154 -- to row 0's stale dB values.  With temporal smoothing on those magnitudes are this channel's smoothing
         // state; with smoothing off nothing holds them and row 0 stands in: a stated deviation for a starved tick in the middle
         // of a stream, where the sum is garbage either way)
-        const float *stale = ((WF_TRACK && a.bars_only != nullptr) && !mono_mix) ? a.stale_row
+        const float *stale = (a.bars_only != nullptr && !mono_mix) ? a.stale_row
                              : (mono_mix && ch == 1 && (a.mode & WF_MODE_TSMOOTH)) ? ts
                                                                                     : rows + (size_t)(mono_mix ? 0u : ch) * MO;
         load_row<RG, BLU>(stale, t, mag, NB);
@@ -665,15 +642,11 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
     if(count_arrivals) {
         asm volatile("" ::: "memory");
         if(lane == 0)
-            __hip_atomic_fetch_add(arrivals, 1, WF_ARRIVE_ORDER_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(arrivals, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     // the bar tables of this thread: requested here so that their L2 latency runs under the dB math and the row stores
     if constexpr(!COEF_EARLY && DISP != 2)
         bars_fetch_entries<G, PS_OK, DISP == 1>(a.bar, t, bar_entries, WF_PS_FINISHER);
-    if constexpr(WF_DEFER_STATE && !BLU && DEC == 0) {
-        if(process && !mono_mix)
-            p4_store_state<G>(a, t, ts, mag); // behind the table requests (p4_split_smooth<.., DEFER>)
-    }
     const bool have_row = do_db && !(mono_mix && ch == 1); // this subgroup produces row `ch` (and row 1 too when one
                                                             // captured channel is shown as stereo, reference :141-142)
     const bool dup_row = have_row && (a.out_ch > a.cap_ch);
@@ -681,7 +654,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
     bool row_exceeds = false; // bars-only handles: this thread's part of the row has a value > floor - 10
     if(have_row && row_thread) {
         p4_db<RG, BLU>(a, t, mag, d, vol_comp, NB);
-        if(!SPLIT && (WF_TRACK && a.bars_only != nullptr)) {
+        if(!SPLIT && a.bars_only != nullptr) {
             // taken here, where d[] is produced: reading the array again under a later branch makes ROCm 7.2's clang merge
             // that read with a global load through a pointer phi, i.e. a flat pointer into scratch, and its backend aborts
             // ("Illegal instruction detected: Operand has incorrect register class", V_CMP_NE_U32 0, src_private_base)
@@ -693,9 +666,9 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         // completing in order, is not a wait for these stores' acknowledgement -- measured +-0 for both, -10 % for bars at
         // N = 2048, and is no longer in the tree.)
         if(!a.skip_decibels) {
-            store_row<RG, BLU, WF_NT_ROWS>(rows + (size_t)ch * MO, t, d, NB);
+            store_row<RG, BLU, true>(rows + (size_t)ch * MO, t, d, NB);
             if(dup_row)
-                store_row<RG, BLU, WF_NT_ROWS>(rows + (size_t)MO, t, d, NB);
+                store_row<RG, BLU, true>(rows + (size_t)MO, t, d, NB);
         }
     }
     WF_STAMP(10);
@@ -703,7 +676,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         (SPLIT ? a.flags_out : a.stream_flags)[stream] =
             paused ? sflags
                    : ((sflags & (WF_STREAM_HIDDEN | WF_STREAM_TIMEOUT | WF_STREAM_WRAPPED | WF_STREAM_STARVED)) | ((hidden || plan.last_silent) ? WF_STREAM_LAST_SILENT : 0u));
-    if(!SPLIT && (WF_TRACK && a.bars_only != nullptr) && active) {
+    if(!SPLIT && a.bars_only != nullptr && active) {
         // bars-only handles: what the next tick's silence test would find in the row this spectrum owns (see TickArgs)
         bool exceeds = false, write = true;
         if(have_row) {
@@ -735,9 +708,6 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
     }
 
     // ---- bars: what render_bars derives from the rows just written (reference src/source.cpp:1500-1557) ---------------
-#ifndef WF_TAIL_PRIO
-#define WF_TAIL_PRIO 0
-#endif
     // the further bars buffers (BarArgs::out2_delta) of a spectrum whose displayed row(s) this tick leaves as they are: copied over
     if(!BLU && MIRROR && has_display && a.bar.out2_n > 0 && active && ch < a.bar.disp_ch) {
         const bool have_row_ = do_db && !(mono_mix && ch == 1);
@@ -755,11 +725,8 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         }
     }
     if(has_display && !WF_EXP_NO_TAIL) {
-        // The display phase runs with raised issue priority: what is left of the workgroup's life is a short serial stretch (one
-        // wavefront per spectrum at the end) that holds the workgroup's LDS, and on a SIMD shared with three wavefronts in their
-        // transform passes every instruction of it otherwise waits its turn
-        if(WF_TAIL_PRIO > 0)
-            __builtin_amdgcn_s_setprio(WF_TAIL_PRIO);
+        // (The display phase runs at the issue priority of everything else: raising it for this short serial stretch -- one wavefront
+        // per spectrum at the end, holding the workgroup's LDS -- bought nothing, EXPERIMENTS.md.)
         // mono mixdown displays one row per stream: its curve points are shared by the threads of both spectra of the workgroup
         // (the plugin's default configuration: 800 points, 4 steps of 256 threads instead of 7 of 128)
         constexpr bool both = BOTH;
@@ -772,7 +739,7 @@ __global__ __launch_bounds__(V.spw * G::T, (tick_waves_per_simd<G, V>())) void s
         };
         // every thread of the spectrum is done reading its exchange buffer
         if(count_arrivals) {
-            while(__hip_atomic_load(arrivals, WF_ARRIVE_ORDER_ACQ, __HIP_MEMORY_SCOPE_WORKGROUP) < WPS)
+            while(__hip_atomic_load(arrivals, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < WPS)
                 __builtin_amdgcn_s_sleep(1);
             asm volatile("" ::: "memory");
         } else if(!(mono_mix && !SPLIT))

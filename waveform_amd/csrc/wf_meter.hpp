@@ -14,7 +14,8 @@
 // m_last_silent couples them (:262-268).
 #pragma once
 #include <hip/hip_runtime.h>
-#include "wf_tick_phases.hpp"
+#include "wf_tick_args.hpp"
+#include "wf_dev_helpers.hpp"
 
 namespace wf {
 

@@ -8,8 +8,8 @@
 // at 48 kHz, 1760, 1456, 880, 720, 352 at 44.1 kHz -- and the slider moves in steps of 64.  For n/2 = 2^a 3^b 5^c 7^d 11^e 13^f (times one of 17, 19, 23)
 // the packed n/2-point transform is a Stockham autosort FFT of two to four passes whose radices come from
 // {2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 16} and, in the first pass only, {17, 19, 20, 23, 25}:
-//   * it lives where Bluestein's first transform lived: the fetch (windowed sample pairs, p1_fetch_blu) and the epilogue (real split
-//     with W_n^k, slope, smoothing: p4_direct) are the Bluestein path's own, with tables that carry the plain window and ones;
+//   * it lives where Bluestein's first transform lived: the fetch (windowed sample pairs, mr_fetch) and the epilogue (real split
+//     with W_n^k, slope, smoothing: p4_mr at the end of this file) are the Bluestein path's, without the chirp factors;
 //   * the exchange buffer of the power-of-two container (M >= n - 1 complex points) is two halves of >= n/2 points: a pass reads one
 //     half and writes the other, one barrier per pass, a thread takes the butterflies t, t + T, ... one at a time (R points in
 //     registers);
@@ -22,6 +22,9 @@
 #include "wf_tick_phases.hpp"
 
 namespace wf {
+
+// where the finished Z[k] sits in the exchange buffer (MrPlan, wf_tick_args.hpp)
+WF_DEV int mr_z_addr(const MrPlan &p, int k) { return (k & 3) * p.s3 + (k >> 2); }
 
 // ---- compile-time twiddles: cos / sin of 2 pi m / r as literals after unrolling -------------------------------------
 constexpr double mr_pi = 3.14159265358979323846264338327950288;
@@ -552,6 +555,78 @@ template<class G, int R0, int R1, int R2, class Sync> WF_DEV void mr_transform_f
     sync();
     mr_last_r<R2>(process, lds, p.tw + R1 * R0, R0 * R1, t, sync, [lds, &p](int k, cf v) { lds_st2(lds, mr_z_addr(p, k), v); });
     sync();
+}
+
+// ---- the epilogue: the Bluestein path's real split (p4_direct, wf_bluestein.hpp), with its operands requested ahead ------------
+// n/2 <= M/2 bins (the transform works between the two halves of the container's exchange buffer): a thread owns at most P/8
+// groups of four bins.  Per group: the smoothing state (f4) and W_n^k of its four bins (2 x f4); the slope factors are formed
+// (1 + 3 k slope / (n/2 - 1), Policy<G>::SLOPE_LINEAR's reasoning).  One-wavefront containers request them right behind the
+// window fetch -- the state only: 8 registers at 16 points per thread; with the twiddles too the 2048-sample container spilled
+// 56 B per lane -- so that its trip to HBM runs under the transform instead of behind it (what the power-of-two one-wavefront
+// geometries do: Policy MODE 1); everything else at the start of the epilogue, all at once.
+template<class G> struct MrOps {
+    static constexpr int GR = (G::P / 8) > 0 ? G::P / 8 : 1;
+    f4 st[GR], wa[GR], wb[GR];
+};
+// STATE: the smoothing state (HBM: the long trip); TWIDDLES: W_n^k (a table every stream shares: L2)
+template<class G, bool STATE, bool TWIDDLES> WF_DEV void mr_ops_request(const TickArgs &a, int t, const float *ts, MrOps<G> &o)
+{
+    constexpr int T = G::T;
+    const int np = (int)a.row_bins;
+    WF_UNROLL
+    for(int u = 0; u < MrOps<G>::GR; ++u) {
+        const int k0 = 4 * (t + T * u);
+        const int at = k0 < np ? k0 : 0; // (threads beyond the row load bin 0's operands and never use them)
+        if(STATE)
+            o.st[u] = (a.mode & WF_MODE_TSMOOTH) ? ld_state(ts + at) : f4{0.0f, 0.0f, 0.0f, 0.0f};
+        if(TWIDDLES) {
+            o.wa[u] = ld4(reinterpret_cast<const float *>(a.blu_w + at));
+            o.wb[u] = ld4(reinterpret_cast<const float *>(a.blu_w + at + 2));
+        }
+    }
+}
+template<class G, bool TS, bool FPK>
+WF_DEV void p4_split_mr_impl(const TickArgs &a, int t, const cf *lds, float *ts, const MrOps<G> &o, float (&mag)[G::P])
+{
+    constexpr int T = G::T;
+    const int np = (int)a.row_bins; // blu_n / 2
+    WF_UNROLL
+    for(int u = 0; u < MrOps<G>::GR; ++u) {
+        const int k0 = 4 * (t + T * u);
+        if(k0 < np) {
+            const cf W[4] = {cf{o.wa[u].x, o.wa[u].y}, cf{o.wa[u].z, o.wa[u].w}, cf{o.wb[u].x, o.wb[u].y}, cf{o.wb[u].z, o.wb[u].w}};
+            const float st4v[4] = {o.st[u].x, o.st[u].y, o.st[u].z, o.st[u].w};
+            WF_UNROLL
+            for(int i = 0; i < 4; ++i) {
+                const int k = k0 + i, km = (k == 0) ? 0 : np - k;
+                const cf A = lds_ld2(lds, mr_z_addr(a.mr, k)), B = lds_ld2(lds, mr_z_addr(a.mr, km));
+                const float er = A.x + B.x, ei = A.y - B.y;
+                const float dr = A.x - B.x, di = A.y + B.y;
+                const float pr = fmaf(W[i].x, dr, -(W[i].y * di)); // Re(W D)
+                const float pi = fmaf(W[i].x, di, W[i].y * dr);    // Im(W D)
+                float m = mag2(er + pi, ei - pr) * a.half_coef * fmaf((float)k, a.slope_step, 1.0f);
+                if(TS) {
+                    float old = st4v[i];
+                    if(FPK)
+                        old = fmaxf(m, old);
+                    m = spectrum_ema(a.g, old, a.g2, m);
+                }
+                mag[4 * u + i] = m;
+            }
+            if(TS)
+                st_state(ts + k0, f4{mag[4 * u], mag[4 * u + 1], mag[4 * u + 2], mag[4 * u + 3]});
+        }
+    }
+}
+template<class G> WF_DEV void p4_mr(const TickArgs &a, int t, const cf *lds, float *ts, const MrOps<G> &o, float (&mag)[G::P])
+{
+    if(a.mode & WF_MODE_TSMOOTH) {
+        if(a.mode & WF_MODE_FAST_PEAKS)
+            p4_split_mr_impl<G, true, true>(a, t, lds, ts, o, mag);
+        else
+            p4_split_mr_impl<G, true, false>(a, t, lds, ts, o, mag);
+    } else
+        p4_split_mr_impl<G, false, false>(a, t, lds, ts, o, mag);
 }
 
 } // namespace wf

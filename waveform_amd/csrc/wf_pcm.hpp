@@ -16,7 +16,7 @@
 // The ring stays float32; everything downstream (rms_block_kernel, wpos_advance_kernel, the tick) is unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "wf_tick_phases.hpp"
+#include "wf_tick_args.hpp" // WF_STREAM_*
 #include "wf_hip.h"
 
 namespace wf {

@@ -8,7 +8,7 @@
 //   fill_f32_kernel / fill_u32_kernel       state initialisation (reference src/source.cpp:1170-1182)
 #pragma once
 #include <hip/hip_runtime.h>
-#include "wf_tick_phases.hpp"
+#include "wf_tick_args.hpp" // WF_STREAM_*
 #include "wf_synth.h"
 #include "wf_hip.h"
 

@@ -16,7 +16,8 @@
 // (every tick's sum is rebuilt from the stored terms, in a fixed order).
 #pragma once
 #include <hip/hip_runtime.h>
-#include "wf_tick_phases.hpp"
+#include "wf_tick_args.hpp"
+#include "wf_dev_helpers.hpp"
 #include "wf_synth.h"
 #include "wf_wave_reduce.hpp"
 

@@ -12,7 +12,8 @@
 // One wavefront per stream (see waveform_tick_kernel).  HBM traffic: read + write of out_ch * width floats per stream and tick plus the few samples picked from the ring.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "wf_tick_phases.hpp"
+#include "wf_tick_args.hpp"
+#include "wf_dev_helpers.hpp"
 
 namespace wf {
 
