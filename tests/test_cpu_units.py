@@ -3,6 +3,7 @@ the kernel's phase functions run in the wavefront emulator vs the oracle, C-ABI 
 import sys
 import ctypes as C
 import re
+import struct
 import subprocess
 from pathlib import Path
 
@@ -464,6 +465,51 @@ def test_power_of_two_kernels_do_not_spill():
             limit = 256 if "GeomILi32768ELi512E" in name else 128
             assert vgprs <= limit, f"{name} needs {vgprs} VGPRs (limit {limit}): a wave per SIMD fewer"
     assert seen >= 12 and seen_mixed >= 6 and seen_small >= 1
+
+
+def _gfx950_kernels(obj: Path):
+    """the kernel symbols (functions) of the gfx950 code object inside an object file that hipcc wrote: the .hip_fatbin section is
+    an offload bundle (magic, entry count, then offset / size / triple per entry) and the entry of the device is an ELF64 file"""
+    def sections(elf):
+        shoff, = struct.unpack_from("<Q", elf, 0x28)
+        entsize, num, strndx = struct.unpack_from("<HHH", elf, 0x3A)
+        recs = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * entsize) for i in range(num)]
+        names = recs[strndx][4]
+        return [(elf[names + r[0]:elf.index(b"\0", names + r[0])].decode(), r) for r in recs]
+    host = obj.read_bytes()
+    fatbin = next(host[r[4]:r[4] + r[5]] for name, r in sections(host) if name == ".hip_fatbin")
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    assert fatbin.startswith(magic), obj
+    pos, code = len(magic) + 8, None
+    for _ in range(struct.unpack_from("<Q", fatbin, len(magic))[0]):
+        off, size, tlen = struct.unpack_from("<QQQ", fatbin, pos)
+        if b"gfx950" in fatbin[pos + 24:pos + 24 + tlen]:
+            code = fatbin[off:off + size]
+        pos += 24 + tlen
+    assert code is not None and code[:4] == b"\x7fELF", obj
+    secs = sections(code)
+    symtab = next(r for name, r in secs if name == ".symtab")
+    strings = secs[symtab[6]][1][4]
+    out = []
+    for i in range(symtab[5] // 24):
+        name, info, _, shndx, _, _ = struct.unpack_from("<IBBHQQ", code, symtab[4] + i * 24)
+        if info & 15 == 2 and shndx:  # a defined function
+            out.append(code[strings + name:code.index(b"\0", strings + name)].decode())
+    return out
+
+
+def test_instantiations_of_the_tick_kernel_per_geometry():
+    """How many instantiations of spectrum_tick_kernel each geometry's object carries (waveform_amd/csrc/wf_tick_geom.hip: the tables
+    of Pow2Family and BluFamily and the families setup_tick_geometry names): an instantiation that is launched without being in a
+    table has no dynamic-LDS attribute and fails on the GPU only, for the one configuration that reaches it.  A change of the
+    dispatch that adds or loses an instantiation fails here; a deliberate one updates COUNTS below.  Symbol names only."""
+    COUNTS = {512: 32, 1024: 28, 2048: 38, 4096: 38, 8192: 58, 16384: 52, 32768: 24}
+    for n, want in COUNTS.items():
+        obj = ROOT / "build" / "hip" / f"wf_tick_geom_{n}.o"
+        assert obj.exists(), "build the library first: make -C waveform_amd/csrc"
+        kernels = _gfx950_kernels(obj)
+        assert len(kernels) == len(set(kernels)) and all("spectrum_tick_kernel" in k for k in kernels), (n, kernels)
+        assert len(kernels) == want, f"wf_tick_geom_{n}.o: {len(kernels)} instantiations of spectrum_tick_kernel, {want} on record"
 
 
 def test_compatibility_path_kernels_stay_near_their_register_budget(tmp_path):

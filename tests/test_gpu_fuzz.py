@@ -482,7 +482,7 @@ def test_smooth_sizes_take_the_mixed_radix_kernel_and_the_others_bluestein():
     # above 16384: rows of a mixed-radix transform where n/2 = C R has a plan without a prime pass (two rows: both and the end of the
     # tick in one kernel), else (n a multiple of 16 -- every
     # position of the reference's slider is one of 64) rows by Bluestein inside LDS (16400 = 2 x 41 x 10 x 10 included).  Every legal size
-    # takes one of the two: Bluestein through device memory is left to the development builds' WF_HIP_NO_BLUESTEIN_ROWS=1
+    # takes one of the two
     for n, kernel in ((48000, "big_mr_rows_kernel"), (32000, "big_mr_whole_kernel"), (65520, "big_mr_rows_kernel"), (20480, "big_mr_whole_kernel"), (30000, "big_mr_whole_kernel"),
                       (16400, "big_br_{columns,rows}_kernel"), (48016, "big_br_{columns,rows}_kernel"), (33824, "big_br_{columns,rows}_kernel"),
                       (65424, "big_br_{columns,rows}_kernel"), (17488, "big_br_{columns,rows}_kernel")):

@@ -170,3 +170,64 @@ def test_bars_mirrors_set_late():
             hip.stream_destroy(consumer)
             for p in sets:
                 hip.free(p)
+
+
+# The tick kernel's launch keys with mirrors, family by family (waveform_amd/csrc/wf_tick_geom.hip: Pow2Family's table is indexed by
+# aligned / mirrors / display kind).  name: what kernel_name() must say, so that a case cannot drift to another family.
+MIRROR_CASES = {
+    "512_bars": (512, dict(), "tables via LDS"),                                    # two spectra per workgroup, prefix-sum bars
+    "512_curve": (512, dict(bars=0, curve=1, interp_mode=2), "tables via LDS"),     # ... the general display code
+    "256_bars": (256, dict(), "zero-padded"),                                       # one instantiation with mirrors, scalar fetch
+    "1024_monomix_curve": (1024, dict(stereo=0, bars=0, curve=1, interp_mode=2), "curve row shared by both spectra"),
+    "8192_split_bars": (8192, dict(), ",split"),                                    # serves the mirrors in its only instantiation
+    "8192_one_channel_bars": (8192, dict(capture_channels=1), "SPW=1>"),
+}
+
+
+def _run_mirrored(cfg, name, mirrors, odd):
+    """four ticks of a two-stream handle, with the mirror sets in place from before tick 0 or without; odd: 3 frames pushed first, so
+    that every window starts off the 16-byte grid.  Returns the outputs after every tick, the set handed over among them."""
+    n, streams, ticks = int(cfg.fft_size), 2, 4
+    hip, outs, last = _Hip(), [], None
+    with wf.SpectrumBatch(cfg, streams, ring_frames=_lead(n) + HOP * (ticks + 1) + 4) as b:
+        assert name in b.kernel_name() and b.num_bars > 0, (b.kernel_name(), b.num_bars)
+        shape = (streams, b.display_channels, b.num_bars)
+        sets = [hip.alloc(int(np.prod(shape)) * 4) for _ in range(2)] if mirrors else []
+        consumer = hip.stream()
+        try:
+            if mirrors:
+                b.set_bars_mirrors([sets[0]], [sets[1]])
+            if odd:
+                b.push_audio(synth.block(SEED, 0, streams, b.capture_channels, 0, odd))
+            b.push_audio(synth.block(SEED, 0, streams, b.capture_channels, odd, _lead(n)))
+            for t in range(ticks):
+                b.push_audio(synth.block(SEED, 0, streams, b.capture_channels, odd + _lead(n) + t * HOP, HOP))
+                b.tick()
+                o = dict(decibels=b.decibels(), bars=b.bars(), last_silent=b.last_silent())
+                if mirrors:
+                    ptr = b.bars_mirror_ready(consumer)
+                    assert ptr in sets and ptr != last, f"tick {t}: the set handed over"
+                    last = ptr
+                    assert hip.stream_sync(consumer) == 0
+                    o["handed_over"] = hip.download(ptr, shape)
+                outs.append(o)
+        finally:
+            b.sync()
+            hip.stream_destroy(consumer)
+            for p in sets:
+                hip.free(p)
+    return outs
+
+
+@pytest.mark.parametrize("odd", [0, 3], ids=["aligned", "unaligned"])
+@pytest.mark.parametrize("case", MIRROR_CASES)
+def test_bars_mirrors_on_every_family(case, odd):
+    """twins, one with mirror sets and one without: rows, bars and m_last_silent equal bit for bit after every tick (the
+    instantiation that also stores into the mirrors computes what the plain one does), and every set handed over equals bars()"""
+    n, over, name = MIRROR_CASES[case]
+    cfg = _cfg(n, **over)
+    with_m, plain = _run_mirrored(cfg, name, True, odd), _run_mirrored(cfg, name, False, odd)
+    _assert_same(with_m, plain, ticks=range(4), what=f"{case}: mirrors against none")
+    for t, o in enumerate(with_m):
+        assert same(o["handed_over"], o["bars"]), f"{case}: mirror set handed over after tick {t}"
+    assert not same(with_m[0]["bars"], with_m[3]["bars"])  # (the ticks did something)

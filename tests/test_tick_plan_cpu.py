@@ -34,7 +34,7 @@ static const char *name(wf::Family f) {
   case wf::Family::POW2: return "POW2"; case wf::Family::ZERO_PADDED: return "ZERO_PADDED"; case wf::Family::MIXED_RADIX: return "MIXED_RADIX";
   case wf::Family::FIXED_PLAN: return "FIXED_PLAN"; case wf::Family::BLUESTEIN: return "BLUESTEIN"; case wf::Family::WHOLE_65536: return "WHOLE_65536";
   case wf::Family::MR_TWO_ROWS: return "MR_TWO_ROWS"; case wf::Family::MR_ROWS: return "MR_ROWS"; case wf::Family::BLUESTEIN_ROWS: return "BLUESTEIN_ROWS";
-  default: return "DEVICE_MEMORY";
+  default: return "NONE";
   }
 }
 static wf_config config(unsigned n, int layout) {
@@ -112,13 +112,16 @@ def plans(tmp_path_factory):
 
 
 def test_every_legal_size_gets_one_family(plans):
-    """none is refused (DEVICE_MEMORY is what the release library has no kernel for), the layout does not change the family, and the
-    counts per family are those of the GPU sweep over all 4089 sizes"""
+    """none is refused (NONE is what the library has no kernel for), the layout does not change the family, every size above 16384
+    -- but 32768, the last power of two inside a CU's LDS -- takes the one kernel of 65536 or rows of one kind or the other (what
+    retiring the chain through device memory rests on), and the counts per family are those of the GPU sweep over all 4089 sizes"""
     sizes = range(128, 65536 + 1, 16)
     assert len(plans["T"]) == 3 * len(sizes) == 3 * 4089
     for n in sizes:
         fams = {plans["T"][(n, lay)]["family"] for lay in LAYOUTS}
         assert len(fams) == 1 and fams <= set(PATH), (n, fams)
+        if n > 16384:
+            assert fams <= ({"POW2"} if n == 32768 else {"WHOLE_65536", "MR_TWO_ROWS", "MR_ROWS", "BLUESTEIN_ROWS"}), (n, fams)
     got = Counter("ok: " + PATH[plans["T"][(n, "stereo")]["family"]] for n in sizes)
     want = json.loads((PROFILES / "r06z_sizes_all_parity.json").read_text())["by_path"]
     assert dict(got) == want

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/variant.sh NAME "EXTRA FLAGS" -- a development build of the library into variants/lib_NAME.so (travels with gpurun,
-# git-ignored); select it with WF_HIP_LIB=variants/lib_NAME.so.  Built with -DWF_DEV_BUILD: the WF_HIP_* environment overrides of the plan
-# (WF_HIP_LANES, WF_HIP_SPLIT, WF_HIP_RING_PAD, WF_HIP_TLDS ...) exist in these builds only.  e.g. tools/variant.sh t4096 "-DWF_GEOM_ONLY=4096 -DWF_PHASE_TIMING"
+# git-ignored); select it with WF_HIP_LIB=variants/lib_NAME.so.  Built with -DWF_DEV_BUILD: the environment overrides of the plan
+# (WF_HIP_LANES, WF_HIP_BAR_PIECES, WF_HIP_BAR_PS) exist in these builds only.  e.g. tools/variant.sh t4096 "-DWF_GEOM_ONLY=4096 -DWF_PHASE_TIMING"
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../waveform_amd/csrc"

@@ -3,20 +3,17 @@
 // The reference accepts every multiple of 16 up to 65536 samples with "enable large FFT" (src/source.cpp:349, :359-363,
 // :562-565).  Up to 32768 samples (16384 complex points, 132 KB) a spectrum lives in one workgroup's LDS
 // (spectrum_tick_kernel).  Beyond that:
-//   65536 samples                    -> 32768 complex points (the packed real transform)
-//   n = 16400 .. 65520, not 2^k      -> Bluestein (direct form) over L = 32768 / 65536 / 131072 complex points (two transforms)
-// A transform of L = L1 * 16384 points (L1 = 2, 4, 8) is done in two steps through a scratch buffer in device memory
-// (decimation in frequency, n = n1 * 16384 + n2, k = k1 + L1 * k2):
-//   big_columns_kernel   v[k1][n2] = W_L^(n2 k1) * sum_n1 u[n1 * 16384 + n2] W_L1^(n1 k1)      (u = the windowed samples, see MODE)
-//   big_rows_kernel      U[k1 + L1 k2] = sum_n2 v[k1][n2] W_16384^(n2 k2)   -- the 32768-sample geometry's three LDS passes
-// then big_epilogue_kernel does what P4 and the end of spectrum_tick_kernel do (real split or |c_k|, slope, temporal
+//   65536 samples          -> 32768 complex points (the packed real transform): both rows of 16384 points and the end of the tick in
+//                             one kernel (big_whole_kernel)
+//   n = 16400 .. 65520     -> the packed real transform of n/2 = C R points as C rows (decimation in frequency over the columns):
+//                             mixed-radix rows, two of them in one kernel (big_mr_whole_kernel) or up to eight with the column step
+//                             folded into the fetch (big_mr_rows_kernel); else 8 or 16 rows by Bluestein INSIDE LDS
+//                             (big_br_columns_kernel, big_br_rows_kernel) -- which of them: wf_tick_plan.cpp, plan_rows
+// Behind the rows kernels big_epilogue_kernel does what P4 and the end of spectrum_tick_kernel do (real split, slope, temporal
 // smoothing, silence state machine, dBFS, volume normalisation, roll-off; reference src/source_generic.cpp:63-179) on
 // 16384 bins per workgroup, and big_outputs_kernel what render_bars / render_curve derive from the finished rows
 // (src/source.cpp:1360-1425, :1500-1564).  The channels of a stream are coupled as in split mode: "has a non-zero sample"
-// through a word the columns kernel ORs into, "previous row entirely <= floor - 10" through the rotating verdict words.
-//
-// This is the compatibility path (every transform moves its data through L2 / Infinity Cache three times); the sizes
-// the slider produces by default never reach it.
+// through a word the kernel that reads the ring ORs into, "previous row entirely <= floor - 10" through the rotating verdict words.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wf_geometry.hpp"
@@ -29,155 +26,12 @@ namespace wf {
 
 // (GBig, BIG_L2, BIG_TP: wf_geometry.hpp)
 
-struct BigArgs {
-    const float *ring;
-    const uint32_t *wpos;
-    const uint32_t *delay_stream;
-    uint32_t ring_mask, ring_stride, delay, cap_ch;
-    uint32_t n;              // samples per window (m_fft_size)
-    uint32_t L;              // complex points per transform (L1 * 16384)
-    const float *window;     // [n] (MODE 0)
-    const cf *blu_a;         // [L] window_j * conj(w_j), zero from n on (MODE 1)
-    const cf *blu_b;         // [L] FFT_L of the chirp (MODE 2)
-    const cf *tw_big;        // [L1][16384] W_L^(n2 k1)
-    const cf *tw1, *tw2;     // the row transform's tables
-    cf *v;                   // [n_spec][L1][16384] columns' output
-    cf *z;                   // [n_spec][L] rows' output, natural order
-    uint32_t *nz;            // [n_spec] != 0: the window has a non-zero sample
-    uint32_t spec_base;      // first spectrum of this launch
-};
-
-// MODE 0: u[j] = (x[2j] w[2j], x[2j+1] w[2j+1])  (packed real transform of n = 2L samples, reference :97-106)
-// MODE 1: u[j] = x[j] * blu_a[j]                  (Bluestein, first transform: the chirped window)
-// MODE 2: u[j] = conj(z[j] * blu_b[j])            (Bluestein, second transform)
-template<int L1, int MODE> __global__ __launch_bounds__(256) void big_columns_kernel(const BigArgs a)
-{
-    const uint32_t spec = a.spec_base + blockIdx.y;
-    const uint32_t n2 = 2u * (blockIdx.x * 256u + threadIdx.x); // this thread's pair of columns
-    cf u0[L1], u1[L1];
-    uint32_t acc = 0;
-    if constexpr(MODE == 2) {
-        const cf *zin = a.z + (size_t)spec * a.L;
-#pragma unroll
-        for(int n1 = 0; n1 < L1; ++n1) {
-            const uint32_t j = (uint32_t)n1 * BIG_L2 + n2;
-            const f4 s = ld4(reinterpret_cast<const float *>(zin + j));
-            const f4 b = ld4(reinterpret_cast<const float *>(a.blu_b + j));
-            const cf p0 = cmul(cf{s.x, s.y}, cf{b.x, b.y}), p1 = cmul(cf{s.z, s.w}, cf{b.z, b.w});
-            u0[n1] = cf{p0.x, -p0.y};
-            u1[n1] = cf{p1.x, -p1.y};
-        }
-    } else {
-        const uint32_t stream = spec >> (a.cap_ch - 1u);
-        const uint32_t delay = a.delay + (a.delay_stream ? a.delay_stream[stream] : 0u);
-        const uint32_t start = (a.wpos[stream] - delay - a.n) & a.ring_mask;
-        const float *x = a.ring + (size_t)spec * a.ring_stride;
-#pragma unroll
-        for(int n1 = 0; n1 < L1; ++n1) {
-            const uint32_t j = (uint32_t)n1 * BIG_L2 + n2;
-            if constexpr(MODE == 0) {
-                float s[4];
-#pragma unroll
-                for(uint32_t e = 0; e < 4; ++e) {
-                    s[e] = x[(start + 2u * j + e) & a.ring_mask];
-                    acc |= f32_bits(s[e]);
-                }
-                const f4 w = ld4(a.window + 2u * j);
-                u0[n1] = cf{s[0] * w.x, s[1] * w.y};
-                u1[n1] = cf{s[2] * w.z, s[3] * w.w};
-            } else {
-                const bool in0 = j < a.n, in1 = j + 1u < a.n;
-                const float v0 = x[(start + (in0 ? j : 0u)) & a.ring_mask], v1 = x[(start + (in1 ? j + 1u : 0u)) & a.ring_mask];
-                const float s0 = in0 ? v0 : 0.0f, s1 = in1 ? v1 : 0.0f;
-                acc |= f32_bits(s0) | f32_bits(s1);
-                const f4 q = ld4(reinterpret_cast<const float *>(a.blu_a + j));
-                u0[n1] = cf{s0 * q.x, s0 * q.y};
-                u1[n1] = cf{s1 * q.z, s1 * q.w};
-            }
-        }
-    }
-    dft_dif<L1>(u0);
-    dft_dif<L1>(u1);
-    cf *v = a.v + (size_t)spec * a.L;
-    constexpr int LB = ilog2(L1);
-#pragma unroll
-    for(int k1 = 0; k1 < L1; ++k1) {
-        cf c0 = u0[brev(k1, LB)], c1 = u1[brev(k1, LB)];
-        if(k1 > 0) {
-            const f4 w = ld4(reinterpret_cast<const float *>(a.tw_big + (size_t)k1 * BIG_L2 + n2));
-            c0 = cmul(c0, cf{w.x, w.y});
-            c1 = cmul(c1, cf{w.z, w.w});
-        }
-        st4(reinterpret_cast<float *>(v + (size_t)k1 * BIG_L2 + n2), f4{c0.x, c0.y, c1.x, c1.y});
-    }
-    if constexpr(MODE != 2) {
-        // x != 0.0f for any sample of the window (reference :63-72): -0.0f is zero, NaNs are not
-        if(__any((acc & 0x7fffffffu) != 0u) && (threadIdx.x & 63u) == 0u)
-            atomicOr(a.nz + spec, 1u);
-    }
-}
-
-// one row of 16384 points per workgroup: the three LDS passes of the 32768-sample geometry, then out in natural order
-template<int L1> __global__ __launch_bounds__(GBig::T, 4) void big_rows_kernel(const BigArgs a)
-{
-    using G = GBig;
-    constexpr int T = G::T, P = G::P, R1 = G::R1, M1 = G::M1;
-    static_assert(G::B1 == 1, "the row loader fetches one point per pass-1 row");
-    extern __shared__ __attribute__((aligned(16))) unsigned char big_smem[];
-    cf *lds = reinterpret_cast<cf *>(big_smem);
-    cf *tw2_lds = lds + G::LDS_CF;
-    const int t = (int)threadIdx.x;
-    const uint32_t k1 = blockIdx.x, spec = a.spec_base + blockIdx.y;
-    const cf *v = a.v + (size_t)spec * a.L + (size_t)k1 * BIG_L2;
-    TickArgs ta{};
-    ta.tw1 = a.tw1;
-    P1Regs<G> r;
-#pragma unroll
-    for(int j = 0; j < R1; ++j) {
-        const f2 q = ld2(reinterpret_cast<const float *>(v + j * M1 + t));
-        r.smp[j][0] = q.x;
-        r.smp[j][1] = q.y;
-        r.win[j][0] = r.win[j][1] = 1.0f;
-        if(j >= 1 && tw1_row_loaded(j))
-            p1_load_tw1<G>(ta, t, j, r.tw1[j]);
-    }
-    // the pass-2 twiddles by LDS-DMA, as in spectrum_tick_kernel
-    {
-        constexpr int BYTES = G::R2 * G::R3 * (int)sizeof(cf), PER = 64 * 16;
-        const int wave = t >> 6, lane = t & 63;
-#pragma unroll
-        for(int c = 0; c < BYTES / PER; ++c)
-            if((c % (T / 64)) == wave) {
-                const char *g = reinterpret_cast<const char *>(a.tw2) + c * PER + lane * 16;
-                char *l = reinterpret_cast<char *>(tw2_lds) + c * PER;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g, (__attribute__((address_space(3))) void *)l, 16,
-                                                 0, 0);
-            }
-    }
-    p1_window_pass1<G>(ta, t, r, lds);
-    __syncthreads();
-    cf pts[P];
-    p2_read<G>(t, lds, pts);
-    __syncthreads();
-    p2_pass2_write<G>(tw2_lds, t, lds, pts);
-    __syncthreads();
-    p3_read<G>(t, lds, pts);
-    __syncthreads();
-    p3_pass3_write<G>(t, lds, pts);
-    __syncthreads();
-    cf *z = a.z + (size_t)spec * a.L;
-#pragma unroll
-    for(int i = 0; i < P; ++i) {
-        const int k2 = t + T * i;
-        const cf c = lds_ld2(lds, ex3_addr<G>(k2));
-        *reinterpret_cast<f2 *>(z + (size_t)k1 + (size_t)L1 * k2) = f2{c.x, c.y};
-    }
-}
+// dynamic LDS of a workgroup that transforms rows of 16384 points on the 32768-sample geometry: the exchange buffer and the pass-2
+// twiddles (big_whole_kernel)
 template<int L1> constexpr size_t big_rows_lds_bytes() { return (size_t)GBig::LDS_CF * sizeof(cf) + (size_t)GBig::R2 * GBig::R3 * sizeof(cf) + 16; }
 
 // ---- epilogue ------------------------------------------------------------------------------------------------------
 // MODE 1: bins from the packed transform Z of big_m points: 2X[k] = (Z[k] + conj Z[m-k]) - i W_2m^k (Z[k] - conj Z[m-k])
-// MODE 2: bins are |c_k| of the Bluestein convolution
 template<int MODE, bool TS, bool FPK>
 WF_DEV void p4_big_impl(const TickArgs &a, int t, int kbase, int nb, const cf *z, float *ts, float (&mag)[GBig::P])
 {
@@ -211,23 +65,18 @@ WF_DEV void p4_big_impl(const TickArgs &a, int t, int kbase, int nb, const cf *z
             const f4 za = ld4(reinterpret_cast<const float *>(z + kk)), zb = ld4(reinterpret_cast<const float *>(z + kk + 2));
             A[0] = cf{za.x, za.y}; A[1] = cf{za.z, za.w}; A[2] = cf{zb.x, zb.y}; A[3] = cf{zb.z, zb.w};
         }
-        if constexpr(MODE == 1 || MODE == 3) {
-            const f4 wa = ld4(reinterpret_cast<const float *>(a.big_tws + kk)), wb = ld4(reinterpret_cast<const float *>(a.big_tws + kk + 2));
-            const cf W[4] = {cf{wa.x, wa.y}, cf{wa.z, wa.w}, cf{wb.x, wb.y}, cf{wb.z, wb.w}};
+        static_assert(MODE == 1 || MODE == 3);
+        const f4 wa = ld4(reinterpret_cast<const float *>(a.big_tws + kk)), wb = ld4(reinterpret_cast<const float *>(a.big_tws + kk + 2));
+        const cf W[4] = {cf{wa.x, wa.y}, cf{wa.z, wa.w}, cf{wb.x, wb.y}, cf{wb.z, wb.w}};
 #pragma unroll
-            for(int i = 0; i < 4; ++i) {
-                const int km = (kk + i) == 0 ? 0 : m - kk - i; // Z[m] is Z[0]; m need not be a power of two
-                const f2 bq = ld2(reinterpret_cast<const float *>(MODE == 3 ? zt(km) : z + km));
-                const float er = A[i].x + bq.x, ei = A[i].y - bq.y;
-                const float dr = A[i].x - bq.x, di = A[i].y + bq.y;
-                const float pr = fmaf(W[i].x, dr, -(W[i].y * di));
-                const float pi = fmaf(W[i].x, di, W[i].y * dr);
-                mag[4 * u + i] = mag2(er + pi, ei - pr) * a.half_coef;
-            }
-        } else {
-#pragma unroll
-            for(int i = 0; i < 4; ++i)
-                mag[4 * u + i] = mag2(A[i].x, A[i].y) * a.half_coef;
+        for(int i = 0; i < 4; ++i) {
+            const int km = (kk + i) == 0 ? 0 : m - kk - i; // Z[m] is Z[0]; m need not be a power of two
+            const f2 bq = ld2(reinterpret_cast<const float *>(MODE == 3 ? zt(km) : z + km));
+            const float er = A[i].x + bq.x, ei = A[i].y - bq.y;
+            const float dr = A[i].x - bq.x, di = A[i].y + bq.y;
+            const float pr = fmaf(W[i].x, dr, -(W[i].y * di));
+            const float pi = fmaf(W[i].x, di, W[i].y * dr);
+            mag[4 * u + i] = mag2(er + pi, ei - pr) * a.half_coef;
         }
         const float sl4[4] = {sv.x, sv.y, sv.z, sv.w}, st4v[4] = {st.x, st.y, st.z, st.w};
         p4_slope_smooth_group<G, TS, FPK>(a, t, u, ts, st4v, sl4, mag);
@@ -364,7 +213,7 @@ template<int MODE> __global__ __launch_bounds__(GBig::T, 4) void big_epilogue_ke
 // leaves two independent 16384-point rows, and row k1 delivers exactly the bins of parity k1: U[k1 + 2 k2].  The real split
 // pairs bin k with bin m - k (m = 32768) -- the SAME parity -- so a row needs nothing from the other one.  big_whole_kernel
 // therefore (1) forms the rows' inputs itself: windowed sample pairs straight from the ring, u0 + u1 for row 0 and
-// (u0 - u1) W_L^n2 for row 1 (what big_columns_kernel writes to a scratch buffer for the other sizes), (2) transforms row 0 and
+// (u0 - u1) W_L^n2 for row 1 (the column step of the other sizes up here), (2) transforms row 0 and
 // then row 1 in the exchange buffer, each followed by its real split into registers, and (3) finishes the tick from those
 // registers.  Device-memory traffic per transform: 26 N bytes (columns, rows, epilogue: round 2) -> 18 N (round 3: rows with the
 // column step and the split folded in, magnitudes through memory, epilogue) -> 10 N, what the tick itself needs; three kernels ->

@@ -1,9 +1,8 @@
-// wf_big_dispatch.hip -- kernel dispatch of the FFT sizes whose transform does not fit a CU's LDS (wf_big.hpp: 65536 samples and
-// the other sizes above 16384: columns -> rows (twice for Bluestein) -> epilogue -> outputs through device memory), and of
+// wf_big_dispatch.hip -- kernel dispatch of the FFT sizes whose transform does not fit a CU's LDS (wf_big.hpp: 65536 samples in one
+// kernel; the other sizes above 16384 as rows -- mixed radix, or Bluestein inside LDS -- then the epilogue), and of
 // big_outputs_kernel for the displays that are finished behind the tick kernel from its stored rows.  gfx950 only.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 
 #include "wf_hip_internal.hpp"
 #include "wf_big.hpp"
@@ -30,65 +29,6 @@ int launch_tick_big_whole(wf_hip *h, const wf::TickArgs &a0, bool aligned, hipSt
     WF_HIP_TRY(h, hipGetLastError());
     return WF_HIP_OK;
 }
-
-#ifdef WF_DEV_BUILD
-// The chain through device memory: columns -> rows (twice, with a pointwise product in between, for Bluestein's direct form) ->
-// epilogue.  Rounds 2-4 ran the sizes above 16384 on it; since round 5 every legal size has a faster path (big_whole_kernel, mixed-radix
-// rows, Bluestein rows inside LDS), and the chain is compiled into the development builds only, as the A/B baseline
-// (WF_HIP_BIG_WHOLE=0, WF_HIP_NO_MIXED_RADIX=1 + WF_HIP_NO_BLUESTEIN_ROWS=1).
-template<int L1> int launch_tick_big_l(wf_hip *h, const wf::TickArgs &a0, hipStream_t st)
-{
-    const uint32_t n_spec = a0.stream_count * a0.cap_ch;
-    wf::BigArgs b{};
-    b.ring = a0.ring;
-    b.wpos = a0.wpos;
-    b.delay_stream = a0.delay_stream;
-    b.ring_mask = a0.ring_mask;
-    b.ring_stride = a0.ring_stride;
-    b.delay = a0.delay;
-    b.cap_ch = a0.cap_ch;
-    b.n = h->N;
-    b.L = h->plan.big_l;
-    b.window = a0.window;
-    b.blu_a = a0.blu_a;
-    b.blu_b = a0.blu_b;
-    b.tw_big = a0.big_tw;
-    b.tw1 = a0.tw1;
-    b.tw2 = a0.tw2;
-    b.v = h->d_big_v;
-    b.z = const_cast<wf::cf *>(a0.big_z); // (TickArgs carries the epilogue's read-only view of the scratch)
-    b.nz = a0.big_nz_out;
-    b.spec_base = a0.stream_base * a0.cap_ch;
-    WF_HIP_TRY(h, hipMemsetAsync(a0.big_nz_out + b.spec_base, 0, (size_t)n_spec * sizeof(uint32_t), st));
-    const dim3 gcol(wf::BIG_L2 / 512u, n_spec), grow(L1, n_spec);
-    const size_t rows_lds = wf::big_rows_lds_bytes<L1>();
-    if(h->plan.blu) {
-        hipLaunchKernelGGL((wf::big_columns_kernel<L1, 1>), gcol, dim3(256), 0, st, b);
-        hipLaunchKernelGGL((wf::big_rows_kernel<L1>), grow, dim3(wf::GBig::T), rows_lds, st, b);
-        hipLaunchKernelGGL((wf::big_columns_kernel<L1, 2>), gcol, dim3(256), 0, st, b);
-        hipLaunchKernelGGL((wf::big_rows_kernel<L1>), grow, dim3(wf::GBig::T), rows_lds, st, b);
-    } else {
-        hipLaunchKernelGGL((wf::big_columns_kernel<L1, 0>), gcol, dim3(256), 0, st, b);
-        hipLaunchKernelGGL((wf::big_rows_kernel<L1>), grow, dim3(wf::GBig::T), rows_lds, st, b);
-    }
-    const uint32_t parts = (h->M + (uint32_t)wf::BIG_TP - 1u) / (uint32_t)wf::BIG_TP;
-    // mono mixdown: channel 1 of every stream, then channel 0 (TickArgs::split_ch)
-    for(int pass = 0; pass < (h->plan.split_mono ? 2 : 1); ++pass) {
-        wf::TickArgs a = a0;
-        a.split_ch = h->plan.split_mono ? (uint32_t)(1 - pass) : 0xffffffffu;
-        const dim3 grid(parts, h->plan.split_mono ? a.stream_count : n_spec);
-        if(h->plan.blu)
-            hipLaunchKernelGGL((wf::big_epilogue_kernel<2>), grid, dim3(wf::GBig::T), 0, st, a);
-        else
-            hipLaunchKernelGGL((wf::big_epilogue_kernel<1>), grid, dim3(wf::GBig::T), 0, st, a);
-    }
-    if(a0.bar.out != nullptr)
-        hipLaunchKernelGGL(wf::big_outputs_kernel, dim3(a0.stream_count * a0.bar.disp_ch), dim3(wf::GBig::T), h->disp.big_out_lds, st, a0);
-    WF_HIP_TRY(h, hipGetLastError());
-    return WF_HIP_OK;
-}
-
-#endif // WF_DEV_BUILD
 
 // fft sizes above 16384 whose n/2 is two rows of a mixed-radix transform: both rows and the end of the tick in one workgroup
 // (wf_big.hpp: big_mr_whole_kernel)
@@ -169,12 +109,7 @@ int launch_tick_big_part(wf_hip *h, const wf::TickArgs &s, bool aligned, hipStre
     case wf::Family::MR_ROWS: return launch_tick_big_mr(h, s, st);
     case wf::Family::BLUESTEIN_ROWS: return h->plan.big_rows == 16u ? launch_tick_big_br_g<16>(h, s, st) : launch_tick_big_br_g<8>(h, s, st);
     case wf::Family::WHOLE_65536: return launch_tick_big_whole(h, s, aligned, st);
-    default:
-#ifdef WF_DEV_BUILD
-        return h->plan.big_rows == 2 ? launch_tick_big_l<2>(h, s, st) : h->plan.big_rows == 4 ? launch_tick_big_l<4>(h, s, st) : launch_tick_big_l<8>(h, s, st);
-#else
-        return fail(h, WF_HIP_ERR_UNSUPPORTED, "fft_size %u: no kernel for this size in this build", h->N); // (unreachable: setup_launch_big refuses)
-#endif
+    default: return fail(h, WF_HIP_ERR_UNSUPPORTED, "fft_size %u: no kernel for this size in this build", h->N); // (unreachable: setup_launch_big refuses)
     }
 }
 
@@ -192,22 +127,12 @@ int launch_tick_big(wf_hip *h, const wf::TickArgs &a, bool aligned, hipStream_t 
     return WF_HIP_OK;
 }
 
-#ifdef WF_DEV_BUILD
-template<int L1> int setup_big_rows(wf_hip *h)
-{
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::big_rows_kernel<L1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)wf::big_rows_lds_bytes<L1>()));
-    return WF_HIP_OK;
-}
-#endif
-
 } // namespace
 
 namespace wf::host {
 
 int setup_launch_big(wf_hip *h)
 {
-    int rc = WF_HIP_OK;
     const wf::TransformPlan &t = h->plan;
     if(t.big_mr()) {
         WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::big_mr_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -222,18 +147,9 @@ int setup_launch_big(wf_hip *h)
                                           (int)wf::big_br_lds_bytes<wf::G8192>()));
         WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::big_br_rows_kernel<wf::G16384>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)wf::big_br_lds_bytes<wf::G16384>()));
-    } else {
-#ifdef WF_DEV_BUILD
-        rc = t.big_rows == 2 ? setup_big_rows<2>(h) : t.big_rows == 4 ? setup_big_rows<4>(h) : setup_big_rows<8>(h);
-#else
-        if(t.family != wf::Family::WHOLE_65536) // (no legal size gets here: every multiple of 16 above 16384 has rows of one kind or the other)
-            return fail(h, WF_HIP_ERR_UNSUPPORTED, "fft_size %u: neither a power of two nor a length with a row decomposition (a multiple of 16 has one)", h->N);
-#endif
-    }
-    if(rc)
-        return rc;
+    } else if(!t.big_whole()) // (Family::NONE; no legal size gets here: every multiple of 16 above 16384 has rows of one kind or the other)
+        return fail(h, WF_HIP_ERR_UNSUPPORTED, "fft_size %u: neither a power of two nor a length with a row decomposition (a multiple of 16 has one)", h->N);
     // fft_size 65536 (the one power of two up here): both rows and the end of the tick in one kernel, no scratch in device memory
-    // (PlanOverrides::big_whole, development builds: through the columns -> rows -> epilogue chain instead)
     if(t.big_whole()) {
         WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::big_whole_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)wf::big_rows_lds_bytes<2>()));
@@ -258,14 +174,8 @@ int setup_launch_big(wf_hip *h)
     } else if(t.big_br())
         snprintf(name, sizeof(name), "big_br_{columns,rows}_kernel + big_epilogue_kernel<N=%u: %u rows of %u complex points by Bluestein over %u points inside LDS>",
                  h->N, t.big_rows, h->M / t.big_rows, t.br_l);
-    else if(t.big_whole())
-        snprintf(name, sizeof(name), "big_whole_kernel<N=%u: both rows of 16384 complex points and the end of the tick in one workgroup>", h->N);
-    else if(t.blu)
-        snprintf(name, sizeof(name), "big_{columns,rows,epilogue}_kernel<N=%u by Bluestein over %u = %u x 16384 complex points through device memory>",
-                 h->N, t.big_l, t.big_rows);
     else
-        snprintf(name, sizeof(name), "big_{columns,rows,epilogue}_kernel<N=%u: %u = %u x 16384 complex points through device memory>", h->N,
-                 t.big_l, t.big_rows);
+        snprintf(name, sizeof(name), "big_whole_kernel<N=%u: both rows of 16384 complex points and the end of the tick in one workgroup>", h->N);
     h->kernel_name = name;
     return WF_HIP_OK;
 }

@@ -108,7 +108,6 @@ struct wf_hip {
     uint32_t waves_per_spectrum = 1;
     bool verdict_tracking = false;
     bool split = false;              // the channels of a stream run in different workgroups (spectrum_tick_kernel<.., SPLIT>)
-    wf::cf *d_big_v = nullptr;       // the columns' output of the chain through device memory (development builds: wf_big.hpp BigArgs::v)
     int interp_shape[2] = {0, 0};    // {tab.interp_radius, tab.interp_taps} (WF_HIP_TABLE_INTERP_SHAPE)
     float *d_bars = nullptr;
     float *d_bars_pre = nullptr;    // BarArgs::pre_out: [n_streams][disp_ch], mirrored displays only
@@ -228,8 +227,7 @@ struct wf_hip {
     // the whole float range: the first ticks behind a reset through a narrow window, a few samples under sin^16 tails, give
     // |X| ~ 1e-26).  Headroom: N * amplitude * in_scale squared must stay below FLT_MAX; the factor is 2^40 up to 4096 samples and
     // halves with every doubling beyond (wf::plan_transform), which keeps the overflow point at an amplitude of 4096 (+72 dBFS) from
-    // 4096 samples up (the reference's hypotf overflows far later still: a stated deviation).  Bluestein
-    // through device memory squares values that still carry its factor L: 2^24 there.  (plan.in_scale)
+    // 4096 samples up (the reference's hypotf overflows far later still: a stated deviation).  (plan.in_scale)
     uint8_t *d_mask = nullptr;
     size_t mask_bytes = 0;
     float *d_stage = nullptr;

@@ -73,33 +73,11 @@ namespace {
 
 using namespace wf::host;
 
-// The development overrides of the plan, from the environment (development builds only; wf_tick_plan.hpp says what each does)
+// The development overrides of the plan, from the environment (development builds only; tests/lanes_child.py sets the one there is)
 wf::PlanOverrides read_overrides()
 {
     wf::PlanOverrides ov;
 #ifdef WF_DEV_BUILD
-    if(const char *e = std::getenv("WF_HIP_NO_MIXED_RADIX")) // (A/B against Bluestein)
-        ov.mixed_radix = e[0] != '1';
-    if(const char *e = std::getenv("WF_HIP_NO_BLUESTEIN_ROWS")) // (A/B against Bluestein through device memory)
-        ov.bluestein_rows = e[0] != '1';
-    if(const char *e = std::getenv("WF_HIP_BR_ROWS"))
-        ov.br_first = std::atoi(e) == 8 ? 8u : 16u;
-    if(const char *e = std::getenv("WF_HIP_MR_WHOLE"))
-        ov.mr_whole = e[0] != '0';
-    if(const char *e = std::getenv("WF_HIP_BIG_WHOLE"))
-        ov.big_whole = e[0] != '0';
-    if(const char *e = std::getenv("WF_HIP_SPLIT"))
-        ov.split = e[0] == '1' ? 1 : 0;
-    if(const char *e = std::getenv("WF_HIP_MR_PLAN"))
-        for(const char *q = e; *q && ov.mr_plan_n < 4;) {
-            ov.mr_plan[ov.mr_plan_n++] = std::atoi(q);
-            while(*q && *q != ',') ++q;
-            if(*q == ',') ++q;
-        }
-    if(const char *e = std::getenv("WF_HIP_MR_SMALL"))
-        ov.mr_small = e[0] != '0';
-    if(const char *e = std::getenv("WF_HIP_MR_PLAN_KERNEL"))
-        ov.mr_plan_kernel = e[0] != '0';
     if(const char *e = std::getenv("WF_HIP_LANES"))
         ov.lanes = std::max(1, std::atoi(e));
 #endif
@@ -107,7 +85,7 @@ wf::PlanOverrides read_overrides()
 }
 
 // ---- validate and plan: everything that needs no device ------------------------------------------------------------------
-int plan_handle(const wf_config *cfg_in, int device, uint32_t max_streams, uint32_t ring_frames, const wf::PlanOverrides &ov, wf_hip **out)
+int plan_handle(const wf_config *cfg_in, int device, uint32_t max_streams, uint32_t ring_frames, wf_hip **out)
 {
     wf::HostTables tab;
     wf_config cfg = *cfg_in;
@@ -149,7 +127,7 @@ int plan_handle(const wf_config *cfg_in, int device, uint32_t max_streams, uint3
     h->disp_ch = h->tab.display_channels;
     h->num_bars = (uint32_t)h->tab.num_bars;
     h->ring_cap = next_pow2(ring_frames ? std::max(ring_frames, h->N) : std::max(2 * h->N, 4096u));
-    h->plan = wf::plan_transform(cfg, ov);
+    h->plan = wf::plan_transform(cfg, wf::PlanOverrides{});
     h->tick.mr.passes = h->plan.passes;
     std::copy(h->plan.radix, h->plan.radix + 4, h->tick.mr.radix);
     h->wave = cfg.waveform != 0;
@@ -162,13 +140,8 @@ int plan_handle(const wf_config *cfg_in, int device, uint32_t max_streams, uint3
     // Deep rings (a window of fft_size samples somewhere in a row of >= 256 KB) with a power-of-two row stride put every
     // stream's window at the same offset modulo the stride; 64 KB + 256 B of padding per row spreads them over the memory
     // channels: +2.5-4 % on the 1 MB rows of bench.py (60.0-60.3 -> 61.7-63.2 % of peak, three interleaved runs), nothing
-    // to gain on shallow rings.  WF_HIP_RING_PAD=<floats> overrides (development aid).
-    uint32_t pad = h->ring_cap >= 65536u ? 16448u : 0u;
-#ifdef WF_DEV_BUILD
-    if(const char *e = std::getenv("WF_HIP_RING_PAD"))
-        pad = (uint32_t)std::strtoul(e, nullptr, 10) & ~3u;
-#endif
-    h->ring_stride = h->ring_cap + pad;
+    // to gain on shallow rings.
+    h->ring_stride = h->ring_cap + (h->ring_cap >= 65536u ? 16448u : 0u);
     if(h->wave)
         fill_wave_args(h, wave_samples);
     return WF_HIP_OK;
@@ -310,12 +283,7 @@ int plan_curve(wf_hip *h, DisplayRoom &room)
     wf::CurveLaneTables cl;
     // mono mixdown with both channels of a stream in one workgroup: the one displayed row is finished by the threads
     // of both spectra (spectrum_tick_kernel, BarArgs::both_subs) -- the kernels that exist with BOTH: wf_tick_geom.hip, setup_launch
-    bool both = !cfg->stereo && cfg->capture_channels == 2 && !room.own_kernel && !h->plan.want_split && !h->plan.blu && h->N >= 1024u;
-#ifdef WF_DEV_BUILD
-    both = both && std::getenv("WF_HIP_TLDS") == nullptr;
-    if(const char *e = std::getenv("WF_HIP_CURVE_BOTH"))
-        both = both && e[0] != '0';
-#endif
+    const bool both = !cfg->stereo && cfg->capture_channels == 2 && !room.own_kernel && !h->plan.want_split && !h->plan.blu && h->N >= 1024u;
     b.both_subs = both ? 1 : 0;
     if(both)
         room.threads *= 2;
@@ -377,12 +345,8 @@ int plan_bar_layout(wf_hip *h, const DisplayRoom &room)
         WF_HIP_TRY(h, hipStreamSynchronize(h->stream)); // the staging vectors die here
     }
     // (wave-local layout: no workgroup barrier inside the reduction; not with the filter, whose inputs are staged by
-    // bar index behind a barrier anyway.  WF_HIP_BARS_WAVE_LOCAL=0: the plain layout, development aid)
-    bool local = h->tab.gauss_radius == 0;
-#ifdef WF_DEV_BUILD
-    if(const char *e = std::getenv("WF_HIP_BARS_WAVE_LOCAL"))
-        local = local && e[0] != '0';
-#endif
+    // bar index behind a barrier anyway)
+    const bool local = h->tab.gauss_radius == 0;
     if(!b.piece_mode && b.ps_lanes == 0 && wf::bar_segments(h->tab, threads, points / 4 + 2, lanes, local)) {
         b.wave_local = lanes.wave_local ? 1 : 0;
         b.num_segs = lanes.num_segs;
@@ -411,11 +375,7 @@ int plan_own_kernel_display(wf_hip *h)
     b.big_num_tasks = 0;
     if(!b.curve && !h->tab.bar_off.empty()) {
         std::vector<int> task, bar_task(h->tab.bar_off.size(), 0);
-        int cap = 2048;
-#ifdef WF_DEV_BUILD
-        if(const char *e = std::getenv("WF_HIP_BIG_TASK")) // (development: the task size, a multiple of 64)
-            cap = std::max(64, std::atoi(e) & ~63);
-#endif
+        const int cap = 2048;
         for(size_t bq = 0; bq + 1 < h->tab.bar_off.size(); ++bq) {
             bar_task[bq] = (int)(task.size() / 4);
             const int e0 = h->tab.bar_off[bq], e1 = h->tab.bar_off[bq + 1];
@@ -549,11 +509,6 @@ int plan_display(wf_hip *h)
         return WF_HIP_OK;
     const size_t mark = h->allocs.size();
     int orc = plan_outputs(h, false);
-#ifdef WF_DEV_BUILD
-    if(const char *e = std::getenv("WF_HIP_EXT_OUTPUTS")) // 1: the display from the stored rows by big_outputs_kernel even where the tick kernel could finish it (A/B)
-        if(e[0] == '1' && orc == WF_HIP_OK)
-            orc = WF_HIP_ERR_UNSUPPORTED;
-#endif
     if(orc == WF_HIP_ERR_UNSUPPORTED && h->plan.big_l == 0) {
         // give back what the first plan uploaded, forget what it decided, plan again for big_outputs_kernel
         WF_HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -700,7 +655,7 @@ int upload_big_tables(wf_hip *h, const std::vector<wf::cfloat> &br_rowtw)
     wf::TickArgs &a = h->tick;
     const wf::TransformPlan &t = h->plan;
     std::vector<wf::cfloat> twb, twsb;
-    wf::build_big_twiddles(t.big_l, t.big_rows, t.blu ? 0u : h->N, twb, twsb);
+    wf::build_big_twiddles(t.big_l, t.big_rows, h->N, twb, twsb);
     WF_TRY_RC(upload(h, &a.big_tw, t.big_br() ? br_rowtw : twb));
     WF_TRY_RC(upload(h, &a.big_tws, twsb));
     WF_HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -708,16 +663,13 @@ int upload_big_tables(wf_hip *h, const std::vector<wf::cfloat> &br_rowtw)
     if(t.big_whole() || t.big_mrw()) { // (fft_size 65536 and the two-row mixed-radix sizes: no scratch at all, the magnitudes stay in registers)
     } else if(t.big_br()) { // (columns -> rows in place -> epilogue)
         WF_TRY_RC(dev_alloc(h, &z, spectra(h) * t.big_rows * t.br_rs));
-    } else if(t.big_mr()) { // (the rows read the ring themselves: one scratch buffer, for Z)
-        WF_TRY_RC(dev_alloc(h, &z, spectra(h) * t.big_l));
-    } else {
-        WF_TRY_RC(dev_alloc(h, &h->d_big_v, spectra(h) * t.big_l));
+    } else { // (mixed-radix rows: they read the ring themselves: one scratch buffer, for Z)
         WF_TRY_RC(dev_alloc(h, &z, spectra(h) * t.big_l));
     }
     a.big_z = z;
     WF_TRY_RC(dev_alloc(h, &a.big_nz_out, spectra(h)));
     a.big_nz = a.big_nz_out;
-    a.big_m = t.blu ? 0u : h->N / 2;
+    a.big_m = h->N / 2;
     a.big_l = t.big_br() ? t.big_rows * t.br_rs : t.big_l;
     a.big_rs = t.br_rs;
     return WF_HIP_OK;
@@ -742,9 +694,9 @@ int upload_fft_tables(wf_hip *h)
 }
 
 // ---- the lanes ---------------------------------------------------------------------------------------------------------
-int open_lanes(wf_hip *h, int cu_count, const wf::PlanOverrides &ov)
+int open_lanes(wf_hip *h, int cu_count)
 {
-    int lanes = wf::plan_lanes(h->plan, h->n_streams, h->cap_ch, h->num_bars, h->wg_lds, h->wg_threads, cu_count, ov);
+    int lanes = wf::plan_lanes(h->plan, h->n_streams, h->cap_ch, h->num_bars, h->wg_lds, h->wg_threads, cu_count, read_overrides());
 #ifdef WF_PHASE_TIMING
     lanes = 1;
 #endif
@@ -769,8 +721,6 @@ void fill_tick_constants(wf_hip *h)
     a.split_ch = 0xffffffffu;
     a.half_coef = 0.5f * (2.0f / h->tab.window_sum); // mag_coefficient (reference src/source_generic.cpp:110), halved: the
                                                      // kernel produces 2X[k] from the real split
-    if(t.blu && t.big_l) // direct form: |c_k| / L, times mag_coefficient (the packed form's tables carry the 1 / L, and its real split the 1 / 2)
-        a.half_coef = (2.0f / h->tab.window_sum) / (float)t.big_l;
     a.half_coef *= 1.0f / t.in_scale; // the window tables on the device carry in_scale
     a.slope_step = h->tab.slope.empty() ? 0.0f : (float)(3.0 * (double)h->cfg.slope / (double)(h->M - 1));
     a.row_bins = h->M;
@@ -795,7 +745,7 @@ void fill_tick_constants(wf_hip *h)
 }
 
 // the stages of wf_hip_create behind the plan, in order
-int build_handle(wf_hip *h, const wf::PlanOverrides &ov)
+int build_handle(wf_hip *h)
 {
     int cu_count = 0;
     WF_TRY_RC(open_device(h, &cu_count));
@@ -809,7 +759,7 @@ int build_handle(wf_hip *h, const wf::PlanOverrides &ov)
     WF_TRY_RC(upload_window_tables(h));
     WF_TRY_RC(plan_display(h));
     WF_TRY_RC(upload_fft_tables(h));
-    WF_TRY_RC(open_lanes(h, cu_count, ov));
+    WF_TRY_RC(open_lanes(h, cu_count));
     fill_tick_constants(h);
     return finish_create(h);
 }
@@ -825,10 +775,9 @@ int wf_hip_create(const wf_config *cfg, int device, uint32_t max_streams, uint32
     *out = nullptr;
     if(cfg == nullptr || max_streams == 0)
         return fail(nullptr, WF_HIP_ERR_INVALID, "cfg is NULL or max_streams is 0");
-    const wf::PlanOverrides ov = read_overrides();
     wf_hip *h = nullptr;
-    WF_TRY_RC(plan_handle(cfg, device, max_streams, ring_frames, ov, &h));
-    const int rc = build_handle(h, ov);
+    WF_TRY_RC(plan_handle(cfg, device, max_streams, ring_frames, &h));
+    const int rc = build_handle(h);
     if(rc != WF_HIP_OK) {
         g_create_error = h->last_error;
         wf_hip_destroy(h);

@@ -1,10 +1,9 @@
 // wf_tick_geom.hip -- kernel dispatch of ONE FFT geometry: compiled once per geometry (-DWF_TU_GEOM=512 ... 32768, see the
-// Makefile), so that the ~70 instantiations of spectrum_tick_kernel build in parallel instead of in one translation unit.
+// Makefile), so that the 270 instantiations of spectrum_tick_kernel build in parallel instead of in one translation unit.
 // Host side: the launch functions wf_hip_tick calls through wf_hip::launch, and setup_tick_<N>() which wf_hip_create
 // (wf_hip_plan.hip) calls to map the handle's finished plan (wf_hip::plan, wf_tick_plan.hpp) to one of them; nothing is planned here.  gfx950 only.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 
 #include "wf_hip_internal.hpp"
 #include "wf_kernels.hpp"
@@ -22,85 +21,43 @@ using wf::host::fail;
 // else (DISP 0); with MIR the stores into wf_hip_set_bars_mirrors' buffers.  One launch = one of them, picked here.
 inline int display_kind(const wf::TickArgs &a)
 {
-#ifdef WF_DEV_BUILD
-    static const bool off = getenv("WF_HIP_DISP") && atoi(getenv("WF_HIP_DISP")) == 0; // (A/B aid: the general instantiation for everything)
-    if(off)
-        return 0;
-#endif
     if(a.bar.out == nullptr)
         return 2;
     return (a.bar.ps_lanes > 0 && a.bar.curve == 0) ? 1 : 0;
 }
-template<class G, int SPW, bool ALIGNED, bool SPLIT, int DEC, bool TLDS, bool BOTH, bool MIR, int DISP>
-void launch_pow2_one(dim3 grid, dim3 block, size_t lds, hipStream_t st, const wf::TickArgs &a)
-{
-    hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .aligned = ALIGNED, .split = SPLIT, .dec = DEC, .tlds = TLDS, .both = BOTH, .mir = MIR, .disp = DISP}>), grid,
-                       block, lds, st, a);
-}
-// SPECIAL: whether this family has display-specific instantiations at all (the curve-sharing and decimated kernels keep the general one)
-template<class G, int SPW, bool SPLIT, int DEC, bool TLDS, bool BOTH, bool SPECIAL>
-void launch_pow2(dim3 grid, dim3 block, size_t lds, hipStream_t st, const wf::TickArgs &a, bool aligned)
-{
-    constexpr bool SPLIT_MIR = SPLIT; // (the split kernels serve the mirrors in their only instantiation: spectrum_tick_kernel's MIRROR)
-    const bool mir = !SPLIT_MIR && a.bar.out2_n > 0;
-    const int disp = SPECIAL ? display_kind(a) : 0;
-#define WF_L(AL, MIR_, DISP_) launch_pow2_one<G, SPW, AL, SPLIT, DEC, TLDS, BOTH, MIR_, DISP_>(grid, block, lds, st, a)
-    if constexpr(SPECIAL) {
-        if(disp == 2) {
-            if(aligned) WF_L(true, false, 2); else WF_L(false, false, 2);
-            return;
-        }
-        if(disp == 1) {
-            if constexpr(SPLIT_MIR) {
-                if(aligned) WF_L(true, false, 1); else WF_L(false, false, 1);
-            } else if(mir) {
-                if(aligned) WF_L(true, true, 1); else WF_L(false, true, 1);
-            } else {
-                if(aligned) WF_L(true, false, 1); else WF_L(false, false, 1);
-            }
-            return;
-        }
+using TickKernel = void (*)(wf::TickArgs);
+
+// What a launch of a power-of-two family can ask for -- aligned or not, mirrors or not, display kind 0 / 1 / 2 -- and the
+// instantiation that serves it.  The family is everything a launch cannot change; SPECIAL: whether it has display-specific
+// instantiations at all (the curve-sharing and decimated kernels keep the general one).  kernel<>() holds the rules that prune the
+// 12 requests to the instantiations that exist, once; setup walks the table, the launch indexes it.
+template<class G, int SPW, bool SPLIT, int DEC, bool TLDS, bool BOTH, bool SPECIAL> struct Pow2Family {
+    template<bool AL, bool MIR, int DISP> static constexpr TickKernel kernel()
+    {
+        constexpr int disp = SPECIAL ? DISP : 0;
+        // the split kernels serve the mirrors in their only instantiation (spectrum_tick_kernel's MIRROR); no display, no mirrors
+        constexpr bool mir = MIR && !SPLIT && disp != 2;
+        constexpr bool al = AL && !(DEC > 0 && mir); // (the decimated sizes with mirrors: the scalar fetch for both alignments)
+        return &wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .aligned = al, .split = SPLIT, .dec = DEC, .tlds = TLDS, .both = BOTH, .mir = mir, .disp = disp}>;
     }
-    if constexpr(SPLIT_MIR) {
-        if(aligned) WF_L(true, false, 0); else WF_L(false, false, 0);
-    } else if(mir) {
-        if constexpr(DEC > 0)
-            WF_L(false, true, 0); // (the decimated sizes: the scalar fetch for both alignments)
-        else {
-            if(aligned) WF_L(true, true, 0); else WF_L(false, true, 0);
-        }
-    } else {
-        if(aligned) WF_L(true, false, 0); else WF_L(false, false, 0);
+    static constexpr TickKernel table[2][2][3] = {
+        {{kernel<false, false, 0>(), kernel<false, false, 1>(), kernel<false, false, 2>()}, {kernel<false, true, 0>(), kernel<false, true, 1>(), kernel<false, true, 2>()}},
+        {{kernel<true, false, 0>(), kernel<true, false, 1>(), kernel<true, false, 2>()}, {kernel<true, true, 0>(), kernel<true, true, 1>(), kernel<true, true, 2>()}}};
+
+    static void launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const wf::TickArgs &a, bool aligned)
+    {
+        hipLaunchKernelGGL(table[aligned][a.bar.out2_n > 0][display_kind(a)], grid, block, lds, st, a);
     }
-#undef WF_L
-}
-template<class G, int SPW, bool SPLIT, int DEC, bool TLDS, bool BOTH, bool SPECIAL>
-int setup_pow2_lds(wf_hip *h, int lds)
-{
-#define WF_A(AL, MIR_, DISP_)                                                                                                                  \
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(                                                                          \
-                                          &wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .aligned = AL, .split = SPLIT, .dec = DEC, .tlds = TLDS, .both = BOTH, .mir = MIR_, .disp = DISP_}>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-    WF_A(true, false, 0);
-    WF_A(false, false, 0);
-    if constexpr(!SPLIT) {
-        WF_A(false, true, 0);
-        if constexpr(DEC == 0)
-            WF_A(true, true, 0);
+    // (entries that alias after pruning get the attribute once more: the same value)
+    static int setup_lds(wf_hip *h, int lds)
+    {
+        for(const auto &by_mir : table)
+            for(const auto &by_disp : by_mir)
+                for(const TickKernel k : by_disp)
+                    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        return WF_HIP_OK;
     }
-    if constexpr(SPECIAL) {
-        WF_A(true, false, 1);
-        WF_A(false, false, 1);
-        WF_A(true, false, 2);
-        WF_A(false, false, 2);
-        if constexpr(!SPLIT) {
-            WF_A(true, true, 1);
-            WF_A(false, true, 1);
-        }
-    }
-#undef WF_A
-    return WF_HIP_OK;
-}
+};
 
 template<class G> int launch_tick_split(wf_hip *h, const wf::TickArgs &a0, bool aligned, hipStream_t st)
 {
@@ -112,7 +69,7 @@ template<class G> int launch_tick_split(wf_hip *h, const wf::TickArgs &a0, bool 
         wf::TickArgs a = a0;
         a.split_ch = two ? (uint32_t)(1 - pass) : 0xffffffffu;
         const dim3 grid(two ? a.stream_count : a.stream_count * a.cap_ch);
-        launch_pow2<G, 1, true, 0, false, false, true>(grid, block, lds, st, a, aligned);
+        Pow2Family<G, 1, true, 0, false, false, true>::launch(grid, block, lds, st, a, aligned);
     }
     return WF_HIP_OK;
 }
@@ -120,7 +77,7 @@ template<class G> int launch_tick_split(wf_hip *h, const wf::TickArgs &a0, bool 
 template<class G> int setup_launch_split(wf_hip *h)
 {
     const int lds = (int)wf::tick_lds_bytes<G, 1>();
-    WF_TRY_RC((setup_pow2_lds<G, 1, true, 0, false, false, true>(h, lds)));
+    WF_TRY_RC((Pow2Family<G, 1, true, 0, false, false, true>::setup_lds(h, lds)));
     h->launch = &launch_tick_split<G>;
     h->wg_lds = (uint32_t)lds;
     h->wg_threads = (uint32_t)G::T;
@@ -138,14 +95,14 @@ template<class G, int DEC> int launch_tick_dec(wf_hip *, const wf::TickArgs &a, 
     const uint32_t n_spec = a.stream_count * a.cap_ch;
     const dim3 grid((n_spec + 1) / 2), block(G::T * 2);
     const size_t lds = wf::tick_lds_bytes<G, 2>();
-    launch_pow2<G, 2, false, DEC, false, false, false>(grid, block, lds, st, a, aligned);
+    Pow2Family<G, 2, false, DEC, false, false, false>::launch(grid, block, lds, st, a, aligned);
     return WF_HIP_OK;
 }
 
 template<class G, int DEC> int setup_launch_dec(wf_hip *h)
 {
     const int lds = (int)wf::tick_lds_bytes<G, 2>();
-    WF_TRY_RC((setup_pow2_lds<G, 2, false, DEC, false, false, false>(h, lds)));
+    WF_TRY_RC((Pow2Family<G, 2, false, DEC, false, false, false>::setup_lds(h, lds)));
     h->launch = &launch_tick_dec<G, DEC>;
     h->wg_lds = (uint32_t)lds;
     h->wg_threads = (uint32_t)G::T * 2u;
@@ -155,9 +112,26 @@ template<class G, int DEC> int setup_launch_dec(wf_hip *h)
     return WF_HIP_OK;
 }
 
+// The instantiations of a Bluestein / mixed-radix family: the general one and, for the small-radix instantiation of the 2048- and
+// 4096-sample containers, the four plans it carries as compile-time constants (TransformPlan::plan_id; table row 1 + plan_id - P0,
+// row 0: the general one), each with and without the display code (DISP 0 / 2)
+template<class G, int SPW, bool SPLIT, bool MR, bool MRS> struct BluFamily {
+    static constexpr bool FIXED = MRS && (G::N == 2048 || G::N == 4096);
+    static constexpr int P0 = G::N == 2048 ? 1 : 5; // the container's four fixed plans (spectrum_tick_kernel's PLAN)
+    template<int ROW, bool NODISP> static constexpr TickKernel kernel()
+    {
+        constexpr int plan = FIXED && ROW > 0 ? P0 + ROW - 1 : 0;
+        return &wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = NODISP ? 2 : 0, .plan = plan}>;
+    }
+    static constexpr TickKernel table[5][2] = {{kernel<0, false>(), kernel<0, true>()}, {kernel<1, false>(), kernel<1, true>()}, {kernel<2, false>(), kernel<2, true>()},
+                                               {kernel<3, false>(), kernel<3, true>()}, {kernel<4, false>(), kernel<4, true>()}};
+    static int row(int plan_id) { return FIXED && plan_id >= P0 && plan_id < P0 + 4 ? 1 + plan_id - P0 : 0; }
+};
+
 // Bluestein path (FFT sizes that are not powers of two): always the scalar fetch
 template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int launch_tick_blu(wf_hip *h, const wf::TickArgs &a0, bool, hipStream_t st)
 {
+    using Family = BluFamily<G, SPW, SPLIT, MR, MRS>;
     const uint32_t n_spec = a0.stream_count * a0.cap_ch;
     const dim3 block(G::T * SPW);
     // (mixed radix: the exchange buffers by the transform's size, MrPlan::lds_cf)
@@ -168,27 +142,9 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int la
         a.split_ch = two ? (uint32_t)(1 - pass) : 0xffffffffu;
         const dim3 grid(two ? a.stream_count : (n_spec + SPW - 1) / SPW);
         // (no display: the instantiation without any display code -- spectrum_tick_kernel<.., DISP = 2>; the sizes with a
-        // compile-time plan: the instantiation of that plan alone -- <.., PLAN>, TransformPlan::plan_id)
+        // compile-time plan: the instantiation of that plan alone -- <.., PLAN>)
         const bool nodisp = MRS && display_kind(a) == 2; // (the small-radix instantiation only: N = 4160 on the all-radix one measured -1.8 %)
-#define WF_LP(PLAN_)                                                                                                                                            \
-    do {                                                                                                                                                       \
-        if(nodisp)                                                                                                                                             \
-            hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = 2, .plan = PLAN_}>), grid, block, lds, st, a); \
-        else                                                                                                                                                   \
-            hipLaunchKernelGGL((wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .plan = PLAN_}>), grid, block, lds, st, a); \
-    } while(0)
-        if constexpr(MRS && (G::N == 2048 || G::N == 4096)) {
-            constexpr int P0 = G::N == 2048 ? 1 : 5; // the container's four fixed plans (spectrum_tick_kernel's PLAN)
-            switch(h->plan.plan_id - P0) {
-            case 0: WF_LP(P0); break;
-            case 1: WF_LP(P0 + 1); break;
-            case 2: WF_LP(P0 + 2); break;
-            case 3: WF_LP(P0 + 3); break;
-            default: WF_LP(0); break;
-            }
-        } else
-            WF_LP(0);
-#undef WF_LP
+        hipLaunchKernelGGL(Family::table[Family::row(h->plan.plan_id)][nodisp], grid, block, lds, st, a);
     }
     return WF_HIP_OK;
 }
@@ -198,24 +154,9 @@ template<class G, int SPW, bool SPLIT, bool MR = false, bool MRS = false> int se
     int lds = (int)wf::tick_lds_bytes<G, SPW>();
     // (the attribute belongs to the kernel, not to this handle: always the container's size -- another handle of another fft size
     // on the same instantiation may need all of it)
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS}>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = 2}>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if constexpr(MRS && (G::N == 2048 || G::N == 4096)) {
-        // (the fixed plans of this container: TransformPlan::plan_id picks one per launch)
-        constexpr int P0 = G::N == 2048 ? 1 : 5;
-#define WF_AP(PLAN_)                                                                                                                                          \
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .plan = PLAN_}>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                                                       \
-    WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&wf::spectrum_tick_kernel<G, wf::Variant{.spw = SPW, .split = SPLIT, .blu = true, .mr = MR, .mrs = MRS, .disp = 2, .plan = PLAN_}>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-        WF_AP(P0);
-        WF_AP(P0 + 1);
-        WF_AP(P0 + 2);
-        WF_AP(P0 + 3);
-#undef WF_AP
-    }
+    for(const auto &by_disp : BluFamily<G, SPW, SPLIT, MR, MRS>::table) // (without fixed plans every row is the general instantiation)
+        for(const TickKernel k : by_disp)
+            WF_HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     if constexpr(MR) {
         // the spectrum's exchange buffer by the transform's size, not the container's (MrPlan::lds_cf): room for more spectra per CU
         wf::MrPlan &mr = h->tick.mr;
@@ -268,14 +209,14 @@ template<class G, int SPW, bool TLDS, bool BOTH = false> int launch_tick(wf_hip 
     const uint32_t n_spec = a.stream_count * a.cap_ch;
     const dim3 grid((n_spec + SPW - 1) / SPW), block(G::T * SPW);
     const size_t lds = wf::tick_lds_bytes<G, SPW>();
-    launch_pow2<G, SPW, false, 0, TLDS, BOTH, !BOTH>(grid, block, lds, st, a, aligned);
+    Pow2Family<G, SPW, false, 0, TLDS, BOTH, !BOTH>::launch(grid, block, lds, st, a, aligned);
     return WF_HIP_OK;
 }
 
 template<class G, int SPW, bool TLDS, bool BOTH = false> int setup_launch_impl(wf_hip *h)
 {
     const int lds = (int)wf::tick_lds_bytes<G, SPW>();
-    WF_TRY_RC((setup_pow2_lds<G, SPW, false, 0, TLDS, BOTH, !BOTH>(h, lds)));
+    WF_TRY_RC((Pow2Family<G, SPW, false, 0, TLDS, BOTH, !BOTH>::setup_lds(h, lds)));
     h->launch = &launch_tick<G, SPW, TLDS, BOTH>;
     h->wg_lds = (uint32_t)lds;
     h->wg_threads = (uint32_t)(G::T * SPW);
@@ -289,17 +230,15 @@ template<class G, int SPW, bool TLDS, bool BOTH = false> int setup_launch_impl(w
 // Workgroups of two spectra can stage the window / pass-1 twiddle tables in LDS once (spectrum_tick_kernel<.., TLDS>).
 // Measured on MI355X (interleaved A/B): N = 1024 63.4 -> 68.7 % of the HBM peak (8-byte table loads, 23 per thread, become
 // 8 DMA requests per wavefront), N = 2048 +-1 %, N = 4096 -1.5 % (the extra barrier costs what the halved table traffic
-// saves), N = 8192 +1 %: on for the 8-point geometry only.  WF_HIP_TLDS=0/1 overrides (development aid).
+// saves), N = 8192 +1 %: on for the 8-point geometry only.
 template<class G, int SPW> int setup_launch(wf_hip *h)
 {
     if constexpr(SPW == 2) {
-        bool tlds = G::P <= 8;
-#ifdef WF_DEV_BUILD
-        if(const char *e = std::getenv("WF_HIP_TLDS"))
-            tlds = e[0] == '1';
-#endif
-        // mono mixdown with a curve display: the kernel whose two spectra share the row (a TLDS override keeps the plain one)
-        if(h->tick.bar.both_subs && h->N == (uint32_t)G::N && tlds == (G::P <= 8)) {
+        // (not `if constexpr`: the form a geometry does not take stays instantiated although nothing launches it -- the object's
+        // kernels are on record in tests/test_cpu_units.py, and dropping ten per geometry is a change of its own)
+        const bool tlds = G::P <= 8;
+        // mono mixdown with a curve display: the kernel whose two spectra share the row
+        if(h->tick.bar.both_subs && h->N == (uint32_t)G::N) {
             if constexpr(G::P <= 8)
                 return setup_launch_impl<G, 2, true, true>(h);
             else

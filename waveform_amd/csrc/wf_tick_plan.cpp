@@ -11,32 +11,9 @@ namespace wf {
 
 namespace {
 
-// WF_HIP_MR_PLAN: another order or split of the same product, where the kernels can run it
-void override_mr_plan(TransformPlan &t, const PlanOverrides &ov, uint32_t threads)
-{
-    const int n = ov.mr_plan_n;
-    const int *r = ov.mr_plan;
-    if(n < 2 || n > 4)
-        return;
-    uint64_t prod = 1;
-    for(int i = 0; i < n; ++i)
-        prod *= (uint64_t)std::max(r[i], 1);
-    bool ok = prod == t.n / 2 && r[n - 1] <= 16 && (t.n / 2) / (uint32_t)r[n - 1] <= threads;
-    for(int i = 0; i < n; ++i) {
-        const int v = r[i];
-        ok = ok && (v == 2 || v == 3 || v == 4 || v == 5 || v == 6 || v == 8 || v == 9 || v == 10 || v == 12 || v == 15 || v == 16 || v == 7 || v == 11 || v == 13 ||
-                    (i == 0 && (v == 20 || v == 25 || v == 17 || v == 19 || v == 23 || v == t.radix[0])));
-    }
-    if(ok) {
-        t.passes = n;
-        for(int i = 0; i < 4; ++i)
-            t.radix[i] = i < n ? r[i] : 0;
-    }
-}
-
 // sizes up to 16384 that are not powers of two: Bluestein over the container of geom_n / 2 points, or -- sizes with small prime
 // factors -- the same instantiation's fetch and epilogue around a direct mixed-radix transform
-void plan_in_lds(TransformPlan &t, const PlanOverrides &ov)
+void plan_in_lds(TransformPlan &t)
 {
     t.family = Family::BLUESTEIN;
     uint32_t threads = 0, points = 0;
@@ -50,7 +27,7 @@ void plan_in_lds(TransformPlan &t, const PlanOverrides &ov)
             threads = (uint32_t)G::T, points = (uint32_t)G::P, container = (uint64_t)G::M;
         }
     });
-    if(!threads || !ov.mixed_radix)
+    if(!threads)
         return;
     const int passes = plan_mixed_radix(t.n / 2, threads, t.radix, container);
     if(passes <= 0) {
@@ -59,10 +36,9 @@ void plan_in_lds(TransformPlan &t, const PlanOverrides &ov)
     }
     t.family = Family::MIXED_RADIX;
     t.passes = passes;
-    override_mr_plan(t, ov, threads);
     // one-wavefront containers: plans made of small radices take the instantiation that carries only those (five waves per SIMD)
-    t.mr_small = threads <= 256u && points > 8u && mr_small_radices(t.radix, t.passes) && ov.mr_small;
-    if(t.mr_small && (t.geom_n == 2048u || t.geom_n == 4096u) && t.passes == 3 && ov.mr_plan_kernel) {
+    t.mr_small = threads <= 256u && points > 8u && mr_small_radices(t.radix, t.passes);
+    if(t.mr_small && (t.geom_n == 2048u || t.geom_n == 4096u) && t.passes == 3) {
         // the sizes the plugin picks by itself run their plan as compile-time constants, in an instantiation of their own
         static const int fixed[8][3] = {{5, 10, 8}, {5, 12, 8}, {10, 6, 6}, {11, 5, 8}, {10, 8, 10}, {10, 8, 12}, {10, 10, 10}, {10, 8, 11}};
         const int p0 = t.geom_n == 2048u ? 1 : 5; // the container's four fixed plans (spectrum_tick_kernel's PLAN)
@@ -75,8 +51,8 @@ void plan_in_lds(TransformPlan &t, const PlanOverrides &ov)
 }
 
 // above 16384 samples and not a power of two: where n/2 = C R with R <= 8192 a length that has a mixed-radix plan, C <= 8
-// rows of that transform (big_mr_rows_kernel) instead of Bluestein through device memory
-void plan_rows(TransformPlan &t, const PlanOverrides &ov)
+// rows of that transform (big_mr_rows_kernel)
+void plan_rows(TransformPlan &t)
 {
     const uint32_t np = t.n / 2;
     // ... and where n/2 = C R with C = 8 or 4 and R <= 4096: the rows by Bluestein over the 8192- / 16384-sample geometry INSIDE
@@ -85,7 +61,7 @@ void plan_rows(TransformPlan &t, const PlanOverrides &ov)
     // 48064 x 256 streams 0.254 ms with 8 rows over 8192 points, 0.194 with 16 over 4096, 0.209 with 32 over 2048
     // (32 rows over 1024 / 2048 points: 0.209 -- profiles/r05m_bluestein_rows_ab.txt; not compiled in any more)
     uint32_t br_c = 0;
-    for(uint32_t c = ov.br_first; c >= 8u && !br_c && ov.bluestein_rows; c >>= 1)
+    for(uint32_t c = 16; c >= 8u && !br_c; c >>= 1)
         if(np % c == 0 && np / c <= 4096u && np / c >= 512u)
             br_c = c;
     for(uint32_t c = 2; c <= 8 && !t.big_mr(); ++c) {
@@ -94,7 +70,7 @@ void plan_rows(TransformPlan &t, const PlanOverrides &ov)
         int radix[4] = {0, 0, 0, 0};
         int passes = 0;
         bool whole = false;
-        if(c == 2u && ov.mr_whole) { // two rows: on 512 threads where a plan exists -- one kernel (big_mr_whole_kernel)
+        if(c == 2u) { // two rows: on 512 threads where a plan exists -- one kernel (big_mr_whole_kernel)
             passes = plan_mixed_radix(np / c, 512u, radix);
             whole = passes > 0;
         }
@@ -126,7 +102,7 @@ void plan_rows(TransformPlan &t, const PlanOverrides &ov)
 
 } // namespace
 
-TransformPlan plan_transform(const wf_config &cfg, const PlanOverrides &ov)
+TransformPlan plan_transform(const wf_config &cfg, const PlanOverrides &)
 {
     TransformPlan t;
     t.n = cfg.fft_size;
@@ -136,18 +112,17 @@ TransformPlan plan_transform(const wf_config &cfg, const PlanOverrides &ov)
     t.big_rows = t.big_l / 16384u;
     t.geom_n = t.big_l ? 32768u : L ? 2 * L : std::max(t.n, 512u); // big: the row transform's geometry
     if(!t.blu)
-        t.family = t.big_l ? (ov.big_whole ? Family::WHOLE_65536 : Family::DEVICE_MEMORY) : t.n < 512u ? Family::ZERO_PADDED : Family::POW2;
+        t.family = t.big_l ? Family::WHOLE_65536 : t.n < 512u ? Family::ZERO_PADDED : Family::POW2;
     else if(!t.big_l)
-        plan_in_lds(t, ov);
+        plan_in_lds(t);
     else {
-        t.family = Family::DEVICE_MEMORY;
-        if(ov.mixed_radix)
-            plan_rows(t, ov);
+        t.family = Family::NONE; // (what a size keeps that plan_rows cannot place; every multiple of 16 has rows of one kind or the other)
+        plan_rows(t);
     }
     // Split mode: the channels of a stereo pair in different workgroups.  Measured on MI355X: N = 16384 45 -> 52 % of the HBM
     // peak (two workgroups per CU instead of one), N = 8192 57.2 -> 58.5 % (four instead of two), N = 32768 cannot run a
-    // pair any other way.  WF_HIP_SPLIT=0/1 overrides (development aid; mono mixdown and single-channel captures never split).
-    t.want_split = t.geom_n >= 8192u && ov.split != 0;
+    // pair any other way (mono mixdown and single-channel captures never split).
+    t.want_split = t.geom_n >= 8192u;
     t.want_split = t.want_split && cfg.capture_channels == 2 && cfg.stereo;
     // mono mixdown needs both channels' magnitudes; where a workgroup holds one spectrum (132 KB of LDS) the pair runs split
     // as well, channel 1 a launch ahead of channel 0
@@ -161,8 +136,6 @@ TransformPlan plan_transform(const wf_config &cfg, const PlanOverrides &ov)
     while((1u << lg) < t.n)
         ++lg;
     t.in_scale = std::ldexp(1.0f, std::min(40, 52 - lg));
-    if(t.big_l && t.blu) // Bluestein through device memory squares values that still carry its factor L
-        t.in_scale = 0x1p24f;
     return t;
 }
 

@@ -19,31 +19,21 @@ enum class Family {
     MR_TWO_ROWS,    // above 16384: n/2 as two mixed-radix rows on 512 threads, one kernel (big_mr_whole_kernel)
     MR_ROWS,        // above 16384: big_rows mixed-radix rows, then the epilogue (big_mr_rows_kernel)
     BLUESTEIN_ROWS, // above 16384: big_rows rows, each by Bluestein over br_l points inside LDS (big_br_rows_kernel)
-    DEVICE_MEMORY,  // above 16384 through device memory (columns -> rows -> epilogue): development builds' A/B baseline only
+    NONE,           // above 16384 with no row decomposition: no kernel, wf_hip_create refuses (no multiple of 16 ends here)
 };
 
-// The development overrides (WF_HIP_* of the environment, read by the .hip units under WF_DEV_BUILD) as plain values; the
+// The development overrides (WF_HIP_* of the environment, read by wf_hip_plan.hip under WF_DEV_BUILD) as plain values; the
 // defaults are what the release library does.
 struct PlanOverrides {
-    bool mixed_radix = true;    // WF_HIP_NO_MIXED_RADIX=1 clears it: Bluestein for every size that is not a power of two
-    bool bluestein_rows = true; // WF_HIP_NO_BLUESTEIN_ROWS=1 clears it
-    uint32_t br_first = 16;     // WF_HIP_BR_ROWS=8: every Bluestein-rows size on 8 rows
-    bool mr_whole = true;       // WF_HIP_MR_WHOLE=0: two rows through rows + epilogue like the others
-    bool big_whole = true;      // WF_HIP_BIG_WHOLE=0: 65536 through device memory
-    int split = -1;             // WF_HIP_SPLIT=0/1; -1: the rule
-    int mr_plan[4] = {0, 0, 0, 0}; // WF_HIP_MR_PLAN="25,16": another order or split of the same product
-    int mr_plan_n = 0;
-    bool mr_small = true;       // WF_HIP_MR_SMALL=0: the instantiation with every radix
-    bool mr_plan_kernel = true; // WF_HIP_MR_PLAN_KERNEL=0: the instantiation that carries every plan
-    int lanes = 0;              // WF_HIP_LANES; 0: the rule
+    int lanes = 0; // WF_HIP_LANES; 0: the rule
 };
 
 struct TransformPlan {
     Family family = Family::POW2;
     uint32_t n = 0;        // cfg.fft_size
     uint32_t geom_n = 0;   // the fft size whose geometry runs the batch (big: the row transform's)
-    // runs in the Bluestein instantiation of the geometry (BLUESTEIN, MIXED_RADIX, FIXED_PLAN) or with Bluestein's chirp tables
-    // through device memory; false for the rows families, which are plain packed real transforms
+    // runs in the Bluestein instantiation of the geometry (BLUESTEIN, MIXED_RADIX, FIXED_PLAN); false for the rows families, which
+    // are plain packed real transforms
     bool blu = false;
     // transforms beyond a CU's LDS (wf_big.hpp): big_l complex points per spectrum in big_rows rows
     uint32_t big_l = 0, big_rows = 0;
@@ -65,7 +55,7 @@ struct TransformPlan {
 };
 
 // `cfg` after wf::normalize_config (and waveform_config / meter_config): a legal fft_size is never refused
-TransformPlan plan_transform(const wf_config &cfg, const PlanOverrides &ov);
+TransformPlan plan_transform(const wf_config &cfg, const PlanOverrides &ov); // (no override bears on the transform today)
 
 constexpr int MAX_LANES = 4;
 // wg_lds / wg_threads: dynamic LDS and threads of one workgroup of the tick kernel; cu_count: the device's compute units
